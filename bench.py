@@ -12,7 +12,9 @@ are cut into N contiguous ranges balanced by residual blocks (`mpsfm_amd.dist.sh
 BASELINE config 4 names ("1000 images / 800k points ... landmark-sharded across 8 GPUs":
 `--config C4 --gpus 8 --scaling strong`); the replicated dense solve bounds it.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run prints the headline figures of the timed steps only; `--full` adds what takes
+runs of its own: the live roofline timing of the sweep / dense kernels, the CPU baseline and the side measurements.
+`--dump-outputs DIR` writes what the last timed solve hands its caller (poses, landmarks, costs) as DIR/<name>.npy.
 """
 
 from __future__ import annotations
@@ -37,10 +39,16 @@ def parse():
     ap.add_argument("--config", default="C3")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=os.environ.get("MPSFM_BENCH_SCALING", "weak"),
                     help="weak: every rank draws the configuration's landmark count; strong: the configuration's landmarks are sharded")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the sweep / dense kernels on their own (roofline), the CPU baseline and the side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed solve's results to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and the side measurements")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg")
-    ap.add_argument("--kernel-reps", type=int, default=20, help="launches used to time the sweep / dense kernels")
-    return ap.parse_args()
+    ap.add_argument("--kernel-reps", type=int, default=20, help="with --full: launches used to time the sweep / dense kernels")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
@@ -48,7 +56,7 @@ def main():
     import torch
 
     from mpsfm_amd import capi
-    from mpsfm_amd.synthetic import CONFIGS, algorithmic_bytes_sweep, algorithmic_flops_sweep, make_config
+    from mpsfm_amd.synthetic import CONFIGS, make_config
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -159,10 +167,95 @@ def main():
     iters = sum(s["num_iterations"] for s in sums)
     revals = sum(s["num_residual_evals"] for s in sums)  # already the all-rank total
     last = sums[-1]
+    t_lin, t_den, t_upd = last["time_linearize_s"], last["time_dense_s"], last["time_update_s"]
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, h, prob, last)
+
+    out = {
+        "metric": f"BA residual-evals/sec (LM iterations/sec alongside), {CONFIGS[args.config][0]} imgs / {CONFIGS[args.config][1] // 1000}k pts "
+                  + ("prior-BA" if CONFIGS[args.config][2] else "reprojection-only BA"),
+        "value": revals / dt,
+        "unit": "residual-block evals/s",
+        "lm_iterations_per_s": iters / dt,
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": (f"{args.config}: {CONFIGS[args.config][0]} cameras, {CONFIGS[args.config][1]} landmarks per rank, "
+                         f"{prob.n_obs} reprojection + {prob.n_dobs} log-depth blocks per rank, SoftL1/Cauchy, Ceres-default LM"
+                         if not (args.scaling == "strong" and world > 1) else
+                         f"{args.config}: {CONFIGS[args.config][0]} cameras, {CONFIGS[args.config][1]} landmarks IN TOTAL cut into {world} landmark "
+                         f"ranges (rank 0: {prob.n_pts} landmarks, {prob.n_obs} reprojection + {prob.n_dobs} log-depth blocks), SoftL1/Cauchy, Ceres-default LM"),
+            "parallelism": ((f"landmark-sharded x{world} ({args.scaling}: " + ("the configuration's landmarks split" if args.scaling == "strong" else "the configuration's landmark count per rank")
+                             + (f"), {collective}" if collective else ")")) if (world > 1 or collective) else "single GPU"),
+            "residual_blocks_total": last["num_residual_blocks"],
+        },
+        "solve": {
+            "lm_iterations": last["num_iterations"], "successful": last["num_successful_steps"],
+            "initial_cost": last["initial_cost"], "final_cost": last["final_cost"], "termination": last["termination"],
+            "device_ms": {"track_sweep": 1e3 * t_lin, "dense_solve": 1e3 * t_den, "update_sweep": 1e3 * t_upd,
+                          "total": 1e3 * last["time_total_s"]},
+        },
+    }
+    if args.full:
+        out["roofline"], out["roofline_other"] = roofline_leg(h, prob, last, args.kernel_reps)
+
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # CPU baseline and side measurements at N=1 only
+        out["cpu_baseline"] = cpu_baseline(args, last)
+        try:
+            out["extras"] = {"integration_290x387": integration_leg(local_rank)}
+        except Exception as e:  # noqa: BLE001 - never lose the headline line to the side measurement
+            out["extras"] = {"integration_290x387": {"error": repr(e)}}
+        try:
+            out["extras"]["one_shot_ms"] = one_shot_leg(local_rank)
+        except Exception as e:  # noqa: BLE001
+            out["extras"]["one_shot_ms"] = {"error": repr(e)}
+        try:  # what one Optimizer.ba() call pays from host buffers (device table build + uploads + solve + read-back): never `value`
+            out["one_shot_ms"] = {k: v.get("min") for k, v in out["extras"]["one_shot_ms"].items() if isinstance(v, dict)}
+        except Exception:  # noqa: BLE001
+            pass
+        try:
+            out["extras"]["other_configs_one_gpu"] = other_configs_leg(local_rank)
+        except Exception as e:  # noqa: BLE001
+            out["extras"]["other_configs_one_gpu"] = {"error": repr(e)}
+    if rank == 0:
+        print(json.dumps(out))
+    h.close()
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(dst, h, prob, last):
+    """What the timed solve hands its caller, from its last step: the refined poses and landmarks (this rank's shard) and the
+    summary's costs, counts and per-iteration trace.  Timings are left out: they differ from run to run."""
+    os.makedirs(dst, exist_ok=True)
+    res = prob.copy()
+    h.get_state(res)
+    arrays = {
+        "cam_quat": res.cam_quat, "cam_t": res.cam_t, "pts": res.pts,
+        "cost": [last["initial_cost"], last["final_cost"], last["fixed_cost"]],
+        "counts": [last["num_iterations"], last["num_successful_steps"], last["num_unsuccessful_steps"], last["num_residual_evals"]],
+        "trace_cost": last["trace_cost"], "trace_radius": last["trace_radius"], "trace_accepted": last["trace_accepted"],
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(dst, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def roofline_leg(h, prob, last, kernel_reps):
+    """The track sweep and the dense solve timed on their own with HIP events, against the roofline: (dominant, other)."""
+    from mpsfm_amd.synthetic import algorithmic_bytes_sweep, algorithmic_flops_sweep
 
     # ---- roofline of the two priced kernels, timed live with HIP events on the solver's stream
     h.reset_state()
-    reps = max(1, args.kernel_reps)
+    reps = max(1, kernel_reps)
     sweeps, parts = [], []
     for _ in range(reps + 2):
         sweeps.append(h.sweep_once(1e4))
@@ -235,66 +328,7 @@ def main():
                 roof_dense["mfma_util_source"] = os.path.basename(cands[-1])
         except Exception:  # noqa: BLE001
             pass
-
-    out = {
-        "metric": f"BA residual-evals/sec (LM iterations/sec alongside), {CONFIGS[args.config][0]} imgs / {CONFIGS[args.config][1] // 1000}k pts "
-                  + ("prior-BA" if CONFIGS[args.config][2] else "reprojection-only BA"),
-        "value": revals / dt,
-        "unit": "residual-block evals/s",
-        "lm_iterations_per_s": iters / dt,
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / args.steps,
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": (f"{args.config}: {CONFIGS[args.config][0]} cameras, {CONFIGS[args.config][1]} landmarks per rank, "
-                         f"{prob.n_obs} reprojection + {prob.n_dobs} log-depth blocks per rank, SoftL1/Cauchy, Ceres-default LM"
-                         if not (args.scaling == "strong" and world > 1) else
-                         f"{args.config}: {CONFIGS[args.config][0]} cameras, {CONFIGS[args.config][1]} landmarks IN TOTAL cut into {world} landmark "
-                         f"ranges (rank 0: {prob.n_pts} landmarks, {prob.n_obs} reprojection + {prob.n_dobs} log-depth blocks), SoftL1/Cauchy, Ceres-default LM"),
-            "parallelism": ((f"landmark-sharded x{world} ({args.scaling}: " + ("the configuration's landmarks split" if args.scaling == "strong" else "the configuration's landmark count per rank")
-                             + (f"), {collective}" if collective else ")")) if (world > 1 or collective) else "single GPU"),
-            "residual_blocks_total": last["num_residual_blocks"],
-        },
-        "solve": {
-            "lm_iterations": last["num_iterations"], "successful": last["num_successful_steps"],
-            "initial_cost": last["initial_cost"], "final_cost": last["final_cost"], "termination": last["termination"],
-            "device_ms": {"track_sweep": 1e3 * t_lin, "dense_solve": 1e3 * t_den, "update_sweep": 1e3 * t_upd,
-                          "total": 1e3 * last["time_total_s"]},
-        },
-        "roofline": dominant,
-        "roofline_other": other,
-    }
-
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # CPU baseline and side measurements at N=1 only
-        out["cpu_baseline"] = cpu_baseline(args, last)
-        try:
-            out["extras"] = {"integration_290x387": integration_leg(local_rank)}
-        except Exception as e:  # noqa: BLE001 - never lose the headline line to the side measurement
-            out["extras"] = {"integration_290x387": {"error": repr(e)}}
-        try:
-            out["extras"]["one_shot_ms"] = one_shot_leg(local_rank)
-        except Exception as e:  # noqa: BLE001
-            out["extras"]["one_shot_ms"] = {"error": repr(e)}
-        try:  # what one Optimizer.ba() call pays from host buffers (device table build + uploads + solve + read-back): never `value`
-            out["one_shot_ms"] = {k: v.get("min") for k, v in out["extras"]["one_shot_ms"].items() if isinstance(v, dict)}
-        except Exception:  # noqa: BLE001
-            pass
-        try:
-            out["extras"]["other_configs_one_gpu"] = other_configs_leg(local_rank)
-        except Exception as e:  # noqa: BLE001
-            out["extras"]["other_configs_one_gpu"] = {"error": repr(e)}
-    if rank == 0:
-        print(json.dumps(out))
-    h.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    return dominant, other
 
 
 def one_shot_leg(device):

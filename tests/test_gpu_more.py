@@ -326,11 +326,11 @@ def test_max_iterations_and_tight_tolerances(speculate, monkeypatch):
 
 
 @pytest.mark.parametrize("collective", ["rccl", "hook", "rccl-fails"])
-def test_rccl_single_rank(collective):
+def test_rccl_single_rank(collective, tmp_path):
     """bench.py with a one-rank NCCL(RCCL) process group.  "rccl": the library's own communicator (ncclCommInitRank from a
     unique id, ncclAllReduce on the solver's stream, no Python in the LM loop); "hook": the torch.distributed hook with
     the zero-copy tensor view and the shared stream; "rccl-fails": the native path's first solve is made to fail, the run
-    must continue on the hook by itself.  Same result as the plain single-GPU solve."""
+    must continue on the hook by itself.  Same result as the plain single-GPU solve, also in what --dump-outputs writes."""
     import json
     import os
     import subprocess
@@ -342,13 +342,20 @@ def test_rccl_single_rank(collective):
     if collective == "rccl-fails":
         env["MPSFM_BENCH_INJECT_NATIVE_FAILURE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "C2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--kernel-reps", "2"], capture_output=True, text=True, env=env, timeout=600)
+                        "--no-cpu-baseline", "--kernel-reps", "2", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env,
+                       timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     ref, _ = make_config("C2")
     s = capi.ba_solve(ref)
     assert d["solve"]["final_cost"] == pytest.approx(s["final_cost"], rel=1e-9)
     assert d["solve"]["lm_iterations"] == s["num_iterations"]
+    assert np.load(tmp_path / "cost.npy")[1] == pytest.approx(s["final_cost"], rel=1e-9)
+    assert np.load(tmp_path / "counts.npy")[0] == s["num_iterations"]
+    # relative: C2 holds landmarks far out along their rays (|x| ~ 1e6), which the two solves place alike to ~1e-7 relative;
+    # the perturbed initial state lies outside this bound almost everywhere
+    np.testing.assert_allclose(np.load(tmp_path / "pts.npy"), ref.pts, rtol=1e-5, atol=1e-8)
+    np.testing.assert_allclose(np.load(tmp_path / "cam_t.npy"), ref.cam_t, rtol=1e-5, atol=1e-8)
     assert ("native RCCL" if collective == "rccl" else "hook") in d["config"]["parallelism"]
     if collective == "rccl-fails":
         assert "falling back" in r.stderr
