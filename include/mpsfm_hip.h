@@ -426,6 +426,41 @@ int mpsfm_integration_variances(const mpsfm_int_problem* problem, int32_t device
                                 double* var_out /* [n_query] */, double* field_out /* [H*W] or NULL */,
                                 mpsfm_int_summary* summary);
 
+/* ---- depth-consistency check of a registered image against its local bundle (reference
+ *    mpsfm/sfm/mapper/depthconsistency.py:62-159 check_depth_consistency, :224-246 check_bundle_depth_concistency;
+ *    reconstruction/mixins/depth_utils.py:9-48 reproject_depth).  For every pair (a, b) both legs a -> b and b -> a:
+ *    every pixel of the source map is unprojected with the map intrinsics and projected into the target map; it is in
+ *    canvas when p.x >= 0, p.x + 0.5 < W, p.y >= 0, p.y + 0.5 < H and its depth there is > 0.  The z-buffer keeps the
+ *    LAST writer in raster order per target pixel (int(p.y), int(p.x)) (the reference's find_min_buffer compares against
+ *    an all-inf buffer).  Test value t = (buffer - depth_target) / sqrt((std_bar c)^2 + (std_target c)^2) with std_bar^2
+ *    the (2,2) entry of the source pixel's lifted covariance (unscaled intrinsics, map coordinates, var / psm^2) rotated
+ *    by R_t^T R_s ... R_s^T R_t, std_target = sqrt(var_target / psm_target^2).  surface |t| < s, occluded t > s,
+ *    invalid t < -s.  counts[p][leg] = {in canvas, surface, occluded, invalid} (leg 0: a -> b, 1: b -> a);
+ *    codes[2 p + leg] (may be NULL, as may the array itself) receives one byte per SOURCE pixel, bit 0 in canvas,
+ *    bit 1 surface, bit 2 occluded, bit 3 invalid.  Values <= 0 of the depth maps of every image in a pair are set to
+ *    0.1 in the caller's arrays, as the reference does in place.  An empty pair list is a no-op. ---- */
+typedef struct mpsfm_dc_image {
+  int32_t H, W;
+  double* depth;                /* [H][W] depth.data (in/out: the <= 0 -> 0.1 clamp is written back) */
+  const double* variance;       /* [H][W] depth.uncertainty                                          */
+  double prior_std_multiplier;  /* depth.conf.prior_std_multiplier                                   */
+  double intr_scaled[4];        /* fx sx, fy sy, cx sx, cy sy: PINHOLE of the map                    */
+  double intr[4];               /* fx fy cx cy of the camera (lifted covariance)                     */
+  double cam_from_world[12];    /* [3][4] row-major                                                  */
+} mpsfm_dc_image;
+
+typedef struct mpsfm_dc_summary {
+  float ms;          /* device time of the launches (HIP events), transfers excluded */
+  int32_t n_legs;
+  int64_t n_pixels;  /* source pixels over all legs */
+} mpsfm_dc_summary;
+
+int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images /* [n_images] */, int32_t n_pairs,
+                            const int32_t* pair_a, const int32_t* pair_b /* [n_pairs] */, double c, double score_thresh,
+                            int32_t device, int64_t* counts /* [n_pairs][2][4] */,
+                            uint8_t* const* codes /* [2 n_pairs] pointers to Hs*Ws, or NULL */,
+                            mpsfm_dc_summary* summary /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ EXPORTS = [
     "mpsfm_ba_sweep_once", "mpsfm_ba_get_reduced_system", "mpsfm_ba_reduced_dim",
     "mpsfm_ba_get_dense_solution", "mpsfm_ba_dense_solve_once", "mpsfm_ba_dense_plan", "mpsfm_point_covs",
     "mpsfm_triangulate_tracks", "mpsfm_filter_tracks", "mpsfm_integrate_depth", "mpsfm_integrate_depth_batch",
-    "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id",
+    "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
 ]
 
 _lib = None
@@ -457,3 +457,64 @@ def tri_estimate_batch(cand_start, view_cam_from_world, view_intr, view_xy, min_
     L.mpsfm_tri_estimate_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     _check(L.mpsfm_tri_estimate_batch(C.byref(c), device, xyz.ctypes.data, ok.ctypes.data, inl.ctypes.data))
     return xyz, ok.astype(bool), inl.astype(bool)
+
+
+class CDcImage(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p), ("variance", C.c_void_p),
+                ("prior_std_multiplier", C.c_double), ("intr_scaled", C.c_double * 4), ("intr", C.c_double * 4),
+                ("cam_from_world", C.c_double * 12)]
+
+
+class CDcSummary(C.Structure):
+    _fields_ = [("ms", C.c_float), ("n_legs", C.c_int32), ("n_pixels", C.c_int64)]
+
+
+DC_IN, DC_SURFACE, DC_OCCL, DC_INVALID = 1, 2, 4, 8  # code bits of depth_consistency(return_codes=True)
+
+
+def depth_consistency(images, pairs, c=15.0, score_thresh=0.6, device=0, return_codes=False):
+    """mpsfm_depth_consistency: both legs of every pair (a, b) in one launch sequence.
+
+    `images`: list of dicts with depth [H,W] float64 (C-contiguous; values <= 0 are set to 0.1 IN PLACE, as the reference
+    does), variance [H,W], prior_std_multiplier, intr_scaled (fx sx, fy sy, cx sx, cy sy), intr (fx fy cx cy) and
+    cam_from_world [3,4].  `pairs`: list of (a, b) indices into `images`.
+    Returns (counts int64 [n_pairs, 2, 4] = {in canvas, surface, occluded, invalid} per leg (0: a -> b, 1: b -> a),
+    summary dict[, codes: list over pairs of (codes of a [Ha,Wa], codes of b [Hb,Wb]) uint8]) ."""
+    n_img, n_pairs = len(images), len(pairs)
+    arr = (CDcImage * max(n_img, 1))()
+    keep = []
+    for k, im in enumerate(images):
+        d = im["depth"]
+        if not (isinstance(d, np.ndarray) and d.dtype == np.float64 and d.ndim == 2 and d.flags.c_contiguous and d.flags.writeable):
+            raise ValueError("depth maps must be writable C-contiguous float64 [H, W] arrays (the clamp is written back)")
+        v = np.ascontiguousarray(im["variance"], np.float64)
+        if v.shape != d.shape:
+            raise ValueError("variance and depth maps differ in shape")
+        keep.append(v)
+        e = arr[k]
+        e.H, e.W = d.shape
+        e.depth, e.variance = d.ctypes.data, v.ctypes.data
+        e.prior_std_multiplier = float(im["prior_std_multiplier"])
+        e.intr_scaled = (C.c_double * 4)(*[float(x) for x in im["intr_scaled"]])
+        e.intr = (C.c_double * 4)(*[float(x) for x in im["intr"]])
+        e.cam_from_world = (C.c_double * 12)(*[float(x) for x in np.asarray(im["cam_from_world"], np.float64).reshape(12)])
+    pa = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+    pb = np.ascontiguousarray([p[1] for p in pairs], np.int32)
+    counts = np.zeros((n_pairs, 2, 4), np.int64)
+    codes, cptr = None, None
+    if return_codes:
+        codes = []
+        for a, b in pairs:
+            sa = images[a]["depth"].shape if 0 <= a < n_img else (0, 0)
+            sb = images[b]["depth"].shape if 0 <= b < n_img else (0, 0)
+            codes.append((np.zeros(sa, np.uint8), np.zeros(sb, np.uint8)))
+        cptr = (C.c_void_p * max(2 * n_pairs, 1))(*[m.ctypes.data for cd in codes for m in cd])
+    S = CDcSummary()
+    L = lib()
+    L.mpsfm_depth_consistency.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_depth_consistency(n_img, C.addressof(arr), n_pairs, pa.ctypes.data, pb.ctypes.data, float(c),
+                                     float(score_thresh), int(device), counts.ctypes.data,
+                                     C.addressof(cptr) if cptr is not None else None, C.byref(S)))
+    summary = dict(ms=S.ms, n_legs=S.n_legs, n_pixels=S.n_pixels)
+    return (counts, summary, codes) if return_codes else (counts, summary)

@@ -1,0 +1,3 @@
+from .depthconsistency import DepthConsistencyChecker
+
+__all__ = ["DepthConsistencyChecker"]
