@@ -74,6 +74,9 @@ double* dense_pinv(double* work, int nt, const DenseOverlap* ov, const LevelPlan
 thread_local std::string g_err;
 extern int g_dbg_flags;  // dense_chol.hip: bits 0-7 dense-solve ablations, bits 8-15 track-sweep ablations
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
+// the single-launch solver's skew hook (mpsfm_debug_local_skew): process-wide like g_dbg_flags, read when a solve is launched
+static int32_t g_skew_chunk = 0, g_skew_mask = 0;
+static int64_t g_skew_ticks = 0;
 
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
@@ -1768,7 +1771,7 @@ static int build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const mpsfm_ba_s
   if ((rc = dev_alloc(&h->d_red, (size_t)h->red_count))) return rc;
   h->d_Sblk = h->d_red; h->d_gc = h->d_red + h->sblk_count; h->d_wv = h->d_gc + h->n_user; h->d_diagU = h->d_wv + h->n_user;
   h->d_redsc = h->d_diagU + h->n_user;
-  if ((rc = dev_alloc(&h->d_part, (size_t)std::max(h->nchunks + h->nlong, 1) * 4))) return rc;
+  if ((rc = dev_alloc(&h->d_part, (size_t)std::max(h->nchunks + h->nlong, 1) * 4 * 2))) return rc;  // (second half: the single launch's odd iterations)
   if ((rc = dev_alloc(&h->d_part2, (size_t)std::max(h->nchunks + h->nlong, 1) * 8))) return rc;
   if ((rc = dev_alloc(&h->d_scal, (size_t)U_COUNT))) return rc;
   if ((rc = dev_alloc(&h->d_costpart, (size_t)1024 * 4))) return rc;
@@ -1997,9 +2000,11 @@ static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
                 o.min_trust_region_radius, o.max_num_iterations, o.max_num_consecutive_invalid_steps};
   la.log = o.verbose > 0 ? h->d_local_log : nullptr;
   la.acc[0] = h->d_local_acc; la.acc[1] = h->d_local_acc + kLocalAccDoubles;
+  la.part[0] = h->d_part; la.part[1] = h->d_part + (size_t)h->nchunks * 4;  // (nlong == 0 here; the chain only ever uses the first half)
   la.bar = reinterpret_cast<int32_t*>(h->d_local_sync); la.clk = reinterpret_cast<long long*>(h->d_local_sync + 1);
   la.ncv = h->ncv; la.nc = h->nc; la.nchunks = h->nchunks;
   la.q = h->d_q; la.t = h->d_t; la.camtab = h->d_camtab; la.pts = h->d_pts; la.cs = h->d_cs; la.fixed_parts = fixed_parts;
+  la.skew_chunk = g_skew_chunk; la.skew_mask = g_skew_ticks > 0 ? g_skew_mask : 0; la.skew_ticks = g_skew_ticks;
   if (launch_local_lm(la, s) != (int)hipSuccess) {
     (void)hipGetLastError();
     HIP_TRY(hipStreamSynchronize(s));  // the pinned control block is free again
@@ -2606,12 +2611,23 @@ int mpsfm_ba_sweep_parts(mpsfm_ba_handle* h, float ms[3], int64_t info[4]) {
 
 // phase clocks of the last single-launch solve (local_lm.hip), 100 MHz ticks: sweep, barrier 1, dense + cameras, update, barrier 2,
 // decision, iterations, then (debug flag 64 << 8) inside the dense phase: assemble, stacked factorisations, their barrier, trailing
-// updates, back substitution; returns 0 when the handle does not take that path
+// updates, back substitution (none of these while mpsfm_debug_local_skew is armed: slot 11 then sums the ticks the hook waited);
+// returns 0 when the handle does not take that path
 int mpsfm_debug_local_clocks(mpsfm_ba_handle* h, int64_t out[12]) {
   if (!h || !h->local_ok) return 0;
   if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return 0;
   if (hipMemcpy(out, h->d_local_sync + 1, sizeof(int64_t) * 12, hipMemcpyDeviceToHost) != hipSuccess) return 0;
   return 1;
+}
+// test hook of the single-launch solver: in every solve launched from now on, workgroup `chunk` (negative: counted from the last;
+// reduced modulo the grid) waits `ticks` of the 100 MHz wall clock at each phase point of `phase_mask` (bits: P after barrier 0, A
+// track sweep, B after barrier 1, D update sweep, E after barrier 2); clock slot 11 of mpsfm_debug_local_clocks sums the wait.
+// (0, 0, 0): off.  At most 2 ms per point, far below the grid barrier's bounded spin.
+int mpsfm_debug_local_skew(int32_t chunk, int32_t phase_mask, int64_t ticks) {
+  if (ticks < 0 || ticks > kSkewMaxTicks) return fail(MPSFM_EINVAL, "skew ticks must lie in [0, 200000] (2 ms at 100 MHz)");
+  if (phase_mask & ~kSkewAll) return fail(MPSFM_EINVAL, "skew phase mask: bits 0-4 (P, A, B, D, E)");
+  g_skew_chunk = chunk; g_skew_mask = phase_mask; g_skew_ticks = ticks;
+  return 0;
 }
 int mpsfm_ba_dense_solve_once(mpsfm_ba_handle* h, float* elapsed_ms) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");

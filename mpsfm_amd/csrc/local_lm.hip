@@ -4,7 +4,9 @@
 // launch runs the whole trust-region loop, one workgroup per landmark chunk, two grid barriers per iteration:
 //
 //   A  track sweep of the workgroup's chunk (dense_sweep_chunk, the body of k_track_sweep_dense) at the current state; the chunk's
-//      slab is added into a dense accumulator of the reduced system (<= 96 x 96) with device-scope atomics
+//      slab is added into a dense accumulator of the reduced system (<= 96 x 96) with device-scope atomics, its partial row goes to
+//      the iteration's half of the partial rows (iterations alternate, like the accumulators: E below may still be reading the other
+//      half in a slower workgroup, and no barrier lies between that read and this write)
 //   -- grid barrier 1 --
 //   B  EVERY workgroup loads the reduced system, damps it and solves it in LDS (right-looking tile Cholesky, the stacked one-wave
 //      panel factorisation of dense_tile.h, forward substitution riding along as one more stacked row, block back substitution
@@ -80,6 +82,26 @@ __device__ __forceinline__ bool grid_barrier(int32_t* bar, LocalState& S, int nw
   }
   __syncthreads();
   return S.flag != 0;
+}
+
+// Test hook (mpsfm_debug_local_skew): the chosen workgroup waits at an armed phase point, so that the others run ahead of it as far as
+// the barriers let them.  Thread 0 polls the wall clock (and the abort flag: a barrier that gave up ends the wait), the workgroup joins
+// it at the workgroup barrier; the ticks waited add up in clock slot 11.  Off: one uniform branch.
+__device__ __forceinline__ void skew_point(const LocalArgs& G, int32_t point, int cix, int nwg) {
+  if (!(G.skew_mask & point)) return;
+  int c = G.skew_chunk % nwg;
+  if (c < 0) c += nwg;
+  if (cix != c) return;
+  if (threadIdx.x == 0) {
+    const long long t0 = wall_clock64();
+    long long t = t0;
+    while (t - t0 < G.skew_ticks && __hip_atomic_load(&G.bar[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+      __builtin_amdgcn_s_sleep(8);
+      t = wall_clock64();
+    }
+    G.clk[11] += t - t0;
+  }
+  __syncthreads();
 }
 
 __device__ __forceinline__ double* tile_at(DenseSolveLds& D, int i, int j) { return D.T[i * (i + 1) / 2 + j]; }
@@ -308,6 +330,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_local_lm(LocalArgs G) {
     if (tid == 0) A.part2[(size_t)cix * 8 + 5] = (S.red[0] + S.red[1]) + (S.red[2] + S.red[3]);
   }
   if (!grid_barrier(G.bar, S, nwg)) return;
+  skew_point(G, kSkewP, cix, nwg);
   {
     double v = 0.0;
     for (int r = tid; r < G.nchunks; r += kThreads) v += A.part2[(size_t)r * 8 + 5];
@@ -329,13 +352,15 @@ __global__ __launch_bounds__(kThreads, 1) void k_local_lm(LocalArgs G) {
     if (S.L.term != kLmRunning) break;  // (workgroup-uniform: every thread reads the same LDS word behind a barrier)
     const int par = it & 1;
     double* acc = G.acc[par];
+    double* part = G.part[par];
     const double lm_radius = S.L.radius;
+    skew_point(G, kSkewA, cix, nwg);
     if (writer && tid == 0) tk0 = wall_clock64();
     long long tka = 0;
     if ((A.dbg & 64) && tid == 0) tka = wall_clock64();
 
     // ---- A: track sweep of the chunk, slab into the accumulator ---------------------------------------------------------------------
-    dense_sweep_chunk<true>(A, cix, lm_radius, S.tab, U.sweep);
+    dense_sweep_chunk<true>(A, cix, lm_radius, S.tab, U.sweep, part);
     __syncthreads();  // the slab's stores (this workgroup's own) are visible to all its threads
     {
       const double* slab = A.slab + (size_t)H.slab0 * 18;
@@ -359,13 +384,15 @@ __global__ __launch_bounds__(kThreads, 1) void k_local_lm(LocalArgs G) {
     }
     long long tkb = 0;
     if (writer && tid == 0) tkb = wall_clock64();
-    if ((A.dbg & 64) && tid == 0) A.part[(size_t)cix * 4 + 3] = (double)(wall_clock64() - tka);  // this chunk's sweep + flush (diagnostics)
+    if ((A.dbg & 64) && tid == 0) part[(size_t)cix * 4 + 3] = (double)(wall_clock64() - tka);  // this chunk's sweep + flush (diagnostics)
     if (!grid_barrier(G.bar, S, nwg)) return;
     long long tk1 = 0;
     if (writer && tid == 0) tk1 = wall_clock64();
 
     // ---- B: the reduced system, every workgroup for itself ------------------------------------------------------------------------------
-    local_dense_solve(S, U.dense, acc, n, lm_radius, A.min_diag, A.max_diag, (writer && tid == 0 && (A.dbg & 64)) ? G.clk : nullptr);
+    skew_point(G, kSkewB, cix, nwg);
+    local_dense_solve(S, U.dense, acc, n, lm_radius, A.min_diag, A.max_diag,
+                      (writer && tid == 0 && (A.dbg & 64) && G.skew_mask == 0) ? G.clk : nullptr);  // (slot 11: the skew hook's)
 
     // ---- C: candidate cameras (camera_candidate: k_cam_update's arithmetic), one thread per variable camera ---------------------------------------------
     if (tid < ncv) {
@@ -387,6 +414,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_local_lm(LocalArgs G) {
     if (writer && tid == 0) tk2 = wall_clock64();
 
     // ---- D: update sweep of the chunk; the other accumulator starts the next iteration from zero --------------------------------------
+    skew_point(G, kSkewD, cix, nwg);
     update_sweep_chunk<true>(A, cix, lm_radius, S.tab, S.tab2, S.y, U.upd, CamUpdArgs{}, false);
     {
       double* other = G.acc[par ^ 1];
@@ -397,6 +425,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_local_lm(LocalArgs G) {
     if (!grid_barrier(G.bar, S, nwg)) return;
     long long tkd = 0;
     if (writer && tid == 0) tkd = wall_clock64();
+    skew_point(G, kSkewE, cix, nwg);
 
     // ---- E: the iteration's scalars (k_lm_reduce_decide's order) and the decision, the same in every workgroup -----------------------
     {
@@ -405,7 +434,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_local_lm(LocalArgs G) {
       // wave adds them, eight lanes per column, in a fixed order: cheaper than eight wave reductions
       double* rows = reinterpret_cast<double*>(&U);
       for (int r = tid; r < G.nchunks; r += kThreads) {
-        const double* a = A.part + (size_t)r * 4;
+        const double* a = part + (size_t)r * 4;
         const double* b = A.part2 + (size_t)r * 8;
         const double a0 = a[0], a1 = a[1], a2 = a[2], b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3], b4 = b[4];
         double* o = rows + (size_t)r * 8;

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_track_sweep_dense(SweepArgs A) 
   // One workgroup per chunk.  Persistent workgroups (3 per CU taking chunks from a cost-sorted list through a shared counter) were
   // measured and dropped: the slots stay full, but every chunk then takes longer (wave life 21.5 -> 24.7 us at C3: the sweep is
   // bound by the CU's shared pipes, not by the 22 % of slot time the dispatcher leaves empty) — 0.118 against 0.111 ms.
-  dense_sweep_chunk<false>(A, blockIdx.x + A.chunk0, lm_radius, nullptr, S);
+  dense_sweep_chunk<false>(A, blockIdx.x + A.chunk0, lm_radius, nullptr, S, A.part);
 }
 
 // One wave per destination part: sums the part's slab sources in table order and adds the sum into the (zeroed) reduced buffer.

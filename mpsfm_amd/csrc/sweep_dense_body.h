@@ -239,9 +239,10 @@ struct __attribute__((aligned(16))) DenseLds {
 static_assert(kObsMax <= 254, "record indices in DenseLds::rec are 8 bits, 255 marks an empty cell");
 static_assert(sizeof(DenseLds) <= 54608, "three workgroups per CU need at most 160 KiB / 3 of LDS each");
 
-// The sweep of chunk `cix` by one workgroup of kThreads threads: slab and partial row written, see sweep_dense.hip.
+// The sweep of chunk `cix` by one workgroup of kThreads threads: slab and partial row (of `part`: A.part, or the single-launch
+// solver's half of the iteration's parity) written, see sweep_dense.hip.
 template <bool kLocal>
-__device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, double lm_radius, const double* l_tab, DenseLds& S) {
+__device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, double lm_radius, const double* l_tab, DenseLds& S, double* part) {
   const int tid = thread_index<kLocal>();
   // timing trace (dbg flag 128, scripts/dbg_sweep_trace.py): lane 0 of every wave stamps the shader clock at the phase boundaries
   // into diagV, which only the Jacobi-scaling pass uses (16 slots x 4 waves per chunk)
@@ -457,7 +458,7 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
     MPSFM_STAMP(9);
     if (trace) trace[13] = (long long)wall_clock64();
     if (tid == 0) {
-      double* p = A.part + (size_t)cix * 4;
+      double* p = part + (size_t)cix * 4;
       p[0] = (S.red[0] + S.red[1]) + (S.red[2] + S.red[3]);
       p[1] = (S.red[4] + S.red[5]) + (S.red[6] + S.red[7]);
       p[2] = fmax(fmax(S.red[8], S.red[9]), fmax(S.red[10], S.red[11]));

@@ -1,10 +1,11 @@
-"""Resident solve of small (local-BA sized) problems: per-iteration split."""
+"""Resident solve of small (local-BA sized) problems: per-iteration split.  Arguments: shapes as CAMS/POINTS (default: the list below)."""
 import sys
 sys.path.insert(0, '.')
 import numpy as np
 from mpsfm_amd import capi
 from mpsfm_amd.synthetic import make_scene
-for ncam, npts in ((6, 1500), (7, 1800), (10, 3000), (12, 4000), (24, 10000)):
+shapes = [tuple(int(x) for x in a.split("/")) for a in sys.argv[1:]] or [(6, 1500), (7, 1800), (10, 3000), (12, 4000), (24, 10000)]
+for ncam, npts in shapes:
     prob, _ = make_scene(ncam, npts, True, seed=3)
     h = capi.BAHandle(prob)
     for _ in range(3):

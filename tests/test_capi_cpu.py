@@ -160,3 +160,22 @@ def test_non_pinhole_camera_models_are_refused():
     for name in ("SIMPLE_RADIAL", "OPENCV"):
         with pytest.raises(NotImplementedError):
             pinhole_params(types.SimpleNamespace(params=np.zeros(8), model=types.SimpleNamespace(name=name)))
+
+
+def test_local_skew_hook_checks_its_arguments():
+    """The single-launch solver's test hook (mpsfm_debug_local_skew): at most 2 ms per phase point, five phase bits; (0, 0, 0) is off."""
+    import ctypes as C
+
+    L = capi.lib()
+    L.mpsfm_debug_local_skew.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+    L.mpsfm_debug_local_skew.restype = C.c_int
+    try:
+        assert L.mpsfm_debug_local_skew(0, 16, 200001) == -1  # MPSFM_EINVAL
+        assert b"200000" in L.mpsfm_last_error()
+        assert L.mpsfm_debug_local_skew(0, 16, -1) == -1
+        assert L.mpsfm_debug_local_skew(0, 32, 1000) == -1
+        assert L.mpsfm_debug_local_skew(0, -1, 1000) == -1
+        assert L.mpsfm_debug_local_skew(-1, 31, 200000) == 0
+        assert L.mpsfm_debug_local_skew(7, 16, 0) == 0
+    finally:
+        assert L.mpsfm_debug_local_skew(0, 0, 0) == 0
