@@ -461,6 +461,58 @@ int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images /* [n_image
                             uint8_t* const* codes /* [2 n_pairs] pointers to Hs*Ws, or NULL */,
                             mpsfm_dc_summary* summary /* may be NULL */);
 
+/* ---- absolute pose: LO-RANSAC with P3P samples and EPnP local optimisation on one 2D-3D problem (reference
+ *    mpsfm/sfm/estimators/absolute_pose.py:6-25 -> pycolmap.estimate_and_refine_absolute_pose, estimation half;
+ *    call sites mpsfm/sfm/mapper/registration.py:169, :232, :263, base.py:329-336).  COLMAP 3.11
+ *    EstimateAbsolutePose (LORANSAC<P3PEstimator, EPNPEstimator, InlierSupportMeasurer>) restated from the upstream
+ *    sources as recalled; the reference's COLMAP fork is not in its tree: parity unpinned.
+ *    Points go through CamFromImg ((x - cx) / fx, (y - cy) / fy); the threshold is max_error / ((fx + fy) / 2).  Residual:
+ *    squared reprojection error in the normalised plane, DBL_MAX at camera depth <= DBL_EPSILON; inlier: residual <=
+ *    threshold^2.  Support: more inliers, then the smaller inlier residual sum.  max_num_trials is first capped by
+ *    ComputeNumTrials(floor(min_inlier_ratio 1e5), 1e5, confidence, multiplier); after each new best model the dynamic
+ *    bound is ComputeNumTrials(best inliers, N, ...) = ceil(log(1 - confidence) / log(1 - (k / N)^3) multiplier).  A sample
+ *    model that becomes the best with >= 4 inliers starts up to 10 EPnP rounds on the current inlier set, continued while the
+ *    inlier count grows.  P3P: Grunert's quartic, roots with |imag| <= 1e-10, negative lengths rejected, pose by Horn's
+ *    closed-form absolute orientation; a sample whose three world points are collinear (sin^2 of the angle at the first
+ *    point <= 1e-20) gives no model (upstream would return an arbitrary rotation about the line).
+ *    SAMPLER (deliberate deviation from COLMAP's RandomSampler): counter-based, trial t draws from (seed, t) alone.  With
+ *    mix(z) = z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31 (splitmix64's
+ *    finaliser), PHI = 0x9E3779B97F4A7C15 and all arithmetic mod 2^64:
+ *        base = mix(seed + (t + 1) PHI);  draw j = 1, 2, ...: r_j = mix(base + j PHI), index = floor(r_j N / 2^64)
+ *    the first three distinct indices, in draw order, are the sample (a repeated index is drawn again).
+ *    Sample models do not depend on the loop state, so trials are generated and scored in batches of batch_trials
+ *    (0: default) and the host replays the sequential loop over the scored table; trials past the stop inside the last
+ *    batch are wasted work, not a different result.  Scoring sums are fixed-order: results are identical run to run.
+ *    inlier_mask[i] = 1 for the inliers of the final model.  N < 3, N > INT32_MAX, NULL pointers, non-finite inputs and
+ *    invalid options are MPSFM_EINVAL before any HIP call.  No model: result->success = 0 and return value 0. ---- */
+typedef struct mpsfm_abs_pose_options {
+  double max_error;                  /* pixels (12.0) */
+  double min_inlier_ratio;           /* 0.25 in the reference (pycolmap default 0.1) */
+  double confidence;                 /* 0.99999 */
+  double dyn_num_trials_multiplier;  /* 3.0 */
+  int64_t min_num_trials;            /* 100 */
+  int64_t max_num_trials;            /* 10000 */
+  uint64_t seed;                     /* sampler seed (see above) */
+  int32_t batch_trials;              /* trials per generated / scored batch; 0: default */
+  int32_t pad;
+} mpsfm_abs_pose_options;
+
+typedef struct mpsfm_abs_pose_result {
+  double cam_from_world[12];  /* [3][4] row-major, the RANSAC model (sample or local) */
+  int64_t num_inliers;
+  int64_t num_trials;         /* LORANSAC's report.num_trials */
+  int64_t max_num_trials;     /* after the min_inlier_ratio cap */
+  int64_t num_models;         /* P3P models scored (all batches, wasted ones included) */
+  int32_t success;
+  int32_t lo_rounds;          /* EPnP local estimates run */
+  int32_t num_batches;
+  float ms;                   /* device time of the launches (HIP events), transfers and host work excluded */
+} mpsfm_abs_pose_result;
+
+int mpsfm_abs_pose_estimate(int64_t n, const double* points2D /* [n][2] pixels */, const double* points3D /* [n][3] */,
+                            const double* intr /* PINHOLE fx fy cx cy */, const mpsfm_abs_pose_options* options,
+                            int32_t device, uint8_t* inlier_mask /* [n] */, mpsfm_abs_pose_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ EXPORTS = [
     "mpsfm_ba_get_dense_solution", "mpsfm_ba_dense_solve_once", "mpsfm_ba_dense_plan", "mpsfm_point_covs",
     "mpsfm_triangulate_tracks", "mpsfm_filter_tracks", "mpsfm_integrate_depth", "mpsfm_integrate_depth_batch",
     "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
+    "mpsfm_abs_pose_estimate",
 ]
 
 _lib = None
@@ -518,3 +519,46 @@ def depth_consistency(images, pairs, c=15.0, score_thresh=0.6, device=0, return_
                                      C.addressof(cptr) if cptr is not None else None, C.byref(S)))
     summary = dict(ms=S.ms, n_legs=S.n_legs, n_pixels=S.n_pixels)
     return (counts, summary, codes) if return_codes else (counts, summary)
+
+
+class CAbsPoseOptions(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
+                ("dyn_num_trials_multiplier", C.c_double), ("min_num_trials", C.c_int64), ("max_num_trials", C.c_int64),
+                ("seed", C.c_uint64), ("batch_trials", C.c_int32), ("pad", C.c_int32)]
+
+
+class CAbsPoseResult(C.Structure):
+    _fields_ = [("cam_from_world", C.c_double * 12), ("num_inliers", C.c_int64), ("num_trials", C.c_int64), ("max_num_trials", C.c_int64),
+                ("num_models", C.c_int64), ("success", C.c_int32), ("lo_rounds", C.c_int32), ("num_batches", C.c_int32), ("ms", C.c_float)]
+
+
+ABS_POSE_DEFAULTS = dict(max_error=12.0, min_inlier_ratio=0.25, confidence=0.99999, dyn_num_trials_multiplier=3.0, min_num_trials=100,
+                         max_num_trials=10000, seed=0, batch_trials=0)
+
+
+def abs_pose_estimate(points2D, points3D, intr, device=0, **options) -> dict:
+    """mpsfm_abs_pose_estimate: LO-RANSAC (P3P + EPnP) of one 2D-3D problem with PINHOLE intr = (fx, fy, cx, cy).
+    `options`: keys of ABS_POSE_DEFAULTS.  Returns dict(success, cam_from_world [3,4], num_inliers, inlier_mask bool [n],
+    num_trials, max_num_trials, num_models, lo_rounds, num_batches, ms)."""
+    o = dict(ABS_POSE_DEFAULTS)
+    unknown = set(options) - set(o)
+    if unknown:
+        raise KeyError(f"unknown option(s) {sorted(unknown)}")
+    o.update(options)
+    p2 = np.ascontiguousarray(points2D, np.float64).reshape(-1, 2)
+    p3 = np.ascontiguousarray(points3D, np.float64).reshape(-1, 3)
+    if len(p2) != len(p3):
+        raise ValueError("points2D and points3D differ in length")
+    K = np.ascontiguousarray(intr, np.float64).reshape(4)
+    n = len(p2)
+    opt = CAbsPoseOptions(float(o["max_error"]), float(o["min_inlier_ratio"]), float(o["confidence"]), float(o["dyn_num_trials_multiplier"]),
+                          int(o["min_num_trials"]), int(o["max_num_trials"]), int(o["seed"]) & ((1 << 64) - 1), int(o["batch_trials"]), 0)
+    mask = np.zeros(max(n, 1), np.uint8)
+    R = CAbsPoseResult()
+    L = lib()
+    L.mpsfm_abs_pose_estimate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_abs_pose_estimate(n, p2.ctypes.data, p3.ctypes.data, K.ctypes.data, C.byref(opt), int(device), mask.ctypes.data,
+                                     C.byref(R)))
+    return dict(success=bool(R.success), cam_from_world=np.array(R.cam_from_world[:]).reshape(3, 4), num_inliers=int(R.num_inliers),
+                inlier_mask=mask[:n].astype(bool), num_trials=int(R.num_trials), max_num_trials=int(R.max_num_trials),
+                num_models=int(R.num_models), lo_rounds=int(R.lo_rounds), num_batches=int(R.num_batches), ms=float(R.ms))
