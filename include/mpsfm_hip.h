@@ -513,6 +513,60 @@ int mpsfm_abs_pose_estimate(int64_t n, const double* points2D /* [n][2] pixels *
                             const double* intr /* PINHOLE fx fy cx cy */, const mpsfm_abs_pose_options* options,
                             int32_t device, uint8_t* inlier_mask /* [n] */, mpsfm_abs_pose_result* result);
 
+/* ---- relative pose: LO-RANSAC with five-point samples and five-point local optimisation on one two-view problem, then the
+ *    pose of the best essential matrix (reference mpsfm/sfm/estimators/relative_pose.py:7-17 ->
+ *    pycolmap.essential_matrix_estimation; call sites mpsfm/sfm/mapper/registration.py:247-248, base.py:259-260).  COLMAP 3.11
+ *    EstimateEssentialMatrix (LORANSAC<EssentialMatrixFivePointEstimator x2, InlierSupportMeasurer>) and
+ *    PoseFromEssentialMatrix restated as recalled; parity with the reference's COLMAP fork unpinned.
+ *    Points go through CamFromImg of their camera; the threshold is 0.5 (max_error / f1 + max_error / f2) with f = (fx + fy) / 2.
+ *    Residual: squared Sampson error of x2^T E x1 in normalised coordinates; inlier: residual <= threshold^2.  Support,
+ *    min_inlier_ratio cap, dynamic bound and stop test as in mpsfm_abs_pose_estimate with sample size 5 (exponent 5).  A
+ *    sample model that becomes the best with more than 5 inliers starts up to 10 rounds of the non-minimal five-point
+ *    estimator on the current inlier set, continued while the inlier count grows.
+ *    Five-point solver: the 4-D nullspace of Q (minimal: Householder QR of the 5 x 9 Q; non-minimal: the eigenvectors of the
+ *    4 smallest eigenvalues of Q^T Q, reduced on the device in a fixed order, where upstream takes an SVD of Q), the 10 x 20
+ *    cubic constraints, Gauss-Jordan, the degree-10 determinant of B(z), real roots (|imag| <= 1e-10 (1 + |z|)), three
+ *    Gauss-Newton steps of each root on the ten constraints.  A sample whose Q has rank < 5 gives no model.  Each E is
+ *    scaled to unit Frobenius norm with its largest-magnitude entry positive (the first in row-major order on ties), and the
+ *    models of a trial are ordered lexicographically by their row-major entries: choices of ours that make the result
+ *    independent of the nullspace basis and the root-finding route.
+ *    Sampler: the counter recipe of mpsfm_abs_pose_estimate, the first FIVE distinct indices.
+ *    Pose: E = U diag(s) V^T with det U = det V = +1 (third columns flipped), t = U[:, 2] with its largest-magnitude
+ *    component positive (ours: fixes the candidate order), R1 = U W V^T, R2 = U W^T V^T, W = [[0,1,0],[-1,0,0],[0,0,1]];
+ *    candidates (R1, t), (R2, t), (R1, -t), (R2, -t); every inlier triangulated by two-view DLT, counted when both depths
+ *    (third coordinate in each camera) lie in (DBL_EPSILON, 1000 |t|); the most points win, the later candidate on a tie.
+ *    inlier_mask = RANSAC's mask of the best E.  Argument checks as mpsfm_abs_pose_estimate (N < 5 ...), before any HIP call.
+ *    No model: result->success = 0 and return value 0. ---- */
+typedef struct mpsfm_rel_pose_options {
+  double max_error;                  /* pixels (pycolmap RANSACOptions: 4.0) */
+  double min_inlier_ratio;           /* 0.01 */
+  double confidence;                 /* 0.9999 */
+  double dyn_num_trials_multiplier;  /* 3.0 */
+  int64_t min_num_trials;            /* 1000 */
+  int64_t max_num_trials;            /* 100000 */
+  uint64_t seed;                     /* sampler seed */
+  int32_t batch_trials;              /* trials per generated / scored batch; 0: default */
+  int32_t reserved;
+} mpsfm_rel_pose_options;
+
+typedef struct mpsfm_rel_pose_result {
+  double E[9];                   /* row-major, canonical form */
+  double cam2_from_cam1[12];     /* [3][4] row-major, |t| = 1 */
+  int64_t num_inliers;
+  int64_t num_trials;            /* LORANSAC's report.num_trials */
+  int64_t max_num_trials;        /* after the min_inlier_ratio cap */
+  int64_t num_models;            /* model slots scored (all batches, 10 per trial) */
+  int64_t lo_rounds;             /* local estimates run */
+  int64_t num_batches;
+  int64_t num_cheirality_points; /* inliers in front of both cameras for the chosen pose */
+  int32_t success;
+  float ms;                      /* device time of the launches (HIP events), transfers and host work excluded */
+} mpsfm_rel_pose_result;
+
+int mpsfm_rel_pose_estimate(int64_t n, const double* points1 /* [n][2] pixels */, const double* points2 /* [n][2] pixels */,
+                            const double* intr1, const double* intr2 /* PINHOLE fx fy cx cy */, const mpsfm_rel_pose_options* options,
+                            int32_t device, uint8_t* inlier_mask /* [n] */, mpsfm_rel_pose_result* result);
+
 #ifdef __cplusplus
 }
 #endif

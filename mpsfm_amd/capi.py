@@ -24,7 +24,7 @@ EXPORTS = [
     "mpsfm_ba_get_dense_solution", "mpsfm_ba_dense_solve_once", "mpsfm_ba_dense_plan", "mpsfm_point_covs",
     "mpsfm_triangulate_tracks", "mpsfm_filter_tracks", "mpsfm_integrate_depth", "mpsfm_integrate_depth_batch",
     "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
-    "mpsfm_abs_pose_estimate",
+    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate",
 ]
 
 _lib = None
@@ -562,3 +562,51 @@ def abs_pose_estimate(points2D, points3D, intr, device=0, **options) -> dict:
     return dict(success=bool(R.success), cam_from_world=np.array(R.cam_from_world[:]).reshape(3, 4), num_inliers=int(R.num_inliers),
                 inlier_mask=mask[:n].astype(bool), num_trials=int(R.num_trials), max_num_trials=int(R.max_num_trials),
                 num_models=int(R.num_models), lo_rounds=int(R.lo_rounds), num_batches=int(R.num_batches), ms=float(R.ms))
+
+
+class CRelPoseOptions(C.Structure):
+    _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
+                ("dyn_num_trials_multiplier", C.c_double), ("min_num_trials", C.c_int64), ("max_num_trials", C.c_int64),
+                ("seed", C.c_uint64), ("batch_trials", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CRelPoseResult(C.Structure):
+    _fields_ = [("E", C.c_double * 9), ("cam2_from_cam1", C.c_double * 12), ("num_inliers", C.c_int64), ("num_trials", C.c_int64),
+                ("max_num_trials", C.c_int64), ("num_models", C.c_int64), ("lo_rounds", C.c_int64), ("num_batches", C.c_int64),
+                ("num_cheirality_points", C.c_int64), ("success", C.c_int32), ("ms", C.c_float)]
+
+
+# pycolmap 3.11 RANSACOptions() as recalled
+REL_POSE_DEFAULTS = dict(max_error=4.0, min_inlier_ratio=0.01, confidence=0.9999, dyn_num_trials_multiplier=3.0, min_num_trials=1000,
+                         max_num_trials=100000, seed=0, batch_trials=0)
+
+
+def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> dict:
+    """mpsfm_rel_pose_estimate: LO-RANSAC (five-point) of one two-view problem with PINHOLE intr = (fx, fy, cx, cy), then the
+    pose.  `options`: keys of REL_POSE_DEFAULTS.  Returns dict(success, E [3,3], cam2_from_cam1 [3,4], num_inliers,
+    inlier_mask bool [n], num_trials, max_num_trials, num_models, lo_rounds, num_batches, num_cheirality_points, ms)."""
+    o = dict(REL_POSE_DEFAULTS)
+    unknown = set(options) - set(o)
+    if unknown:
+        raise KeyError(f"unknown option(s) {sorted(unknown)}")
+    o.update(options)
+    p1 = np.ascontiguousarray(points1, np.float64).reshape(-1, 2)
+    p2 = np.ascontiguousarray(points2, np.float64).reshape(-1, 2)
+    if len(p1) != len(p2):
+        raise ValueError("points1 and points2 differ in length")
+    K1 = np.ascontiguousarray(intr1, np.float64).reshape(4)
+    K2 = np.ascontiguousarray(intr2, np.float64).reshape(4)
+    n = len(p1)
+    opt = CRelPoseOptions(float(o["max_error"]), float(o["min_inlier_ratio"]), float(o["confidence"]), float(o["dyn_num_trials_multiplier"]),
+                          int(o["min_num_trials"]), int(o["max_num_trials"]), int(o["seed"]) & ((1 << 64) - 1), int(o["batch_trials"]), 0)
+    mask = np.zeros(max(n, 1), np.uint8)
+    R = CRelPoseResult()
+    L = lib()
+    L.mpsfm_rel_pose_estimate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p]
+    _check(L.mpsfm_rel_pose_estimate(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, C.byref(opt), int(device),
+                                     mask.ctypes.data, C.byref(R)))
+    return dict(success=bool(R.success), E=np.array(R.E[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4),
+                num_inliers=int(R.num_inliers), inlier_mask=mask[:n].astype(bool), num_trials=int(R.num_trials),
+                max_num_trials=int(R.max_num_trials), num_models=int(R.num_models), lo_rounds=int(R.lo_rounds),
+                num_batches=int(R.num_batches), num_cheirality_points=int(R.num_cheirality_points), ms=float(R.ms))

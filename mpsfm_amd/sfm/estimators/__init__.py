@@ -1,3 +1,4 @@
 from .absolute_pose import AbsolutePose
+from .relative_pose import RelativePose
 
-__all__ = ["AbsolutePose"]
+__all__ = ["AbsolutePose", "RelativePose"]
