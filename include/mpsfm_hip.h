@@ -567,6 +567,95 @@ int mpsfm_rel_pose_estimate(int64_t n, const double* points1 /* [n][2] pixels */
                             const double* intr1, const double* intr2 /* PINHOLE fx fy cx cy */, const mpsfm_rel_pose_options* options,
                             int32_t device, uint8_t* inlier_mask /* [n] */, mpsfm_rel_pose_result* result);
 
+/* ---- registration: the per-match arithmetic of MpsfmRegistration (reference mpsfm/sfm/mapper/registration.py).
+ *
+ *    mpsfm_registration_pairs: the 2D-3D pairs of one register_next_image for ALL reference images in one launch
+ *    (:68-94 _find_2D3D_pairs, :341-373 _collect_pairs, :375-382 _lift_points_to_3d).  Per match i with reference image
+ *    r = match_ref[i], reference keypoint ref_xy[i] and point index p = match_pt[i] (-1: the keypoint has no 3-D point):
+ *      p >= 0 and not pt_risky[p]      xyz = pts[p]                                              kind TRIANGULATED
+ *      else, lifted_registration != 0  d = bilinear sample of refs[r].depth_map at ref_xy[i] (PriorUtils._data_at_kps:
+ *                                      grid_sample, bilinear, zero padding, align_corners=True, keypoint scaled by sx, sy;
+ *                                      no validity and no d > 0 test, as the reference),
+ *                                      xyz = R_r^T ([(x - cx) / fx, (y - cy) / fy, 1] d - t_r)   kind LIFTED
+ *      else                            xyz = 0                                                   kind DROPPED
+ *    Every product and sum of the sample and of the lift is rounded on its own (no fused multiply-add): the sample equals
+ *    the NumPy restatement bit for bit.
+ *
+ *    mpsfm_init_pair_candidates: the candidate points of an init pair, image 1 at the identity and image 2 at
+ *    cam2_from_cam1 (:38-66 _candidate_points3D_for_init, :384-391 _lift_points_for_init, :419-441
+ *    _candidate_lift_for_init).  Per match i that `select` keeps (NULL: all), as `what` asks:
+ *      MPSFM_INIT_TRIANGULATE  the two-view EstimateTriangulation (COLMAP 3.11 as recalled: LORANSAC over
+ *                              TriangulationEstimator with the angular residual) with the device functions of
+ *                              mpsfm_tri_estimate_batch: ok and xyz equal that entry point's on the same candidate bit for
+ *                              bit (xyz = 0 where not ok);
+ *      MPSFM_INIT_LIFT         d = bilinear sample of prior_map (depth.data_prior) at xy1, valid <=> the bilinear sample of
+ *                              valid_map there == 1 exactly, xyz = [(x - cx) / fx, (y - cy) / fy, 1] (d rescale);
+ *      for each candidate      the reference's calculate_triangulation_angle in degrees and has_point_positive_depth
+ *                              (depth >= 2^-52) in both cameras.
+ *    THE ANGLE IS THE REFERENCE'S, NOT THE GEOMETRIC ONE (mpsfm/utils/geometry.py:54-65 takes norms where its variable
+ *    names say squared norms): with b = |C1 - C2|, r1 = |X - C1|, r2 = |X - C2| (plain lengths) it is
+ *    a = acos((r1 + r2 - b) / (2 sqrt(r1 r2))), folded as min(a, pi - a), 0 when the denominator is 0, NaN where acos
+ *    gives NaN (Python's min(nan, x) is nan).  The reference's thresholds act on this value.
+ *    Matches that `select` drops, and the kinds `what` does not ask for, get zeros.
+ *
+ *    Both: caller owns all buffers, nothing is retained; MPSFM_EINVAL for NULL pointers, negative counts, match_ref or
+ *    match_pt out of range and maps smaller than 2 x 2, checked on the host before anything is launched;
+ *    MPSFM_ENODEVICE without a device.  *ms (may be NULL): device time of the launch (HIP events), transfers excluded. ---- */
+enum { MPSFM_REG_DROPPED = 0, MPSFM_REG_TRIANGULATED = 1, MPSFM_REG_LIFTED = 2 };
+
+typedef struct mpsfm_reg_image {
+  int32_t map_h, map_w;
+  const double* depth_map;  /* depth.data, [map_h][map_w] */
+  double sx, sy;            /* camera.sx, camera.sy: keypoint -> map coordinates */
+  double intr[4];           /* PINHOLE fx fy cx cy */
+  double quat_xyzw[4];      /* cam_from_world rotation */
+  double t[3];              /* cam_from_world translation */
+} mpsfm_reg_image;
+
+int mpsfm_registration_pairs(int32_t n_refs, const mpsfm_reg_image* refs /* [n_refs] */, int64_t n_matches,
+                             const int32_t* match_ref /* [n] index into refs */, const double* ref_xy /* [n][2] */,
+                             const int32_t* match_pt /* [n] index into pts or -1 */,
+                             const uint8_t* pt_risky /* [n_pts] or NULL: none */, int32_t n_pts, const double* pts /* [n_pts][3] */,
+                             int32_t lifted_registration, int32_t device, double* xyz /* [n][3] */,
+                             uint8_t* kind /* [n] MPSFM_REG_* */, float* ms /* may be NULL */);
+
+enum { MPSFM_INIT_TRIANGULATE = 1, MPSFM_INIT_LIFT = 2 };
+/* bits of mpsfm_init_candidates.flags */
+enum {
+  MPSFM_INIT_TRI_OK = 1, MPSFM_INIT_TRI_POSDEPTH1 = 2, MPSFM_INIT_TRI_POSDEPTH2 = 4,
+  MPSFM_INIT_VALID = 8, MPSFM_INIT_LIFT_POSDEPTH1 = 16, MPSFM_INIT_LIFT_POSDEPTH2 = 32
+};
+
+typedef struct mpsfm_init_pair {
+  int64_t n_matches;
+  const double* xy1;          /* [n][2] keypoints of image 1 */
+  const double* xy2;          /* [n][2] keypoints of image 2 */
+  const uint8_t* select;      /* [n] or NULL: 0 = skip this match */
+  double intr1[4], intr2[4];  /* PINHOLE fx fy cx cy */
+  double cam2_from_cam1[12];  /* [3][4] row-major */
+  int32_t map_h, map_w;
+  const double* prior_map;    /* depth.data_prior of image 1, [map_h][map_w] (MPSFM_INIT_LIFT) */
+  const uint8_t* valid_map;   /* depth.valid of image 1 as 0 / 1 bytes (MPSFM_INIT_LIFT) */
+  double sx, sy;              /* camera1.sx, camera1.sy */
+  double rescale;             /* factor on the sampled prior depth (1: none) */
+  double tri_min_angle;       /* radians; EstimateTriangulationOptions default 0 */
+  double tri_max_error;       /* radians; default 2 degrees */
+  int32_t what;               /* MPSFM_INIT_TRIANGULATE | MPSFM_INIT_LIFT */
+  int32_t reserved;
+} mpsfm_init_pair;
+
+typedef struct mpsfm_init_candidates {
+  uint8_t* flags;          /* [n] MPSFM_INIT_* bits */
+  double* tri_xyz;         /* [n][3] */
+  double* tri_angle_deg;   /* [n]    */
+  double* lift_xyz;        /* [n][3] */
+  double* lift_angle_deg;  /* [n]    */
+  double* d_prior;         /* [n] the sampled prior depth, before rescale */
+  float ms;                /* out: device time of the launch */
+} mpsfm_init_candidates;
+
+int mpsfm_init_pair_candidates(const mpsfm_init_pair* pair, int32_t device, mpsfm_init_candidates* out);
+
 #ifdef __cplusplus
 }
 #endif

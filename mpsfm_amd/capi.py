@@ -24,7 +24,7 @@ EXPORTS = [
     "mpsfm_ba_get_dense_solution", "mpsfm_ba_dense_solve_once", "mpsfm_ba_dense_plan", "mpsfm_point_covs",
     "mpsfm_triangulate_tracks", "mpsfm_filter_tracks", "mpsfm_integrate_depth", "mpsfm_integrate_depth_batch",
     "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
-    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate",
+    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
 ]
 
 _lib = None
@@ -610,3 +610,129 @@ def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> di
                 num_inliers=int(R.num_inliers), inlier_mask=mask[:n].astype(bool), num_trials=int(R.num_trials),
                 max_num_trials=int(R.max_num_trials), num_models=int(R.num_models), lo_rounds=int(R.lo_rounds),
                 num_batches=int(R.num_batches), num_cheirality_points=int(R.num_cheirality_points), ms=float(R.ms))
+
+
+class CRegImage(C.Structure):
+    _fields_ = [("map_h", C.c_int32), ("map_w", C.c_int32), ("depth_map", C.c_void_p), ("sx", C.c_double), ("sy", C.c_double),
+                ("intr", C.c_double * 4), ("quat_xyzw", C.c_double * 4), ("t", C.c_double * 3)]
+
+
+REG_DROPPED, REG_TRIANGULATED, REG_LIFTED = 0, 1, 2  # `kind` of registration_pairs
+
+
+def registration_pairs(refs, match_ref, ref_xy, match_pt, pts, pt_risky=None, lifted_registration=True, device=0, return_ms=False):
+    """mpsfm_registration_pairs: the 2D-3D pairs of one registration for all reference images in one launch.
+
+    `refs`: list of dicts with depth_map [H,W] (depth.data; may be None when lifted_registration is off), sx, sy,
+    intr (fx fy cx cy), quat_xyzw and t of cam_from_world.  Per match: `match_ref` index into refs, `ref_xy` keypoint of the
+    reference image, `match_pt` index into `pts` [n_pts,3] or -1; `pt_risky` bool [n_pts] or None.
+    Returns (xyz [n,3], kind uint8 [n] in REG_*)[, device ms]."""
+    match_ref = np.ascontiguousarray(match_ref, np.int32).reshape(-1)
+    match_pt = np.ascontiguousarray(match_pt, np.int32).reshape(-1)
+    ref_xy = np.ascontiguousarray(ref_xy, np.float64).reshape(-1, 2)
+    pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+    n, n_pts, n_refs = len(match_ref), len(pts), len(refs)
+    if not (len(ref_xy) == len(match_pt) == n):
+        raise ValueError("match_ref, ref_xy and match_pt differ in length")
+    if n and (match_ref.min() < 0 or match_ref.max() >= n_refs):
+        raise ValueError("match_ref out of range")
+    if n and (match_pt.min() < -1 or match_pt.max() >= n_pts):
+        raise ValueError("match_pt out of range")
+    risky = None
+    if pt_risky is not None:
+        risky = np.ascontiguousarray(pt_risky, np.uint8).reshape(-1)
+        if len(risky) != n_pts:
+            raise ValueError("pt_risky must have one entry per point")
+    arr = (CRegImage * max(n_refs, 1))()
+    keep = []
+    for k, r in enumerate(refs):
+        e = arr[k]
+        if lifted_registration:
+            m = np.ascontiguousarray(r["depth_map"], np.float64)
+            if m.ndim != 2 or m.shape[0] < 2 or m.shape[1] < 2:
+                raise ValueError("depth maps must be [H, W] arrays of at least 2 x 2")
+            keep.append(m)
+            e.map_h, e.map_w = m.shape
+            e.depth_map = m.ctypes.data
+        e.sx, e.sy = float(r["sx"]), float(r["sy"])
+        e.intr = (C.c_double * 4)(*[float(v) for v in np.asarray(r["intr"], np.float64).reshape(4)])
+        e.quat_xyzw = (C.c_double * 4)(*[float(v) for v in np.asarray(r["quat_xyzw"], np.float64).reshape(4)])
+        e.t = (C.c_double * 3)(*[float(v) for v in np.asarray(r["t"], np.float64).reshape(3)])
+    xyz, kind, ms = np.zeros((n, 3)), np.zeros(n, np.uint8), C.c_float(0)
+    L = lib()
+    L.mpsfm_registration_pairs.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_registration_pairs(n_refs, C.addressof(arr), n, match_ref.ctypes.data, ref_xy.ctypes.data, match_pt.ctypes.data,
+                                      None if risky is None else risky.ctypes.data, n_pts, pts.ctypes.data,
+                                      int(bool(lifted_registration)), int(device), xyz.ctypes.data, kind.ctypes.data, C.addressof(ms)))
+    return (xyz, kind, float(ms.value)) if return_ms else (xyz, kind)
+
+
+class CInitPair(C.Structure):
+    _fields_ = [("n_matches", C.c_int64), ("xy1", C.c_void_p), ("xy2", C.c_void_p), ("select", C.c_void_p),
+                ("intr1", C.c_double * 4), ("intr2", C.c_double * 4), ("cam2_from_cam1", C.c_double * 12),
+                ("map_h", C.c_int32), ("map_w", C.c_int32), ("prior_map", C.c_void_p), ("valid_map", C.c_void_p),
+                ("sx", C.c_double), ("sy", C.c_double), ("rescale", C.c_double), ("tri_min_angle", C.c_double),
+                ("tri_max_error", C.c_double), ("what", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CInitCandidates(C.Structure):
+    _fields_ = [("flags", C.c_void_p), ("tri_xyz", C.c_void_p), ("tri_angle_deg", C.c_void_p), ("lift_xyz", C.c_void_p),
+                ("lift_angle_deg", C.c_void_p), ("d_prior", C.c_void_p), ("ms", C.c_float)]
+
+
+INIT_TRIANGULATE, INIT_LIFT = 1, 2
+INIT_TRI_MAX_ERROR = float(np.deg2rad(2.0))  # EstimateTriangulationOptions.ransac.max_error of pycolmap 3.11 as recalled
+
+
+def init_pair_candidates(xy1, xy2, intr1, intr2, cam2_from_cam1, prior_map=None, valid_map=None, sx=1.0, sy=1.0, rescale=1.0,
+                         select=None, what=INIT_TRIANGULATE | INIT_LIFT, tri_min_angle=0.0, tri_max_error=INIT_TRI_MAX_ERROR,
+                         device=0):
+    """mpsfm_init_pair_candidates: the triangulated and the lifted candidate point of every match of an init pair (image 1 at
+    the identity, image 2 at `cam2_from_cam1` [3,4]) in one launch.  `prior_map` / `valid_map`: depth.data_prior and
+    depth.valid of image 1 (needed with INIT_LIFT).  Returns a dict with, per match, tri_ok, tri_xyz, tri_angle_deg,
+    tri_posdepth1/2, lift_xyz, lift_angle_deg, lift_posdepth1/2, d_prior, valid, and the device time `ms`; the angle is the
+    reference's (see include/mpsfm_hip.h), in degrees."""
+    xy1 = np.ascontiguousarray(xy1, np.float64).reshape(-1, 2)
+    xy2 = np.ascontiguousarray(xy2, np.float64).reshape(-1, 2)
+    n = len(xy1)
+    if len(xy2) != n:
+        raise ValueError("xy1 and xy2 differ in length")
+    what = int(what)
+    if what not in (INIT_TRIANGULATE, INIT_LIFT, INIT_TRIANGULATE | INIT_LIFT):
+        raise ValueError("what must be INIT_TRIANGULATE, INIT_LIFT or both")
+    P = CInitPair()
+    P.n_matches, P.xy1, P.xy2 = n, xy1.ctypes.data, xy2.ctypes.data
+    sel = None
+    if select is not None:
+        sel = np.ascontiguousarray(select, np.uint8).reshape(-1)
+        if len(sel) != n:
+            raise ValueError("select must have one entry per match")
+        P.select = sel.ctypes.data
+    P.intr1 = (C.c_double * 4)(*[float(v) for v in np.asarray(intr1, np.float64).reshape(4)])
+    P.intr2 = (C.c_double * 4)(*[float(v) for v in np.asarray(intr2, np.float64).reshape(4)])
+    P.cam2_from_cam1 = (C.c_double * 12)(*[float(v) for v in np.asarray(cam2_from_cam1, np.float64).reshape(12)])
+    pm = vm = None
+    if what & INIT_LIFT:
+        if prior_map is None or valid_map is None:
+            raise ValueError("INIT_LIFT needs prior_map and valid_map")
+        pm = np.ascontiguousarray(prior_map, np.float64)
+        vm = np.ascontiguousarray(np.asarray(valid_map) != 0, np.uint8)
+        if pm.ndim != 2 or pm.shape != vm.shape or pm.shape[0] < 2 or pm.shape[1] < 2:
+            raise ValueError("prior_map and valid_map must be [H, W] arrays of one shape, at least 2 x 2")
+        P.map_h, P.map_w = pm.shape
+        P.prior_map, P.valid_map = pm.ctypes.data, vm.ctypes.data
+    P.sx, P.sy, P.rescale = float(sx), float(sy), float(rescale)
+    P.tri_min_angle, P.tri_max_error, P.what = float(tri_min_angle), float(tri_max_error), what
+    flags = np.zeros(n, np.uint8)
+    o = {k: np.zeros(s) for k, s in (("tri_xyz", (n, 3)), ("tri_angle_deg", n), ("lift_xyz", (n, 3)), ("lift_angle_deg", n),
+                                     ("d_prior", n))}
+    O = CInitCandidates(flags.ctypes.data, o["tri_xyz"].ctypes.data, o["tri_angle_deg"].ctypes.data, o["lift_xyz"].ctypes.data,
+                        o["lift_angle_deg"].ctypes.data, o["d_prior"].ctypes.data, 0.0)
+    L = lib()
+    L.mpsfm_init_pair_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    _check(L.mpsfm_init_pair_candidates(C.byref(P), int(device), C.byref(O)))
+    for bit, name in enumerate(("tri_ok", "tri_posdepth1", "tri_posdepth2", "valid", "lift_posdepth1", "lift_posdepth2")):
+        o[name] = (flags >> bit & 1).astype(bool)
+    o["ms"] = float(O.ms)
+    return o

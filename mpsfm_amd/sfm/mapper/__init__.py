@@ -1,3 +1,4 @@
 from .depthconsistency import DepthConsistencyChecker
+from .registration import MpsfmRegistration
 
-__all__ = ["DepthConsistencyChecker"]
+__all__ = ["DepthConsistencyChecker", "MpsfmRegistration"]
