@@ -19,6 +19,7 @@
 #define MPSFM_HIP_H
 
 #include <stdint.h>
+#include <stddef.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -461,6 +462,24 @@ int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images /* [n_image
                             uint8_t* const* codes /* [2 n_pairs] pointers to Hs*Ws, or NULL */,
                             mpsfm_dc_summary* summary /* may be NULL */);
 
+/* ---- options of the two LO-RANSAC estimators below (their defaults differ: see each typedef) ---- */
+typedef struct mpsfm_ransac_options {
+  double max_error;                  /* pixels */
+  double min_inlier_ratio;
+  double confidence;
+  double dyn_num_trials_multiplier;
+  int64_t min_num_trials;
+  int64_t max_num_trials;
+  uint64_t seed;                     /* sampler seed (see mpsfm_abs_pose_estimate) */
+  int32_t batch_trials;              /* trials per generated / scored batch; 0: default */
+  int32_t reserved;
+} mpsfm_ransac_options;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_ransac_options) == 64 && offsetof(mpsfm_ransac_options, seed) == 48 &&
+                  offsetof(mpsfm_ransac_options, batch_trials) == 56,
+              "ABI of mpsfm_abs_pose_options / mpsfm_rel_pose_options");
+#endif
+
 /* ---- absolute pose: LO-RANSAC with P3P samples and EPnP local optimisation on one 2D-3D problem (reference
  *    mpsfm/sfm/estimators/absolute_pose.py:6-25 -> pycolmap.estimate_and_refine_absolute_pose, estimation half;
  *    call sites mpsfm/sfm/mapper/registration.py:169, :232, :263, base.py:329-336).  COLMAP 3.11
@@ -485,17 +504,9 @@ int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images /* [n_image
  *    batch are wasted work, not a different result.  Scoring sums are fixed-order: results are identical run to run.
  *    inlier_mask[i] = 1 for the inliers of the final model.  N < 3, N > INT32_MAX, NULL pointers, non-finite inputs and
  *    invalid options are MPSFM_EINVAL before any HIP call.  No model: result->success = 0 and return value 0. ---- */
-typedef struct mpsfm_abs_pose_options {
-  double max_error;                  /* pixels (12.0) */
-  double min_inlier_ratio;           /* 0.25 in the reference (pycolmap default 0.1) */
-  double confidence;                 /* 0.99999 */
-  double dyn_num_trials_multiplier;  /* 3.0 */
-  int64_t min_num_trials;            /* 100 */
-  int64_t max_num_trials;            /* 10000 */
-  uint64_t seed;                     /* sampler seed (see above) */
-  int32_t batch_trials;              /* trials per generated / scored batch; 0: default */
-  int32_t pad;
-} mpsfm_abs_pose_options;
+/* defaults of the reference's call: max_error 12.0, min_inlier_ratio 0.25 (pycolmap default 0.1), confidence 0.99999,
+ * dyn_num_trials_multiplier 3.0, min_num_trials 100, max_num_trials 10000 */
+typedef mpsfm_ransac_options mpsfm_abs_pose_options;
 
 typedef struct mpsfm_abs_pose_result {
   double cam_from_world[12];  /* [3][4] row-major, the RANSAC model (sample or local) */
@@ -537,17 +548,9 @@ int mpsfm_abs_pose_estimate(int64_t n, const double* points2D /* [n][2] pixels *
  *    (third coordinate in each camera) lie in (DBL_EPSILON, 1000 |t|); the most points win, the later candidate on a tie.
  *    inlier_mask = RANSAC's mask of the best E.  Argument checks as mpsfm_abs_pose_estimate (N < 5 ...), before any HIP call.
  *    No model: result->success = 0 and return value 0. ---- */
-typedef struct mpsfm_rel_pose_options {
-  double max_error;                  /* pixels (pycolmap RANSACOptions: 4.0) */
-  double min_inlier_ratio;           /* 0.01 */
-  double confidence;                 /* 0.9999 */
-  double dyn_num_trials_multiplier;  /* 3.0 */
-  int64_t min_num_trials;            /* 1000 */
-  int64_t max_num_trials;            /* 100000 */
-  uint64_t seed;                     /* sampler seed */
-  int32_t batch_trials;              /* trials per generated / scored batch; 0: default */
-  int32_t reserved;
-} mpsfm_rel_pose_options;
+/* defaults (pycolmap RANSACOptions): max_error 4.0, min_inlier_ratio 0.01, confidence 0.9999,
+ * dyn_num_trials_multiplier 3.0, min_num_trials 1000, max_num_trials 100000 */
+typedef mpsfm_ransac_options mpsfm_rel_pose_options;
 
 typedef struct mpsfm_rel_pose_result {
   double E[9];                   /* row-major, canonical form */

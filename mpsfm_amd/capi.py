@@ -521,10 +521,32 @@ def depth_consistency(images, pairs, c=15.0, score_thresh=0.6, device=0, return_
     return (counts, summary, codes) if return_codes else (counts, summary)
 
 
-class CAbsPoseOptions(C.Structure):
+class CRansacOptions(C.Structure):
+    """mpsfm_ransac_options: the options of both LO-RANSAC estimators."""
     _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
                 ("dyn_num_trials_multiplier", C.c_double), ("min_num_trials", C.c_int64), ("max_num_trials", C.c_int64),
-                ("seed", C.c_uint64), ("batch_trials", C.c_int32), ("pad", C.c_int32)]
+                ("seed", C.c_uint64), ("batch_trials", C.c_int32), ("reserved", C.c_int32)]
+
+
+CAbsPoseOptions = CRelPoseOptions = CRansacOptions
+
+
+def _ransac_options(defaults: dict, options: dict) -> CRansacOptions:
+    """`options` over `defaults` as the C struct; a key that is not in `defaults` is a KeyError."""
+    o = dict(defaults)
+    unknown = set(options) - set(o)
+    if unknown:
+        raise KeyError(f"unknown option(s) {sorted(unknown)}")
+    o.update(options)
+    return CRansacOptions(float(o["max_error"]), float(o["min_inlier_ratio"]), float(o["confidence"]), float(o["dyn_num_trials_multiplier"]),
+                          int(o["min_num_trials"]), int(o["max_num_trials"]), int(o["seed"]) & ((1 << 64) - 1), int(o["batch_trials"]), 0)
+
+
+def _ransac_report(R, mask: np.ndarray, n: int) -> dict:
+    """The result fields both estimators report."""
+    return dict(success=bool(R.success), num_inliers=int(R.num_inliers), inlier_mask=mask[:n].astype(bool), num_trials=int(R.num_trials),
+                max_num_trials=int(R.max_num_trials), num_models=int(R.num_models), lo_rounds=int(R.lo_rounds),
+                num_batches=int(R.num_batches), ms=float(R.ms))
 
 
 class CAbsPoseResult(C.Structure):
@@ -540,34 +562,20 @@ def abs_pose_estimate(points2D, points3D, intr, device=0, **options) -> dict:
     """mpsfm_abs_pose_estimate: LO-RANSAC (P3P + EPnP) of one 2D-3D problem with PINHOLE intr = (fx, fy, cx, cy).
     `options`: keys of ABS_POSE_DEFAULTS.  Returns dict(success, cam_from_world [3,4], num_inliers, inlier_mask bool [n],
     num_trials, max_num_trials, num_models, lo_rounds, num_batches, ms)."""
-    o = dict(ABS_POSE_DEFAULTS)
-    unknown = set(options) - set(o)
-    if unknown:
-        raise KeyError(f"unknown option(s) {sorted(unknown)}")
-    o.update(options)
+    opt = _ransac_options(ABS_POSE_DEFAULTS, options)
     p2 = np.ascontiguousarray(points2D, np.float64).reshape(-1, 2)
     p3 = np.ascontiguousarray(points3D, np.float64).reshape(-1, 3)
     if len(p2) != len(p3):
         raise ValueError("points2D and points3D differ in length")
     K = np.ascontiguousarray(intr, np.float64).reshape(4)
     n = len(p2)
-    opt = CAbsPoseOptions(float(o["max_error"]), float(o["min_inlier_ratio"]), float(o["confidence"]), float(o["dyn_num_trials_multiplier"]),
-                          int(o["min_num_trials"]), int(o["max_num_trials"]), int(o["seed"]) & ((1 << 64) - 1), int(o["batch_trials"]), 0)
     mask = np.zeros(max(n, 1), np.uint8)
     R = CAbsPoseResult()
     L = lib()
     L.mpsfm_abs_pose_estimate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     _check(L.mpsfm_abs_pose_estimate(n, p2.ctypes.data, p3.ctypes.data, K.ctypes.data, C.byref(opt), int(device), mask.ctypes.data,
                                      C.byref(R)))
-    return dict(success=bool(R.success), cam_from_world=np.array(R.cam_from_world[:]).reshape(3, 4), num_inliers=int(R.num_inliers),
-                inlier_mask=mask[:n].astype(bool), num_trials=int(R.num_trials), max_num_trials=int(R.max_num_trials),
-                num_models=int(R.num_models), lo_rounds=int(R.lo_rounds), num_batches=int(R.num_batches), ms=float(R.ms))
-
-
-class CRelPoseOptions(C.Structure):
-    _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
-                ("dyn_num_trials_multiplier", C.c_double), ("min_num_trials", C.c_int64), ("max_num_trials", C.c_int64),
-                ("seed", C.c_uint64), ("batch_trials", C.c_int32), ("reserved", C.c_int32)]
+    return dict(_ransac_report(R, mask, n), cam_from_world=np.array(R.cam_from_world[:]).reshape(3, 4))
 
 
 class CRelPoseResult(C.Structure):
@@ -585,11 +593,7 @@ def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> di
     """mpsfm_rel_pose_estimate: LO-RANSAC (five-point) of one two-view problem with PINHOLE intr = (fx, fy, cx, cy), then the
     pose.  `options`: keys of REL_POSE_DEFAULTS.  Returns dict(success, E [3,3], cam2_from_cam1 [3,4], num_inliers,
     inlier_mask bool [n], num_trials, max_num_trials, num_models, lo_rounds, num_batches, num_cheirality_points, ms)."""
-    o = dict(REL_POSE_DEFAULTS)
-    unknown = set(options) - set(o)
-    if unknown:
-        raise KeyError(f"unknown option(s) {sorted(unknown)}")
-    o.update(options)
+    opt = _ransac_options(REL_POSE_DEFAULTS, options)
     p1 = np.ascontiguousarray(points1, np.float64).reshape(-1, 2)
     p2 = np.ascontiguousarray(points2, np.float64).reshape(-1, 2)
     if len(p1) != len(p2):
@@ -597,8 +601,6 @@ def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> di
     K1 = np.ascontiguousarray(intr1, np.float64).reshape(4)
     K2 = np.ascontiguousarray(intr2, np.float64).reshape(4)
     n = len(p1)
-    opt = CRelPoseOptions(float(o["max_error"]), float(o["min_inlier_ratio"]), float(o["confidence"]), float(o["dyn_num_trials_multiplier"]),
-                          int(o["min_num_trials"]), int(o["max_num_trials"]), int(o["seed"]) & ((1 << 64) - 1), int(o["batch_trials"]), 0)
     mask = np.zeros(max(n, 1), np.uint8)
     R = CRelPoseResult()
     L = lib()
@@ -606,10 +608,8 @@ def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> di
                                           C.c_void_p]
     _check(L.mpsfm_rel_pose_estimate(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, C.byref(opt), int(device),
                                      mask.ctypes.data, C.byref(R)))
-    return dict(success=bool(R.success), E=np.array(R.E[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4),
-                num_inliers=int(R.num_inliers), inlier_mask=mask[:n].astype(bool), num_trials=int(R.num_trials),
-                max_num_trials=int(R.max_num_trials), num_models=int(R.num_models), lo_rounds=int(R.lo_rounds),
-                num_batches=int(R.num_batches), num_cheirality_points=int(R.num_cheirality_points), ms=float(R.ms))
+    return dict(_ransac_report(R, mask, n), E=np.array(R.E[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4),
+                num_cheirality_points=int(R.num_cheirality_points))
 
 
 class CRegImage(C.Structure):

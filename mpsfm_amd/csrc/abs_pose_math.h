@@ -1,8 +1,8 @@
-// Constant-size arithmetic of the absolute-pose estimator (abs_pose.hip): the counter-based sampler, P3P (Grunert's
-// quartic + Horn's absolute orientation), the normalised-plane residual, ComputeNumTrials for a minimal sample of 3 and
+// Constant-size arithmetic of the absolute-pose estimator (abs_pose.hip): P3P (Grunert's quartic + Horn's absolute
+// orientation), the normalised-plane residual, the symmetric eigen-solver sym_eig (also rel_pose_math.h's) and
 // the EPnP algebra that follows the O(N) reductions (control points, 12x12 eigenvectors, L6x10 / rho, the three beta
 // approximations with Gauss-Newton, the alignment).  COLMAP 3.11 semantics of P3PEstimator / EPNPEstimator /
-// ComputeSquaredReprojectionError / RANSAC::ComputeNumTrials as recalled (include/mpsfm_hip.h, mpsfm_abs_pose_estimate):
+// ComputeSquaredReprojectionError as recalled (include/mpsfm_hip.h, mpsfm_abs_pose_estimate):
 // parity with the reference's COLMAP fork unpinned.
 #pragma once
 #include "common.h"
@@ -15,34 +15,6 @@
 
 namespace mpsfm {
 
-constexpr uint64_t kApPhi = 0x9E3779B97F4A7C15ull;
-
-__host__ __device__ inline uint64_t ap_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__host__ __device__ inline uint64_t ap_mulhi(uint64_t a, uint64_t b) {
-#ifdef __HIP_DEVICE_COMPILE__
-  return __umul64hi(a, b);
-#else
-  return (uint64_t)(((unsigned __int128)a * b) >> 64);
-#endif
-}
-
-// the three distinct indices of trial t (recipe in include/mpsfm_hip.h)
-__host__ __device__ inline void ap_sample(uint64_t seed, int64_t t, int32_t n, int32_t idx[3]) {
-  const uint64_t base = ap_mix(seed + (uint64_t)(t + 1) * kApPhi);
-  int k = 0;
-  for (uint64_t j = 1; k < 3; ++j) {
-    const int32_t c = (int32_t)ap_mulhi(ap_mix(base + j * kApPhi), (uint64_t)n);
-    bool dup = false;
-    for (int i = 0; i < k; ++i) dup = dup || idx[i] == c;
-    if (!dup) idx[k++] = c;
-  }
-}
-
 // ComputeSquaredReprojectionError for one point: P = [R | t] row-major, x = normalised image point
 __host__ __device__ inline double ap_residual(const double* P, double X, double Y, double Z, double u, double v) {
   const double z = P[8] * X + P[9] * Y + P[10] * Z + P[11];
@@ -52,21 +24,9 @@ __host__ __device__ inline double ap_residual(const double* P, double X, double 
   return dx * dx + dy * dy;
 }
 
-// RANSAC::ComputeNumTrials with kMinNumSamples = 3
-__host__ __device__ inline int64_t ap_num_trials(int64_t num_inliers, int64_t n, double confidence, double multiplier) {
-  const double ratio = (double)num_inliers / (double)n;
-  const double nom = 1.0 - confidence;
-  if (nom <= 0.0) return INT64_MAX;
-  const double denom = 1.0 - pow(ratio, 3.0);
-  if (denom <= 0.0) return 1;
-  if (denom == 1.0) return INT64_MAX;
-  const double v = ceil(log(nom) / log(denom) * multiplier);
-  return v >= 9.2e18 ? INT64_MAX : (int64_t)v;
-}
-
 // ---- symmetric eigen-decomposition (cyclic Jacobi; eigenvalues ascending, eigenvectors in the columns of V) ------------
 template <int N>
-__host__ __device__ inline void ap_sym_eig(double A[N][N], double V[N][N], double w[N]) {
+__host__ __device__ inline void sym_eig(double A[N][N], double V[N][N], double w[N]) {
   for (int i = 0; i < N; ++i)
     for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 60; ++sweep) {
@@ -116,7 +76,7 @@ __host__ __device__ inline void ap_horn(const double S[3][3], double R[9]) {
                     {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
                     {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
   double V[4][4], ev[4];
-  ap_sym_eig<4>(N, V, ev);
+  sym_eig<4>(N, V, ev);
   double w = V[0][3], x = V[1][3], y = V[2][3], z = V[3][3];
   const double nq = sqrt(w * w + x * x + y * y + z * z);
   w /= nq; x /= nq; y /= nq; z /= nq;
@@ -298,7 +258,7 @@ __host__ __device__ inline bool ap_lstsq(const double* A_in, int m, int k, const
 struct ApEpnpFrame { double cws[4][3]; double CCinv[9]; };
 __host__ __device__ inline bool ap_epnp_frame(const double c0[3], const double sc[6], int64_t n, ApEpnpFrame& F) {
   double A[3][3] = {{sc[0], sc[1], sc[2]}, {sc[1], sc[3], sc[4]}, {sc[2], sc[4], sc[5]}}, V[3][3], w[3];
-  ap_sym_eig<3>(A, V, w);  // ascending: PCA axis i (descending) is column 2 - i
+  sym_eig<3>(A, V, w);  // ascending: PCA axis i (descending) is column 2 - i
   // an eigenvector's sign is arbitrary (upstream: whatever Eigen's JacobiSVD returns) and, with noise, EPnP's result depends
   // on it: each axis is oriented so that its largest-magnitude component is positive
   for (int c = 0; c < 3; ++c) {

@@ -1,0 +1,114 @@
+// What every stateless entry point shares on the host: the error helper, the device check and the per-call device scope
+// (stream, cached blocks, optional event pair).  Host code only and no floating-point arithmetic: this header may be
+// included on either side of a header that sets `#pragma clang fp contract`.
+#pragma once
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+namespace mpsfm {
+
+extern thread_local std::string g_err;
+// uploads through the calling thread's pinned staging buffer (ba_solver.hip); staged_drain() completes them
+int staged_upload(void* dst, const void* src, size_t bytes);
+int staged_drain();
+
+inline int fail(int code, const std::string& m) { g_err = m; return code; }
+#define MPSFM_TRY(expr)                                                                              \
+  do {                                                                                               \
+    hipError_t e_ = (expr);                                                                          \
+    if (e_ != hipSuccess) return fail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// the device ordinal of a call: checked, then made current
+inline int open_device(int32_t device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
+  if (device < 0 || device >= ndev) return fail(MPSFM_EINVAL, "device ordinal out of range");
+  if (device >= kMaxDevices) return fail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
+  MPSFM_TRY(hipSetDevice(device));
+  return 0;
+}
+
+struct CallScope {
+  // Every call works on a non-blocking stream of its own from the pool, never on the legacy null stream: the library is
+  // called from several host threads (tests, threaded callers), and null-stream copies / fills issued by one thread while
+  // another thread's solve had a deep queue of launches in flight corrupted that solve (MI355X, ROCm 7.2: reproduced with
+  // tests/test_gpu_fuzz.py::test_random_problems_concurrently until the last null-stream call was gone).
+  hipStream_t st = nullptr;
+  double ms = 0.0;  // device time of the segments closed by end()
+
+  CallScope() = default;
+  CallScope(const CallScope&) = delete;
+  CallScope& operator=(const CallScope&) = delete;
+  // the stream must be idle before the blocks go back to the caching allocator (an early return on a failed call would
+  // otherwise free memory that is still in use) and before the stream goes back to the pool
+  ~CallScope() {
+    if (st) (void)hipStreamSynchronize(st);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (void* p : blocks) cached_free(p);
+    release_stream(st);
+  }
+
+  // takes the stream, and the event pair of a call that reports its device time
+  int open(bool timed = false) {
+    MPSFM_TRY(pooled_stream(&st));
+    if (timed) {
+      MPSFM_TRY(hipEventCreate(&ev[0]));
+      MPSFM_TRY(hipEventCreate(&ev[1]));
+    }
+    return 0;
+  }
+
+  // a cached block that lives as long as the scope; nullptr: out of memory
+  void* get(size_t bytes) {
+    void* p = cached_malloc(bytes ? bytes : 1);
+    if (p) blocks.push_back(p);
+    return p;
+  }
+  template <typename T>
+  T* alloc(size_t count) { return (T*)get(sizeof(T) * count); }
+  // block + queued staged upload (complete after staged_drain())
+  template <typename T>
+  int up(const T** dst, const T* src, size_t count) {
+    T* p = alloc<T>(count);
+    if (!p) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+    *dst = p;
+    return staged_upload(p, src, sizeof(T) * count);
+  }
+  // block + copy on the call's stream; nullptr: out of memory
+  template <typename T>
+  T* put(const T* host, size_t count) {
+    T* p = alloc<T>(count);
+    if (p && count && host) (void)hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, st);
+    return p;
+  }
+  // device -> caller memory, complete on return
+  hipError_t down(void* host, const void* dev, size_t bytes) {
+    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+  }
+
+  // a timed segment on the stream: begin() .. stop(), read with elapsed() once the stream is idle
+  int begin() { MPSFM_TRY(hipEventRecord(ev[0], st)); return 0; }
+  int stop() { MPSFM_TRY(hipEventRecord(ev[1], st)); return 0; }
+  int elapsed(float* t) { MPSFM_TRY(hipEventElapsedTime(t, ev[0], ev[1])); return 0; }
+  // closes a timed segment and adds it to ms: the stream is idle on return
+  int end() {
+    if (int rc = stop()) return rc;
+    MPSFM_TRY(hipStreamSynchronize(st));
+    float t = 0.f;
+    if (int rc = elapsed(&t)) return rc;
+    ms += t;
+    return 0;
+  }
+
+ private:
+  std::vector<void*> blocks;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+}  // namespace mpsfm

@@ -16,19 +16,10 @@
 #include <string>
 #include <vector>
 
+#include "call_scope.h"
 #include "common.h"
 
 namespace mpsfm {
-
-extern thread_local std::string g_err;
-int staged_upload(void* dst, const void* src, size_t bytes);
-int staged_drain();
-static int dcfail(int code, const std::string& m) { g_err = m; return code; }
-#define DC_TRY(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) return dcfail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int kT = 256;
@@ -153,15 +144,15 @@ extern "C" int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images,
                                        const int32_t* pair_b, double c, double score_thresh, int32_t device, int64_t* counts,
                                        uint8_t* const* codes, mpsfm_dc_summary* summary) {
   if (summary) *summary = mpsfm_dc_summary{};
-  if (n_images < 0 || n_pairs < 0) return dcfail(MPSFM_EINVAL, "negative size");
+  if (n_images < 0 || n_pairs < 0) return fail(MPSFM_EINVAL, "negative size");
   if (n_pairs == 0) return 0;
-  if (!images || !pair_a || !pair_b || !counts) return dcfail(MPSFM_EINVAL, "NULL pointer");
-  if (n_pairs > 32767) return dcfail(MPSFM_EINVAL, "more than 32767 pairs (legs are the grid's y dimension)");
+  if (!images || !pair_a || !pair_b || !counts) return fail(MPSFM_EINVAL, "NULL pointer");
+  if (n_pairs > 32767) return fail(MPSFM_EINVAL, "more than 32767 pairs (legs are the grid's y dimension)");
   std::vector<uint8_t> used((size_t)n_images, 0);
   for (int32_t p = 0; p < n_pairs; ++p) {
     const int32_t a = pair_a[p], b = pair_b[p];
-    if (a < 0 || a >= n_images || b < 0 || b >= n_images) return dcfail(MPSFM_EINVAL, "pair index out of range");
-    if (a == b) return dcfail(MPSFM_EINVAL, "a pair of an image with itself");
+    if (a < 0 || a >= n_images || b < 0 || b >= n_images) return fail(MPSFM_EINVAL, "pair index out of range");
+    if (a == b) return fail(MPSFM_EINVAL, "a pair of an image with itself");
     used[(size_t)a] = used[(size_t)b] = 1;
   }
   int64_t npix = 0;
@@ -169,17 +160,13 @@ extern "C" int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images,
   for (int32_t k = 0; k < n_images; ++k) {
     if (!used[(size_t)k]) continue;
     const mpsfm_dc_image& I = images[k];
-    if (I.H <= 0 || I.W <= 0) return dcfail(MPSFM_EINVAL, "non-positive map size");
-    if ((int64_t)I.H * I.W > (int64_t)1 << 30) return dcfail(MPSFM_EINVAL, "map larger than 2^30 pixels");
-    if (!I.depth || !I.variance) return dcfail(MPSFM_EINVAL, "depth or variance map is NULL");
+    if (I.H <= 0 || I.W <= 0) return fail(MPSFM_EINVAL, "non-positive map size");
+    if ((int64_t)I.H * I.W > (int64_t)1 << 30) return fail(MPSFM_EINVAL, "map larger than 2^30 pixels");
+    if (!I.depth || !I.variance) return fail(MPSFM_EINVAL, "depth or variance map is NULL");
     off[(size_t)k] = npix;
     npix += (int64_t)I.H * I.W;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return dcfail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return dcfail(MPSFM_EINVAL, "device ordinal out of range");
-  if (device >= kMaxDevices) return dcfail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
-  DC_TRY(hipSetDevice(device));
+  if (int rc = open_device(device)) return rc;
 
   const int32_t n_legs = 2 * n_pairs;
   std::vector<DcLeg> legs((size_t)n_legs);
@@ -198,32 +185,18 @@ extern "C" int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images,
       max_src = std::max(max_src, (int64_t)L.Hs * L.Ws);
     }
 
-  struct Blocks {  // a pooled non-blocking stream per call, never the legacy null stream (see DevBuf in tri_kernels.hip)
-    std::vector<void*> v;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~Blocks() {
-      if (st) (void)hipStreamSynchronize(st);
-      for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-      for (void* p : v) cached_free(p);
-      release_stream(st);
-    }
-    void* get(size_t bytes) { void* p = cached_malloc(bytes ? bytes : 1); if (p) v.push_back(p); return p; }
-  } B;
-  DC_TRY(pooled_stream(&B.st));
-  DC_TRY(hipEventCreate(&B.ev[0]));
-  DC_TRY(hipEventCreate(&B.ev[1]));
-  double* d_depth = (double*)B.get(sizeof(double) * (size_t)npix);
-  double* d_var = (double*)B.get(sizeof(double) * (size_t)npix);
-  DcLeg* d_legs = (DcLeg*)B.get(sizeof(DcLeg) * legs.size());
-  int32_t* d_tgt = (int32_t*)B.get(sizeof(int32_t) * (size_t)pix);
-  double* d_dep = (double*)B.get(sizeof(double) * (size_t)pix);
-  int32_t* d_win = (int32_t*)B.get(sizeof(int32_t) * (size_t)wpix);
-  uint8_t* d_codes = codes ? (uint8_t*)B.get((size_t)pix) : nullptr;
-  unsigned long long* d_cnt = (unsigned long long*)B.get(sizeof(unsigned long long) * 4 * (size_t)n_legs);
+  CallScope B;
+  if (int rc = B.open(true)) return rc;
+  double* d_depth = B.alloc<double>((size_t)npix);
+  double* d_var = B.alloc<double>((size_t)npix);
+  DcLeg* d_legs = B.alloc<DcLeg>(legs.size());
+  int32_t* d_tgt = B.alloc<int32_t>((size_t)pix);
+  double* d_dep = B.alloc<double>((size_t)pix);
+  int32_t* d_win = B.alloc<int32_t>((size_t)wpix);
+  uint8_t* d_codes = codes ? B.alloc<uint8_t>((size_t)pix) : nullptr;
+  unsigned long long* d_cnt = B.alloc<unsigned long long>(4 * (size_t)n_legs);
   if (!d_depth || !d_var || !d_legs || !d_tgt || !d_dep || !d_win || (codes && !d_codes) || !d_cnt)
-    return dcfail(MPSFM_ENOMEM, "hipMalloc failed");
+    return fail(MPSFM_ENOMEM, "hipMalloc failed");
 
   // reproject_depth clamps the caller's map in place (`depth1[depth1 <= 0] = 0.1`, depth_utils.py:18) for both images of
   // every pair; the clamped maps are what the kernels read.  Each image is uploaded once, however many pairs it is in.
@@ -240,26 +213,26 @@ extern "C" int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images,
   if (int rc = staged_drain()) return rc;
 
   const dim3 grid((unsigned)((max_src + kT - 1) / kT), (unsigned)n_legs);
-  DC_TRY(hipEventRecord(B.ev[0], B.st));
-  DC_TRY(hipMemsetAsync(d_win, 0xFF, sizeof(int32_t) * (size_t)wpix, B.st));
-  DC_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * (size_t)n_legs, B.st));
+  if (int rc = B.begin()) return rc;
+  MPSFM_TRY(hipMemsetAsync(d_win, 0xFF, sizeof(int32_t) * (size_t)wpix, B.st));
+  MPSFM_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * (size_t)n_legs, B.st));
   hipLaunchKernelGGL(k_dc_project, grid, dim3(kT), 0, B.st, d_legs, d_depth, d_tgt, d_dep, d_win);
-  DC_TRY(hipGetLastError());
+  MPSFM_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_dc_classify, grid, dim3(kT), 0, B.st, d_legs, d_depth, d_var, d_tgt, d_dep, d_win, d_codes, d_cnt, c,
                      score_thresh);
-  DC_TRY(hipGetLastError());
-  DC_TRY(hipEventRecord(B.ev[1], B.st));
+  MPSFM_TRY(hipGetLastError());
+  if (int rc = B.stop()) return rc;
   static_assert(sizeof(int64_t) == sizeof(unsigned long long), "counts are 64-bit");
-  DC_TRY(hipMemcpyAsync(counts, d_cnt, sizeof(int64_t) * 4 * (size_t)n_legs, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipMemcpyAsync(counts, d_cnt, sizeof(int64_t) * 4 * (size_t)n_legs, hipMemcpyDeviceToHost, B.st));
   if (codes)
     for (int32_t l = 0; l < n_legs; ++l)
       if (codes[l])
-        DC_TRY(hipMemcpyAsync(codes[l], d_codes + legs[(size_t)l].pix_off, (size_t)legs[(size_t)l].Hs * legs[(size_t)l].Ws,
+        MPSFM_TRY(hipMemcpyAsync(codes[l], d_codes + legs[(size_t)l].pix_off, (size_t)legs[(size_t)l].Hs * legs[(size_t)l].Ws,
                               hipMemcpyDeviceToHost, B.st));
-  DC_TRY(hipStreamSynchronize(B.st));
+  MPSFM_TRY(hipStreamSynchronize(B.st));
   if (summary) {
     float ms = 0.f;
-    DC_TRY(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
+    if (int rc = B.elapsed(&ms)) return rc;
     summary->ms = ms;
     summary->n_legs = n_legs;
     summary->n_pixels = pix;

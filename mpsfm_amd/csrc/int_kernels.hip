@@ -10,20 +10,11 @@
 #include <string>
 #include <vector>
 
+#include "call_scope.h"
 #include "common.h"
 
 namespace mpsfm {
 
-extern thread_local std::string g_err;
-// pinned staging uploads (ba_solver.hip): pageable caller memory is not handed to the runtime directly
-int staged_upload(void* dst, const void* src, size_t bytes);
-int staged_drain();
-static int ifail(int code, const std::string& m) { g_err = m; return code; }
-#define INT_TRY(expr)                                                                                \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return ifail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 constexpr int kIT = 256;  // threads per workgroup
 // Pixels per thread in the CG kernels, chosen per solve: one image (112 k pixels) is latency-bound and fastest
@@ -458,13 +449,6 @@ struct IntPool {
   }
 };
 
-struct StreamGuard {
-  hipStream_t st = nullptr;
-  ~StreamGuard() {
-    if (st) { (void)hipStreamSynchronize(st); release_stream(st); }  // back to the pool, idle
-  }
-};
-
 // b = 1, x0 = 0: the system of IntegrationUncertainty (column sums of the inverse)
 __global__ __launch_bounds__(kIT) void k_int_unit_rhs(IntDev Dall) {
   if (!Dall.act[blockIdx.y]) return;
@@ -491,18 +475,15 @@ struct IntBatch {
 };
 
 static int int_check(const mpsfm_int_problem* P, int32_t device) {
-  if (P->H < 2 || P->W < 2) return ifail(MPSFM_EINVAL, "map must be at least 2x2");
+  if (P->H < 2 || P->W < 2) return fail(MPSFM_EINVAL, "map must be at least 2x2");
   if (!P->depth_prior || !P->depth_uncertainty || !P->valid || !P->normals || !P->normals_var || !P->depth_init)
-    return ifail(MPSFM_EINVAL, "map pointers are NULL");
+    return fail(MPSFM_EINVAL, "map pointers are NULL");
   if (P->n_sparse < 0 || (P->n_sparse > 0 && (!P->sparse_x || !P->sparse_y || !P->sparse_depth3d || !P->sparse_zvar)))
-    return ifail(MPSFM_EINVAL, "sparse arrays are NULL");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ifail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return ifail(MPSFM_EINVAL, "device ordinal out of range");
-  if (device >= kMaxDevices) return ifail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
+    return fail(MPSFM_EINVAL, "sparse arrays are NULL");
+  if (int rc = open_device(device)) return rc;
   for (int i = 0; i < P->n_sparse; ++i)
     if (P->sparse_x[i] < 0 || P->sparse_x[i] >= P->W || P->sparse_y[i] < 0 || P->sparse_y[i] >= P->H)
-      return ifail(MPSFM_EINVAL, "sparse pixel outside the map");
+      return fail(MPSFM_EINVAL, "sparse pixel outside the map");
   return 0;
 }
 
@@ -563,7 +544,7 @@ static int int_setup(const mpsfm_int_problem* Ps, int B, bool use_sparse, bool s
   U.d_K = pool.get<double>((size_t)B * 4);
   U.d_esp = pool.get<double>((size_t)B);
   if (!big || !d_in || !U.d_valid || !D.part || !D.state || !U.d_ids || !U.d_off || !U.d_act || !U.d_keep || !U.d_sp || !U.d_out || !U.d_K || !U.d_esp)
-    return ifail(MPSFM_ENOMEM, "hipMalloc failed");
+    return fail(MPSFM_ENOMEM, "hipMalloc failed");
   D.act = U.d_act;
   {
     double* c = big;
@@ -587,7 +568,7 @@ static int int_setup(const mpsfm_int_problem* Ps, int B, bool use_sparse, bool s
   if (int rc = up(D.spb, spb.data(), sizeof(double) * BN)) return rc;
   if (int rc = up(U.d_K, Kh.data(), sizeof(double) * 4 * B)) return rc;
   if (int rc = up(U.d_off, U.sp_off.data(), sizeof(int32_t) * ((size_t)B + 1))) return rc;
-  INT_TRY(hipMemsetAsync(D.p0, 0, sizeof(double) * 2 * BN, st));
+  MPSFM_TRY(hipMemsetAsync(D.p0, 0, sizeof(double) * 2 * BN, st));
   if (!ids.empty()) {
     if (int rc = up(U.d_ids, ids.data(), sizeof(int32_t) * ids.size())) return rc;
     if (int rc = up(U.d_sp, U.sprec.data(), sizeof(double) * ids.size())) return rc;
@@ -597,16 +578,16 @@ static int int_setup(const mpsfm_int_problem* Ps, int B, bool use_sparse, bool s
   if (int rc = up(U.d_act, U.act.data(), sizeof(int32_t) * B)) return rc;
   // everything staged must be on the device before the first kernel on st (and spd / spb / Kh die with this frame)
   if (int rc = staged_drain()) return rc;
-  INT_TRY(hipStreamSynchronize(st));
+  MPSFM_TRY(hipStreamSynchronize(st));
   double* hblk = pool.get_host<double>((size_t)B * G * 8 + (size_t)B * 9);
-  if (!hblk) return ifail(MPSFM_ENOMEM, "hipHostMalloc failed");
+  if (!hblk) return fail(MPSFM_ENOMEM, "hipHostMalloc failed");
   U.hpart = hblk; U.hstate = hblk + (size_t)B * G * 8; U.hesp = U.hstate + (size_t)B * 8;
   return 0;
 }
 
 static int int_set_active(IntBatch& U, hipStream_t st) {
-  INT_TRY(hipMemcpyAsync(U.d_act, U.act.data(), sizeof(int32_t) * U.B, hipMemcpyHostToDevice, st));
-  INT_TRY(hipStreamSynchronize(st));  // U.act may change right after
+  MPSFM_TRY(hipMemcpyAsync(U.d_act, U.act.data(), sizeof(int32_t) * U.B, hipMemcpyHostToDevice, st));
+  MPSFM_TRY(hipStreamSynchronize(st));  // U.act may change right after
   return 0;
 }
 
@@ -625,7 +606,7 @@ static int int_run_cg(IntBatch& U, hipStream_t st, double rtol, int max_iter, in
   const int pix = ((size_t)U.B * U.N >= kPixSwitch) ? 2 : 1;
   const int Gc = (int)((U.N + (size_t)kIT * pix - 1) / ((size_t)kIT * pix));  // workgroups (= partial rows) of the CG kernels
   const dim3 grid(Gc, U.B);
-  INT_TRY(hipMemsetAsync(D.state, 0, sizeof(double) * 8 * U.B, st));
+  MPSFM_TRY(hipMemsetAsync(D.state, 0, sizeof(double) * 8 * U.B, st));
   if (pix == 2) hipLaunchKernelGGL(k_cg_init<2>, grid, dim3(kIT), 0, st, D);
   else hipLaunchKernelGGL(k_cg_init<1>, grid, dim3(kIT), 0, st, D);
   int k = 0;
@@ -641,7 +622,7 @@ static int int_run_cg(IntBatch& U, hipStream_t st, double rtol, int max_iter, in
         hipLaunchKernelGGL(k_cg_update<1>, grid, dim3(kIT), 0, st, D, Gc, k);
       }
     }
-    INT_TRY(hipMemcpyAsync(U.hstate, D.state, sizeof(double) * 8 * U.B, hipMemcpyDeviceToHost, st)); INT_TRY(hipStreamSynchronize(st));
+    MPSFM_TRY(hipMemcpyAsync(U.hstate, D.state, sizeof(double) * 8 * U.B, hipMemcpyDeviceToHost, st)); MPSFM_TRY(hipStreamSynchronize(st));
     done = true;
     for (int b = 0; b < U.B; ++b)
       if (U.act[(size_t)b]) {
@@ -651,7 +632,7 @@ static int int_run_cg(IntBatch& U, hipStream_t st, double rtol, int max_iter, in
         if (conv) conv[b] = db;
       }
   }
-  INT_TRY(hipGetLastError());
+  MPSFM_TRY(hipGetLastError());
   return 0;
 }
 
@@ -661,25 +642,25 @@ using namespace mpsfm;
 
 extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_problem* Ps, int32_t device, double* const* depth_out,
                                            mpsfm_int_summary* Ss) {
-  if (n_images < 0) return ifail(MPSFM_EINVAL, "negative batch size");
+  if (n_images < 0) return fail(MPSFM_EINVAL, "negative batch size");
   if (n_images == 0) return 0;
-  if (!Ps || !depth_out || !Ss) return ifail(MPSFM_EINVAL, "NULL argument");
+  if (!Ps || !depth_out || !Ss) return fail(MPSFM_EINVAL, "NULL argument");
   const int B = n_images;
   const mpsfm_int_problem* P = &Ps[0];  // the shared configuration
-  if (P->max_iter < 0 || P->max_iter > MPSFM_INT_MAX_IRLS) return ifail(MPSFM_EINVAL, "max_iter out of range");
+  if (P->max_iter < 0 || P->max_iter > MPSFM_INT_MAX_IRLS) return fail(MPSFM_EINVAL, "max_iter out of range");
   for (int b = 0; b < B; ++b) {
-    if (!depth_out[b]) return ifail(MPSFM_EINVAL, "depth_out entry is NULL");
+    if (!depth_out[b]) return fail(MPSFM_EINVAL, "depth_out entry is NULL");
     if (int rc = int_check(&Ps[b], device)) return rc;
-    if (!int_same_config(Ps[0], Ps[b])) return ifail(MPSFM_EINVAL, "images of a batch must share the map size and the configuration");
+    if (!int_same_config(Ps[0], Ps[b])) return fail(MPSFM_EINVAL, "images of a batch must share the map size and the configuration");
   }
-  INT_TRY(hipSetDevice(device));
+  MPSFM_TRY(hipSetDevice(device));
   std::memset(Ss, 0, sizeof(*Ss) * (size_t)B);
   // a stream of its own: concurrent calls from different host threads overlap on the GPU
   // U before the guard: destructors run in reverse order, so every early `return rc` first waits for the stream
   // (the guard) and only then hands U's device blocks back to the caching allocator
   IntBatch U;
-  StreamGuard sg;
-  INT_TRY(pooled_stream(&sg.st));
+  CallScope sg;
+  if (int rc = sg.open()) return rc;
   hipStream_t st = sg.st;
   const size_t N = (size_t)P->H * P->W;
   if (int rc = int_setup(Ps, B, true, P->scale_filter != 0, st, U)) return rc;
@@ -689,15 +670,15 @@ extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_pro
   for (int b = 0; b < B; ++b) {
     keep[(size_t)b] = (Ps[b].init && Ps[b].integrated && Ps[b].wu && Ps[b].wv) ? 1 : 0;
     if (keep[(size_t)b]) {
-      INT_TRY(hipMemcpyAsync(D.wu + (size_t)b * N, Ps[b].wu, sizeof(double) * N, hipMemcpyHostToDevice, st));
-      INT_TRY(hipMemcpyAsync(D.wv + (size_t)b * N, Ps[b].wv, sizeof(double) * N, hipMemcpyHostToDevice, st));
+      MPSFM_TRY(hipMemcpyAsync(D.wu + (size_t)b * N, Ps[b].wu, sizeof(double) * N, hipMemcpyHostToDevice, st));
+      MPSFM_TRY(hipMemcpyAsync(D.wv + (size_t)b * N, Ps[b].wv, sizeof(double) * N, hipMemcpyHostToDevice, st));
     }
   }
-  INT_TRY(hipMemcpyAsync(U.d_keep, keep.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
-  INT_TRY(hipStreamSynchronize(st));
+  MPSFM_TRY(hipMemcpyAsync(U.d_keep, keep.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
+  MPSFM_TRY(hipStreamSynchronize(st));
   hipEvent_t e0, e1;
-  INT_TRY(hipEventCreate(&e0)); INT_TRY(hipEventCreate(&e1));
-  INT_TRY(hipEventRecord(e0, st));
+  MPSFM_TRY(hipEventCreate(&e0)); MPSFM_TRY(hipEventCreate(&e1));
+  MPSFM_TRY(hipEventRecord(e0, st));
   int_launch_prepare(P, U, st);
 
   // energies of the active images -> en[b]
@@ -706,9 +687,9 @@ extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_pro
     hipLaunchKernelGGL(k_int_weights, grid, dim3(kIT), 0, st, D, P->k, P->lambda1, (const int32_t*)U.d_keep);
     hipLaunchKernelGGL(k_int_sparse_energy, dim3(B), dim3(kIT), 0, st, D, (const int32_t*)U.d_off, (const int32_t*)U.d_ids, (const double*)U.d_sp,
                        (const double*)(U.d_sp + U.ids.size()), P->lambda2, U.d_esp);
-    INT_TRY(hipMemcpyAsync(U.hpart, D.part, sizeof(double) * (size_t)B * U.G * 8, hipMemcpyDeviceToHost, st));
-    INT_TRY(hipMemcpyAsync(U.hesp, U.d_esp, sizeof(double) * B, hipMemcpyDeviceToHost, st));
-    INT_TRY(hipStreamSynchronize(st));
+    MPSFM_TRY(hipMemcpyAsync(U.hpart, D.part, sizeof(double) * (size_t)B * U.G * 8, hipMemcpyDeviceToHost, st));
+    MPSFM_TRY(hipMemcpyAsync(U.hesp, U.d_esp, sizeof(double) * B, hipMemcpyDeviceToHost, st));
+    MPSFM_TRY(hipStreamSynchronize(st));
     for (int b = 0; b < B; ++b) {
       if (!U.act[(size_t)b]) continue;
       double e_n = 0.0, e_d = 0.0;
@@ -728,17 +709,17 @@ extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_pro
   };
   auto save_weights = [&]() -> int {
     for (int b = 0; b < B; ++b) {
-      if (Ps[b].wu) INT_TRY(hipMemcpyAsync(Ps[b].wu, D.wu + (size_t)b * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-      if (Ps[b].wv) INT_TRY(hipMemcpyAsync(Ps[b].wv, D.wv + (size_t)b * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+      if (Ps[b].wu) MPSFM_TRY(hipMemcpyAsync(Ps[b].wu, D.wu + (size_t)b * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+      if (Ps[b].wv) MPSFM_TRY(hipMemcpyAsync(Ps[b].wv, D.wv + (size_t)b * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
     }
-    INT_TRY(hipStreamSynchronize(st));
+    MPSFM_TRY(hipStreamSynchronize(st));
     return 0;
   };
 
   if (int rc = energy()) return finish(rc);
   // after the first evaluation the weights are always recomputed (update_W after every CG solve)
   std::fill(keep.begin(), keep.end(), 0);
-  INT_TRY(hipMemcpyAsync(U.d_keep, keep.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
+  MPSFM_TRY(hipMemcpyAsync(U.d_keep, keep.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
   std::vector<double> energy_0((size_t)B), min_energy((size_t)B);
   std::vector<uint8_t> success((size_t)B, 1), ran((size_t)B, 0);
   for (int b = 0; b < B; ++b) {
@@ -792,14 +773,14 @@ extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_pro
     const size_t BN = (size_t)B * N;
     hipLaunchKernelGGL(k_int_exp, dim3((unsigned)((BN + kIT - 1) / kIT)), dim3(kIT), 0, st, BN, (const double*)D.z, U.d_out);
     for (int b = 0; b < B; ++b)
-      if (Ss[b].changed) INT_TRY(hipMemcpyAsync(depth_out[b], U.d_out + (size_t)b * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-    INT_TRY(hipStreamSynchronize(st));
+      if (Ss[b].changed) MPSFM_TRY(hipMemcpyAsync(depth_out[b], U.d_out + (size_t)b * N, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    MPSFM_TRY(hipStreamSynchronize(st));
   }
   return finish(0);
 }
 
 extern "C" int mpsfm_integrate_depth(const mpsfm_int_problem* P, int32_t device, double* depth_out, mpsfm_int_summary* S) {
-  if (!P || !depth_out || !S) return ifail(MPSFM_EINVAL, "NULL argument");
+  if (!P || !depth_out || !S) return fail(MPSFM_EINVAL, "NULL argument");
   double* outs[1] = {depth_out};
   return mpsfm_integrate_depth_batch(1, P, device, outs, S);
 }
@@ -810,28 +791,28 @@ extern "C" int mpsfm_integrate_depth(const mpsfm_int_problem* P, int32_t device,
 extern "C" int mpsfm_integration_variances(const mpsfm_int_problem* P, int32_t device, int32_t use_sparse, int32_t n_query,
                                            const int32_t* qx, const int32_t* qy, double rtol, int32_t max_iter,
                                            double* var_out, double* field_out, mpsfm_int_summary* S) {
-  if (!P || !S) return ifail(MPSFM_EINVAL, "NULL argument");
-  if (n_query < 0 || (n_query > 0 && (!qx || !qy || !var_out))) return ifail(MPSFM_EINVAL, "query arrays are NULL");
-  if (!(rtol > 0.0) || max_iter <= 0) return ifail(MPSFM_EINVAL, "rtol / max_iter must be positive");
+  if (!P || !S) return fail(MPSFM_EINVAL, "NULL argument");
+  if (n_query < 0 || (n_query > 0 && (!qx || !qy || !var_out))) return fail(MPSFM_EINVAL, "query arrays are NULL");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(MPSFM_EINVAL, "rtol / max_iter must be positive");
   if (int rc = int_check(P, device)) return rc;
   for (int i = 0; i < n_query; ++i)
-    if (qx[i] < 0 || qx[i] >= P->W || qy[i] < 0 || qy[i] >= P->H) return ifail(MPSFM_EINVAL, "query pixel outside the map");
-  INT_TRY(hipSetDevice(device));
+    if (qx[i] < 0 || qx[i] >= P->W || qy[i] < 0 || qy[i] >= P->H) return fail(MPSFM_EINVAL, "query pixel outside the map");
+  MPSFM_TRY(hipSetDevice(device));
   std::memset(S, 0, sizeof(*S));
   IntBatch U;  // before the guard, see mpsfm_integrate_depth_batch
-  StreamGuard sg;
-  INT_TRY(pooled_stream(&sg.st));
+  CallScope sg;
+  if (int rc = sg.open()) return rc;
   hipStream_t st = sg.st;
   const int N = P->H * P->W;
   if (int rc = int_setup(P, 1, use_sparse != 0, false, st, U)) return rc;  // calculate_hessian applies no scale filter (:542)
   IntDev& D = U.D;
   const dim3 grid(U.G, 1);
   int32_t zero = 0;
-  INT_TRY(hipMemcpyAsync(U.d_keep, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st));
-  INT_TRY(hipStreamSynchronize(st));
+  MPSFM_TRY(hipMemcpyAsync(U.d_keep, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st));
+  MPSFM_TRY(hipStreamSynchronize(st));
   hipEvent_t e0, e1;
-  INT_TRY(hipEventCreate(&e0)); INT_TRY(hipEventCreate(&e1));
-  INT_TRY(hipEventRecord(e0, st));
+  MPSFM_TRY(hipEventCreate(&e0)); MPSFM_TRY(hipEventCreate(&e1));
+  MPSFM_TRY(hipEventRecord(e0, st));
   int_launch_prepare(P, U, st);
   hipLaunchKernelGGL(k_int_weights, grid, dim3(kIT), 0, st, D, P->k, P->lambda1, (const int32_t*)U.d_keep);  // init=False: weights from the checkpoint
   hipLaunchKernelGGL(k_int_system, grid, dim3(kIT), 0, st, D, P->lambda1);
@@ -851,8 +832,8 @@ extern "C" int mpsfm_integration_variances(const mpsfm_int_problem* P, int32_t d
   std::vector<double> host;
   double* f = field_out;
   if (!f) { host.resize((size_t)N); f = host.data(); }
-  INT_TRY(hipMemcpyAsync(f, D.z, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  INT_TRY(hipStreamSynchronize(st));
+  MPSFM_TRY(hipMemcpyAsync(f, D.z, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  MPSFM_TRY(hipStreamSynchronize(st));
   for (int i = 0; i < n_query; ++i) var_out[i] = f[(size_t)qy[i] * P->W + qx[i]];
   return 0;
 }

@@ -15,18 +15,9 @@
 
 #include "common.h"
 #include "bilinear_sample.h"  // grid_coord + bilinear, and contraction off for the rest of this file
+#include "call_scope.h"
 
 namespace mpsfm {
-
-extern thread_local std::string g_err;
-int staged_upload(void* dst, const void* src, size_t bytes);
-int staged_drain();
-static int pfail(int code, const std::string& m) { g_err = m; return code; }
-#define PRI_TRY(expr)                                                                                \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return pfail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 struct GatherArgs {
   int64_t n_obs;
@@ -78,56 +69,43 @@ using namespace mpsfm;
 
 extern "C" int mpsfm_depth_blocks(const mpsfm_depth_gather* g, int32_t device, uint8_t* flags, double* depth, double* depth3d,
                                   double* magnitude, double* param, double* whitened) {
-  if (!g) return pfail(MPSFM_EINVAL, "gather descriptor is NULL");
-  if (g->n_images < 0 || g->n_obs < 0 || g->n_pts < 0) return pfail(MPSFM_EINVAL, "negative size");
+  if (!g) return fail(MPSFM_EINVAL, "gather descriptor is NULL");
+  if (g->n_images < 0 || g->n_obs < 0 || g->n_pts < 0) return fail(MPSFM_EINVAL, "negative size");
   if (g->n_obs == 0) return 0;
-  if (!flags || !depth || !depth3d || !magnitude || !param || !whitened) return pfail(MPSFM_EINVAL, "output pointer is NULL");
+  if (!flags || !depth || !depth3d || !magnitude || !param || !whitened) return fail(MPSFM_EINVAL, "output pointer is NULL");
   if (!g->map_h || !g->map_w || !g->depth_map || !g->valid_map || !g->sx || !g->sy || !g->cam_quat_xyzw || !g->cam_t)
-    return pfail(MPSFM_EINVAL, "image arrays are NULL");
-  if (!g->obs_img || !g->obs_xy || !g->obs_var || !g->obs_pt || !g->pts) return pfail(MPSFM_EINVAL, "observation arrays are NULL");
-  if (!(g->scale_filter_factor > 0.0)) return pfail(MPSFM_EINVAL, "scale_filter_factor must be positive");
+    return fail(MPSFM_EINVAL, "image arrays are NULL");
+  if (!g->obs_img || !g->obs_xy || !g->obs_var || !g->obs_pt || !g->pts) return fail(MPSFM_EINVAL, "observation arrays are NULL");
+  if (!(g->scale_filter_factor > 0.0)) return fail(MPSFM_EINVAL, "scale_filter_factor must be positive");
   std::vector<int64_t> off((size_t)g->n_images + 1, 0);
   for (int i = 0; i < g->n_images; ++i) {
-    if (g->map_h[i] < 2 || g->map_w[i] < 2 || !g->depth_map[i] || !g->valid_map[i]) return pfail(MPSFM_EINVAL, "map missing or smaller than 2x2");
+    if (g->map_h[i] < 2 || g->map_w[i] < 2 || !g->depth_map[i] || !g->valid_map[i]) return fail(MPSFM_EINVAL, "map missing or smaller than 2x2");
     off[(size_t)i + 1] = off[(size_t)i] + (int64_t)g->map_h[i] * g->map_w[i];
   }
   for (int64_t i = 0; i < g->n_obs; ++i)
     if (g->obs_img[i] < 0 || g->obs_img[i] >= g->n_images || g->obs_pt[i] < 0 || g->obs_pt[i] >= g->n_pts)
-      return pfail(MPSFM_EINVAL, "observation index out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return pfail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return pfail(MPSFM_EINVAL, "device ordinal out of range");
-  if (device >= kMaxDevices) return pfail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
-  PRI_TRY(hipSetDevice(device));
-  struct Blocks {  // a pooled non-blocking stream per call, never the legacy null stream (see DevBuf in tri_kernels.hip)
-    std::vector<void*> v;
-    hipStream_t st = nullptr;
-    ~Blocks() {
-      if (st) (void)hipStreamSynchronize(st);
-      for (void* p : v) cached_free(p);
-      release_stream(st);
-    }
-    void* get(size_t bytes) { void* p = cached_malloc(bytes ? bytes : 1); if (p) v.push_back(p); return p; }
-  } B;
-  PRI_TRY(pooled_stream(&B.st));
+      return fail(MPSFM_EINVAL, "observation index out of range");
+  if (int rc = open_device(device)) return rc;
+  CallScope B;
+  if (int rc = B.open()) return rc;
   const size_t ni = (size_t)g->n_images, no = (size_t)g->n_obs, npix = (size_t)off[ni];
   GatherArgs A{};
   A.n_obs = g->n_obs;
-#define PRI_UP(field, T, src, count)                                                      \
-  {                                                                                       \
-    T* p_ = (T*)B.get(sizeof(T) * (count));                                               \
-    if (!p_) return pfail(MPSFM_ENOMEM, "hipMalloc failed");                              \
-    if (int rc_ = staged_upload(p_, (src), sizeof(T) * (count))) return rc_;              \
-    A.field = p_;                                                                         \
-  }
-  PRI_UP(H, int32_t, g->map_h, ni) PRI_UP(W, int32_t, g->map_w, ni) PRI_UP(map_off, int64_t, off.data(), ni)
-  PRI_UP(sx, double, g->sx, ni) PRI_UP(sy, double, g->sy, ni) PRI_UP(q, double, g->cam_quat_xyzw, 4 * ni) PRI_UP(t, double, g->cam_t, 3 * ni)
-  PRI_UP(obs_img, int32_t, g->obs_img, no) PRI_UP(obs_xy, double, g->obs_xy, 2 * no) PRI_UP(obs_var, double, g->obs_var, no)
-  PRI_UP(obs_pt, int32_t, g->obs_pt, no) PRI_UP(pts, double, g->pts, 3 * (size_t)g->n_pts)
-#undef PRI_UP
-  double* d_depth = (double*)B.get(sizeof(double) * npix);
-  uint8_t* d_valid = (uint8_t*)B.get(npix);
-  if (!d_depth || !d_valid) return pfail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (int rc = B.up(&A.H, g->map_h, ni)) return rc;
+  if (int rc = B.up(&A.W, g->map_w, ni)) return rc;
+  if (int rc = B.up(&A.map_off, off.data(), ni)) return rc;
+  if (int rc = B.up(&A.sx, g->sx, ni)) return rc;
+  if (int rc = B.up(&A.sy, g->sy, ni)) return rc;
+  if (int rc = B.up(&A.q, g->cam_quat_xyzw, 4 * ni)) return rc;
+  if (int rc = B.up(&A.t, g->cam_t, 3 * ni)) return rc;
+  if (int rc = B.up(&A.obs_img, g->obs_img, no)) return rc;
+  if (int rc = B.up(&A.obs_xy, g->obs_xy, 2 * no)) return rc;
+  if (int rc = B.up(&A.obs_var, g->obs_var, no)) return rc;
+  if (int rc = B.up(&A.obs_pt, g->obs_pt, no)) return rc;
+  if (int rc = B.up(&A.pts, g->pts, 3 * (size_t)g->n_pts)) return rc;
+  double* d_depth = B.alloc<double>(npix);
+  uint8_t* d_valid = B.alloc<uint8_t>(npix);
+  if (!d_depth || !d_valid) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   for (size_t i = 0; i < ni; ++i) {
     const size_t n = (size_t)(off[i + 1] - off[i]);
     if (int rc = staged_upload(d_depth + off[i], g->depth_map[i], sizeof(double) * n)) return rc;
@@ -135,17 +113,17 @@ extern "C" int mpsfm_depth_blocks(const mpsfm_depth_gather* g, int32_t device, u
   }
   A.depth = d_depth; A.valid = d_valid;
   A.scale_filter = g->scale_filter; A.gross_outliers = g->gross_outliers; A.factor = g->scale_filter_factor; A.mult = g->multiplier;
-  A.flags = (uint8_t*)B.get(no);
+  A.flags = B.alloc<uint8_t>(no);
   double* outs[5];
-  for (auto& o : outs) { o = (double*)B.get(sizeof(double) * no); if (!o) return pfail(MPSFM_ENOMEM, "hipMalloc failed"); }
-  if (!A.flags) return pfail(MPSFM_ENOMEM, "hipMalloc failed");
+  for (auto& o : outs) { o = B.alloc<double>(no); if (!o) return fail(MPSFM_ENOMEM, "hipMalloc failed"); }
+  if (!A.flags) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   A.d_out = outs[0]; A.z_out = outs[1]; A.mag = outs[2]; A.par = outs[3]; A.whi = outs[4];
   if (int rc = staged_drain()) return rc;
   hipLaunchKernelGGL(k_depth_blocks, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, B.st, A);
-  PRI_TRY(hipGetLastError());
-  PRI_TRY(hipMemcpyAsync(flags, A.flags, no, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipGetLastError());
+  MPSFM_TRY(hipMemcpyAsync(flags, A.flags, no, hipMemcpyDeviceToHost, B.st));
   double* hosts[5] = {depth, depth3d, magnitude, param, whitened};
-  for (int k = 0; k < 5; ++k) PRI_TRY(hipMemcpyAsync(hosts[k], outs[k], sizeof(double) * no, hipMemcpyDeviceToHost, B.st));
-  PRI_TRY(hipStreamSynchronize(B.st));
+  for (int k = 0; k < 5; ++k) MPSFM_TRY(hipMemcpyAsync(hosts[k], outs[k], sizeof(double) * no, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipStreamSynchronize(B.st));
   return 0;
 }

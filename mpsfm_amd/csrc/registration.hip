@@ -13,18 +13,9 @@
 #include "common.h"
 #include "tri_math.h"         // default contraction, as in triangulator.hip: the two-view estimate equals k_tri_ransac's bit for bit
 #include "bilinear_sample.h"  // contraction off from here on: the samples, lifts and angles round every operation on its own
+#include "call_scope.h"
 
 namespace mpsfm {
-
-extern thread_local std::string g_err;
-int staged_upload(void* dst, const void* src, size_t bytes);
-int staged_drain();
-static int rfail(int code, const std::string& m) { g_err = m; return code; }
-#define REG_TRY(expr)                                                                                 \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess) return rfail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 constexpr int kT = 256;
@@ -156,38 +147,6 @@ __global__ __launch_bounds__(kT) void k_init_candidates(InitArgs A) {
   A.tri_ang[i] = ta; A.lift_ang[i] = la; A.d_prior[i] = d;
 }
 
-struct Blocks {  // a pooled non-blocking stream per call, never the legacy null stream (see DevBuf in tri_kernels.hip)
-  std::vector<void*> v;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~Blocks() {
-    if (st) (void)hipStreamSynchronize(st);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    for (void* p : v) cached_free(p);
-    release_stream(st);
-  }
-  void* get(size_t bytes) { void* p = cached_malloc(bytes ? bytes : 1); if (p) v.push_back(p); return p; }
-  template <typename T>
-  int up(const T** dst, const T* src, size_t count) {  // allocate + queue a staged upload
-    T* p = (T*)get(sizeof(T) * count);
-    if (!p) return rfail(MPSFM_ENOMEM, "hipMalloc failed");
-    *dst = p;
-    return staged_upload(p, src, sizeof(T) * count);
-  }
-};
-
-int open_device(int32_t device, Blocks& B) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return rfail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return rfail(MPSFM_EINVAL, "device ordinal out of range");
-  if (device >= kMaxDevices) return rfail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
-  REG_TRY(hipSetDevice(device));
-  REG_TRY(pooled_stream(&B.st));
-  REG_TRY(hipEventCreate(&B.ev[0]));
-  REG_TRY(hipEventCreate(&B.ev[1]));
-  return 0;
-}
 }  // namespace
 
 }  // namespace mpsfm
@@ -199,18 +158,18 @@ extern "C" int mpsfm_registration_pairs(int32_t n_refs, const mpsfm_reg_image* r
                                         const double* pts, int32_t lifted_registration, int32_t device, double* xyz, uint8_t* kind,
                                         float* ms) {
   if (ms) *ms = 0.f;
-  if (n_refs < 0 || n_matches < 0 || n_pts < 0) return rfail(MPSFM_EINVAL, "negative size");
-  if (n_matches > 0 && (!match_ref || !ref_xy || !match_pt || !xyz || !kind)) return rfail(MPSFM_EINVAL, "NULL pointer");
-  if (n_refs > 0 && !refs) return rfail(MPSFM_EINVAL, "refs is NULL");
-  if (n_pts > 0 && !pts) return rfail(MPSFM_EINVAL, "pts is NULL");
+  if (n_refs < 0 || n_matches < 0 || n_pts < 0) return fail(MPSFM_EINVAL, "negative size");
+  if (n_matches > 0 && (!match_ref || !ref_xy || !match_pt || !xyz || !kind)) return fail(MPSFM_EINVAL, "NULL pointer");
+  if (n_refs > 0 && !refs) return fail(MPSFM_EINVAL, "refs is NULL");
+  if (n_pts > 0 && !pts) return fail(MPSFM_EINVAL, "pts is NULL");
   std::vector<RegRef> R((size_t)n_refs);
   int64_t npix = 0;
   for (int32_t r = 0; r < n_refs; ++r) {
     const mpsfm_reg_image& I = refs[r];
     RegRef& o = R[(size_t)r];
     // without lifted_registration no map is read: it may be absent
-    if (lifted_registration && (I.map_h < 2 || I.map_w < 2 || !I.depth_map)) return rfail(MPSFM_EINVAL, "map missing or smaller than 2x2");
-    if (lifted_registration && (int64_t)I.map_h * I.map_w > (int64_t)1 << 30) return rfail(MPSFM_EINVAL, "map larger than 2^30 pixels");
+    if (lifted_registration && (I.map_h < 2 || I.map_w < 2 || !I.depth_map)) return fail(MPSFM_EINVAL, "map missing or smaller than 2x2");
+    if (lifted_registration && (int64_t)I.map_h * I.map_w > (int64_t)1 << 30) return fail(MPSFM_EINVAL, "map larger than 2^30 pixels");
     o.H = I.map_h; o.W = I.map_w; o.off = npix;
     if (lifted_registration) npix += (int64_t)I.map_h * I.map_w;
     o.sx = I.sx; o.sy = I.sy;
@@ -219,11 +178,12 @@ extern "C" int mpsfm_registration_pairs(int32_t n_refs, const mpsfm_reg_image* r
     for (int k = 0; k < 3; ++k) o.t[k] = I.t[k];
   }
   for (int64_t i = 0; i < n_matches; ++i) {
-    if (match_ref[i] < 0 || match_ref[i] >= n_refs) return rfail(MPSFM_EINVAL, "match_ref out of range");
-    if (match_pt[i] < -1 || match_pt[i] >= n_pts) return rfail(MPSFM_EINVAL, "match_pt out of range");
+    if (match_ref[i] < 0 || match_ref[i] >= n_refs) return fail(MPSFM_EINVAL, "match_ref out of range");
+    if (match_pt[i] < -1 || match_pt[i] >= n_pts) return fail(MPSFM_EINVAL, "match_pt out of range");
   }
-  Blocks B;
-  if (int rc = open_device(device, B)) return rc;
+  if (int rc = open_device(device)) return rc;
+  CallScope B;
+  if (int rc = B.open(true)) return rc;
   if (n_matches == 0) return 0;
   const size_t n = (size_t)n_matches;
   RegArgs A{};
@@ -236,40 +196,41 @@ extern "C" int mpsfm_registration_pairs(int32_t n_refs, const mpsfm_reg_image* r
   if (pt_risky && n_pts > 0)
     if (int rc = B.up(&A.risky, pt_risky, (size_t)n_pts)) return rc;
   if (int rc = B.up(&A.pts, pts, 3 * (size_t)n_pts)) return rc;
-  double* d_depth = (double*)B.get(sizeof(double) * (size_t)npix);
-  A.xyz = (double*)B.get(sizeof(double) * 3 * n);
-  A.kind = (uint8_t*)B.get(n);
-  if (!d_depth || !A.xyz || !A.kind) return rfail(MPSFM_ENOMEM, "hipMalloc failed");
+  double* d_depth = B.alloc<double>((size_t)npix);
+  A.xyz = B.alloc<double>(3 * n);
+  A.kind = B.alloc<uint8_t>(n);
+  if (!d_depth || !A.xyz || !A.kind) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   if (lifted_registration)
     for (int32_t r = 0; r < n_refs; ++r)
       if (int rc = staged_upload(d_depth + R[(size_t)r].off, refs[r].depth_map, sizeof(double) * (size_t)R[(size_t)r].H * R[(size_t)r].W)) return rc;
   A.depth = d_depth;
   if (int rc = staged_drain()) return rc;
-  REG_TRY(hipEventRecord(B.ev[0], B.st));
+  if (int rc = B.begin()) return rc;
   hipLaunchKernelGGL(k_reg_pairs, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, B.st, A);
-  REG_TRY(hipGetLastError());
-  REG_TRY(hipEventRecord(B.ev[1], B.st));
-  REG_TRY(hipMemcpyAsync(xyz, A.xyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipMemcpyAsync(kind, A.kind, n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipStreamSynchronize(B.st));
-  if (ms) REG_TRY(hipEventElapsedTime(ms, B.ev[0], B.ev[1]));
+  MPSFM_TRY(hipGetLastError());
+  if (int rc = B.stop()) return rc;
+  MPSFM_TRY(hipMemcpyAsync(xyz, A.xyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipMemcpyAsync(kind, A.kind, n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipStreamSynchronize(B.st));
+  if (ms) return B.elapsed(ms);
   return 0;
 }
 
 extern "C" int mpsfm_init_pair_candidates(const mpsfm_init_pair* p, int32_t device, mpsfm_init_candidates* out) {
-  if (!p || !out) return rfail(MPSFM_EINVAL, "NULL argument");
+  if (!p || !out) return fail(MPSFM_EINVAL, "NULL argument");
   out->ms = 0.f;
-  if (p->n_matches < 0) return rfail(MPSFM_EINVAL, "negative size");
-  if (p->what == 0 || (p->what & ~(MPSFM_INIT_TRIANGULATE | MPSFM_INIT_LIFT))) return rfail(MPSFM_EINVAL, "what must be MPSFM_INIT_TRIANGULATE, MPSFM_INIT_LIFT or both");
+  if (p->n_matches < 0) return fail(MPSFM_EINVAL, "negative size");
+  if (p->what == 0 || (p->what & ~(MPSFM_INIT_TRIANGULATE | MPSFM_INIT_LIFT))) return fail(MPSFM_EINVAL, "what must be MPSFM_INIT_TRIANGULATE, MPSFM_INIT_LIFT or both");
   const bool tri = p->what & MPSFM_INIT_TRIANGULATE, lift = p->what & MPSFM_INIT_LIFT;
   if (p->n_matches > 0 && (!p->xy1 || !out->flags || !out->tri_xyz || !out->tri_angle_deg || !out->lift_xyz || !out->lift_angle_deg || !out->d_prior))
-    return rfail(MPSFM_EINVAL, "NULL pointer");
-  if (p->n_matches > 0 && tri && !p->xy2) return rfail(MPSFM_EINVAL, "xy2 is NULL");
-  if (lift && (p->map_h < 2 || p->map_w < 2 || !p->prior_map || !p->valid_map)) return rfail(MPSFM_EINVAL, "map missing or smaller than 2x2");
-  if (lift && (int64_t)p->map_h * p->map_w > (int64_t)1 << 30) return rfail(MPSFM_EINVAL, "map larger than 2^30 pixels");
-  if (tri && !(p->tri_max_error >= 0.0)) return rfail(MPSFM_EINVAL, "tri_max_error must be non-negative");
-  Blocks B;
-  if (int rc = open_device(device, B)) return rc;
+    return fail(MPSFM_EINVAL, "NULL pointer");
+  if (p->n_matches > 0 && tri && !p->xy2) return fail(MPSFM_EINVAL, "xy2 is NULL");
+  if (lift && (p->map_h < 2 || p->map_w < 2 || !p->prior_map || !p->valid_map)) return fail(MPSFM_EINVAL, "map missing or smaller than 2x2");
+  if (lift && (int64_t)p->map_h * p->map_w > (int64_t)1 << 30) return fail(MPSFM_EINVAL, "map larger than 2^30 pixels");
+  if (tri && !(p->tri_max_error >= 0.0)) return fail(MPSFM_EINVAL, "tri_max_error must be non-negative");
+  if (int rc = open_device(device)) return rc;
+  CallScope B;
+  if (int rc = B.open(true)) return rc;
   if (p->n_matches == 0) return 0;
   const size_t n = (size_t)p->n_matches, npix = lift ? (size_t)p->map_h * p->map_w : 0;
   InitArgs A{};
@@ -292,22 +253,21 @@ extern "C" int mpsfm_init_pair_candidates(const mpsfm_init_pair* p, int32_t devi
     if (int rc = B.up(&A.valid, p->valid_map, npix)) return rc;
   }
   // one block for the float64 outputs: tri_xyz [3n] | lift_xyz [3n] | tri_ang [n] | lift_ang [n] | d_prior [n]
-  double* d_out = (double*)B.get(sizeof(double) * 9 * n);
-  A.flags = (uint8_t*)B.get(n);
-  if (!d_out || !A.flags) return rfail(MPSFM_ENOMEM, "hipMalloc failed");
+  double* d_out = B.alloc<double>(9 * n);
+  A.flags = B.alloc<uint8_t>(n);
+  if (!d_out || !A.flags) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   A.tri_xyz = d_out; A.lift_xyz = d_out + 3 * n; A.tri_ang = d_out + 6 * n; A.lift_ang = d_out + 7 * n; A.d_prior = d_out + 8 * n;
   if (int rc = staged_drain()) return rc;
-  REG_TRY(hipEventRecord(B.ev[0], B.st));
+  if (int rc = B.begin()) return rc;
   hipLaunchKernelGGL(k_init_candidates, dim3((unsigned)((n + kT - 1) / kT)), dim3(kT), 0, B.st, A);
-  REG_TRY(hipGetLastError());
-  REG_TRY(hipEventRecord(B.ev[1], B.st));
-  REG_TRY(hipMemcpyAsync(out->flags, A.flags, n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipMemcpyAsync(out->tri_xyz, A.tri_xyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipMemcpyAsync(out->lift_xyz, A.lift_xyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipMemcpyAsync(out->tri_angle_deg, A.tri_ang, sizeof(double) * n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipMemcpyAsync(out->lift_angle_deg, A.lift_ang, sizeof(double) * n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipMemcpyAsync(out->d_prior, A.d_prior, sizeof(double) * n, hipMemcpyDeviceToHost, B.st));
-  REG_TRY(hipStreamSynchronize(B.st));
-  REG_TRY(hipEventElapsedTime(&out->ms, B.ev[0], B.ev[1]));
-  return 0;
+  MPSFM_TRY(hipGetLastError());
+  if (int rc = B.stop()) return rc;
+  MPSFM_TRY(hipMemcpyAsync(out->flags, A.flags, n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipMemcpyAsync(out->tri_xyz, A.tri_xyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipMemcpyAsync(out->lift_xyz, A.lift_xyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipMemcpyAsync(out->tri_angle_deg, A.tri_ang, sizeof(double) * n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipMemcpyAsync(out->lift_angle_deg, A.lift_ang, sizeof(double) * n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipMemcpyAsync(out->d_prior, A.d_prior, sizeof(double) * n, hipMemcpyDeviceToHost, B.st));
+  MPSFM_TRY(hipStreamSynchronize(B.st));
+  return B.elapsed(&out->ms);
 }

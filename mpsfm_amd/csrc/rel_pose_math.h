@@ -1,6 +1,6 @@
-// Constant-size arithmetic of the relative-pose estimator (rel_pose.hip): the five-index counter sampler, the squared
-// Sampson error, ComputeNumTrials for any sample size, the five-point solver (nullspace -> 10 x 20 cubic constraints ->
-// Gauss-Jordan -> degree-10 polynomial -> real roots -> canonical essential matrices in lexicographic order) and the
+// Constant-size arithmetic of the relative-pose estimator (rel_pose.hip): the squared Sampson error, the five-point
+// solver (nullspace -> 10 x 20 cubic constraints -> Gauss-Jordan -> degree-10 polynomial -> real roots -> canonical
+// essential matrices in lexicographic order) and the
 // essential-matrix decomposition.  COLMAP 3.11 semantics of EssentialMatrixFivePointEstimator / ComputeSquaredSampsonError /
 // DecomposeEssentialMatrix / PoseFromEssentialMatrix as recalled (include/mpsfm_hip.h, mpsfm_rel_pose_estimate): parity with
 // the reference's COLMAP fork unpinned.
@@ -36,30 +36,6 @@ struct RpW {
   int s;
   __host__ __device__ double& operator[](int i) const { return p[(size_t)i * s]; }
 };
-
-// the five distinct indices of trial t (the recipe of ap_sample, first five distinct draws)
-__host__ __device__ inline void rp_sample(uint64_t seed, int64_t t, int32_t n, int32_t idx[kRpSample]) {
-  const uint64_t base = ap_mix(seed + (uint64_t)(t + 1) * kApPhi);
-  int k = 0;
-  for (uint64_t j = 1; k < kRpSample; ++j) {
-    const int32_t c = (int32_t)ap_mulhi(ap_mix(base + j * kApPhi), (uint64_t)n);
-    bool dup = false;
-    for (int i = 0; i < k; ++i) dup = dup || idx[i] == c;
-    if (!dup) idx[k++] = c;
-  }
-}
-
-// RANSAC::ComputeNumTrials with kMinNumSamples = sample_size
-__host__ __device__ inline int64_t rp_num_trials(int64_t num_inliers, int64_t n, double confidence, double multiplier, int sample_size) {
-  const double ratio = (double)num_inliers / (double)n;
-  const double nom = 1.0 - confidence;
-  if (nom <= 0.0) return INT64_MAX;
-  const double denom = 1.0 - pow(ratio, (double)sample_size);
-  if (denom <= 0.0) return 1;
-  if (denom == 1.0) return INT64_MAX;
-  const double v = ceil(log(nom) / log(denom) * multiplier);
-  return v >= 9.2e18 ? INT64_MAX : (int64_t)v;
-}
 
 // ComputeSquaredSampsonError of x2^T E x1 (E row-major, normalised points)
 __host__ __device__ inline double rp_sampson(const double* E, double u1, double v1, double u2, double v2) {
@@ -406,7 +382,7 @@ inline void rp_decompose(const double E[9], double R1[9], double R2[9], double t
   double A[3][3], V[3][3], ev[3];
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) A[i][j] = E[i] * E[j] + E[3 + i] * E[3 + j] + E[6 + i] * E[6 + j];
-  ap_sym_eig<3>(A, V, ev);  // ascending: column 2 = largest
+  sym_eig<3>(A, V, ev);  // ascending: column 2 = largest
   double v[3][3];           // v[c] = column c of V in descending singular-value order
   for (int c = 0; c < 3; ++c)
     for (int d = 0; d < 3; ++d) v[c][d] = V[d][2 - c];

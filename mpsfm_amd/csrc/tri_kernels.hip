@@ -12,56 +12,9 @@
 
 #include "common.h"
 #include "tri_math.h"
+#include "call_scope.h"
 
 namespace mpsfm {
-
-extern thread_local std::string g_err;
-static int tfail(int code, const std::string& m) { g_err = m; return code; }
-#define TRI_TRY(expr)                                                                                \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return tfail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-struct DevBuf {
-  std::vector<void*> ptrs;
-  // Every call works on a non-blocking stream of its own from the pool, never on the legacy null stream: the library is
-  // called from several host threads (tests, threaded callers), and null-stream copies / fills issued by one thread while
-  // another thread's solve had a deep queue of launches in flight corrupted that solve (MI355X, ROCm 7.2: reproduced with
-  // tests/test_gpu_fuzz.py::test_random_problems_concurrently until the last null-stream call was gone).
-  hipStream_t st = nullptr;
-  DevBuf() { if (pooled_stream(&st) != hipSuccess) st = nullptr; }
-  // the stream must be idle before the blocks go back to the caching allocator (an early return on a failed call would
-  // otherwise free memory that is still in use) and before the stream goes back to the pool
-  ~DevBuf() {
-    if (st) (void)hipStreamSynchronize(st);
-    for (void* p : ptrs) cached_free(p);
-    release_stream(st);
-  }
-  // device -> caller memory, complete on return
-  hipError_t down(void* host, const void* dev, size_t bytes) {
-    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-  }
-  template <typename T>
-  T* up(const T* host, size_t n, bool copy = true) {
-    void* p = nullptr;
-    p = cached_malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!p) return nullptr;
-    ptrs.push_back(p);
-    if (copy && n && host) (void)hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, st);
-    return (T*)p;
-  }
-};
-
-static int check_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return tfail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
-  if (device < 0 || device >= n) return tfail(MPSFM_EINVAL, "device ordinal out of range");
-  if (device >= kMaxDevices) return tfail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
-  TRI_TRY(hipSetDevice(device));
-  return 0;
-}
 
 // ---- point covariances -------------------------------------------------------------------------
 __global__ void k_pcov_accum(int64_t nobs, const int32_t* cam, const int32_t* pt, const double* q, const double* t,
@@ -200,34 +153,34 @@ __global__ void k_filter(TrackArgs T, const double* xyz, double* max_angle, doub
 }
 
 static int check_tracks(const mpsfm_tracks* T) {
-  if (!T || T->n_tracks < 0 || T->n_cams < 0) return tfail(MPSFM_EINVAL, "tracks is NULL or has negative sizes");
-  if (T->n_tracks > 0 && !T->track_start) return tfail(MPSFM_EINVAL, "track_start is NULL");
+  if (!T || T->n_tracks < 0 || T->n_cams < 0) return fail(MPSFM_EINVAL, "tracks is NULL or has negative sizes");
+  if (T->n_tracks > 0 && !T->track_start) return fail(MPSFM_EINVAL, "track_start is NULL");
   if (T->n_tracks == 0) return 0;
   if (T->n_intr < 0 || (T->n_cams > 0 && (!T->cam_quat_xyzw || !T->cam_t || !T->cam_intr || !T->cam_intr_idx)))
-    return tfail(MPSFM_EINVAL, "camera arrays are NULL");
-  if (T->track_start[0] != 0) return tfail(MPSFM_EINVAL, "track_start[0] must be 0");
+    return fail(MPSFM_EINVAL, "camera arrays are NULL");
+  if (T->track_start[0] != 0) return fail(MPSFM_EINVAL, "track_start[0] must be 0");
   for (int i = 0; i < T->n_tracks; ++i)
-    if (T->track_start[i + 1] < T->track_start[i]) return tfail(MPSFM_EINVAL, "track_start must be non-decreasing");
+    if (T->track_start[i + 1] < T->track_start[i]) return fail(MPSFM_EINVAL, "track_start must be non-decreasing");
   const int64_t ne = T->track_start[T->n_tracks];
-  if (ne > 0 && (!T->el_cam || !T->el_xy)) return tfail(MPSFM_EINVAL, "track element arrays are NULL");
+  if (ne > 0 && (!T->el_cam || !T->el_xy)) return fail(MPSFM_EINVAL, "track element arrays are NULL");
   for (int64_t e = 0; e < ne; ++e)
-    if (T->el_cam[e] < 0 || T->el_cam[e] >= T->n_cams) return tfail(MPSFM_EINVAL, "el_cam out of range");
+    if (T->el_cam[e] < 0 || T->el_cam[e] >= T->n_cams) return fail(MPSFM_EINVAL, "el_cam out of range");
   for (int i = 0; i < T->n_cams; ++i)
-    if (T->cam_intr_idx[i] < 0 || T->cam_intr_idx[i] >= T->n_intr) return tfail(MPSFM_EINVAL, "cam_intr_idx out of range");
+    if (T->cam_intr_idx[i] < 0 || T->cam_intr_idx[i] >= T->n_intr) return fail(MPSFM_EINVAL, "cam_intr_idx out of range");
   return 0;
 }
 
-static int upload_tracks(const mpsfm_tracks* T, DevBuf& B, TrackArgs& a) {
+static int upload_tracks(const mpsfm_tracks* T, CallScope& B, TrackArgs& a) {
   const int64_t ne = T->n_tracks > 0 ? T->track_start[T->n_tracks] : 0;
   a.n_tracks = T->n_tracks;
-  a.q = B.up(T->cam_quat_xyzw, (size_t)T->n_cams * 4);
-  a.t = B.up(T->cam_t, (size_t)T->n_cams * 3);
-  a.intr = B.up(T->cam_intr, (size_t)T->n_intr * 4);
-  a.intr_idx = B.up(T->cam_intr_idx, (size_t)T->n_cams);
-  a.start = B.up(T->track_start, (size_t)T->n_tracks + 1);
-  a.el_cam = B.up(T->el_cam, (size_t)ne);
-  a.el_xy = B.up(T->el_xy, (size_t)ne * 2);
-  if (!a.q || !a.t || !a.intr || !a.intr_idx || !a.start || !a.el_cam || !a.el_xy) return tfail(MPSFM_ENOMEM, "hipMalloc failed");
+  a.q = B.put(T->cam_quat_xyzw, (size_t)T->n_cams * 4);
+  a.t = B.put(T->cam_t, (size_t)T->n_cams * 3);
+  a.intr = B.put(T->cam_intr, (size_t)T->n_intr * 4);
+  a.intr_idx = B.put(T->cam_intr_idx, (size_t)T->n_cams);
+  a.start = B.put(T->track_start, (size_t)T->n_tracks + 1);
+  a.el_cam = B.put(T->el_cam, (size_t)ne);
+  a.el_xy = B.put(T->el_xy, (size_t)ne * 2);
+  if (!a.q || !a.t || !a.intr || !a.intr_idx || !a.start || !a.el_cam || !a.el_xy) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   return 0;
 }
 
@@ -238,78 +191,78 @@ using namespace mpsfm;
 extern "C" {
 
 int mpsfm_point_covs(const mpsfm_ba_problem* P, const mpsfm_ba_state* st, int32_t device, double* covs) {
-  if (!P || !st || !covs) return tfail(MPSFM_EINVAL, "NULL argument");
-  if (P->n_pts < 0 || P->n_cams < 0 || P->n_obs < 0 || P->n_intr < 0) return tfail(MPSFM_EINVAL, "negative size");
-  if (P->n_obs > 0 && (!P->obs_cam || !P->obs_pt || !P->obs_xy)) return tfail(MPSFM_EINVAL, "observation arrays are NULL");
-  if (P->n_cams > 0 && (!P->cam_intr_idx || !P->cam_intr || !st->cam_quat_xyzw || !st->cam_t)) return tfail(MPSFM_EINVAL, "camera arrays are NULL");
-  if (P->n_pts > 0 && !st->pts) return tfail(MPSFM_EINVAL, "pts is NULL");
+  if (!P || !st || !covs) return fail(MPSFM_EINVAL, "NULL argument");
+  if (P->n_pts < 0 || P->n_cams < 0 || P->n_obs < 0 || P->n_intr < 0) return fail(MPSFM_EINVAL, "negative size");
+  if (P->n_obs > 0 && (!P->obs_cam || !P->obs_pt || !P->obs_xy)) return fail(MPSFM_EINVAL, "observation arrays are NULL");
+  if (P->n_cams > 0 && (!P->cam_intr_idx || !P->cam_intr || !st->cam_quat_xyzw || !st->cam_t)) return fail(MPSFM_EINVAL, "camera arrays are NULL");
+  if (P->n_pts > 0 && !st->pts) return fail(MPSFM_EINVAL, "pts is NULL");
   for (int64_t i = 0; i < P->n_obs; ++i)
     if (P->obs_cam[i] < 0 || P->obs_cam[i] >= P->n_cams || P->obs_pt[i] < 0 || P->obs_pt[i] >= P->n_pts)
-      return tfail(MPSFM_EINVAL, "observation index out of range");
+      return fail(MPSFM_EINVAL, "observation index out of range");
   for (int i = 0; i < P->n_cams; ++i)
-    if (P->cam_intr_idx[i] < 0 || P->cam_intr_idx[i] >= P->n_intr) return tfail(MPSFM_EINVAL, "cam_intr_idx out of range");
-  if (int rc = check_device(device)) return rc;
+    if (P->cam_intr_idx[i] < 0 || P->cam_intr_idx[i] >= P->n_intr) return fail(MPSFM_EINVAL, "cam_intr_idx out of range");
+  if (int rc = open_device(device)) return rc;
   if (P->n_pts == 0) return 0;
-  DevBuf B;
-  if (!B.st) return tfail(MPSFM_EHIP, "hipStreamCreate failed");
-  const int32_t* cam = B.up(P->obs_cam, (size_t)P->n_obs);
-  const int32_t* pt = B.up(P->obs_pt, (size_t)P->n_obs);
-  const double* q = B.up(st->cam_quat_xyzw, (size_t)P->n_cams * 4);
-  const double* t = B.up(st->cam_t, (size_t)P->n_cams * 3);
-  const double* intr = B.up(P->cam_intr, (size_t)P->n_intr * 4);
-  const int32_t* iidx = B.up(P->cam_intr_idx, (size_t)P->n_cams);
-  const double* pts = B.up(st->pts, (size_t)P->n_pts * 3);
-  double* H = B.up<double>(nullptr, (size_t)P->n_pts * 6, false);
-  double* dcov = B.up<double>(nullptr, (size_t)P->n_pts * 9, false);
-  if (!cam || !pt || !q || !t || !intr || !iidx || !pts || !H || !dcov) return tfail(MPSFM_ENOMEM, "hipMalloc failed");
-  TRI_TRY(hipMemsetAsync(H, 0, sizeof(double) * 6 * (size_t)P->n_pts, B.st));
+  CallScope B;
+  if (int rc = B.open()) return rc;
+  const int32_t* cam = B.put(P->obs_cam, (size_t)P->n_obs);
+  const int32_t* pt = B.put(P->obs_pt, (size_t)P->n_obs);
+  const double* q = B.put(st->cam_quat_xyzw, (size_t)P->n_cams * 4);
+  const double* t = B.put(st->cam_t, (size_t)P->n_cams * 3);
+  const double* intr = B.put(P->cam_intr, (size_t)P->n_intr * 4);
+  const int32_t* iidx = B.put(P->cam_intr_idx, (size_t)P->n_cams);
+  const double* pts = B.put(st->pts, (size_t)P->n_pts * 3);
+  double* H = B.alloc<double>((size_t)P->n_pts * 6);
+  double* dcov = B.alloc<double>((size_t)P->n_pts * 9);
+  if (!cam || !pt || !q || !t || !intr || !iidx || !pts || !H || !dcov) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  MPSFM_TRY(hipMemsetAsync(H, 0, sizeof(double) * 6 * (size_t)P->n_pts, B.st));
   if (P->n_obs > 0)
     hipLaunchKernelGGL(k_pcov_accum, dim3((unsigned)((P->n_obs + 255) / 256)), dim3(256), 0, B.st, P->n_obs, cam, pt, q, t, intr,
                        iidx, pts, P->reproj_loss_magnitude, H);
   hipLaunchKernelGGL(k_pcov_invert, dim3((P->n_pts + 255) / 256), dim3(256), 0, B.st, P->n_pts, H, dcov);
-  TRI_TRY(hipGetLastError());
-  TRI_TRY(B.down(covs, dcov, sizeof(double) * 9 * (size_t)P->n_pts));
+  MPSFM_TRY(hipGetLastError());
+  MPSFM_TRY(B.down(covs, dcov, sizeof(double) * 9 * (size_t)P->n_pts));
   return 0;
 }
 
 int mpsfm_triangulate_tracks(const mpsfm_tracks* T, int32_t device, double* xyz) {
   if (int rc = check_tracks(T)) return rc;
-  if (!xyz && T->n_tracks > 0) return tfail(MPSFM_EINVAL, "xyz is NULL");
-  if (int rc = check_device(device)) return rc;
+  if (!xyz && T->n_tracks > 0) return fail(MPSFM_EINVAL, "xyz is NULL");
+  if (int rc = open_device(device)) return rc;
   if (T->n_tracks == 0) return 0;
-  DevBuf B;
-  if (!B.st) return tfail(MPSFM_EHIP, "hipStreamCreate failed");
+  CallScope B;
+  if (int rc = B.open()) return rc;
   TrackArgs a{};
   if (int rc = upload_tracks(T, B, a)) return rc;
-  double* dxyz = B.up<double>(nullptr, (size_t)T->n_tracks * 3, false);
-  if (!dxyz) return tfail(MPSFM_ENOMEM, "hipMalloc failed");
+  double* dxyz = B.alloc<double>((size_t)T->n_tracks * 3);
+  if (!dxyz) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   hipLaunchKernelGGL(k_triangulate, dim3((T->n_tracks + 127) / 128), dim3(128), 0, B.st, a, dxyz);
-  TRI_TRY(hipGetLastError());
-  TRI_TRY(B.down(xyz, dxyz, sizeof(double) * 3 * (size_t)T->n_tracks));
+  MPSFM_TRY(hipGetLastError());
+  MPSFM_TRY(B.down(xyz, dxyz, sizeof(double) * 3 * (size_t)T->n_tracks));
   return 0;
 }
 
 int mpsfm_filter_tracks(const mpsfm_tracks* T, const double* xyz, int32_t device, double* max_tri_angle, double* el_sq_err,
                         uint8_t* el_front) {
   if (int rc = check_tracks(T)) return rc;
-  if (!xyz && T->n_tracks > 0) return tfail(MPSFM_EINVAL, "xyz is NULL");
-  if (int rc = check_device(device)) return rc;
+  if (!xyz && T->n_tracks > 0) return fail(MPSFM_EINVAL, "xyz is NULL");
+  if (int rc = open_device(device)) return rc;
   if (T->n_tracks == 0) return 0;
   const int64_t ne = T->track_start[T->n_tracks];
-  DevBuf B;
-  if (!B.st) return tfail(MPSFM_EHIP, "hipStreamCreate failed");
+  CallScope B;
+  if (int rc = B.open()) return rc;
   TrackArgs a{};
   if (int rc = upload_tracks(T, B, a)) return rc;
-  const double* dxyz = B.up(xyz, (size_t)T->n_tracks * 3);
-  double* dang = max_tri_angle ? B.up<double>(nullptr, (size_t)T->n_tracks, false) : nullptr;
-  double* derr = el_sq_err ? B.up<double>(nullptr, (size_t)ne, false) : nullptr;
-  uint8_t* dfr = el_front ? B.up<uint8_t>(nullptr, (size_t)ne, false) : nullptr;
-  if (!dxyz || (max_tri_angle && !dang) || (el_sq_err && !derr) || (el_front && !dfr)) return tfail(MPSFM_ENOMEM, "hipMalloc failed");
+  const double* dxyz = B.put(xyz, (size_t)T->n_tracks * 3);
+  double* dang = max_tri_angle ? B.alloc<double>((size_t)T->n_tracks) : nullptr;
+  double* derr = el_sq_err ? B.alloc<double>((size_t)ne) : nullptr;
+  uint8_t* dfr = el_front ? B.alloc<uint8_t>((size_t)ne) : nullptr;
+  if (!dxyz || (max_tri_angle && !dang) || (el_sq_err && !derr) || (el_front && !dfr)) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   hipLaunchKernelGGL(k_filter, dim3((T->n_tracks + 127) / 128), dim3(128), 0, B.st, a, dxyz, dang, derr, dfr);
-  TRI_TRY(hipGetLastError());
-  if (dang) TRI_TRY(B.down(max_tri_angle, dang, sizeof(double) * (size_t)T->n_tracks));
-  if (derr) TRI_TRY(B.down(el_sq_err, derr, sizeof(double) * (size_t)ne));
-  if (dfr) TRI_TRY(B.down(el_front, dfr, (size_t)ne));
+  MPSFM_TRY(hipGetLastError());
+  if (dang) MPSFM_TRY(B.down(max_tri_angle, dang, sizeof(double) * (size_t)T->n_tracks));
+  if (derr) MPSFM_TRY(B.down(el_sq_err, derr, sizeof(double) * (size_t)ne));
+  if (dfr) MPSFM_TRY(B.down(el_front, dfr, (size_t)ne));
   return 0;
 }
 

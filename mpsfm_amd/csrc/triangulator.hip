@@ -25,12 +25,9 @@
 
 #include "common.h"
 #include "tri_math.h"
+#include "call_scope.h"
 
 namespace mpsfm {
-extern thread_local std::string g_err;
-int staged_upload(void* dst, const void* src, size_t bytes);
-int staged_drain();
-static int gfail(int code, const std::string& m) { g_err = m; return code; }
 
 struct TriCand {  // one candidate track handed to the batch kernel
   int64_t v0;     // first view in the view array
@@ -48,6 +45,23 @@ __global__ __launch_bounds__(64) void k_tri_ransac(const TriCand* cands, const T
   r.ok = tri_ransac(views + c.v0, c.n, c.opt, r.X, m) ? 1 : 0;
   r.mask = m[0];
   out[i] = r;
+}
+
+// EstimateTriangulation of a batch: candidates and views up, one k_tri_ransac launch, the results back (complete on return)
+static int run_tri_ransac(const std::vector<TriCand>& cands, const std::vector<TriView>& views, TriResult* results) {
+  const size_t nc = cands.size();
+  CallScope S;
+  TriCand* d_c = S.alloc<TriCand>(nc);
+  TriView* d_v = S.alloc<TriView>(views.size());
+  TriResult* d_r = S.alloc<TriResult>(nc);
+  if (!d_c || !d_v || !d_r) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (int rc = staged_upload(d_c, cands.data(), sizeof(TriCand) * nc)) return rc;
+  if (int rc = staged_upload(d_v, views.data(), sizeof(TriView) * views.size())) return rc;
+  if (int rc = staged_drain()) return rc;
+  if (int rc = S.open()) return rc;
+  hipLaunchKernelGGL(k_tri_ransac, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, S.st, d_c, d_v, (int)nc, d_r);
+  MPSFM_TRY(S.down(results, d_r, sizeof(TriResult) * nc));
+  return 0;
 }
 }  // namespace mpsfm
 
@@ -208,24 +222,8 @@ struct mpsfm_triangulator {
       }
       return 0;
     }
-    if (hipSetDevice(device) != hipSuccess) return gfail(MPSFM_EHIP, "hipSetDevice failed");
-    TriCand* d_c = (TriCand*)cached_malloc(sizeof(TriCand) * nc);
-    TriView* d_v = (TriView*)cached_malloc(sizeof(TriView) * views.size());
-    TriResult* d_r = (TriResult*)cached_malloc(sizeof(TriResult) * nc);
-    int rc = 0;
-    if (!d_c || !d_v || !d_r) rc = gfail(MPSFM_ENOMEM, "hipMalloc failed");
-    if (!rc) rc = staged_upload(d_c, cands.data(), sizeof(TriCand) * nc);
-    if (!rc) rc = staged_upload(d_v, views.data(), sizeof(TriView) * views.size());
-    if (!rc) rc = staged_drain();
-    hipStream_t st = nullptr;  // a pooled non-blocking stream, never the legacy null stream (see DevBuf in tri_kernels.hip)
-    if (!rc && pooled_stream(&st) != hipSuccess) rc = gfail(MPSFM_EHIP, "hipStreamCreate failed");
-    if (!rc) {
-      hipLaunchKernelGGL(k_tri_ransac, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, d_c, d_v, (int)nc, d_r);
-      if (hipMemcpyAsync(B.results.data(), d_r, sizeof(TriResult) * nc, hipMemcpyDeviceToHost, st) != hipSuccess) rc = gfail(MPSFM_EHIP, "reading the RANSAC batch back failed");
-    }
-    if (st) { (void)hipStreamSynchronize(st); release_stream(st); }
-    cached_free(d_c); cached_free(d_v); cached_free(d_r);
-    return rc;
+    MPSFM_TRY(hipSetDevice(device));
+    return run_tri_ransac(cands, views, B.results.data());
   }
   // estimate a candidate set: the batch result when set and options are what the batch ran with, else on the spot (host;
   // also every set longer than kTriMaxViews, which the batch never takes)
@@ -461,7 +459,7 @@ struct mpsfm_triangulator {
   }
 };
 
-static int check_engine(mpsfm_triangulator* h) { return h ? 0 : gfail(MPSFM_EINVAL, "triangulator handle is NULL"); }
+static int check_engine(mpsfm_triangulator* h) { return h ? 0 : fail(MPSFM_EINVAL, "triangulator handle is NULL"); }
 
 extern "C" {
 
@@ -473,20 +471,17 @@ void mpsfm_tri_default_options(mpsfm_tri_options* o) {
 }
 
 int mpsfm_triangulator_create(const mpsfm_tri_graph* g, int32_t device, mpsfm_triangulator** out) {
-  if (!g || !out) return gfail(MPSFM_EINVAL, "NULL argument");
+  if (!g || !out) return fail(MPSFM_EINVAL, "NULL argument");
   *out = nullptr;
-  if (g->n_images < 0 || (g->n_images > 0 && (!g->kp_start || !g->cam_intr))) return gfail(MPSFM_EINVAL, "image arrays are NULL");
+  if (g->n_images < 0 || (g->n_images > 0 && (!g->kp_start || !g->cam_intr))) return fail(MPSFM_EINVAL, "image arrays are NULL");
   const int64_t nkp = g->n_images > 0 ? g->kp_start[g->n_images] : 0;
-  if (nkp < 0 || (nkp > 0 && (!g->kp_xy || !g->corr_start))) return gfail(MPSFM_EINVAL, "keypoint arrays are NULL");
-  for (int i = 0; i < g->n_images; ++i) if (g->kp_start[i + 1] < g->kp_start[i]) return gfail(MPSFM_EINVAL, "kp_start must be non-decreasing");
+  if (nkp < 0 || (nkp > 0 && (!g->kp_xy || !g->corr_start))) return fail(MPSFM_EINVAL, "keypoint arrays are NULL");
+  for (int i = 0; i < g->n_images; ++i) if (g->kp_start[i + 1] < g->kp_start[i]) return fail(MPSFM_EINVAL, "kp_start must be non-decreasing");
   const int64_t nco = nkp > 0 ? g->corr_start[nkp] : 0;
-  if (nco > 0 && !g->corr_kp) return gfail(MPSFM_EINVAL, "corr_kp is NULL");
-  for (int64_t k = 0; k < nkp; ++k) if (g->corr_start[k + 1] < g->corr_start[k]) return gfail(MPSFM_EINVAL, "corr_start must be non-decreasing");
-  for (int64_t e = 0; e < nco; ++e) if (g->corr_kp[e] < 0 || g->corr_kp[e] >= nkp) return gfail(MPSFM_EINVAL, "correspondence out of range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gfail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return gfail(MPSFM_EINVAL, "device ordinal out of range");
-  if (device >= kMaxDevices) return gfail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
+  if (nco > 0 && !g->corr_kp) return fail(MPSFM_EINVAL, "corr_kp is NULL");
+  for (int64_t k = 0; k < nkp; ++k) if (g->corr_start[k + 1] < g->corr_start[k]) return fail(MPSFM_EINVAL, "corr_start must be non-decreasing");
+  for (int64_t e = 0; e < nco; ++e) if (g->corr_kp[e] < 0 || g->corr_kp[e] >= nkp) return fail(MPSFM_EINVAL, "correspondence out of range");
+  if (int rc = open_device(device)) return rc;
   auto* h = new mpsfm_triangulator();
   h->device = device;
   h->n_images = g->n_images;
@@ -510,7 +505,7 @@ void mpsfm_triangulator_destroy(mpsfm_triangulator* h) { delete h; }
 int mpsfm_triangulator_set_state(mpsfm_triangulator* h, const mpsfm_tri_state* s) {
   if (int rc = check_engine(h)) return rc;
   if (!s || (h->n_images > 0 && (!s->registered || !s->cam_quat_xyzw || !s->cam_t)) || (h->n_kp() > 0 && !s->kp_point) || (s->n_points > 0 && !s->xyz))
-    return gfail(MPSFM_EINVAL, "state arrays are NULL");
+    return fail(MPSFM_EINVAL, "state arrays are NULL");
   for (int i = 0; i < h->n_images; ++i) {
     h->registered[(size_t)i] = s->registered[i];
     quat_to_R(s->cam_quat_xyzw + 4 * i, &h->R[9 * (size_t)i]);
@@ -524,7 +519,7 @@ int mpsfm_triangulator_set_state(mpsfm_triangulator* h, const mpsfm_tri_state* s
   }
   for (int64_t k = 0; k < h->n_kp(); ++k) {
     const int64_t p = s->kp_point[k];
-    if (p >= s->n_points) return gfail(MPSFM_EINVAL, "kp_point out of range");
+    if (p >= s->n_points) return fail(MPSFM_EINVAL, "kp_point out of range");
     h->kp_pt[(size_t)k] = p < 0 ? -1 : p;
     if (p >= 0) h->pts[(size_t)p].els.push_back(k);
   }
@@ -538,21 +533,21 @@ static void begin_call(mpsfm_triangulator* h) { h->ops.clear(); h->op_els.clear(
 
 int mpsfm_triangulator_triangulate_image(mpsfm_triangulator* h, const mpsfm_tri_options* o, int32_t image, int64_t* count) {
   if (int rc = check_engine(h)) return rc;
-  if (!o || !count || image < 0 || image >= h->n_images) return gfail(MPSFM_EINVAL, "bad argument");
+  if (!o || !count || image < 0 || image >= h->n_images) return fail(MPSFM_EINVAL, "bad argument");
   begin_call(h);
   return h->triangulate_image(*o, image, count);
 }
 
 int mpsfm_triangulator_complete_image(mpsfm_triangulator* h, const mpsfm_tri_options* o, int32_t image, int64_t* count) {
   if (int rc = check_engine(h)) return rc;
-  if (!o || !count || image < 0 || image >= h->n_images) return gfail(MPSFM_EINVAL, "bad argument");
+  if (!o || !count || image < 0 || image >= h->n_images) return fail(MPSFM_EINVAL, "bad argument");
   begin_call(h);
   return h->complete_image(*o, image, count);
 }
 
 int mpsfm_triangulator_complete_tracks(mpsfm_triangulator* h, const mpsfm_tri_options* o, const int64_t* points, int64_t n, int64_t* count) {
   if (int rc = check_engine(h)) return rc;
-  if (!o || !count || (n > 0 && !points)) return gfail(MPSFM_EINVAL, "bad argument");
+  if (!o || !count || (n > 0 && !points)) return fail(MPSFM_EINVAL, "bad argument");
   begin_call(h);
   *count = 0;
   if (n < 0) { for (int64_t p = 0, np = (int64_t)h->pts.size(); p < np; ++p) *count += (int64_t)h->complete(*o, p); }  // all tracks
@@ -562,7 +557,7 @@ int mpsfm_triangulator_complete_tracks(mpsfm_triangulator* h, const mpsfm_tri_op
 
 int mpsfm_triangulator_merge_tracks(mpsfm_triangulator* h, const mpsfm_tri_options* o, const int64_t* points, int64_t n, int64_t* count) {
   if (int rc = check_engine(h)) return rc;
-  if (!o || !count || (n > 0 && !points)) return gfail(MPSFM_EINVAL, "bad argument");
+  if (!o || !count || (n > 0 && !points)) return fail(MPSFM_EINVAL, "bad argument");
   begin_call(h);
   *count = 0;
   if (n < 0) { for (int64_t p = 0, np = (int64_t)h->pts.size(); p < np; ++p) *count += (int64_t)h->merge(*o, p); }
@@ -572,7 +567,7 @@ int mpsfm_triangulator_merge_tracks(mpsfm_triangulator* h, const mpsfm_tri_optio
 
 int mpsfm_triangulator_retriangulate(mpsfm_triangulator* h, const mpsfm_tri_options* o, const int32_t* ignore_images, int32_t n_ignore, int64_t* count) {
   if (int rc = check_engine(h)) return rc;
-  if (!o || !count || (n_ignore > 0 && !ignore_images)) return gfail(MPSFM_EINVAL, "bad argument");
+  if (!o || !count || (n_ignore > 0 && !ignore_images)) return fail(MPSFM_EINVAL, "bad argument");
   begin_call(h);
   std::unordered_set<int> ig(ignore_images, ignore_images + (n_ignore > 0 ? n_ignore : 0));
   return h->retriangulate(*o, ig, count);
@@ -599,20 +594,17 @@ int mpsfm_triangulator_get_op_elements(mpsfm_triangulator* h, int64_t* els) {
 // EstimateTriangulation of independent candidate tracks in one k_tri_ransac launch (the engine's batch, exposed for callers
 // that hold candidate sets themselves and for the parity tests against oracle/track_graph_oracle.py).
 int mpsfm_tri_estimate_batch(const mpsfm_tri_candidates* c, int32_t device, double* xyz, uint8_t* ok, uint8_t* inlier) {
-  if (!c || c->n_candidates < 0 || (c->n_candidates > 0 && (!c->cand_start || !xyz || !ok))) return gfail(MPSFM_EINVAL, "NULL argument");
+  if (!c || c->n_candidates < 0 || (c->n_candidates > 0 && (!c->cand_start || !xyz || !ok))) return fail(MPSFM_EINVAL, "NULL argument");
   const int64_t nc = c->n_candidates;
   const int64_t nv = nc > 0 ? c->cand_start[nc] : 0;
-  if (nv > 0 && (!c->view_cam_from_world || !c->view_intr || !c->view_xy || !inlier)) return gfail(MPSFM_EINVAL, "view arrays are NULL");
-  if (c->residual_type != TRI_RESIDUAL_ANGULAR && c->residual_type != TRI_RESIDUAL_REPROJECTION) return gfail(MPSFM_EINVAL, "unknown residual type");
+  if (nv > 0 && (!c->view_cam_from_world || !c->view_intr || !c->view_xy || !inlier)) return fail(MPSFM_EINVAL, "view arrays are NULL");
+  if (c->residual_type != TRI_RESIDUAL_ANGULAR && c->residual_type != TRI_RESIDUAL_REPROJECTION) return fail(MPSFM_EINVAL, "unknown residual type");
   for (int64_t i = 0; i < nc; ++i) {
     const int64_t n = c->cand_start[i + 1] - c->cand_start[i];
-    if (n < 0) return gfail(MPSFM_EINVAL, "cand_start must be non-decreasing");
-    if (n > kTriMaxViews) return gfail(MPSFM_EUNSUPPORTED, "a candidate track exceeds 64 views (the batch kernel's scratch)");
+    if (n < 0) return fail(MPSFM_EINVAL, "cand_start must be non-decreasing");
+    if (n > kTriMaxViews) return fail(MPSFM_EUNSUPPORTED, "a candidate track exceeds 64 views (the batch kernel's scratch)");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gfail(MPSFM_ENODEVICE, "no HIP device visible: libmpsfm_hip has no CPU fallback");
-  if (device < 0 || device >= ndev) return gfail(MPSFM_EINVAL, "device ordinal out of range");
-  if (device >= kMaxDevices) return gfail(MPSFM_EUNSUPPORTED, "device ordinals beyond 15 are not supported (per-device pools)");
+  if (int rc = open_device(device)) return rc;
   if (nc == 0) return 0;
   std::vector<TriCand> cands((size_t)nc);
   std::vector<TriView> views((size_t)nv);
@@ -630,25 +622,8 @@ int mpsfm_tri_estimate_batch(const mpsfm_tri_candidates* c, int32_t device, doub
     r.residual_type = c->residual_type;
     cands[(size_t)i].v0 = c->cand_start[i]; cands[(size_t)i].n = (int32_t)n; cands[(size_t)i].opt = r;
   }
-  if (hipSetDevice(device) != hipSuccess) return gfail(MPSFM_EHIP, "hipSetDevice failed");
   std::vector<TriResult> results((size_t)nc);
-  TriCand* d_c = (TriCand*)cached_malloc(sizeof(TriCand) * (size_t)nc);
-  TriView* d_v = (TriView*)cached_malloc(sizeof(TriView) * (size_t)(nv > 0 ? nv : 1));
-  TriResult* d_r = (TriResult*)cached_malloc(sizeof(TriResult) * (size_t)nc);
-  int rc = 0;
-  if (!d_c || !d_v || !d_r) rc = gfail(MPSFM_ENOMEM, "hipMalloc failed");
-  if (!rc) rc = staged_upload(d_c, cands.data(), sizeof(TriCand) * (size_t)nc);
-  if (!rc && nv > 0) rc = staged_upload(d_v, views.data(), sizeof(TriView) * (size_t)nv);
-  if (!rc) rc = staged_drain();
-  hipStream_t st = nullptr;
-  if (!rc && pooled_stream(&st) != hipSuccess) rc = gfail(MPSFM_EHIP, "hipStreamCreate failed");
-  if (!rc) {
-    hipLaunchKernelGGL(k_tri_ransac, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, st, d_c, d_v, (int)nc, d_r);
-    if (hipMemcpyAsync(results.data(), d_r, sizeof(TriResult) * (size_t)nc, hipMemcpyDeviceToHost, st) != hipSuccess) rc = gfail(MPSFM_EHIP, "reading the RANSAC batch back failed");
-  }
-  if (st) { (void)hipStreamSynchronize(st); release_stream(st); }
-  cached_free(d_c); cached_free(d_v); cached_free(d_r);
-  if (rc) return rc;
+  if (int rc = run_tri_ransac(cands, views, results.data())) return rc;
   for (int64_t i = 0; i < nc; ++i) {
     const TriResult& r = results[(size_t)i];
     ok[i] = (uint8_t)r.ok;

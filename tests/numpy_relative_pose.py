@@ -27,8 +27,10 @@ import math
 
 import numpy as np
 
-MASK64 = (1 << 64) - 1
-PHI = 0x9E3779B97F4A7C15
+from numpy_loransac import MASK64, PHI, _better, _mix, _support  # noqa: F401  (names the tests use)
+from numpy_loransac import num_trials as _num_trials
+from numpy_loransac import sample as _sample
+
 DBL_MAX = np.finfo(np.float64).max
 DBL_EPS = np.finfo(np.float64).eps
 MAX_ROOT_IMAG = 1e-10  # relative to 1 + |z|
@@ -36,36 +38,14 @@ RANK_TOL = 1e-12       # fifth singular value / largest: below it the nullspace 
 SAMPLE_SIZE = 5
 
 
-def _mix(z: int) -> int:
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & MASK64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & MASK64
-    return z ^ (z >> 31)
-
-
 def sample(seed: int, t: int, n: int, k: int = SAMPLE_SIZE) -> list[int]:
-    """The k distinct indices of trial t: base = mix(seed + (t + 1) PHI), r_j = mix(base + j PHI), idx = r_j n >> 64."""
-    base = _mix((seed + (t + 1) * PHI) & MASK64)
-    out, j = [], 0
-    while len(out) < k:
-        j += 1
-        c = (_mix((base + j * PHI) & MASK64) * n) >> 64
-        if c not in out:
-            out.append(c)
-    return out
+    """The k distinct indices of trial t."""
+    return _sample(seed, t, n, k)
 
 
 def num_trials(num_inliers: int, n: int, confidence: float, multiplier: float, sample_size: int = SAMPLE_SIZE) -> float:
     """RANSAC::ComputeNumTrials with kMinNumSamples = sample_size (math.inf for size_t max)."""
-    ratio = num_inliers / n
-    nom = 1.0 - confidence
-    if nom <= 0:
-        return math.inf
-    denom = 1.0 - math.pow(ratio, float(sample_size))
-    if denom <= 0:
-        return 1
-    if denom == 1.0:
-        return math.inf
-    return math.ceil(math.log(nom) / math.log(denom) * multiplier)
+    return _num_trials(num_inliers, n, confidence, multiplier, sample_size)
 
 
 def sampson(E: np.ndarray, x1: np.ndarray, x2: np.ndarray) -> np.ndarray:
@@ -286,15 +266,6 @@ def pose_from_essential(E, x1, x2, fragile: list | None = None):
 
 
 # ---- LORANSAC -----------------------------------------------------------------------------------------------------
-def _support(res, thr2):
-    inl = res <= thr2
-    return int(inl.sum()), float(res[inl].sum())
-
-
-def _better(a, b):
-    return a[0] > b[0] or (a[0] == b[0] and a[1] < b[1])
-
-
 # pycolmap 3.11 RANSACOptions() as recalled
 DEFAULT_OPTIONS = dict(max_error=4.0, min_inlier_ratio=0.01, confidence=0.9999, dyn_num_trials_multiplier=3.0, min_num_trials=1000,
                        max_num_trials=100000, seed=0)
