@@ -570,6 +570,117 @@ int mpsfm_rel_pose_estimate(int64_t n, const double* points1 /* [n][2] pixels */
                             const double* intr1, const double* intr2 /* PINHOLE fx fy cx cy */, const mpsfm_rel_pose_options* options,
                             int32_t device, uint8_t* inlier_mask /* [n] */, mpsfm_rel_pose_result* result);
 
+/* ---- two-view geometry: geometric verification of ONE image pair (reference
+ *    mpsfm/sfm/scene/correspondences/utils.py:13-32 -> pycolmap.estimate_calibrated_two_view_geometry).  COLMAP 3.11
+ *    EstimateCalibratedTwoViewGeometry, DetectWatermark and EstimateTwoViewGeometryPose restated as recalled; the
+ *    reference's COLMAP fork is not in its tree: parity unpinned.  Stateless, one call per pair; several pairs per launch,
+ *    EstimateMultiple / multiple_models / force_H_use and cameras other than PINHOLE are not provided.
+ *    Three LO-RANSACs run over the same n matches with the same options and the same seed (the counter sampler of
+ *    mpsfm_abs_pose_estimate, the first 5 / 7 / 4 distinct indices); support measure, min_inlier_ratio cap, dynamic bound
+ *    and stop test as there, with the sample size as exponent:
+ *      E  exactly mpsfm_rel_pose_estimate's estimator: normalised points, threshold 0.5 (max_error / f1 + max_error / f2).
+ *      F  LORANSAC<FundamentalMatrixSevenPointEstimator, FundamentalMatrixEightPointEstimator> on pixels, threshold
+ *         max_error, residual = squared Sampson error.  Seven-point: no normalisation, the 2-D nullspace F1, F2 of the 7 x 9
+ *         epipolar matrix (Householder QR), the cubic det(l F1 + (1 - l) F2) = 0, real roots under the |imag| rule of the
+ *         five-point solver, up to three models; a sample of rank < 7 gives no model.  Local optimisation from 8 inliers:
+ *         eight-point with Hartley normalisation (centroid, RMS distance sqrt(2)), rank 2 enforced, T2^T F T1.
+ *      H  LORANSAC<HomographyMatrixEstimator x2> on pixels, threshold max_error, residual = squared forward transfer
+ *         error |x2 - pi(H x1)|^2 (DBL_MAX when the third coordinate is 0).  Normalised DLT (two rows per match), sample
+ *         size 4, local optimisation from 5 inliers; a sample with three collinear points (sin of the angle <= 1e-10) in
+ *         either image or of rank < 8 gives no model.
+ *    Choices of ours, as for E: every F and H has unit Frobenius norm with its largest-magnitude entry positive (first in
+ *    row-major order on ties), a trial's models are ordered lexicographically.  Deviation: the non-minimal estimators take
+ *    the eigenvector of the smallest eigenvalue of the 9 x 9 Gram matrix of the normalised design matrix, reduced on the
+ *    device in a fixed order, where upstream takes an SVD of the design matrix.
+ *    Decision, with nE, nF, nH the inlier counts of the three reports:
+ *      1. no leg has a model, or nE, nF, nH are all < min_num_inliers                        DEGENERATE
+ *      2. else E has a model, nE / nF > min_E_F_inlier_ratio and nE >= min_num_inliers:      mask of the larger of E and F
+ *         (E on equality); nH / nE > max_H_inlier_ratio: PLANAR_OR_PANORAMIC and H's mask if nH is strictly larger;
+ *         otherwise CALIBRATED
+ *      3. else F has a model and nF >= min_num_inliers: F's mask; nH / nF > max_H_inlier_ratio: PLANAR_OR_PANORAMIC with
+ *         the same replacement rule; otherwise UNCALIBRATED
+ *      4. else H has a model and nH >= min_num_inliers: H's mask, PLANAR_OR_PANORAMIC
+ *      5. else DEGENERATE.  Ratios follow IEEE double division.
+ *    n < min_num_inliers: DEGENERATE, an empty mask, return value 0.  MULTIPLE is never produced.
+ *    Watermark (detect_watermark, before the pose): with b = watermark_border_size x the image diagonal, the chosen inliers
+ *    whose points lie outside [b, w - b] x [b, h - b] in BOTH images; if their share of the chosen inliers is >=
+ *    watermark_min_inlier_ratio, a LO-RANSAC for a 2-D translation runs over them (sample size 1, model mean(x2 - x1),
+ *    residual |x2 - x1 - t|^2, threshold max_error, min_inlier_ratio = watermark_min_inlier_ratio); its inliers / the chosen
+ *    inliers >= watermark_min_inlier_ratio: WATERMARK.
+ *    Pose (compute_relative_pose): CALIBRATED: PoseFromEssentialMatrix of the E leg's model on the CHOSEN inliers;
+ *    UNCALIBRATED: the same with E = K2^T F K1 (canonical form); decomposition, candidate order and cheirality rule of
+ *    mpsfm_rel_pose_estimate.  PLANAR_OR_PANORAMIC: Hn = K2^-1 H K1 divided by its middle singular value, sign such that
+ *    det > 0; max |Hn^T Hn - I| < 1e-3: the single candidate (R = Hn, t = 0); otherwise the four (R, t) of Hn = R + t n^T.
+ *    OUR candidate order: the two rotations Ra, Rb with Ra's row-major entries lexicographically smaller, ta and tb signed so
+ *    that their largest-magnitude component is positive: (Ra, ta), (Rb, tb), (Ra, -ta), (Rb, -tb).  Most cheirality points
+ *    (depths in (DBL_EPSILON, 1000 |t|)) win, the later candidate on a tie; then PANORAMIC if t == 0 else PLANAR.
+ *    tri_angle: the median (mean of the two middle values for an even count, 0 without points) of
+ *    CalculateTriangulationAngle (the geometric angle, not the reference's Python helper) over the winner's cheirality
+ *    points, projection centres 0 and -R^T t.  Other configs: identity pose, tri_angle 0.
+ *    E, F, H: the best model of each leg that has one (zeros otherwise), whatever the config.
+ *    Argument checks (NULL, n < 0 or > INT32_MAX, non-finite points, intrinsics as above, sizes <= 0, invalid options)
+ *    are MPSFM_EINVAL before any HIP call.  Results are bitwise identical run to run and for every batch_trials. ---- */
+enum {
+  MPSFM_TVG_UNDEFINED = 0, MPSFM_TVG_DEGENERATE = 1, MPSFM_TVG_CALIBRATED = 2, MPSFM_TVG_UNCALIBRATED = 3, MPSFM_TVG_PLANAR = 4,
+  MPSFM_TVG_PANORAMIC = 5, MPSFM_TVG_PLANAR_OR_PANORAMIC = 6, MPSFM_TVG_WATERMARK = 7, MPSFM_TVG_MULTIPLE = 8
+};
+enum { MPSFM_TVG_LEG_E = 0, MPSFM_TVG_LEG_F = 1, MPSFM_TVG_LEG_H = 2, MPSFM_TVG_LEG_T = 3 /* watermark translation */ };
+
+typedef struct mpsfm_two_view_options {
+  mpsfm_ransac_options ransac;        /* of all legs */
+  int64_t min_num_inliers;
+  double min_E_F_inlier_ratio;
+  double max_H_inlier_ratio;
+  double watermark_min_inlier_ratio;
+  double watermark_border_size;       /* fraction of the image diagonal */
+  int32_t detect_watermark;           /* 0 / 1 */
+  int32_t compute_relative_pose;      /* 0 / 1 */
+} mpsfm_two_view_options;
+
+typedef struct mpsfm_two_view_leg {
+  int64_t num_inliers;     /* of the leg's best model */
+  int64_t num_trials;      /* LORANSAC's report.num_trials */
+  int64_t max_num_trials;  /* after the min_inlier_ratio cap */
+  int64_t lo_rounds;
+  int64_t num_batches;
+  int32_t success;         /* the leg has a model */
+  int32_t reserved;
+} mpsfm_two_view_leg;
+
+typedef struct mpsfm_two_view_result {
+  double E[9], F[9], H[9];        /* row-major, canonical form */
+  double cam2_from_cam1[12];      /* [3][4] row-major */
+  double tri_angle;               /* radians */
+  mpsfm_two_view_leg leg[4];      /* MPSFM_TVG_LEG_* */
+  int64_t num_inliers;            /* of inlier_mask */
+  int64_t num_cheirality_points;  /* of the chosen pose */
+  int64_t num_border_inliers;     /* watermark test */
+  int32_t config;                 /* MPSFM_TVG_* */
+  int32_t success;                /* config is neither UNDEFINED nor DEGENERATE */
+  int32_t watermark;              /* the watermark test fired */
+  float ms;                       /* device time of the launches (HIP events), transfers and host work excluded */
+} mpsfm_two_view_result;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_two_view_options) == 112 && offsetof(mpsfm_two_view_options, min_num_inliers) == 64 &&
+                  offsetof(mpsfm_two_view_options, detect_watermark) == 104,
+              "ABI of mpsfm_two_view_options");
+static_assert(sizeof(mpsfm_two_view_leg) == 48, "ABI of mpsfm_two_view_leg");
+static_assert(sizeof(mpsfm_two_view_result) == 552 && offsetof(mpsfm_two_view_result, tri_angle) == 312 &&
+                  offsetof(mpsfm_two_view_result, leg) == 320 && offsetof(mpsfm_two_view_result, config) == 536,
+              "ABI of mpsfm_two_view_result");
+#endif
+
+/* COLMAP 3.11 TwoViewGeometryOptions as recalled: ransac max_error 4, min_inlier_ratio 0.25, confidence 0.999, multiplier 3,
+ * min_num_trials 100, max_num_trials 10000; min_num_inliers 15, min_E_F_inlier_ratio 0.95, max_H_inlier_ratio 0.8,
+ * watermark_min_inlier_ratio 0.7, watermark_border_size 0.1, detect_watermark 1, compute_relative_pose 0 */
+void mpsfm_two_view_default_options(mpsfm_two_view_options* options);
+
+int mpsfm_two_view_geometry(int64_t n, const double* points1 /* [n][2] pixels */, const double* points2 /* [n][2] pixels */,
+                            const double* intr1, const double* intr2 /* PINHOLE fx fy cx cy */,
+                            const int32_t* size1, const int32_t* size2 /* width, height */,
+                            const mpsfm_two_view_options* options, int32_t device, uint8_t* inlier_mask /* [n] */,
+                            mpsfm_two_view_result* result);
+
 /* ---- registration: the per-match arithmetic of MpsfmRegistration (reference mpsfm/sfm/mapper/registration.py).
  *
  *    mpsfm_registration_pairs: the 2D-3D pairs of one register_next_image for ALL reference images in one launch

@@ -24,7 +24,8 @@ EXPORTS = [
     "mpsfm_ba_get_dense_solution", "mpsfm_ba_dense_solve_once", "mpsfm_ba_dense_plan", "mpsfm_point_covs",
     "mpsfm_triangulate_tracks", "mpsfm_filter_tracks", "mpsfm_integrate_depth", "mpsfm_integrate_depth_batch",
     "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
-    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
+    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_two_view_geometry",
+    "mpsfm_two_view_default_options", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
 ]
 
 _lib = None
@@ -448,6 +449,8 @@ def tri_estimate_batch(cand_start, view_cam_from_world, view_intr, view_xy, min_
     P = np.ascontiguousarray(view_cam_from_world, np.float64).reshape(-1, 12)
     K = np.ascontiguousarray(view_intr, np.float64).reshape(-1, 4)
     xy = np.ascontiguousarray(view_xy, np.float64).reshape(-1, 2)
+    if len(cs) and int(cs[0]) != 0:  # the library's own check, made before the arrays below are sized from cs[-1]
+        raise MpsfmHipError(-1, "cand_start[0] must be 0")
     if not (len(P) == len(K) == len(xy) == (int(cs[-1]) if n >= 0 and len(cs) else 0)):
         raise ValueError("view arrays do not match cand_start")
     mt = None if min_num_trials is None else np.ascontiguousarray(min_num_trials, np.int64)
@@ -610,6 +613,71 @@ def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> di
                                      mask.ctypes.data, C.byref(R)))
     return dict(_ransac_report(R, mask, n), E=np.array(R.E[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4),
                 num_cheirality_points=int(R.num_cheirality_points))
+
+
+class CTwoViewOptions(C.Structure):
+    _fields_ = [("ransac", CRansacOptions), ("min_num_inliers", C.c_int64), ("min_E_F_inlier_ratio", C.c_double),
+                ("max_H_inlier_ratio", C.c_double), ("watermark_min_inlier_ratio", C.c_double), ("watermark_border_size", C.c_double),
+                ("detect_watermark", C.c_int32), ("compute_relative_pose", C.c_int32)]
+
+
+class CTwoViewLeg(C.Structure):
+    _fields_ = [("num_inliers", C.c_int64), ("num_trials", C.c_int64), ("max_num_trials", C.c_int64), ("lo_rounds", C.c_int64),
+                ("num_batches", C.c_int64), ("success", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CTwoViewResult(C.Structure):
+    _fields_ = [("E", C.c_double * 9), ("F", C.c_double * 9), ("H", C.c_double * 9), ("cam2_from_cam1", C.c_double * 12),
+                ("tri_angle", C.c_double), ("leg", CTwoViewLeg * 4), ("num_inliers", C.c_int64), ("num_cheirality_points", C.c_int64),
+                ("num_border_inliers", C.c_int64), ("config", C.c_int32), ("success", C.c_int32), ("watermark", C.c_int32),
+                ("ms", C.c_float)]
+
+
+# COLMAP 3.11 TwoViewGeometryOptions as recalled (mpsfm_two_view_default_options)
+TWO_VIEW_DEFAULTS = dict(max_error=4.0, min_inlier_ratio=0.25, confidence=0.999, dyn_num_trials_multiplier=3.0, min_num_trials=100,
+                         max_num_trials=10000, seed=0, batch_trials=0, min_num_inliers=15, min_E_F_inlier_ratio=0.95,
+                         max_H_inlier_ratio=0.8, watermark_min_inlier_ratio=0.7, watermark_border_size=0.1, detect_watermark=True,
+                         compute_relative_pose=False)
+TWO_VIEW_LEGS = ("E", "F", "H", "T")  # T: the translation of the watermark test
+
+
+def two_view_geometry(points1, points2, intr1, intr2, size1, size2, device=0, **options) -> dict:
+    """mpsfm_two_view_geometry: calibrated two-view geometry of one image pair (E, F and H LO-RANSAC, COLMAP's decision, the
+    watermark test, the relative pose) with PINHOLE intr = (fx, fy, cx, cy) and size = (width, height).  `options`: keys of
+    TWO_VIEW_DEFAULTS.  Returns dict(config, success, E, F, H [3,3], cam2_from_cam1 [3,4], tri_angle (radians), inlier_mask
+    bool [n], num_inliers, num_cheirality_points, num_border_inliers, watermark, legs {E, F, H, T: dict(num_inliers,
+    num_trials, max_num_trials, lo_rounds, num_batches, success)}, ms)."""
+    o = dict(TWO_VIEW_DEFAULTS)
+    unknown = set(options) - set(o)
+    if unknown:
+        raise KeyError(f"unknown option(s) {sorted(unknown)}")
+    o.update(options)
+    ransac = _ransac_options({k: TWO_VIEW_DEFAULTS[k] for k in REL_POSE_DEFAULTS}, {k: o[k] for k in REL_POSE_DEFAULTS})
+    opt = CTwoViewOptions(ransac, int(o["min_num_inliers"]), float(o["min_E_F_inlier_ratio"]), float(o["max_H_inlier_ratio"]),
+                          float(o["watermark_min_inlier_ratio"]), float(o["watermark_border_size"]), int(bool(o["detect_watermark"])),
+                          int(bool(o["compute_relative_pose"])))
+    p1 = np.ascontiguousarray(points1, np.float64).reshape(-1, 2)
+    p2 = np.ascontiguousarray(points2, np.float64).reshape(-1, 2)
+    if len(p1) != len(p2):
+        raise ValueError("points1 and points2 differ in length")
+    K1 = np.ascontiguousarray(intr1, np.float64).reshape(4)
+    K2 = np.ascontiguousarray(intr2, np.float64).reshape(4)
+    s1 = np.ascontiguousarray(size1, np.int32).reshape(2)
+    s2 = np.ascontiguousarray(size2, np.int32).reshape(2)
+    n = len(p1)
+    mask = np.zeros(max(n, 1), np.uint8)
+    R = CTwoViewResult()
+    L = lib()
+    L.mpsfm_two_view_geometry.argtypes = [C.c_int64] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_two_view_geometry(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, s1.ctypes.data, s2.ctypes.data,
+                                     C.byref(opt), int(device), mask.ctypes.data, C.byref(R)))
+    legs = {name: dict(num_inliers=int(g.num_inliers), num_trials=int(g.num_trials), max_num_trials=int(g.max_num_trials),
+                       lo_rounds=int(g.lo_rounds), num_batches=int(g.num_batches), success=bool(g.success))
+            for name, g in zip(TWO_VIEW_LEGS, R.leg)}
+    return dict(config=int(R.config), success=bool(R.success), E=np.array(R.E[:]).reshape(3, 3), F=np.array(R.F[:]).reshape(3, 3),
+                H=np.array(R.H[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4), tri_angle=float(R.tri_angle),
+                inlier_mask=mask[:n].astype(bool), num_inliers=int(R.num_inliers), num_cheirality_points=int(R.num_cheirality_points),
+                num_border_inliers=int(R.num_border_inliers), watermark=bool(R.watermark), legs=legs, ms=float(R.ms))
 
 
 class CRegImage(C.Structure):

@@ -596,6 +596,8 @@ int mpsfm_triangulator_get_op_elements(mpsfm_triangulator* h, int64_t* els) {
 int mpsfm_tri_estimate_batch(const mpsfm_tri_candidates* c, int32_t device, double* xyz, uint8_t* ok, uint8_t* inlier) {
   if (!c || c->n_candidates < 0 || (c->n_candidates > 0 && (!c->cand_start || !xyz || !ok))) return fail(MPSFM_EINVAL, "NULL argument");
   const int64_t nc = c->n_candidates;
+  // the offsets index the view arrays and inlier[] from 0: a first offset other than 0 would read and write outside them
+  if (nc > 0 && c->cand_start[0] != 0) return fail(MPSFM_EINVAL, "cand_start[0] must be 0");
   const int64_t nv = nc > 0 ? c->cand_start[nc] : 0;
   if (nv > 0 && (!c->view_cam_from_world || !c->view_intr || !c->view_xy || !inlier)) return fail(MPSFM_EINVAL, "view arrays are NULL");
   if (c->residual_type != TRI_RESIDUAL_ANGULAR && c->residual_type != TRI_RESIDUAL_REPROJECTION) return fail(MPSFM_EINVAL, "unknown residual type");

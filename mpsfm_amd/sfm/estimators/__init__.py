@@ -1,4 +1,5 @@
 from .absolute_pose import AbsolutePose
 from .relative_pose import RelativePose
+from .two_view_geometry import TwoViewGeometry, TwoViewGeometryConfig, estimate_calibrated_two_view_geometry
 
-__all__ = ["AbsolutePose", "RelativePose"]
+__all__ = ["AbsolutePose", "RelativePose", "TwoViewGeometry", "TwoViewGeometryConfig", "estimate_calibrated_two_view_geometry"]
