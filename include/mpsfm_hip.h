@@ -573,8 +573,8 @@ int mpsfm_rel_pose_estimate(int64_t n, const double* points1 /* [n][2] pixels */
 /* ---- two-view geometry: geometric verification of ONE image pair (reference
  *    mpsfm/sfm/scene/correspondences/utils.py:13-32 -> pycolmap.estimate_calibrated_two_view_geometry).  COLMAP 3.11
  *    EstimateCalibratedTwoViewGeometry, DetectWatermark and EstimateTwoViewGeometryPose restated as recalled; the
- *    reference's COLMAP fork is not in its tree: parity unpinned.  Stateless, one call per pair; several pairs per launch,
- *    EstimateMultiple / multiple_models / force_H_use and cameras other than PINHOLE are not provided.
+ *    reference's COLMAP fork is not in its tree: parity unpinned.  Stateless, one call per pair (many pairs per call:
+ *    mpsfm_two_view_geometry_batch below); EstimateMultiple / multiple_models / force_H_use and cameras other than PINHOLE are not provided.
  *    Three LO-RANSACs run over the same n matches with the same options and the same seed (the counter sampler of
  *    mpsfm_abs_pose_estimate, the first 5 / 7 / 4 distinct indices); support measure, min_inlier_ratio cap, dynamic bound
  *    and stop test as there, with the sample size as exponent:
@@ -680,6 +680,43 @@ int mpsfm_two_view_geometry(int64_t n, const double* points1 /* [n][2] pixels */
                             const int32_t* size1, const int32_t* size2 /* width, height */,
                             const mpsfm_two_view_options* options, int32_t device, uint8_t* inlier_mask /* [n] */,
                             mpsfm_two_view_result* result);
+
+/* ---- two-view geometry of MANY image pairs in one call (reference mpsfm/sfm/scene/correspondences/utils.py:51-77, the pool
+ *    over all matched pairs).  Pair k owns the matches [pair_start[k], pair_start[k + 1]) of points1 / points2 and of
+ *    inlier_mask, row k of intr1 / intr2 / size1 / size2 and results[k]; one set of options serves all pairs, as the reference
+ *    passes it.  results[k] and pair k's slice of inlier_mask are IDENTICAL (every field but ms, bitwise) to what
+ *    mpsfm_two_view_geometry returns for that pair alone with the same options, whatever the other pairs, their order and
+ *    pairs_per_group: every problem sees the operations of its single call in the same order.
+ *    Pairs are processed in groups of consecutive pairs; within a group every leg type (E, F, H, then the watermark
+ *    translation) runs as one lockstep LO-RANSAC over the group's pairs: one launch generates, one scores the next batch of
+ *    every pair, one synchronisation serves them all.  pairs_per_group 0: consecutive pairs while the group's device tables
+ *    stay under 256 MiB, at most 256 pairs; an explicit value is used as given up to 4096.
+ *    results[k].ms is the device time of the whole group pair k ran in (all pairs of a group share it); a pair with
+ *    n < min_num_inliers or n < 4 is DEGENERATE as in the single call, takes part in no launch and reports ms 0.
+ *    Checks, all MPSFM_EINVAL before any HIP call, the message naming the pair: NULL pointers (report may be NULL),
+ *    num_pairs < 0, pair_start[0] != 0, a decreasing offset, a pair of more than INT32_MAX matches, non-finite points,
+ *    intrinsics / sizes the single call refuses, invalid options, pairs_per_group < 0.  num_pairs == 0: returns 0 and touches
+ *    nothing. ---- */
+typedef struct mpsfm_two_view_batch_report {
+  int64_t num_groups;
+  int64_t num_syncs;     /* stream synchronisations of the call */
+  int64_t num_launches;  /* kernel launches of the call */
+  float ms;              /* device time of all launches (sum over the groups) */
+  int32_t reserved;
+} mpsfm_two_view_batch_report;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_two_view_batch_report) == 32 && offsetof(mpsfm_two_view_batch_report, num_syncs) == 8 &&
+                  offsetof(mpsfm_two_view_batch_report, num_launches) == 16 && offsetof(mpsfm_two_view_batch_report, ms) == 24,
+              "ABI of mpsfm_two_view_batch_report");
+#endif
+
+int mpsfm_two_view_geometry_batch(int64_t num_pairs, const int64_t* pair_start /* [num_pairs + 1], pair_start[0] == 0 */,
+                                  const double* points1 /* [N][2] */, const double* points2 /* [N][2], N = pair_start[num_pairs] */,
+                                  const double* intr1, const double* intr2 /* [num_pairs][4] */,
+                                  const int32_t* size1, const int32_t* size2 /* [num_pairs][2] */,
+                                  const mpsfm_two_view_options* options, int32_t pairs_per_group /* 0: default */, int32_t device,
+                                  uint8_t* inlier_mask /* [N] */, mpsfm_two_view_result* results /* [num_pairs] */,
+                                  mpsfm_two_view_batch_report* report /* may be NULL */);
 
 /* ---- registration: the per-match arithmetic of MpsfmRegistration (reference mpsfm/sfm/mapper/registration.py).
  *

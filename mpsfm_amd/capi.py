@@ -24,7 +24,7 @@ EXPORTS = [
     "mpsfm_ba_get_dense_solution", "mpsfm_ba_dense_solve_once", "mpsfm_ba_dense_plan", "mpsfm_point_covs",
     "mpsfm_triangulate_tracks", "mpsfm_filter_tracks", "mpsfm_integrate_depth", "mpsfm_integrate_depth_batch",
     "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
-    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_two_view_geometry",
+    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_two_view_geometry", "mpsfm_two_view_geometry_batch",
     "mpsfm_two_view_default_options", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
 ]
 
@@ -641,29 +641,52 @@ TWO_VIEW_DEFAULTS = dict(max_error=4.0, min_inlier_ratio=0.25, confidence=0.999,
 TWO_VIEW_LEGS = ("E", "F", "H", "T")  # T: the translation of the watermark test
 
 
-def two_view_geometry(points1, points2, intr1, intr2, size1, size2, device=0, **options) -> dict:
-    """mpsfm_two_view_geometry: calibrated two-view geometry of one image pair (E, F and H LO-RANSAC, COLMAP's decision, the
-    watermark test, the relative pose) with PINHOLE intr = (fx, fy, cx, cy) and size = (width, height).  `options`: keys of
-    TWO_VIEW_DEFAULTS.  Returns dict(config, success, E, F, H [3,3], cam2_from_cam1 [3,4], tri_angle (radians), inlier_mask
-    bool [n], num_inliers, num_cheirality_points, num_border_inliers, watermark, legs {E, F, H, T: dict(num_inliers,
-    num_trials, max_num_trials, lo_rounds, num_batches, success)}, ms)."""
+class CTwoViewBatchReport(C.Structure):
+    """mpsfm_two_view_batch_report"""
+    _fields_ = [("num_groups", C.c_int64), ("num_syncs", C.c_int64), ("num_launches", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+
+def _two_view_options(options: dict) -> CTwoViewOptions:
+    """`options` over TWO_VIEW_DEFAULTS as the C struct; an unknown key is a KeyError."""
     o = dict(TWO_VIEW_DEFAULTS)
     unknown = set(options) - set(o)
     if unknown:
         raise KeyError(f"unknown option(s) {sorted(unknown)}")
     o.update(options)
     ransac = _ransac_options({k: TWO_VIEW_DEFAULTS[k] for k in REL_POSE_DEFAULTS}, {k: o[k] for k in REL_POSE_DEFAULTS})
-    opt = CTwoViewOptions(ransac, int(o["min_num_inliers"]), float(o["min_E_F_inlier_ratio"]), float(o["max_H_inlier_ratio"]),
-                          float(o["watermark_min_inlier_ratio"]), float(o["watermark_border_size"]), int(bool(o["detect_watermark"])),
-                          int(bool(o["compute_relative_pose"])))
+    return CTwoViewOptions(ransac, int(o["min_num_inliers"]), float(o["min_E_F_inlier_ratio"]), float(o["max_H_inlier_ratio"]),
+                           float(o["watermark_min_inlier_ratio"]), float(o["watermark_border_size"]), int(bool(o["detect_watermark"])),
+                           int(bool(o["compute_relative_pose"])))
+
+
+def _two_view_pair(points1, points2, intr1, intr2, size1, size2):
+    """The arrays of one pair as the C entry points read them."""
     p1 = np.ascontiguousarray(points1, np.float64).reshape(-1, 2)
     p2 = np.ascontiguousarray(points2, np.float64).reshape(-1, 2)
     if len(p1) != len(p2):
         raise ValueError("points1 and points2 differ in length")
-    K1 = np.ascontiguousarray(intr1, np.float64).reshape(4)
-    K2 = np.ascontiguousarray(intr2, np.float64).reshape(4)
-    s1 = np.ascontiguousarray(size1, np.int32).reshape(2)
-    s2 = np.ascontiguousarray(size2, np.int32).reshape(2)
+    return (p1, p2, np.ascontiguousarray(intr1, np.float64).reshape(4), np.ascontiguousarray(intr2, np.float64).reshape(4),
+            np.ascontiguousarray(size1, np.int32).reshape(2), np.ascontiguousarray(size2, np.int32).reshape(2))
+
+
+def _two_view_result(R, mask: np.ndarray) -> dict:
+    legs = {name: dict(num_inliers=int(g.num_inliers), num_trials=int(g.num_trials), max_num_trials=int(g.max_num_trials),
+                       lo_rounds=int(g.lo_rounds), num_batches=int(g.num_batches), success=bool(g.success))
+            for name, g in zip(TWO_VIEW_LEGS, R.leg)}
+    return dict(config=int(R.config), success=bool(R.success), E=np.array(R.E[:]).reshape(3, 3), F=np.array(R.F[:]).reshape(3, 3),
+                H=np.array(R.H[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4), tri_angle=float(R.tri_angle),
+                inlier_mask=mask.astype(bool), num_inliers=int(R.num_inliers), num_cheirality_points=int(R.num_cheirality_points),
+                num_border_inliers=int(R.num_border_inliers), watermark=bool(R.watermark), legs=legs, ms=float(R.ms))
+
+
+def two_view_geometry(points1, points2, intr1, intr2, size1, size2, device=0, **options) -> dict:
+    """mpsfm_two_view_geometry: calibrated two-view geometry of one image pair (E, F and H LO-RANSAC, COLMAP's decision, the
+    watermark test, the relative pose) with PINHOLE intr = (fx, fy, cx, cy) and size = (width, height).  `options`: keys of
+    TWO_VIEW_DEFAULTS.  Returns dict(config, success, E, F, H [3,3], cam2_from_cam1 [3,4], tri_angle (radians), inlier_mask
+    bool [n], num_inliers, num_cheirality_points, num_border_inliers, watermark, legs {E, F, H, T: dict(num_inliers,
+    num_trials, max_num_trials, lo_rounds, num_batches, success)}, ms)."""
+    opt = _two_view_options(options)
+    p1, p2, K1, K2, s1, s2 = _two_view_pair(points1, points2, intr1, intr2, size1, size2)
     n = len(p1)
     mask = np.zeros(max(n, 1), np.uint8)
     R = CTwoViewResult()
@@ -671,13 +694,41 @@ def two_view_geometry(points1, points2, intr1, intr2, size1, size2, device=0, **
     L.mpsfm_two_view_geometry.argtypes = [C.c_int64] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_void_p]
     _check(L.mpsfm_two_view_geometry(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, s1.ctypes.data, s2.ctypes.data,
                                      C.byref(opt), int(device), mask.ctypes.data, C.byref(R)))
-    legs = {name: dict(num_inliers=int(g.num_inliers), num_trials=int(g.num_trials), max_num_trials=int(g.max_num_trials),
-                       lo_rounds=int(g.lo_rounds), num_batches=int(g.num_batches), success=bool(g.success))
-            for name, g in zip(TWO_VIEW_LEGS, R.leg)}
-    return dict(config=int(R.config), success=bool(R.success), E=np.array(R.E[:]).reshape(3, 3), F=np.array(R.F[:]).reshape(3, 3),
-                H=np.array(R.H[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4), tri_angle=float(R.tri_angle),
-                inlier_mask=mask[:n].astype(bool), num_inliers=int(R.num_inliers), num_cheirality_points=int(R.num_cheirality_points),
-                num_border_inliers=int(R.num_border_inliers), watermark=bool(R.watermark), legs=legs, ms=float(R.ms))
+    return _two_view_result(R, mask[:n])
+
+
+def two_view_geometry_batch(pairs, device=0, pairs_per_group=0, return_report=False, **options):
+    """mpsfm_two_view_geometry_batch: the two-view geometry of many image pairs in one call.  `pairs`: a sequence of
+    (points1, points2, intr1, intr2, size1, size2) as two_view_geometry takes them; `options` (keys of TWO_VIEW_DEFAULTS) serve
+    every pair.  Returns the list of the dicts two_view_geometry returns, each identical to that pair's single call but for
+    `ms`, which is the device time of the whole group the pair ran in; with `return_report` also dict(num_groups, num_syncs,
+    num_launches, ms) of the call.  `pairs_per_group` 0: the library's default grouping."""
+    opt = _two_view_options(options)
+    arrs = [_two_view_pair(*p) for p in pairs]
+    P = len(arrs)
+    start = np.zeros(P + 1, np.int64)
+    if P:
+        start[1:] = np.cumsum([len(a[0]) for a in arrs])
+    N = int(start[-1])
+
+    def cat(k, cols, dtype):
+        return np.ascontiguousarray(np.concatenate([a[k].reshape(-1, cols) for a in arrs]), dtype) if P else np.zeros((0, cols), dtype)
+
+    p1, p2 = cat(0, 2, np.float64), cat(1, 2, np.float64)
+    K1, K2 = cat(2, 4, np.float64), cat(3, 4, np.float64)
+    s1, s2 = cat(4, 2, np.int32), cat(5, 2, np.int32)
+    mask = np.zeros(max(N, 1), np.uint8)
+    R = (CTwoViewResult * max(P, 1))()
+    rep = CTwoViewBatchReport()
+    L = lib()
+    L.mpsfm_two_view_geometry_batch.argtypes = [C.c_int64] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3
+    _check(L.mpsfm_two_view_geometry_batch(P, start.ctypes.data, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data,
+                                           s1.ctypes.data, s2.ctypes.data, C.byref(opt), int(pairs_per_group), int(device),
+                                           mask.ctypes.data, R, C.byref(rep)))
+    out = [_two_view_result(R[k], mask[start[k]:start[k + 1]]) for k in range(P)]
+    if return_report:
+        return out, dict(num_groups=int(rep.num_groups), num_syncs=int(rep.num_syncs), num_launches=int(rep.num_launches), ms=float(rep.ms))
+    return out
 
 
 class CRegImage(C.Structure):

@@ -8,7 +8,8 @@ carries what the reference reads: ``config`` (compares equal to the plain ints o
 
 Deviations, all documented in DESIGN.md section 4j: the sampler is counter-based, so ``random_seed < 0`` maps to the fixed
 seed 0 and every call is deterministic; models are canonical and a trial's models are in lexicographic order; cameras other
-than (SIMPLE_)PINHOLE are refused; ``multiple_models`` / ``force_H_use`` are not provided; one pair per call.
+than (SIMPLE_)PINHOLE are refused; ``multiple_models`` / ``force_H_use`` are not provided.
+``estimate_calibrated_two_view_geometry_batch`` takes many pairs in one call (``mpsfm_two_view_geometry_batch``, section 4k).
 """
 
 from __future__ import annotations
@@ -123,14 +124,9 @@ def _image_size(camera, intr) -> tuple[int, int]:
     return int(w), int(h)
 
 
-def estimate_calibrated_two_view_geometry(cam0, kps0, cam1, kps1, matches, options=None, device: int = 0, backend=None) -> TwoViewGeometry:
-    """The two-view geometry of one pair: keypoints [n, 2] pixels of both images, matches [(m, 2) int] into them, and the
-    nested option dict the reference passes ({"ransac": {...}, "compute_relative_pose": True}).  `backend`: an object with
-    capi's ``two_view_geometry`` (tests inject the NumPy restatement); None: libmpsfm_hip."""
+def _prepare(cam0, kps0, cam1, kps1, matches, what="a match"):
+    """One pair as the backend takes it: (positional arguments of two_view_geometry, the match rows)."""
     intr0, intr1 = pinhole_params(cam0), pinhole_params(cam1)
-    o = _merge_options(options)
-    ro = o.pop("ransac")
-    seed = int(ro.pop("random_seed"))
     m = np.asarray(matches)
     if m.size == 0:
         m = m.reshape(0, 2)
@@ -140,12 +136,46 @@ def estimate_calibrated_two_view_geometry(cam0, kps0, cam1, kps1, matches, optio
     k1 = np.asarray(kps1, np.float64).reshape(-1, 2)
     idx = m.astype(np.int64)
     if len(idx) and (idx.min() < 0 or idx[:, 0].max() >= len(k0) or idx[:, 1].max() >= len(k1)):
-        raise IndexError("a match indexes past the keypoints")
-    fn = (backend or capi).two_view_geometry
-    est = fn(k0[idx[:, 0]], k1[idx[:, 1]], intr0, intr1, _image_size(cam0, intr0), _image_size(cam1, intr1), device=device,
-             seed=seed if seed >= 0 else 0, **ro, **o)
+        raise IndexError(f"{what} indexes past the keypoints")
+    return (k0[idx[:, 0]], k1[idx[:, 1]], intr0, intr1, _image_size(cam0, intr0), _image_size(cam1, intr1)), m
+
+
+def _backend_options(options) -> dict:
+    """The nested option dict as the keyword arguments of the backend."""
+    o = _merge_options(options)
+    ro = o.pop("ransac")
+    seed = int(ro.pop("random_seed"))
+    return dict(seed=seed if seed >= 0 else 0, **ro, **o)
+
+
+def _result(est, m, compute_relative_pose) -> TwoViewGeometry:
     P = np.asarray(est["cam2_from_cam1"], np.float64)
-    pose = make_rigid3d(quat_from_R(P[:, :3])[0], P[:, 3]) if est["config"] in (2, 3, 4, 5) and o["compute_relative_pose"] else None
+    pose = make_rigid3d(quat_from_R(P[:, :3])[0], P[:, 3]) if est["config"] in (2, 3, 4, 5) and compute_relative_pose else None
     tvg = TwoViewGeometry(est["config"], est["E"], est["F"], est["H"], pose, m[np.asarray(est["inlier_mask"], bool)], est["tri_angle"])
     tvg.estimate = est
     return tvg
+
+
+def estimate_calibrated_two_view_geometry(cam0, kps0, cam1, kps1, matches, options=None, device: int = 0, backend=None) -> TwoViewGeometry:
+    """The two-view geometry of one pair: keypoints [n, 2] pixels of both images, matches [(m, 2) int] into them, and the
+    nested option dict the reference passes ({"ransac": {...}, "compute_relative_pose": True}).  `backend`: an object with
+    capi's ``two_view_geometry`` (tests inject the NumPy restatement); None: libmpsfm_hip."""
+    kw = _backend_options(options)
+    args, m = _prepare(cam0, kps0, cam1, kps1, matches)
+    est = (backend or capi).two_view_geometry(*args, device=device, **kw)
+    return _result(est, m, kw["compute_relative_pose"])
+
+
+def estimate_calibrated_two_view_geometry_batch(items, options=None, device: int = 0, backend=None) -> list:
+    """The two-view geometries of many pairs in one call of ``mpsfm_two_view_geometry_batch``: `items` is a sequence of
+    (cam0, kps0, cam1, kps1, matches), `options` serve every pair; the list of TwoViewGeometry in input order, each what
+    estimate_calibrated_two_view_geometry returns for that pair.  A `backend` without ``two_view_geometry_batch`` is called
+    pair by pair."""
+    kw = _backend_options(options)
+    prepared = [_prepare(*item, what=f"pair {k}: a match") for k, item in enumerate(items)]
+    be = backend or capi
+    if hasattr(be, "two_view_geometry_batch"):
+        ests = be.two_view_geometry_batch([args for args, _ in prepared], device=device, **kw)
+    else:
+        ests = [be.two_view_geometry(*args, device=device, **kw) for args, _ in prepared]
+    return [_result(est, m, kw["compute_relative_pose"]) for est, (_, m) in zip(ests, prepared)]

@@ -2,8 +2,9 @@
 
 Mirror of reference ``mpsfm/sfm/scene/correspondences/utils.py`` (``process_pair`` :13-32, ``geometric_verification``
 :51-77) with the reference's signatures and options (max_num_trials 20000, min_inlier_ratio 0.1, compute_relative_pose).
-Each pair is one stateless call of ``mpsfm_two_view_geometry``; a plain loop over the pairs in this process replaces the
-reference's process pool (pairs are not batched on the device and not spread over threads: DESIGN.md section 4j).
+By default each pair is one stateless call of ``mpsfm_two_view_geometry`` in a plain loop over the pairs in this process;
+``batched=True`` gathers all pairs and makes one call of ``mpsfm_two_view_geometry_batch`` in place of the reference's process
+pool, with the same result for every pair.
 ``Correspondences.populate``, the HDF5 gathering and the correspondence graph stay with the reference.
 """
 
@@ -11,22 +12,21 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..estimators.two_view_geometry import estimate_calibrated_two_view_geometry
+from ..estimators.two_view_geometry import estimate_calibrated_two_view_geometry, estimate_calibrated_two_view_geometry_batch
+
+
+def pair_options(max_error) -> dict:
+    """The options the reference passes for every pair."""
+    return {
+        "ransac": {"max_num_trials": 20000, "min_inlier_ratio": 0.1, "max_error": max_error},
+        "compute_relative_pose": True,
+    }
 
 
 def process_pair(data, max_error, backend=None):
     """Estimates the two-view geometry of one gathered pair: (tvg, matches, name0, name1)."""
     tvg = estimate_calibrated_two_view_geometry(
-        data["cam0"],
-        data["kps0"],
-        data["cam1"],
-        data["kps1"],
-        data["matches"],
-        {
-            "ransac": {"max_num_trials": 20000, "min_inlier_ratio": 0.1, "max_error": max_error},
-            "compute_relative_pose": True,
-        },
-        backend=backend,
+        data["cam0"], data["kps0"], data["cam1"], data["kps1"], data["matches"], pair_options(max_error), backend=backend
     )
     return (tvg, data["matches"], data["name0"], data["name1"])
 
@@ -43,14 +43,22 @@ def gather_data(name0, name1, rec_name_to_id, reference, keypoints_cache, matche
     return out
 
 
-def geometric_verification(reference, pairs, max_error: float = 4.0, keypoints=None, matches=None, backend=None):
-    """Geometric verification of `pairs` [(name0, name1)]: (inlier_masks, tvg_cache), both keyed (name0, name1)."""
+def geometric_verification(reference, pairs, max_error: float = 4.0, keypoints=None, matches=None, backend=None, batched: bool = False):
+    """Geometric verification of `pairs` [(name0, name1)]: (inlier_masks, tvg_cache), both keyed (name0, name1).  `batched`: all
+    pairs in one call of the batched estimator instead of one call per pair; the results are the same."""
     tvg_cache = {}
     inlier_masks = {}
     rec_name_to_id = {im.name: im.image_id for im in reference.images.values()}
-    for name0, name1 in pairs:
-        data = gather_data(name0, name1, rec_name_to_id, reference, keypoints, matches)
-        tvg, matches_, name0, name1 = process_pair(data, max_error, backend=backend)
+    gathered = (gather_data(name0, name1, rec_name_to_id, reference, keypoints, matches) for name0, name1 in pairs)
+    if batched:
+        gathered = list(gathered)
+        tvgs = estimate_calibrated_two_view_geometry_batch(
+            [(d["cam0"], d["kps0"], d["cam1"], d["kps1"], d["matches"]) for d in gathered], pair_options(max_error), backend=backend
+        )
+        done = ((tvg, d["matches"], d["name0"], d["name1"]) for tvg, d in zip(tvgs, gathered))
+    else:
+        done = (process_pair(data, max_error, backend=backend) for data in gathered)
+    for tvg, matches_, name0, name1 in done:
         tvg_cache[name0, name1] = tvg
         # the reference's expression: a match row is an inlier when an equal row is among the inlier matches, so every copy of
         # a duplicated row shares one answer

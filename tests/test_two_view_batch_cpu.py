@@ -1,0 +1,306 @@
+"""CPU checks of the batched two-view geometry: the host logic of estimate_calibrated_two_view_geometry_batch and
+geometric_verification(batched=True) driven through the NumPy restatement, the argument checks of
+mpsfm_two_view_geometry_batch before any device is touched, the ABI of its report struct, and the resource use of the new
+kernels."""
+
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import numpy_two_view_geometry as TV
+from mpsfm_amd import capi
+from mpsfm_amd.sfm.estimators import estimate_calibrated_two_view_geometry_batch
+from mpsfm_amd.sfm.scene.correspondences import geometric_verification
+
+HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "mpsfm_hip.h")
+
+
+# ---- the drop-ins' host logic, the restatement as the backend ---------------------------------------------------------------
+class Restatement:
+    """numpy_two_view_geometry behind capi.two_view_geometry's signature (the class of tests/test_two_view_geometry_cpu.py);
+    it has no two_view_geometry_batch, so the batched drop-in calls it pair by pair"""
+
+    def __init__(self):
+        self.calls = []
+
+    def two_view_geometry(self, p1, p2, K1, K2, s1, s2, device=0, batch_trials=0, **o):
+        self.calls.append(dict(o, n=len(p1), size1=tuple(s1), size2=tuple(s2)))
+        r = TV.estimate(p1, p2, K1, K2, s1, s2, **o)
+        z = np.zeros((3, 3))
+        return dict(r, E=z if r["E"] is None else r["E"], F=z if r["F"] is None else r["F"], H=z if r["H"] is None else r["H"])
+
+
+class _Cam:
+    def __init__(self, params, model="PINHOLE", size=None):
+        self.model, self.params = model, np.asarray(params, np.float64)
+        if size is not None:
+            self.width, self.height = size
+
+
+class _Image:
+    def __init__(self, name, image_id, camera_id):
+        self.name, self.image_id, self.camera_id = name, image_id, camera_id
+
+
+class _Reconstruction:
+    def __init__(self):
+        self.images, self.cameras = {}, {}
+
+
+def _pair_data(seed, n=120):
+    """keypoints of two images and the match rows into them, the matches in shuffled keypoint order"""
+    s = TV.synthetic_pair("general", n, 0.25, seed=seed, noise_px=0.5)
+    rng = np.random.default_rng(seed)
+    o0, o1 = rng.permutation(n), rng.permutation(n)
+    kps0, kps1 = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.float32)
+    kps0[o0], kps1[o1] = s["points1"], s["points2"]
+    return s, kps0, kps1, np.c_[o0, o1].astype(np.int32)
+
+
+@pytest.fixture(scope="module")
+def three_pairs():
+    """three pairs of 120 matches: a plain one, one with a duplicated inlier and a duplicated outlier row, an empty one"""
+    rec, kps, matches = _Reconstruction(), {}, {}
+    names = [("a.jpg", "b.jpg"), ("c.jpg", "d.jpg"), ("e.jpg", "f.jpg")]
+    for k, (n0, n1) in enumerate(names):
+        s, k0, k1, m = _pair_data(seed=10 + k)
+        if k == 1:
+            out, inl = np.nonzero(~s["inliers"])[0][0], np.nonzero(s["inliers"])[0][0]
+            m = np.r_[m, m[[out, inl]]]
+        if k == 2:
+            m = np.zeros((0, 2), np.int32)
+        for j, (name, kp, intr, size) in enumerate(((n0, k0, s["intr1"], s["size1"]), (n1, k1, s["intr2"], s["size2"]))):
+            iid = 2 * k + j + 1
+            rec.images[iid] = _Image(name, iid, iid)
+            rec.cameras[iid] = _Cam(intr, size=size)
+            kps[name] = kp
+        matches[n0, n1] = m
+    loop_be = Restatement()
+    loop = geometric_verification(rec, names, max_error=4.0, keypoints=kps, matches=matches, backend=loop_be)
+    return rec, names, kps, matches, loop, loop_be
+
+
+def test_batched_verification_equals_the_loop(three_pairs):
+    rec, names, kps, matches, (masks, cache), loop_be = three_pairs
+    be = Restatement()
+    bmasks, bcache = geometric_verification(rec, names, max_error=4.0, keypoints=kps, matches=matches, backend=be, batched=True)
+    assert list(bmasks) == list(masks) == names and list(bcache) == list(cache) == names
+    # the backend is called once per pair, in order, with the reference's options
+    assert [c["n"] for c in be.calls] == [120, 122, 0] and be.calls == loop_be.calls
+    for c in be.calls:
+        assert c["max_num_trials"] == 20000 and c["min_inlier_ratio"] == 0.1 and c["max_error"] == 4.0 and c["compute_relative_pose"] is True
+        assert c["seed"] == 0 and c["confidence"] == 0.999 and c["min_num_inliers"] == 15
+    for key in names:
+        m = matches[key]
+        assert bmasks[key].dtype == masks[key].dtype == bool and bmasks[key].shape == masks[key].shape == (len(m),)
+        assert np.array_equal(bmasks[key], masks[key])
+        a, b = cache[key], bcache[key]
+        assert a.config == b.config and type(b.config) is type(a.config)
+        assert b.inlier_matches.dtype == a.inlier_matches.dtype and np.array_equal(a.inlier_matches, b.inlier_matches)
+        assert a.tri_angle == b.tri_angle and np.array_equal(a.cam2_from_cam1.matrix(), b.cam2_from_cam1.matrix())
+    assert [int(bcache[k].config) for k in names] == [2, 2, 1] and bmasks[names[0]].sum() >= 80
+    # every copy of a duplicated row shares one answer: the inlier copy is in, the outlier copy is out
+    assert bmasks[names[1]][121] and not bmasks[names[1]][120]
+    assert bmasks[names[2]].shape == (0,) and bcache[names[2]].inlier_matches.shape == (0, 2)
+
+
+def test_batched_estimate_shares_the_single_functions_checks(three_pairs):
+    rec, names, kps, matches, (_, cache), _ = three_pairs
+    cams = {n: rec.cameras[[i for i, im in rec.images.items() if im.name == n][0]] for pair in names for n in pair}
+    items = [(cams[a], kps[a], cams[b], kps[b], matches[a, b]) for a, b in names]
+    be = Restatement()
+    opts = {"ransac": {"max_num_trials": 20000, "min_inlier_ratio": 0.1, "max_error": 4.0}, "compute_relative_pose": True}
+    tvgs = estimate_calibrated_two_view_geometry_batch(items, opts, backend=be)
+    assert len(tvgs) == 3 and len(be.calls) == 3
+    for tvg, key in zip(tvgs, names):
+        assert tvg.config == cache[key].config and np.array_equal(tvg.inlier_matches, cache[key].inlier_matches)
+        assert set(tvg.estimate) == set(cache[key].estimate)
+    assert estimate_calibrated_two_view_geometry_batch([], opts, backend=be) == []
+    bad = list(items)
+    bad[1] = (bad[1][0], bad[1][1][:5], *bad[1][2:])
+    with pytest.raises(IndexError, match="pair 1"):
+        estimate_calibrated_two_view_geometry_batch(bad, opts, backend=be)
+    assert len(be.calls) == 3  # refused before any pair ran
+    with pytest.raises(NotImplementedError):
+        estimate_calibrated_two_view_geometry_batch(items, {"multiple_models": True}, backend=be)
+    with pytest.raises(KeyError):
+        estimate_calibrated_two_view_geometry_batch(items, {"ransac": {"max_eror": 2}}, backend=be)
+
+    class Batched(Restatement):  # a backend with the batched method gets ONE call
+        def two_view_geometry_batch(self, pairs, device=0, **o):
+            self.batch_sizes = [len(p[0]) for p in pairs]
+            return [self.two_view_geometry(*p, device=device, **o) for p in pairs]
+
+    bb = Batched()
+    again = estimate_calibrated_two_view_geometry_batch(items, opts, backend=bb)
+    assert bb.batch_sizes == [120, 122, 0] and [int(t.config) for t in again] == [int(t.config) for t in tvgs]
+
+
+# ---- the entry point's argument checks ------------------------------------------------------------------------------------
+def _default_options():
+    L = capi.lib()
+    L.mpsfm_two_view_default_options.restype = None
+    L.mpsfm_two_view_default_options.argtypes = [C.c_void_p]
+    o = capi.CTwoViewOptions()
+    L.mpsfm_two_view_default_options(C.byref(o))
+    return o
+
+
+class _Batch:
+    """three pairs of 20, 0 and 30 matches as the C entry point reads them; every member can be replaced or set to None"""
+
+    def __init__(self):
+        rng = np.random.default_rng(0)
+        self.num_pairs = 3
+        self.start = np.array([0, 20, 20, 50], np.int64)
+        self.p1, self.p2 = rng.uniform(0, 900, (50, 2)), rng.uniform(0, 900, (50, 2))
+        self.K1 = np.tile([[800.0, 820.0, 640.0, 480.0]], (3, 1))
+        self.K2 = np.tile([[900.0, 880.0, 600.0, 500.0]], (3, 1))
+        self.s1 = np.tile(np.array([[1280, 960]], np.int32), (3, 1))
+        self.s2 = np.tile(np.array([[1200, 1000]], np.int32), (3, 1))
+        self.o = _default_options()
+        self.group = 0
+        self.mask = np.zeros(50, np.uint8)
+        self.res = (capi.CTwoViewResult * 3)()
+        self.rep = capi.CTwoViewBatchReport()
+
+    def call(self):
+        L = capi.lib()
+        L.mpsfm_two_view_geometry_batch.argtypes = [C.c_int64] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        ref = lambda a: None if a is None else C.cast(C.byref(a), C.c_void_p)  # noqa: E731
+        return L.mpsfm_two_view_geometry_batch(self.num_pairs, ptr(self.start), ptr(self.p1), ptr(self.p2), ptr(self.K1), ptr(self.K2),
+                                               ptr(self.s1), ptr(self.s2), ref(self.o), self.group, 0, ptr(self.mask), ref(self.res),
+                                               ref(self.rep))
+
+
+def _error():
+    return capi.lib().mpsfm_last_error().decode()
+
+
+def test_batch_entry_point_validates_arguments_first():
+    einval = -1
+    for member in ("start", "p1", "p2", "K1", "K2", "s1", "s2", "o", "mask", "res"):
+        b = _Batch()
+        setattr(b, member, None)
+        assert b.call() == einval, member
+    b = _Batch()
+    b.num_pairs = -1
+    assert b.call() == einval
+    b = _Batch()
+    b.group = -1
+    assert b.call() == einval and "pairs_per_group" in _error()
+    b = _Batch()
+    b.start[0] = 1
+    assert b.call() == einval and "pair_start[0]" in _error()
+    b = _Batch()
+    b.start[2] = 10  # pair 1 would have -10 matches
+    assert b.call() == einval and "pair 1" in _error()
+    b = _Batch()
+    b.start[3] = 20 + 2**31  # pair 2: more than INT32_MAX matches (refused before a point is read)
+    assert b.call() == einval and "pair 2" in _error()
+    for which, row, pair in (("p1", 0, 0), ("p2", 19, 0), ("p1", 20, 2), ("p2", 49, 2)):
+        b = _Batch()
+        getattr(b, which)[row, row % 2] = np.nan if row % 2 else np.inf
+        assert b.call() == einval and f"pair {pair}" in _error() and "non-finite" in _error()
+    for which in ("K1", "K2"):
+        for pair, col, value in ((0, 0, 0.0), (1, 1, 0.0), (2, 2, np.nan)):  # pair 1 has no matches and is checked all the same
+            b = _Batch()
+            getattr(b, which)[pair, col] = value
+            assert b.call() == einval and f"pair {pair}" in _error() and "intrinsics" in _error()
+    for which, pair, value in (("s1", 1, (0, 960)), ("s2", 2, (1200, -1))):
+        b = _Batch()
+        getattr(b, which)[pair] = value
+        assert b.call() == einval and f"pair {pair}" in _error() and "sizes" in _error()
+    for field, value in (("max_error", 0.0), ("min_inlier_ratio", 1.5), ("max_num_trials", 10), ("batch_trials", -3), ("batch_trials", 1 << 20)):
+        b = _Batch()
+        setattr(b.o.ransac, field, value)
+        assert b.call() == einval and "options" in _error()
+    for field, value in (("min_num_inliers", -1), ("max_H_inlier_ratio", -0.1), ("watermark_border_size", 0.7), ("detect_watermark", 2)):
+        b = _Batch()
+        setattr(b.o, field, value)
+        assert b.call() == einval and "options" in _error()
+    # no pairs: 0, and nothing is touched (not even the pointers)
+    b = _Batch()
+    b.num_pairs = 0
+    b.mask[:] = 7
+    b.rep.num_syncs = 5
+    assert b.call() == 0 and (b.mask == 7).all() and b.rep.num_syncs == 5
+    for member in ("start", "p1", "res"):
+        setattr(b, member, None)
+    assert b.call() == 0
+    assert capi.two_view_geometry_batch([]) == []
+    # the wrapper's own checks
+    p = (np.zeros((4, 2)), np.zeros((4, 2)), b.K1[0], b.K2[0], (1280, 960), (1200, 1000))
+    with pytest.raises(KeyError):
+        capi.two_view_geometry_batch([p], max_eror=3.0)
+    with pytest.raises(ValueError):
+        capi.two_view_geometry_batch([(p[0], p[1][:2], *p[2:])])
+    with pytest.raises(capi.MpsfmHipError) as e:
+        capi.two_view_geometry_batch([p, (*p[:4], (1280, 0), p[5])])
+    assert e.value.code == -1 and "pair 1" in str(e.value)
+
+
+def test_batch_entry_point_without_device_fails_loudly():
+    if capi.device_count() > 0:
+        pytest.skip("a gfx950 device is visible")
+    b = _Batch()
+    assert b.call() == -2  # a valid call: MPSFM_ENODEVICE, no CPU fallback
+    b.rep = None
+    assert b.call() == -2  # the report may be NULL
+    with pytest.raises(capi.MpsfmHipError) as e:
+        capi.two_view_geometry_batch([(b.p1[:20], b.p2[:20], b.K1[0], b.K2[0], b.s1[0], b.s2[0])])
+    assert e.value.code == -2
+
+
+def test_report_struct_matches_the_headers_static_assert():
+    text = open(HEADER).read()
+    m = re.search(r"static_assert\(sizeof\(mpsfm_two_view_batch_report\) == (\d+)(.*?)\"ABI of mpsfm_two_view_batch_report\"", text, flags=re.S)
+    assert m, "the header asserts the ABI of mpsfm_two_view_batch_report"
+    offsets = {name: int(v) for name, v in re.findall(r"offsetof\(mpsfm_two_view_batch_report, (\w+)\) == (\d+)", m.group(2))}
+    R = capi.CTwoViewBatchReport
+    assert C.sizeof(R) == int(m.group(1)) == 32
+    assert offsets == {"num_syncs": 8, "num_launches": 16, "ms": 24}
+    for name, off in offsets.items():
+        assert getattr(R, name).offset == off
+    assert R.num_groups.offset == 0 and [f[0] for f in R._fields_][:4] == ["num_groups", "num_syncs", "num_launches", "ms"]
+    assert "mpsfm_two_view_geometry_batch" in capi.EXPORTS and hasattr(capi.lib(), "mpsfm_two_view_geometry_batch")
+    assert capi.lib().mpsfm_abi_version() == 2  # the addition is purely additive
+
+
+# ---- the kernels ------------------------------------------------------------------------------------------------------------
+NEW_KERNELS = ("k_bt_five", "k_bt_f7", "k_bt_h4", "k_bt_t1", "k_bt_score", "k_bt_sum", "k_bt_moments", "k_bt_gram", "k_bt_egram",
+               "k_bt_tsum", "k_bt_mask", "k_bt_pose")
+
+
+def test_new_kernels_compile_for_gfx950_without_scratch():
+    from mpsfm_amd import build
+
+    assert "two_view_batch.hip" in build.SOURCES and "two_view_problem.h" in build.HEADERS
+    src = os.path.join(build.CSRC, "two_view_batch.hip")
+    r = subprocess.run([build._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", src, "-o", os.devnull,
+                        "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    found = {}
+    for name, body, lds in re.findall(r"Function Name: (\S+)(.*?)LDS Size \[bytes/block\]: (\d+)", r.stdout, flags=re.S):
+        for k in NEW_KERNELS:
+            if k + "E" in name or k + "I" in name:  # the mangled name: <length><name>E... or, for a template, <name>I...
+                tag = k + ("<H>" if "Lb1" in name else "<F>" if "Lb0" in name else "<T>" if "TvTranslation" in name else
+                           "<E>" if "RpProblem" in name else "")
+                found[tag] = (int(re.search(r"VGPRs: (\d+)", body).group(1)), int(lds),
+                              int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", body).group(1)))
+    print("kernel: (VGPRs, LDS bytes, scratch bytes)")
+    for k, v in sorted(found.items()):
+        print(f"  {k}: {v}")
+    for k in NEW_KERNELS:
+        hits = [v for name, v in found.items() if name == k or name.startswith(k + "<")]
+        assert hits, (k, r.stdout)
+        assert all(scratch == 0 for _, _, scratch in hits), (k, hits)
+    assert {t for t in found if t.startswith("k_bt_score")} == {"k_bt_score<E>", "k_bt_score<F>", "k_bt_score<H>", "k_bt_score<T>"}
+    assert {t for t in found if t.startswith("k_bt_mask")} == {"k_bt_mask<E>", "k_bt_mask<F>", "k_bt_mask<H>"}
+    for k in ("k_bt_five", "k_bt_f7", "k_bt_h4"):
+        assert found[k][1] <= 64 * 1024  # the per-thread LDS slices fit a workgroup's 64 KiB
