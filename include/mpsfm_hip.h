@@ -807,6 +807,58 @@ typedef struct mpsfm_init_candidates {
 
 int mpsfm_init_pair_candidates(const mpsfm_init_pair* pair, int32_t device, mpsfm_init_candidates* out);
 
+/* ---- thinning a dense matcher's output: the fixed-radius neighbour geometry of the reference's
+ *    mpsfm/extraction/pairwise (models/utils/generic.py sparse_nms, models/utils/warp.py assign_keypoints,
+ *    match_dense_2view.py:127-161), which the reference does with a SciPy KD-tree on the host.  All distance arithmetic is
+ *    fp64 dx*dx + dy*dy with every operation rounded on its own; the comparisons below are exact.
+ *
+ *    mpsfm_radius_nms: greedy radius suppression.  The points are visited in priority order; a visited point that is still
+ *    alive is kept and suppresses every point at squared distance <= radius*radius.  Priority is `order` when given (a
+ *    permutation of 0 .. n-1, highest priority first), else score descending with ties going to the LOWER INDEX (-0.0
+ *    counts as +0.0).  The reference's own order among equal scores is whatever its unstable torch.argsort gives; `order`
+ *    lets a caller impose one.  keep[i] = 1 for kept points; the result does not depend on how the device schedules the
+ *    work.
+ *
+ *    mpsfm_thin_dense_matches: both passes of the `dense` leg for one pair in one call, the survivors never leaving the
+ *    device.  Pass 1 is the suppression over [sparse0; dense0] with scores [100 ...; dscores], pass 2 the suppression over
+ *    [sparse1; the dense1 of pass 1's survivors] with the same scores; n_sparse == 0 is the dense-only branch.  keep[j] = 1
+ *    for the dense matches that survive both.  REFERENCE_SLICE: the reference takes the survivors of a pass as
+ *    sparse_nms(comb, ...)[n_sparse:] - n_sparse, which assumes that all n_sparse sparse points survive.  When only
+ *    k < n_sparse of them do (matched sparse keypoints closer than the radius), that expression ALSO DROPS THE FIRST
+ *    n_sparse - k SURVIVING DENSE MATCHES (in index order).  reference_slice != 0 reproduces this in both passes,
+ *    reference_slice == 0 keeps every surviving dense match.  Scores above 100 are not special: such a dense match outranks
+ *    the sparse points, as it does in the reference.
+ *
+ *    mpsfm_assign_keypoints: ids[i] = the keypoint nearest to query[i] among those with squared distance strictly
+ *    < max_error*max_error (a query at exactly max_error gets -1, as SciPy's query with distance_upper_bound does), the
+ *    lowest index among equidistant nearest ones, -1 when there is none.  Either side empty: all -1, nothing is launched.
+ *
+ *    All three: caller owns all buffers, nothing is retained; MPSFM_EINVAL for NULL pointers, negative counts or radius,
+ *    more than 2^27 points, non-finite coordinates, scores or radius, a bounding box wider than DBL_MAX and an `order` that
+ *    is no permutation, checked on the host before any device is touched; an empty call returns 0 without a device;
+ *    MPSFM_ENODEVICE without a device. ---- */
+typedef struct mpsfm_nms_info {
+  int32_t rounds;           /* round launches up to and including the first that left no point undecided */
+  int32_t launches;         /* round launches enqueued (rounds go out in groups, the count is read once per group) */
+  int32_t cells;            /* occupied grid cells */
+  int32_t max_cell_points;  /* the largest cell population */
+  float ms;                 /* device time from the first kernel to the last (HIP events), transfers excluded */
+  int32_t reserved;
+} mpsfm_nms_info;           /* mpsfm_thin_dense_matches: rounds, launches and ms summed over its two passes, cells and
+                               max_cell_points the larger of the two */
+
+int mpsfm_radius_nms(int64_t n, const double* points /* [n][2] */, const double* scores /* [n] */,
+                     const int64_t* order /* [n] or NULL */, double radius, int32_t device, uint8_t* keep /* [n] */,
+                     int64_t* num_kept, mpsfm_nms_info* info /* may be NULL */);
+
+int mpsfm_thin_dense_matches(int64_t n_sparse, const double* sparse0, const double* sparse1 /* [n_sparse][2] */, int64_t n_dense,
+                             const double* dense0, const double* dense1 /* [n_dense][2] */, const double* dscores /* [n_dense] */,
+                             double radius, int32_t reference_slice, int32_t device, uint8_t* keep /* [n_dense] */,
+                             int64_t* num_kept, mpsfm_nms_info* info /* may be NULL */);
+
+int mpsfm_assign_keypoints(int64_t n_query, const double* query /* [n_query][2] */, int64_t n_kps, const double* kps /* [n_kps][2] */,
+                           double max_error, int32_t device, int64_t* ids /* [n_query] */, float* ms /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

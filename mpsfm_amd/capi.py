@@ -26,6 +26,7 @@ EXPORTS = [
     "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
     "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_two_view_geometry", "mpsfm_two_view_geometry_batch",
     "mpsfm_two_view_default_options", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
+    "mpsfm_radius_nms", "mpsfm_thin_dense_matches", "mpsfm_assign_keypoints",
 ]
 
 _lib = None
@@ -855,3 +856,84 @@ def init_pair_candidates(xy1, xy2, intr1, intr2, cam2_from_cam1, prior_map=None,
         o[name] = (flags >> bit & 1).astype(bool)
     o["ms"] = float(O.ms)
     return o
+
+
+class CNmsInfo(C.Structure):
+    """mpsfm_nms_info"""
+    _fields_ = [("rounds", C.c_int32), ("launches", C.c_int32), ("cells", C.c_int32), ("max_cell_points", C.c_int32), ("ms", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+def _nms_info(I) -> dict:
+    return dict(rounds=int(I.rounds), launches=int(I.launches), cells=int(I.cells), max_cell_points=int(I.max_cell_points), ms=float(I.ms))
+
+
+def _xy(a, what="points") -> np.ndarray:
+    """[n, 2] float64, C-contiguous (float32 input is widened exactly)."""
+    a = np.ascontiguousarray(a, np.float64)
+    if a.size == 0:
+        return a.reshape(0, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"{what} must be an [n, 2] array")
+    return a
+
+
+def radius_nms(points, scores, radius, order=None, device=0, return_info=False):
+    """mpsfm_radius_nms: greedy radius suppression in priority order (`order`, a permutation with the highest priority first,
+    else score descending with ties to the lower index).  Returns keep bool [n][, info dict(rounds, launches, cells,
+    max_cell_points, ms)]."""
+    p = _xy(points)
+    n = len(p)
+    s = np.ascontiguousarray(scores, np.float64).reshape(-1)
+    if len(s) != n:
+        raise ValueError("points and scores differ in length")
+    o = None
+    if order is not None:
+        o = np.ascontiguousarray(order, np.int64).reshape(-1)
+        if len(o) != n:
+            raise ValueError("order must have one entry per point")
+    keep, kept, I = np.zeros(max(n, 1), np.uint8), C.c_int64(0), CNmsInfo()
+    L = lib()
+    L.mpsfm_radius_nms.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_radius_nms(n, p.ctypes.data, s.ctypes.data, None if o is None else o.ctypes.data, float(radius), int(device),
+                              keep.ctypes.data, C.addressof(kept), C.addressof(I)))
+    keep = keep[:n].astype(bool)
+    assert int(kept.value) == int(keep.sum())
+    return (keep, _nms_info(I)) if return_info else keep
+
+
+def thin_dense_matches_mask(dense0, dense1, dscores, sparse0=None, sparse1=None, radius=6.0, reference_slice=True, device=0,
+                            return_info=False):
+    """mpsfm_thin_dense_matches: both suppression passes of one pair's dense matches in one call.  Returns keep bool [n_dense]
+    [, info dict].  `reference_slice`: see include/mpsfm_hip.h (the reference's slice drops surviving dense matches when
+    matched sparse keypoints suppress each other)."""
+    d0, d1 = _xy(dense0, "dense0"), _xy(dense1, "dense1")
+    sc = np.ascontiguousarray(dscores, np.float64).reshape(-1)
+    nd = len(d0)
+    if len(d1) != nd or len(sc) != nd:
+        raise ValueError("dense0, dense1 and dscores differ in length")
+    s0 = _xy(np.zeros((0, 2)) if sparse0 is None else sparse0, "sparse0")
+    s1 = _xy(np.zeros((0, 2)) if sparse1 is None else sparse1, "sparse1")
+    if len(s0) != len(s1):
+        raise ValueError("sparse0 and sparse1 differ in length")
+    keep, kept, I = np.zeros(max(nd, 1), np.uint8), C.c_int64(0), CNmsInfo()
+    L = lib()
+    L.mpsfm_thin_dense_matches.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_thin_dense_matches(len(s0), s0.ctypes.data, s1.ctypes.data, nd, d0.ctypes.data, d1.ctypes.data, sc.ctypes.data,
+                                      float(radius), int(bool(reference_slice)), int(device), keep.ctypes.data, C.addressof(kept),
+                                      C.addressof(I)))
+    keep = keep[:nd].astype(bool)
+    return (keep, _nms_info(I)) if return_info else keep
+
+
+def assign_keypoints_ids(query, kps, max_error, device=0, return_ms=False):
+    """mpsfm_assign_keypoints: per query the nearest keypoint strictly closer than max_error (lowest index among equidistant
+    ones) or -1.  Returns ids int64 [n_query][, device ms]."""
+    q, k = _xy(query, "query"), _xy(kps, "kps")
+    ids, ms = np.full(len(q), -1, np.int64), C.c_float(0)
+    L = lib()
+    L.mpsfm_assign_keypoints.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_assign_keypoints(len(q), q.ctypes.data, len(k), k.ctypes.data, float(max_error), int(device), ids.ctypes.data,
+                                    C.addressof(ms)))
+    return (ids, float(ms.value)) if return_ms else ids
