@@ -222,7 +222,12 @@ int mpsfm_ba_dense_plan(mpsfm_ba_handle* h, int64_t info[10]);
 
 /* -- point covariances: replaces pycolmap.estimate_ba_covariance(POINTS)
  *    (bundle_adjustment.py:244-261).  cov[j] = (sum_i magnitude * Jp_i^T Jp_i)^-1 over the
- *    reprojection blocks of point j with every other variable held constant. ------------- */
+ *    reprojection blocks of point j with every other variable held constant.
+ *    A point with fewer than two observations gets NaN in all nine entries: one observation
+ *    leaves the sum with rank 2, and the count decides, not a pivot, so the answer is the same
+ *    on every run.  A point with two or more observations whose sum is not numerically positive
+ *    definite gets NaN as well.  The summation order over the observations of a point is free
+ *    (atomics): results of two calls agree to rounding, not bit for bit. ------------------- */
 int mpsfm_point_covs(const mpsfm_ba_problem* problem, const mpsfm_ba_state* state,
                      int32_t device, double* covs /* [n_pts][3][3] */);
 
@@ -241,13 +246,25 @@ typedef struct mpsfm_tracks {
 } mpsfm_tracks;
 
 /* Linear multi-view triangulation of every track (COLMAP TriangulateMultiViewPoint):
- * xyz[t] = smallest eigenvector of sum_i (P_i - x_i x_i^T P_i)^T (...), dehomogenised. */
+ * xyz[t] = smallest eigenvector of sum_i (P_i - x_i x_i^T P_i)^T (...), dehomogenised.
+ * A track of fewer than two elements has no two rays to intersect: xyz[t] is NaN in all three
+ * coordinates.  A rank-deficient track of two or more elements (the same camera and pixel twice,
+ * cameras with one centre and one ray) gets the plain arithmetic: some vector of the null space,
+ * dehomogenised, which may be non-finite. */
 int mpsfm_triangulate_tracks(const mpsfm_tracks* tracks, int32_t device,
                              double* xyz /* [n_tracks][3] out */);
 
 /* Per-track quality numbers at given points: max pairwise triangulation angle (radians),
- * per-element squared reprojection error and cheirality (depth > 0) flags.
- * Any output pointer may be NULL. */
+ * per-element squared reprojection error and cheirality flags.  Any output pointer may be NULL.
+ *   max_tri_angle  largest angle between the rays of two elements, by the law of cosines on squared
+ *                  lengths, folded to [0, pi/2]; exactly 0 for a track of fewer than two elements and
+ *                  for a pair with a ray of zero length (the point at a projection centre).
+ *   el_front       1 where the depth zc of the point in the element's camera is >= 2^-52 (DBL_EPSILON).
+ *   el_sq_err      the plain formula |K (xc, yc) / zc + c - xy|^2 whatever the sign of zc: finite, and
+ *                  possibly small, for a point mirrored behind the camera; inf or NaN for zc == 0.
+ *                  (COLMAP's CalculateSquaredReprojectionError returns DBL_MAX for zc < eps instead.)
+ *                  A caller must therefore treat el_front == 0 as "bad" by itself, as
+ *                  reprojection_decisions in mpsfm_amd/sfm/scene/observations.py does. */
 int mpsfm_filter_tracks(const mpsfm_tracks* tracks, const double* xyz /* [n_tracks][3] */,
                         int32_t device, double* max_tri_angle /* [n_tracks] */,
                         double* el_sq_err /* [n_el] */, uint8_t* el_front /* [n_el] */);

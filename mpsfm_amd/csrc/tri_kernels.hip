@@ -41,13 +41,16 @@ __global__ void k_pcov_accum(int64_t nobs, const int32_t* cam, const int32_t* pt
   atomicAdd(&h[4], mag * (j0[1] * j0[2] + j1[1] * j1[2]));
   atomicAdd(&h[5], mag * (j0[2] * j0[2] + j1[2] * j1[2]));
 }
-__global__ void k_pcov_invert(int np, const double* H, double* cov) {
+// n_seen[p]: observations of point p, saturated at 2 (counted on the host beside the index check).  Fewer than two leave
+// H with rank <= 2: whether the last pivot of spd3_inverse then comes out positive is rounding and atomic order, so the
+// count decides, not the pivot.
+__global__ void k_pcov_invert(int np, const double* H, const uint8_t* n_seen, double* cov) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= np) return;
   double V[6], Vi[6];
   for (int k = 0; k < 6; ++k) V[k] = H[6 * (size_t)p + k];
   double* o = cov + 9 * (size_t)p;
-  if (!spd3_inverse(V, Vi)) {
+  if (n_seen[p] < 2 || !spd3_inverse(V, Vi)) {
     for (int k = 0; k < 9; ++k) o[k] = __builtin_nan("");
     return;
   }
@@ -66,6 +69,10 @@ struct TrackArgs {
 __global__ void k_triangulate(TrackArgs T, double* xyz) {
   const int tr = blockIdx.x * blockDim.x + threadIdx.x;
   if (tr >= T.n_tracks) return;
+  if (T.start[tr + 1] - T.start[tr] < 2) {  // no two rays to intersect: A has rank <= 2 and its null vector is arbitrary
+    xyz[3 * (size_t)tr] = xyz[3 * (size_t)tr + 1] = xyz[3 * (size_t)tr + 2] = __builtin_nan("");
+    return;
+  }
   double A[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
   for (int64_t e = T.start[tr]; e < T.start[tr + 1]; ++e) {
     const int cam = T.el_cam[e];
@@ -196,9 +203,13 @@ int mpsfm_point_covs(const mpsfm_ba_problem* P, const mpsfm_ba_state* st, int32_
   if (P->n_obs > 0 && (!P->obs_cam || !P->obs_pt || !P->obs_xy)) return fail(MPSFM_EINVAL, "observation arrays are NULL");
   if (P->n_cams > 0 && (!P->cam_intr_idx || !P->cam_intr || !st->cam_quat_xyzw || !st->cam_t)) return fail(MPSFM_EINVAL, "camera arrays are NULL");
   if (P->n_pts > 0 && !st->pts) return fail(MPSFM_EINVAL, "pts is NULL");
-  for (int64_t i = 0; i < P->n_obs; ++i)
+  std::vector<uint8_t> n_seen((size_t)P->n_pts, 0);  // observations per point, saturated at 2
+  for (int64_t i = 0; i < P->n_obs; ++i) {
     if (P->obs_cam[i] < 0 || P->obs_cam[i] >= P->n_cams || P->obs_pt[i] < 0 || P->obs_pt[i] >= P->n_pts)
       return fail(MPSFM_EINVAL, "observation index out of range");
+    uint8_t& n = n_seen[(size_t)P->obs_pt[i]];
+    n = n < 2 ? n + 1 : 2;
+  }
   for (int i = 0; i < P->n_cams; ++i)
     if (P->cam_intr_idx[i] < 0 || P->cam_intr_idx[i] >= P->n_intr) return fail(MPSFM_EINVAL, "cam_intr_idx out of range");
   if (int rc = open_device(device)) return rc;
@@ -212,14 +223,15 @@ int mpsfm_point_covs(const mpsfm_ba_problem* P, const mpsfm_ba_state* st, int32_
   const double* intr = B.put(P->cam_intr, (size_t)P->n_intr * 4);
   const int32_t* iidx = B.put(P->cam_intr_idx, (size_t)P->n_cams);
   const double* pts = B.put(st->pts, (size_t)P->n_pts * 3);
+  const uint8_t* seen = B.put(n_seen.data(), (size_t)P->n_pts);
   double* H = B.alloc<double>((size_t)P->n_pts * 6);
   double* dcov = B.alloc<double>((size_t)P->n_pts * 9);
-  if (!cam || !pt || !q || !t || !intr || !iidx || !pts || !H || !dcov) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!cam || !pt || !q || !t || !intr || !iidx || !pts || !seen || !H || !dcov) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   MPSFM_TRY(hipMemsetAsync(H, 0, sizeof(double) * 6 * (size_t)P->n_pts, B.st));
   if (P->n_obs > 0)
     hipLaunchKernelGGL(k_pcov_accum, dim3((unsigned)((P->n_obs + 255) / 256)), dim3(256), 0, B.st, P->n_obs, cam, pt, q, t, intr,
                        iidx, pts, P->reproj_loss_magnitude, H);
-  hipLaunchKernelGGL(k_pcov_invert, dim3((P->n_pts + 255) / 256), dim3(256), 0, B.st, P->n_pts, H, dcov);
+  hipLaunchKernelGGL(k_pcov_invert, dim3((P->n_pts + 255) / 256), dim3(256), 0, B.st, P->n_pts, H, seen, dcov);
   MPSFM_TRY(hipGetLastError());
   MPSFM_TRY(B.down(covs, dcov, sizeof(double) * 9 * (size_t)P->n_pts));
   return 0;

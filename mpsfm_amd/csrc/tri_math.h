@@ -10,7 +10,8 @@
 
 namespace mpsfm {
 
-// smallest eigenvector of a symmetric 4x4 by cyclic Jacobi rotations
+// smallest eigenvector of a symmetric 4x4 by cyclic Jacobi rotations.  The normal matrix of fewer than two views has rank
+// <= 2 and no single smallest eigenvector: callers answer such a track themselves (NaN point / no model), never from here.
 __host__ __device__ inline void sym4_min_eigvec(double A[4][4], double v[4]) {
   double Q[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
   for (int sweep = 0; sweep < 30; ++sweep) {
@@ -146,6 +147,7 @@ struct TriRansacOptions {
 
 // TriangulationEstimator::Estimate for the views listed in idx[0..m): fills X, returns false when no model
 __host__ __device__ inline bool tri_estimate(const TriView* views, const int* idx, int m, double min_tri_angle, double* X) {
+  if (m < 2) return false;
   if (m == 2) {
     const TriView &a = views[idx[0]], &b = views[idx[1]];
     tri_two_view(a, b, X);

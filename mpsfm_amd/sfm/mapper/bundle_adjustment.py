@@ -320,7 +320,8 @@ class Optimizer(BaseClass):
     def calculate_point_covs(self, bundle):
         """Calculates point covariances for the given bundle (reference :244-261): reprojection-only
         problem, trivial loss with magnitude 1/kp_std^2, every bundle point variable (which pulls in
-        its observations outside the bundle), covariance of each point with all else constant."""
+        its observations outside the bundle), covariance of each point with all else constant.  A point with fewer
+        than two observations gets an all-NaN covariance, stored like any other (PointCovs hands the NaN on)."""
         rec = self.mpsfm_rec
         optim_ids = list(bundle["optim_ids"])
         (image_ids, _, point_ids, pt_of, obs_cam, obs_pt, obs_xy, pose_const, pt_const,

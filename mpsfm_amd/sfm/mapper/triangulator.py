@@ -59,7 +59,8 @@ def track_quality(scene, point3D_ids, device: int = 0):
 
 
 def triangulate_points(scene, point3D_ids, device: int = 0) -> np.ndarray:
-    """Linear multi-view triangulation of the tracks of the given points (HIP batch kernel)."""
+    """Linear multi-view triangulation of the tracks of the given points (HIP batch kernel).  Nothing is stored: the
+    coordinates go back to the caller, NaN for a point whose track has fewer than two elements."""
     from ... import capi
 
     tr, _ = tracks_from_scene(scene, point3D_ids)

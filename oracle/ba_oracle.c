@@ -1093,14 +1093,16 @@ ORACLE_API int oracle_reduced_dim(const mpsfm_ba_problem* P) {
 
 /* Point covariances (reference bundle_adjustment.py:244-261 -> pycolmap.estimate_ba_covariance
  * with params=POINTS): reprojection-only problem, trivial loss scaled by the magnitude,
- * cov_j = (sum_i k Jp_i^T Jp_i)^-1, conditioned on every other variable.  Points with no
- * observation (or a singular block) get NaN. */
+ * cov_j = (sum_i k Jp_i^T Jp_i)^-1, conditioned on every other variable.  Points with fewer
+ * than two observations (decided by the count, not by a pivot) or a singular block get NaN. */
 ORACLE_API int oracle_point_covs(const mpsfm_ba_problem* P, const mpsfm_ba_state* st, double* covs) {
   if (!check_problem(P)) return MPSFM_EINVAL;
   const int np = P->n_pts;
   double* H = (double*)calloc((size_t)np * 6 + 6, sizeof(double));
+  int* n_seen = (int*)calloc((size_t)np + 1, sizeof(int));
   for (int64_t i = 0; i < P->n_obs; ++i) {
     const int cam = P->obs_cam[i], pt = P->obs_pt[i];
+    n_seen[pt]++;
     double R[9], r[2], Jc[12], Jp[6];
     quat_to_R(st->cam_quat_xyzw + 4 * cam, R);
     block_eval(0, R, st->cam_t + 3 * cam, P->cam_intr + 4 * P->cam_intr_idx[cam], st->pts + 3 * pt,
@@ -1116,11 +1118,12 @@ ORACLE_API int oracle_point_covs(const mpsfm_ba_problem* P, const mpsfm_ba_state
   for (int p = 0; p < np; ++p) {
     double Vi[6];
     double* o = covs + 9 * p;
-    if (!spd3_inverse(H + 6 * p, Vi)) { for (int k = 0; k < 9; ++k) o[k] = NAN; continue; }
+    if (n_seen[p] < 2 || !spd3_inverse(H + 6 * p, Vi)) { for (int k = 0; k < 9; ++k) o[k] = NAN; continue; }
     o[0] = Vi[0]; o[1] = Vi[1]; o[2] = Vi[2];
     o[3] = Vi[1]; o[4] = Vi[3]; o[5] = Vi[4];
     o[6] = Vi[2]; o[7] = Vi[4]; o[8] = Vi[5];
   }
+  free(n_seen);
   free(H);
   return 0;
 }

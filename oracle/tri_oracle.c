@@ -59,6 +59,10 @@ static void sym4_min_eigvec(double A[16], double v[4]) {
 
 ORACLE_API int oracle_triangulate_tracks(const mpsfm_tracks* T, double* xyz) {
   for (int t = 0; t < T->n_tracks; ++t) {
+    if (T->track_start[t + 1] - T->track_start[t] < 2) { /* no two rays to intersect */
+      xyz[3 * t] = xyz[3 * t + 1] = xyz[3 * t + 2] = NAN;
+      continue;
+    }
     double A[16];
     memset(A, 0, sizeof(A));
     for (int64_t e = T->track_start[t]; e < T->track_start[t + 1]; ++e) {
