@@ -332,7 +332,10 @@ int mpsfm_triangulator_stats(mpsfm_triangulator* h, int64_t* batch, int64_t* bat
 /* COLMAP's EstimateTriangulation (LORANSAC<TriangulationEstimator, ..., InlierSupportMeasurer, CombinationSampler>, what
  * IncrementalTriangulator::Create / CompleteImage run per candidate track; reference call sites
  * mpsfm/sfm/mapper/triangulator.py:88-100, 123) for many independent candidate tracks in ONE launch: one thread per
- * candidate, at most 64 views each (MPSFM_EUNSUPPORTED beyond).  The engine above uses the same kernel for its batches. */
+ * candidate, at most 64 views each (MPSFM_EUNSUPPORTED beyond).  The engine above uses the same kernel for its batches.
+ * A candidate without a model, and any candidate of 0 or 1 views, gives ok = 0, xyz = (0, 0, 0) and inlier = 0 for each of
+ * its views; its neighbours in the batch are not affected.  min_num_trials[i] is taken as given (0: the stop rule alone
+ * ends the loop; C(n, 2) or more: every pair is drawn). */
 typedef struct mpsfm_tri_candidates {
   int64_t n_candidates;
   const int64_t* cand_start;          /* [n_candidates+1] CSR into the view arrays                                  */

@@ -2,17 +2,22 @@
 the friendly scenes, against hand-made exact cases, and on the case sets of tests/test_gpu_exact_geometry.py (every
 forward-checked case is informative; the unaltered oracle and the NumPy evaluation pass every criterion)."""
 
+import builtins
+import linecache
 import math
+import sys
 
 import mpmath as mp
 import numpy as np
 import pytest
 
 import exact_geometry as G
+import numpy_registration as NR
 from mpsfm_amd.problem import Tracks
 from mpsfm_amd.sfm.scene.observations import reprojection_decisions
 from mpsfm_amd.synthetic import make_scene
 from oracle import cpu_oracle as O
+from oracle import track_graph_oracle as TG
 
 
 @pytest.fixture(scope="module")
@@ -134,3 +139,220 @@ def test_an_element_behind_its_camera_is_bad_whatever_its_error():
     assert (~front).sum() >= 8 and bad[~front].all()
     behind = err[~front]
     assert np.isnan(behind).any() and np.isinf(behind).any() and (behind < 1e-12).any()
+
+
+# ---- candidate tracks and init-pair points: the exact walk, its golden file, the restatements, the mutations --------------
+HANDFUL = ("friendly3", "outlier5_middle", "two_pairs_tie", "parallax_below", "behind_one", "depth0.01", "one_view", "threshold_px", "random3", "random8")
+
+
+def _named():
+    g = G.candidate_golden()
+    return [c for c, grp in enumerate(g["groups"]) if grp != "random"]
+
+
+def _join(a):
+    return [mp.mpf(float(h)) + mp.mpf(float(l)) for h, l in np.asarray(a).reshape(-1, 2)]
+
+
+def test_golden_candidates_are_the_case_set_and_a_handful_walks_again():
+    """tests/golden/exact_candidates.npz holds the inputs of candidate_cases() and what exact_loransac finds: the inputs
+    are compared all (to 1e-12: the builder goes through libm), a handful of candidates is walked again from the stored
+    inputs and compared in full."""
+    arr, g = G.candidate_cases().arrays(), G.candidate_golden()
+    assert arr["labels"].tolist() == g["labels"].tolist() and arr["groups"].tolist() == g["groups"].tolist()
+    np.testing.assert_array_equal(arr["cand_start"], g["cand_start"])
+    np.testing.assert_array_equal(arr["min_num_trials"], g["min_num_trials"])
+    for k in ("P", "K", "xy"):
+        np.testing.assert_allclose(arr[k], g[k], rtol=1e-12, atol=1e-12, err_msg=k)
+    which = [g["labels"].tolist().index(lab) for lab in HANDFUL]
+    o = G.walk_candidates(g, which)
+    with mp.workdps(G.DPS):
+        for rt in (0, 1):
+            for k in ("ok", "mask", "idx", "trials", "lo_rounds"):
+                np.testing.assert_array_equal(o[f"{k}{rt}"], g[f"{k}{rt}"][which], err_msg=f"{k}{rt}")
+            np.testing.assert_allclose(o[f"margin{rt}"], g[f"margin{rt}"][which], rtol=1e-6)
+            for k in ("X", "A", "lam"):
+                for a, b in zip(_join(o[f"{k}{rt}"]), _join(g[f"{k}{rt}"][which])):
+                    assert abs(a - b) <= mp.mpf(10) ** -28 * (1 + abs(b)), (k, rt)
+
+
+def test_open_candidates_stay_under_the_cap():
+    """No named candidate outside the threshold group is open, every threshold case is open for at least one residual
+    type, and at most 2 % of the random set is open."""
+    g = G.candidate_golden()
+    labels, groups = g["labels"].tolist(), g["groups"].tolist()
+    for rt in (0, 1):
+        open_ = {lab for lab, grp, m in zip(labels, groups, g[f"margin{rt}"]) if grp != "random" and not m > 1}
+        assert open_ <= {lab for lab, grp in zip(labels, groups) if grp == "threshold"}, open_
+        rnd = np.array([m for grp, m in zip(groups, g[f"margin{rt}"]) if grp == "random"])
+        assert len(rnd) == G.N_RANDOM and (~(rnd > 1)).sum() <= 0.02 * len(rnd), (rt, int((~(rnd > 1)).sum()))
+        ok = g[f"ok{rt}"][[grp == "random" for grp in groups]]
+        assert ok.sum() > 50 and (~ok).sum() > 5  # both outcomes occur
+        print(f"residual type {rt}: open named {sorted(open_)}, open random {int((~(rnd > 1)).sum())} of {len(rnd)}")
+    for lab, grp in zip(labels, groups):
+        c = labels.index(lab)
+        if grp == "threshold":
+            assert min(g["margin0"][c], g["margin1"][c]) <= 1, lab
+        if lab in ("empty", "one_view"):
+            assert not g["ok0"][c] and not g["ok1"][c]
+    # the walk took the paths the cases are there for
+    c = labels.index("outlier64_last")
+    assert int(g["mask0"][c]) == 2 ** 63 - 1 and int(g["mask0"][labels.index("friendly64")]) == 2 ** 64 - 1
+    assert g["trials0"][labels.index("clean20")] <= 3 and g["trials0"][labels.index("friendly15")] == 105 and g["trials0"][labels.index("friendly16")] <= 3
+    assert g["trials0"][labels.index("first_pairs_outliers20")] > 19 + 18 + 17 and not g["ok0"][labels.index("majority_outliers5")]
+    assert g["ok0"][labels.index("parallax_above")] and not g["ok0"][labels.index("parallax_below")]
+    c = labels.index("lo_two_rounds20")
+    assert g["lo_rounds0"][c] >= 2 and g["lo_rounds1"][c] >= 2
+    c = labels.index("behind_second_low_parallax")
+    assert not g["ok0"][c] and not g["ok1"][c] and min(g["margin0"][c], g["margin1"][c]) > 1
+
+
+@pytest.mark.parametrize("rt", [0, 1])
+def test_restatement_passes_every_candidate_criterion(rt):
+    """oracle.track_graph_oracle.loransac_estimate (NumPy SVD / eigh, float64) on every candidate, and on one block-edge
+    launch; its open candidates are those of the exact walk."""
+    stats = []
+    fails, open_ = G.candidate_failures(G.restatement_batch, rt, stats=stats)
+    print({k: f"{v:.3g}" for k, v in G._largest(stats).items()}, "open:", open_)
+    assert fails == []
+    friendly = [c for c, grp in enumerate(G.candidate_golden()["groups"]) if grp == "friendly"]
+    fails, open_ = G.candidate_failures(G.restatement_batch, rt, [friendly[k % len(friendly)] for k in range(65)])
+    assert fails == [] and open_ == []
+
+
+@pytest.mark.parametrize("what", [1, 2, 3])
+def test_restatement_passes_every_init_pair_criterion(what):
+    """tests/numpy_registration.py on the init-pair cases: both rescale values, with and without select, both angles."""
+    for rescale, min_angle, sel in ((1.0, 0.0, False), (0.437, math.radians(1.5), True)):
+        stats = []
+        fails, open_ = G.init_pair_failures(NR.init_pair_candidates, what, rescale, min_angle, use_select=sel, stats=stats)
+        print({k: f"{v:.3g}" for k, v in G._largest(stats).items()}, "open:", len(open_))
+        assert fails == []
+        friendly = set(G.init_pair_cases()["groups"]["friendly"])
+        assert not friendly & set(open_)
+
+
+def test_init_pair_cases_hold_what_they_are_for():
+    """NaN angles from the restatement where the argument is within rounding of 1, a lifted point behind camera 2, failed
+    and successful triangulations, skipped matches."""
+    Z = G.init_pair_cases()
+    o = NR.init_pair_candidates(xy1=Z["xy1"], xy2=Z["xy2"], intr1=Z["intr1"], intr2=Z["intr2"], cam2_from_cam1=Z["P2"], prior_map=Z["prior_map"],
+                                valid_map=Z["valid_map"], sx=Z["sx"], sy=Z["sy"], tri_max_error=G.INIT_MAX_ERROR)
+    gr = Z["groups"]
+    assert len(gr["friendly"]) > G.INIT_BLOCK_EDGES[-1] and gr["friendly"] == list(range(len(gr["friendly"])))
+    assert o["tri_ok"][gr["friendly"]].all() and not o["tri_ok"][gr["tri_behind"]].any()
+    assert (abs(1 - o["lift_c"][gr["lift_huge"]]) < 1e-15).all() and len(gr["lift_huge"]) == 12
+    assert np.isnan(o["lift_angle_deg"][gr["lift_huge"]]).sum() >= 1 and (o["lift_angle_deg"][gr["lift_huge"]] >= 0).sum() >= 6
+    assert o["tri_ok"][gr["low_parallax"]].all() and (o["tri_c"][gr["low_parallax"]] > 0.999).all()
+    assert o["lift_posdepth1"][gr["lift_behind2"]].all() and not o["lift_posdepth2"][gr["lift_behind2"]].any()
+    assert (Z["select"] == 0).sum() > 10 and not Z["valid_map"].all()
+    print("NaN lift angles of the restatement:", int(np.isnan(o["lift_angle_deg"]).sum()))
+
+
+def _estimate_mutant(strict_angle=False, first_depth_only=False):
+    def estimate(views, min_tri_angle):
+        passes = (lambda a: a > min_tri_angle) if strict_angle else (lambda a: a >= min_tri_angle)
+        if len(views) == 2:
+            X = TG.triangulate_point(views[0].P, views[1].P, views[0].xn, views[1].xn)
+        else:
+            X = TG.triangulate_multi_view_point([v.P for v in views], [v.xn for v in views])
+        if X is None or not all(TG.has_point_positive_depth(v.P, X) for v in (views[:1] if first_depth_only else views)):
+            return []
+        return [X] if any(passes(TG.calculate_triangulation_angle(views[i].C, views[j].C, X)) for i in range(len(views)) for j in range(i)) else []
+
+    return estimate
+
+
+def _support_mutant(strict=False, skip_last=False):
+    def support(residuals, max_residual):
+        inl = residuals < max_residual if strict else residuals <= max_residual
+        if skip_last:
+            inl = inl.copy()
+            inl[-1] = False
+        return int(inl.sum()), float(residuals[inl].sum())
+
+    return support
+
+
+def _squared_lengths_angle(C1, C2, X):
+    X = np.asarray(X, np.float64).reshape(-1, 3)
+    b, r1, r2 = ((np.asarray(C1) - np.asarray(C2)) ** 2).sum(), ((X - C1) ** 2).sum(1), ((X - C2) ** 2).sum(1)
+    den = 2.0 * np.sqrt(r1 * r2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        c = (r1 + r2 - b) / den
+        a = np.abs(np.arccos(c))
+    a = np.where(den == 0.0, 0.0, np.minimum(a, np.pi - a))
+    return a * (180.0 / np.pi), np.where(den == 0.0, 0.0, c)
+
+
+def _one_local_round(*a):
+    """`range` for oracle.track_graph_oracle: one round on the line of the local-optimisation loop (the one that names
+    kMaxNumLocalTrials), the builtin everywhere else, so a candidate of ten views keeps its pairs."""
+    f = sys._getframe(1)
+    if a == (10,) and "kMaxNumLocalTrials" in linecache.getline(f.f_code.co_filename, f.f_lineno):
+        _one_local_round.hits += 1
+        return builtins.range(1)
+    return builtins.range(*a)
+
+
+_one_local_round.hits = 0
+
+
+# mutation -> (where it is applied, named cases that must flag it).  An empty tuple: the mutation cannot be flagged, for the
+# reason given in the docstring of test_mutations_of_the_candidate_restatement.
+CANDIDATE_MUTATIONS = {
+    "angle > for >=": (("estimator_estimate", _estimate_mutant(strict_angle=True)), ()),
+    "residual < for <=": (("_support", _support_mutant(strict=True)), ()),
+    "depth test on the first view only": (("estimator_estimate", _estimate_mutant(first_depth_only=True)), ("behind_second_low_parallax",)),
+    "last view skipped in the support": (("_support", _support_mutant(skip_last=True)), ("two_pairs_tie",)),
+    "tie-break without the residual sum": (("_left_better", lambda a, b: a[0] > b[0]), ("two_pairs_tie",)),
+    "one local-optimisation round": (("range", _one_local_round), ("lo_two_rounds20",)),
+    "n <= 15 rule at 14": (dict(rule_n=14), ("outlier15_middle",)),
+    "n <= 15 rule at 16": (dict(rule_n=16), ("exhaustive_matters16",)),
+    "pairs in the reverse order": (dict(reverse=True), ("two_structures20",)),
+    "bit 63 dropped": (dict(drop_bit63=True), ("friendly64",)),
+}
+
+
+@pytest.mark.parametrize("name", list(CANDIDATE_MUTATIONS))
+def test_mutations_of_the_candidate_restatement(name, monkeypatch):
+    """One step of the restatement altered at a time (monkeypatched; nothing under oracle/ changes), run over the named
+    candidates: the listed cases flag it.  The depth test on the first view only is flagged by
+    behind_second_low_parallax: the homogeneous two-view solve does not see the sign of a depth, so a pair with a view the
+    point is behind gives the true point and collects the other views.  Two alterations cannot be flagged by any decided
+    case: `>` for `>=` at min_tri_angle and `<` for `<=` at the residual bound differ from the original only where a
+    computed value equals its threshold bit for bit, and there both outcomes are legal (the threshold group).  For these
+    the test asserts that nothing is flagged, so that the statement stays true."""
+    how, catchers = CANDIDATE_MUTATIONS[name]
+    kw = {}
+    if isinstance(how, dict):
+        kw = how
+    else:
+        monkeypatch.setattr(TG, how[0], how[1], raising=False)
+    flagged = set()
+    for rt in (0, 1):
+        fails, _ = G.candidate_failures(lambda *a: G.restatement_batch(*a, **kw), rt, _named())
+        flagged |= {f.split(" ")[0] for f in fails}
+    print(name, "flagged by", sorted(flagged))
+    assert set(catchers) <= flagged
+    if not isinstance(how, dict) and how[0] == "range":
+        assert _one_local_round.hits > 0  # the shim found the loop it is meant for
+    if not catchers:
+        assert flagged == set()
+
+
+@pytest.mark.parametrize("name", ["squared lengths", "NaN clamped to 0"])
+def test_mutations_of_the_init_pair_restatement(name, monkeypatch):
+    """The reference's angle on squared lengths is flagged by every friendly match.  Its NaN clamped to 0 cannot be
+    flagged: in exact arithmetic the argument never exceeds 1, a NaN is the rounding of an argument within eps of 1, and
+    there the exact angle is below the bound of the form, so 0 is as legal as NaN (ref_angle_ratio's docstring)."""
+    orig = NR.reference_angle_deg
+    if name == "squared lengths":
+        monkeypatch.setattr(NR, "reference_angle_deg", _squared_lengths_angle)
+    else:
+        monkeypatch.setattr(NR, "reference_angle_deg", lambda *a: tuple(np.nan_to_num(v) for v in orig(*a)))
+    fails, _ = G.init_pair_failures(NR.init_pair_candidates, 3)
+    if name == "squared lengths":
+        assert sum("(friendly) tri_angle_deg" in f for f in fails) > 200 and sum("(friendly) lift_angle_deg" in f for f in fails) > 200
+    else:
+        assert fails == []

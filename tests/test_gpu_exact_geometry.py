@@ -1,4 +1,5 @@
-"""mpsfm_triangulate_tracks, mpsfm_filter_tracks and mpsfm_point_covs against the exact reference of
+"""mpsfm_triangulate_tracks, mpsfm_filter_tracks, mpsfm_point_covs, mpsfm_tri_estimate_batch and
+mpsfm_init_pair_candidates against the exact reference of
 tests/exact_geometry.py (mpmath, 60 digits; validated on the CPU by tests/test_exact_geometry_cpu.py), at the shapes and
 edges where the kernels can go wrong.  The case sets and the comparison functions live in exact_geometry.py; the same
 functions ran the C oracle with one arithmetic step altered at a time, and every alteration that can change an output
@@ -54,6 +55,79 @@ oracle (the kernels' arithmetic, Jacobi and Cholesky included) stands beside it 
   angle                        0.108    0.108      C_a = 1
   squared error                0.220    0.220      C_e = 2
   covariance                   13.5     7.84       C_p = 128  (the 5000-observation landmark; 0.96 elsewhere)
+
+Candidate tracks (mpsfm_tri_estimate_batch) and init-pair points (mpsfm_init_pair_candidates)
+
+The reference is exact_loransac of exact_geometry.py: the loop of tri_ransac_scratch walked with exact arithmetic
+(lexicographic pairs, tri_estimate's depth and angle tests, support by count then residual sum, local optimisation from
+more than two inliers for up to ten rounds while the count grows, the tri_num_trials stop rule with min_num_trials, the
+final mask).  The two-view sample model is the smallest eigenvector of the exact A2 = sum row^T row over the four
+unnormalised rows x P_2 - P_0, y P_2 - P_1 of tri_two_view; the multi-view model is triangulation_matrix's form on the
+inlier set.  The walk of a 64-view candidate costs thousands of models, so tests/golden/exact_candidates.npz holds the
+inputs and what the walk found (made by tests/golden/make_golden_exact_candidates.py; the CPU file walks a handful again).
+
+Margin.  Every comparison on the exact path is at a distance from its threshold; the margin of the comparison is that
+distance over a bound of the error the device can make in the compared quantity, and the margin of the candidate is the
+smallest of them.  Above 1 the candidate is decided: ok and the mask are asserted exactly, the point by the backward
+criterion above on the matrix of the exact index set, and by the forward criterion where informative.  Otherwise it is
+open: ok = 0 with zeros or ok = 1 with a finite point and at least two inliers.  A bound has two parts.
+
+  1. The quantity's own rounding at a given point X, C eps form:
+     depth             form = sum_j |P_2j X_j| + |t_2|: the terms that cancel in zc                              (C_z)
+     triangulation     form = kappa of the pair, above                                                          (C_a)
+       angle
+     sq. reprojection  form = e + s, above; the threshold max_error^2 is itself rounded: + eps max_error^2       (C_e)
+     angular residual  e = acos(cs), cs = a.b / (|a| |b|), a = (xn, 1), b = P X.  b_k sums terms of the magnitudes
+                       m_k = sum_j |P_kj X_j| + |t_k|, so b moves by eps |m| and the angle by eps |m| / |b|, i.e. cs by
+                       sin(e) eps |m| / |b|; the products of the dot add eps sum_k |a_k b_k| / (|a| |b|) <= eps, the two
+                       norms and the division eps 2 |cs|.  acos has the slope 1 / sin e, and below sqrt(eps) the square
+                       root takes over as for kappa:
+                         form = [sin(e) |m| / |b| + sum |a_k b_k| / (|a| |b|) + 2 |cs|] / max(sin e, sqrt(eps))
+                       The compared quantity is e^2: bound 2 e de + de^2 + eps max_error^2.                      (C_r)
+     residual sums     the sum of the bounds of the inliers' residuals + n eps sum; compared only at equal counts
+     counts            integers: exact once every residual comparison is decided
+     stop rule         v = 3 log(1 - confidence) / log(1 - r^2), r = k / n; 1 - confidence is exact in fp64; r, its square
+                       and the difference carry eps (1 + 3 r^2 / denom) relative to denom = 1 - r^2, which the logarithm
+                       divides by |log denom|; the rest is a few eps:
+                         form = |v| (3 + (1 + 3 r^2 / denom) / |log denom| + 1 / |log(1 - confidence)|)
+                       and the margin is the distance of v from the nearest integer (the ceil) over C_s eps form.   (C_s)
+  2. The first-order effect of the model's forward error.  A computed v that meets the backward criterion is an
+     eigenvector of A + E with |E| <= C_t eps |A|_F, so dv = sum_k c_k v_k over the other eigenvectors with
+     |c_k| <= C_t eps |A|_F / (lambda_k - lambda_1), and X = v[:3] / v[3] moves by d_k = c_k (v_k[:3] - X v_k[3]) / v[3] per
+     direction.  (Its norm, with every gap replaced by the smallest, is the forward bound above.)  A quantity q with the
+     gradient g in X moves by at most sum_k |g . d_k|; g is evaluated in mpmath: the third row of P for the depth,
+     -R^T (a^ - cs b^) / (|b| sin e) for e, the sum of the two ray terms for the triangulation angle, 2 du grad du +
+     2 dv grad dv for the reprojection error (plus the squares of the first-order terms), and the length bound 1 / |b| or
+     1 / |d1| + 1 / |d2| times |d_k| where sin = 0 leaves the gradient without a direction.  Nothing is decided from a model
+     whose gap is not above 4 C_t eps |A|_F.
+  A false outcome of tri_estimate is as firm as its firmest failing test, a true one as its weakest test; with
+  min_tri_angle = 0 the angle test always passes (the device's angle is never negative).
+
+The reference's angle (ref_angle_deg, law of cosines on plain lengths) is compared at the kernel's own point:
+c = (r1 + r2 - b) / (2 sqrt(r1 r2)); the lengths carry eps (g + 2) with the g of kappa, so
+  dc = [(g1 + 2) r1 + (g2 + 2) r2 + (gb + 2) b] / (2 sqrt(r1 r2)) + |c| ((g1 + g2) / 2 + 5)
+and the angle must lie within C_ra eps (dc / max(sin acos c, sqrt(eps)) + angle).  In exact arithmetic |c| <= 1 always
+((sqrt r1 - sqrt r2)^2 <= |r1 - r2| <= b <= r1 + r2), so the NaN the reference returns for c > 1 is rounding: it is legal
+where 1 - |c| <= C_ra eps dc and nowhere else.  The depth flags are exact where |zc - 2^-52| > C_z eps form.  The lift is
+compared with the exact product from the kernel's own d_prior: |L_k - exact_k| <= C_l eps |exact_k|.
+
+The scene translated by 1e4: |A|_F is 1e9 there, C_t eps |A|_F / (lambda_2 - lambda_1) |(X, 1)| allows the point to move
+by several 1e-2, and at the rig's own size (depth 10) no comparison of residual sums can be decided from that.  The case is
+therefore two views (no sums to compare) of a scene ten times the size, and three views of one three hundred times the size;
+five views at the rig's size are decided when translated by 1e3 (shift1e3).  No named case outside the threshold group
+is open, and none of the 200 random candidates is.
+
+  quantity                     NumPy    restatement   constant
+  two-view point, backward     2.48     9.18          C_t = 16 as above: the issue keeps the criterion unchanged, which is
+  two-view point, forward      0.688    4.40          stricter than the 32 the rule would give here (the restatement's
+  multi-view point, backward   2.36     2.12          two-view figure is an SVD of the rows with xn rounded first)
+  multi-view point, forward    0.622    0.639
+  depth                        0.490    0.503         C_z = 4
+  angular residual             0.580    0.467         C_r = 8
+  squared reprojection         0.0804   0.0621        C_e = 2 as above
+  stop rule (all k < n <= 64)  0.361    0.361         C_s = 4
+  reference's angle            0.167    0.167         C_ra = 2
+  lift                         1.09     1.09          C_l = 16
 """
 
 import numpy as np
@@ -174,3 +248,94 @@ def test_point_covs_hard_cases_twice():
         assert np.isnan(c).all() == (lab in ("no_obs", "one_obs")), lab
     for lab in ("parallax0.01", "two_obs_a", "obs5000", "zc_0.01"):  # well conditioned: finite
         assert np.isfinite(covs[labels.index(lab)]).all(), lab
+
+
+# ---- mpsfm_tri_estimate_batch and mpsfm_init_pair_candidates against the exact walk ----------------------------------------
+def _batch(box=None):
+    def call(cs, P, K, xy, min_angle, max_error, rt, min_num_trials):
+        out = capi.tri_estimate_batch(cs, P, K, xy, min_angle, max_error, rt, min_num_trials)
+        if box is not None:
+            box.append(out)
+        return out
+
+    return call
+
+
+@pytest.mark.parametrize("residual_type", [G.ANGULAR, G.REPROJECTION])
+def test_candidate_cases_twice(residual_type):
+    """One launch over every candidate that leaves min_num_trials to the library and one over those that set it: ok and
+    the mask exact where decided, the point by the backward (and forward) criterion on the matrix of the exact index set,
+    zeros for every failed candidate; open candidates (the threshold group) give one of the two legal outcomes.
+    Run twice: one thread per candidate and no atomics, so the two runs are equal bit for bit."""
+    stats, out = [], []
+    fails, open_ = G.candidate_failures(_batch(out), residual_type, stats=stats)
+    _report(stats)
+    print("open:", open_)
+    assert fails == []
+    g = G.candidate_golden()
+    assert set(open_) <= {str(l) for l, grp in zip(g["labels"], g["groups"]) if grp == "threshold"}
+    again = []
+    G.candidate_failures(_batch(again), residual_type)
+    assert len(out) == len(again) == 2
+    for a, b in zip(out, again):
+        for x, y in zip(a, b):
+            assert x.tobytes() == y.tobytes()
+
+
+@pytest.mark.parametrize("n_candidates", G.CAND_BLOCK_EDGES)
+def test_candidate_block_edges(n_candidates):
+    """The friendly candidates (2, 3, 5, 15, 16, 63, 64 views) repeated up to candidate counts around the 64 threads of a
+    block, for both residual types."""
+    g = G.candidate_golden()
+    friendly = [c for c, grp in enumerate(g["groups"]) if grp == "friendly"]
+    which = [friendly[k % len(friendly)] for k in range(n_candidates)]
+    for rt in (G.ANGULAR, G.REPROJECTION):
+        fails, open_ = G.candidate_failures(_batch(), rt, which)
+        assert fails == [] and open_ == []
+
+
+def test_candidate_contract():
+    """Candidates of 0 and 1 views between ordinary ones give ok = 0 and zeros, their neighbours are untouched; a
+    caller's min_num_trials of 0, 1 and C(n, 2) is honoured (the three settings end at different points where the exact
+    walk says so); the explicit array with the library's own rule in it equals NULL."""
+    g = G.candidate_golden()
+    labels = g["labels"].tolist()
+    contract = [c for c, grp in enumerate(g["groups"]) if grp == "contract"]
+    short = [contract.index(labels.index(lab)) for lab in ("empty", "one_view")]
+    for rt in (G.ANGULAR, G.REPROJECTION):
+        out = []
+        fails, open_ = G.candidate_failures(_batch(out), rt, contract, explicit_trials=True)
+        assert fails == [] and open_ == []
+        xyz, ok, inl = out[0]
+        start = G.candidate_launch(contract)[0]
+        for k in short:
+            assert not ok[k] and not xyz[k].any() and not inl[start[k]:start[k + 1]].any()
+        assert ok[[k for k in range(len(contract)) if k not in short]].all()
+        named = [c for c, grp in enumerate(g["groups"]) if grp in ("friendly", "outliers", "geometry")]
+        a, b = [], []
+        G.candidate_failures(_batch(a), rt, named)
+        G.candidate_failures(_batch(b), rt, named, explicit_trials=True)
+        for x, y in zip(a[0], b[0]):
+            assert x.tobytes() == y.tobytes()
+    m0, m120 = labels.index("trials_noisy16_mnt0"), labels.index("trials_noisy16_mnt120")
+    assert g["idx0"][m0] != g["idx0"][m120] or g["idx1"][m0] != g["idx1"][m120]  # the settings do differ in the exact walk
+
+
+@pytest.mark.parametrize("what", [G.INIT_TRIANGULATE, G.INIT_LIFT, G.INIT_TRIANGULATE | G.INIT_LIFT])
+def test_init_pair_cases(what):
+    """Friendly matches, low parallax down to an acos argument within eps of 1 (NaN legal there and nowhere else), a lifted
+    point behind camera 2, diverging rays; rescale 1 and 0.437, select with zeros, tri_min_angle 0 and 1.5 degrees."""
+    for rescale, min_angle, sel in ((1.0, 0.0, False), (0.437, np.deg2rad(1.5), True)):
+        stats = []
+        fails, open_ = G.init_pair_failures(capi.init_pair_candidates, what, rescale, min_angle, use_select=sel, stats=stats)
+        _report(stats)
+        print("open matches:", open_)
+        assert fails == []
+        assert not set(G.init_pair_cases()["groups"]["friendly"]) & set(open_)
+
+
+@pytest.mark.parametrize("n_matches", G.INIT_BLOCK_EDGES)
+def test_init_pair_block_edges(n_matches):
+    """n_matches around the 256 threads of a k_init_candidates block."""
+    fails, open_ = G.init_pair_failures(capi.init_pair_candidates, G.INIT_TRIANGULATE | G.INIT_LIFT, 0.437, 0.0, n_matches=n_matches, use_select=True)
+    assert fails == [] and open_ == []
