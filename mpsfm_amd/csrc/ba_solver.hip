@@ -5,28 +5,21 @@
 // ba_kernels.hip / dense_chol.hip; this file only orders launches and takes the accept/reject
 // decisions from a handful of scalars.
 #include <algorithm>
-#include <memory>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <cstdio>
 #include <cstring>
-#include <numeric>
 #include <string>
-#include <thread>
-#include <tuple>
-#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
 #include <dlfcn.h>
-#include <pthread.h>
-#include <sched.h>
 
 #include "common.h"
+#include "build_host.h"
 #include "devbuild.h"
 #include "local_lm.h"
 
@@ -345,68 +338,6 @@ static int dev_upload(T** p, const std::vector<T>& v) {
   if ((rc = G.init())) return rc;
   return G.push(*p, v.data(), v.size() * sizeof(T));  // build() drains once after the last table
 }
-// Large host blocks of the table build come from a process-wide cache: a fresh 40 MB block costs its page faults on first
-// touch and an munmap on release (several ms per create at C3); a recycled one costs neither.  Power-of-two buckets from
-// 1 MB, at most 512 MB kept (MPSFM_HOST_CACHE_MB).
-struct HostBlockCache {
-  static constexpr size_t kMinBytes = size_t(1) << 20;
-  const size_t kHostCacheBytes = [] {  // MPSFM_HOST_CACHE_MB: how much released host memory is kept for the next build (0: none)
-    const char* e = std::getenv("MPSFM_HOST_CACHE_MB");
-    return (size_t)((e && std::atoi(e) >= 0) ? std::atoi(e) : 512) << 20;
-  }();
-  std::mutex mu;
-  std::vector<std::pair<size_t, void*>> free_blocks;
-  size_t cached = 0;
-  static size_t bucket(size_t bytes) { size_t b = kMinBytes; while (b < bytes) b <<= 1; return b; }
-  void* take(size_t bytes, size_t& got) {
-    if (bytes < kMinBytes) { got = 0; return ::operator new(std::max<size_t>(bytes, 1)); }
-    got = bucket(bytes);
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (size_t i = 0; i < free_blocks.size(); ++i)
-        if (free_blocks[i].first == got) {
-          void* p = free_blocks[i].second;
-          free_blocks[i] = free_blocks.back(); free_blocks.pop_back();
-          cached -= got;
-          return p;
-        }
-    }
-    return ::operator new(got);
-  }
-  void give(void* p, size_t got) {
-    if (!p) return;
-    if (got) {
-      std::lock_guard<std::mutex> lk(mu);
-      if (cached + got <= kHostCacheBytes) { free_blocks.emplace_back(got, p); cached += got; return; }
-    }
-    ::operator delete(p);
-  }
-  ~HostBlockCache() { for (auto& b : free_blocks) ::operator delete(b.second); }
-};
-static HostBlockCache& host_cache() { static HostBlockCache c; return c; }
-
-// uninitialised host array of trivially copyable elements (std::vector would zero-fill tens of MB on one thread)
-template <typename T>
-struct HostBuf {
-  static_assert(std::is_trivially_copyable<T>::value && std::is_trivially_destructible<T>::value, "HostBuf holds raw storage");
-  T* p = nullptr;
-  size_t n = 0, got = 0;
-  HostBuf() = default;
-  HostBuf(const HostBuf&) = delete;
-  HostBuf& operator=(const HostBuf&) = delete;
-  ~HostBuf() { host_cache().give(p, got); }
-  void alloc(size_t k) {
-    host_cache().give(p, got);
-    p = static_cast<T*>(host_cache().take(std::max<size_t>(k, 1) * sizeof(T), got));
-    n = k;
-  }
-  void release() { host_cache().give(p, got); p = nullptr; n = got = 0; }
-  size_t size() const { return n; }
-  T* data() { return p; }
-  const T* data() const { return p; }
-  T& operator[](size_t i) { return p[i]; }
-  const T& operator[](size_t i) const { return p[i]; }
-};
 template <typename T>
 static int dev_upload(T** p, HostBuf<T>& v) {
   int rc = dev_alloc(p, v.size());
@@ -432,11 +363,9 @@ struct mpsfm_ba_handle {
   hipStream_t stream = nullptr;
   void* comm = nullptr;  // ncclComm_t of a landmark-sharded run with use_rccl
   DenseOverlap ov;  // second stream for the dense factorisation in outer panels (MPSFM_CHOL_NB)
-  std::vector<int32_t> sky_first;   // block skyline of S (BlockSky), host copies
-  std::vector<int64_t> sky_start;
+  SPattern spat;                    // which blocks of S exist: block skyline or index form (up to kIndexMaxSlots slots), host copies
   int32_t* d_sky_first = nullptr;
   int64_t* d_sky_start = nullptr;
-  std::vector<int32_t> sky_index;   // index form of BlockSky (up to kIndexMaxSlots slots), host copy
   int32_t* d_sky_index = nullptr;
   CholPlan plan;                    // camera order, tile elimination tree and launch tables of the dense factorisation (chol_plan.h)
   LevelPlanDev lp;
@@ -465,7 +394,7 @@ struct mpsfm_ba_handle {
   bool built_on_device = false;
   LongHdr* d_lhdr = nullptr;
   double* d_wl = nullptr;
-  int64_t red_count = 0, sblk_count = 0, sblk_blocks = 0;
+  int64_t red_count = 0, sblk_count = 0;
   std::vector<int32_t> perm;        // re-ordered landmark -> caller's index
   int32_t* d_cam_of_slot = nullptr; // slot -> camera (the fused camera update of k_update_sweep)
   int32_t* d_perm = nullptr;        // device copy, and the landmarks in the caller's order as last uploaded: the state crosses the bus
@@ -478,15 +407,9 @@ struct mpsfm_ba_handle {
   int32_t *d_intr_idx = nullptr, *d_cam_slot = nullptr;
   double *d_ps = nullptr, *d_diagV = nullptr;
   ChunkHdr* d_chunks = nullptr;
-  int32_t *d_chunk_cams = nullptr, *d_rec_cam = nullptr, *d_rec_pt = nullptr, *d_pt_rec_start = nullptr, *d_blk_ent_start = nullptr;
+  int32_t *d_chunk_cams = nullptr, *d_blk_ent_start = nullptr;
   uint32_t *d_blk_desc = nullptr, *d_ents = nullptr;
-  uint32_t* d_rec_meta = nullptr;
-  uint16_t* d_pt_kv = nullptr;
-  double *d_rec_xy = nullptr, *d_rec_d = nullptr, *d_rec_m = nullptr, *d_rec_a = nullptr;
-  // fixed blocks (constant camera and constant landmark)
-  int32_t *d_fx_cam = nullptr, *d_fx_pt = nullptr;
-  uint32_t* d_fx_meta = nullptr;
-  double *d_fx_xy = nullptr, *d_fx_d = nullptr, *d_fx_m = nullptr, *d_fx_a = nullptr;
+  RecTablesDev rt;           // record and fixed-record tables
   // reduced buffer: Sblk | gc | wv | diagU | scalars
   double* d_red = nullptr;
   double *d_Sblk = nullptr, *d_gc = nullptr, *d_wv = nullptr, *d_diagU = nullptr, *d_redsc = nullptr;
@@ -520,13 +443,12 @@ static void free_handle(mpsfm_ba_handle* h) {
   if (h->ov.s2) (void)hipStreamSynchronize(h->ov.s2);
   void* ptrs[] = {h->d_q, h->d_t, h->d_q2, h->d_t2, h->d_q0, h->d_t0, h->d_pts, h->d_pts2, h->d_pts0, h->d_intr, h->d_cmask,
                   h->d_cs, h->d_camtab, h->d_camtab2, h->d_intr_idx, h->d_cam_slot, h->d_ps, h->d_diagV, h->d_chunks,
-                  h->d_chunk_cams, h->d_rec_cam, h->d_rec_pt, h->d_pt_rec_start, h->d_blk_ent_start, h->d_blk_desc, h->d_ents, h->d_rec_meta, h->d_pt_kv,
-                  h->d_rec_xy, h->d_rec_d, h->d_rec_m, h->d_rec_a, h->d_fx_cam, h->d_fx_pt, h->d_fx_meta, h->d_fx_xy, h->d_fx_d,
-                  h->d_fx_m, h->d_fx_a, h->d_red, h->d_part, h->d_part2, h->d_scal, h->d_costpart, h->d_A, h->d_yc, h->d_dwork, h->d_fail, h->d_lhdr, h->d_wl, h->d_slab, h->d_red_dests, h->d_red_srcs,
+                  h->d_chunk_cams, h->d_blk_ent_start, h->d_blk_desc, h->d_ents, h->d_red, h->d_part, h->d_part2, h->d_scal, h->d_costpart, h->d_A, h->d_yc, h->d_dwork, h->d_fail, h->d_lhdr, h->d_wl, h->d_slab, h->d_red_dests, h->d_red_srcs,
                   h->d_sky_first, h->d_sky_start, h->d_sky_index,
                   h->d_local_acc, h->d_local_sync, h->d_local_log, h->d_perm, h->d_user_pts, h->d_cam_of_slot,
                   h->d_lp_items, h->d_lp_srcs, h->d_lp_rows, h->d_lp_struct_start, h->d_lp_struct_rows, h->d_lp_back_cols, h->d_lp_asm, h->d_lp_live, h->d_lp_col_slot};
   for (void* p : ptrs) cached_free(p);
+  h->rt.release();
   if (h->comm) (void)rccl().CommDestroy(h->comm);
   release_pinned(h->h_scal);
   release_pinned(h->h_ctl);
@@ -598,133 +520,6 @@ static int allreduce_dev(mpsfm_ba_handle* h, double* buf, int64_t count) {
   return 0;
 }
 
-struct Blk { int32_t cam; int32_t key; uint8_t kind; int64_t src; };
-
-// ---- host threads for the table build (plain std::thread: no OpenMP runtime beside torch's) -------
-// CPUs this process may use: scheduler affinity capped by the cgroup quota; MPSFM_HOST_THREADS overrides.
-static int host_threads() {
-  static const int n = [] {
-    if (const char* e = std::getenv("MPSFM_HOST_THREADS")) { const int v = std::atoi(e); if (v > 0) return std::min(v, 64); }
-    int cpus = 1;
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) cpus = std::max(1, CPU_COUNT(&set));
-    if (FILE* f = std::fopen("/sys/fs/cgroup/cpu.max", "r")) {
-      char a[64]; double per = 0.0;
-      if (std::fscanf(f, "%63s %lf", a, &per) == 2 && std::strcmp(a, "max") != 0 && per > 0.0)
-        cpus = std::min(cpus, std::max(1, (int)(std::atof(a) / per + 0.5)));
-      std::fclose(f);
-    }
-    return std::min(cpus, 32);
-  }();
-  return n;
-}
-// Persistent workers for the phases of the table build: creating and joining 15 threads costs ~0.4 ms, and one create runs
-// a dozen phases.  One job at a time; a caller that finds the pool busy (another handle being created) starts plain threads
-// as before.  Parts are claimed with the job's generation, so a worker that wakes late never touches a newer job; a forked
-// child starts over with a pool of its own (the parent's workers do not exist there).
-class HostPool {
- public:
-  typedef void (*Call)(void* ctx, int part, int nparts);
-  // false: the pool is busy, nothing ran
-  bool try_run(int nparts, Call call, void* ctx) {
-    std::unique_lock<std::mutex> job(job_mu_, std::try_to_lock);
-    if (!job.owns_lock()) return false;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      if (workers_.empty()) {
-        const int nw = std::max(host_threads() - 1, 1);
-        for (int i = 0; i < nw; ++i) workers_.emplace_back([this] { work(); });
-      }
-      call_ = call; ctx_ = ctx; nparts_ = nparts;
-      done_.store(0, std::memory_order_relaxed);
-      ++gen_;
-      state_.store((gen_ << 32) | 1u, std::memory_order_release);  // part 0 is the caller's
-    }
-    cv_work_.notify_all();
-    call(ctx, 0, nparts);
-    finish_part();
-    claim_loop(gen_, call, ctx, nparts);
-    std::unique_lock<std::mutex> lk(mu_);
-    cv_done_.wait(lk, [&] { return done_.load(std::memory_order_acquire) == nparts; });
-    return true;
-  }
-  ~HostPool() {
-    { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
-    cv_work_.notify_all();
-    for (auto& w : workers_) w.join();
-  }
-
- private:
-  void finish_part() {
-    if (done_.fetch_add(1, std::memory_order_acq_rel) + 1 == nparts_) { std::lock_guard<std::mutex> lk(mu_); cv_done_.notify_all(); }
-  }
-  void claim_loop(uint64_t gen, Call call, void* ctx, int nparts) {
-    uint64_t s = state_.load(std::memory_order_acquire);
-    while ((s >> 32) == gen && (int)(s & 0xffffffffu) < nparts) {
-      if (state_.compare_exchange_weak(s, s + 1, std::memory_order_acq_rel)) {
-        call(ctx, (int)(s & 0xffffffffu), nparts);
-        finish_part();
-        s = state_.load(std::memory_order_acquire);
-      }
-    }
-  }
-  void work() {
-    uint64_t seen = 0;
-    for (;;) {
-      Call call; void* ctx; int nparts; uint64_t gen;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_work_.wait(lk, [&] { return stop_ || gen_ != seen; });
-        if (stop_) return;
-        seen = gen = gen_; call = call_; ctx = ctx_; nparts = nparts_;
-      }
-      claim_loop(gen, call, ctx, nparts);
-    }
-  }
-  std::mutex job_mu_, mu_;
-  std::condition_variable cv_work_, cv_done_;
-  std::vector<std::thread> workers_;
-  std::atomic<uint64_t> state_{0};
-  std::atomic<int> done_{0};
-  uint64_t gen_ = 0;
-  Call call_ = nullptr; void* ctx_ = nullptr; int nparts_ = 0;
-  bool stop_ = false;
-};
-static std::atomic<HostPool*> g_host_pool{nullptr};
-static HostPool* host_pool() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    pthread_atfork(nullptr, nullptr, [] { g_host_pool.store(nullptr); });  // child: the old pool is abandoned, never destroyed
-    std::atexit([] { delete g_host_pool.exchange(nullptr); });
-  });
-  HostPool* p = g_host_pool.load(std::memory_order_acquire);
-  if (!p) {
-    HostPool* fresh = new HostPool();
-    if (g_host_pool.compare_exchange_strong(p, fresh)) p = fresh; else delete fresh;
-  }
-  return p;
-}
-// f(part, nparts) on nparts threads (the calling thread takes part 0)
-template <class F>
-static void run_parts(int nparts, F&& f) {
-  if (nparts <= 1) { f(0, std::max(nparts, 1)); return; }
-  static const bool use_pool = !(std::getenv("MPSFM_HOST_POOL") && std::atoi(std::getenv("MPSFM_HOST_POOL")) == 0);
-  typedef typename std::remove_reference<F>::type Fn;
-  if (use_pool && host_pool()->try_run(nparts, [](void* c, int t, int n) { (*static_cast<Fn*>(c))(t, n); }, const_cast<void*>(static_cast<const void*>(&f)))) return;
-  std::vector<std::thread> th;
-  th.reserve((size_t)std::max(nparts - 1, 0));
-  for (int t = 1; t < nparts; ++t) th.emplace_back([&f, t, nparts] { f(t, nparts); });
-  f(0, nparts);
-  for (auto& x : th) x.join();
-}
-// f(begin, end) over [0, n) cut into nearly equal contiguous parts
-template <class F>
-static void parallel_ranges(int64_t n, int64_t min_grain, F&& f) {
-  const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), n / std::max<int64_t>(min_grain, 1)));
-  if (parts <= 1) { f((int64_t)0, n); return; }
-  run_parts(parts, [&](int t, int np) { f(n * t / np, n * (t + 1) / np); });
-}
-
 static void staged_copy(char* dst, const char* src, size_t n) {
   constexpr size_t kGrain = (size_t)1 << 20;
   static const int max_threads = [] { const char* e = std::getenv("MPSFM_STAGE_THREADS"); return e ? std::max(std::atoi(e), 1) : 6; }();
@@ -736,50 +531,17 @@ static void staged_copy(char* dst, const char* src, size_t n) {
   });
 }
 
-// Build the re-ordered, chunked record tables and upload everything.
-// the tables of the level-scheduled factorisation (h->plan) to the device
-// The camera graph of a landmark-sharded run is the UNION over the ranks, and the exchange can only SUM doubles: every rank
-// packs its adjacency bits as indicator digits in base (world + 1), E digits per double (E chosen so that a sum of `world`
-// such numbers stays below 2^53, i.e. exact), the packed vectors are summed, and a digit > 0 means "some rank has the edge".
-static int graph_digits(int world) {
-  int E = 1;
-  double cap = 9007199254740992.0 / (world + 1);
-  while (cap >= (world + 1) && E < 16) { cap /= (world + 1); ++E; }
-  return E;
-}
-static void pack_graph(const CamGraph& graph, int world, std::vector<double>& packed) {
-  const int E = graph_digits(world), n = graph.n;
-  const int64_t nbits = (int64_t)n * n;
-  packed.assign((size_t)((nbits + E - 1) / E), 0.0);
-  double pw[16];
-  pw[0] = 1.0;
-  for (int e = 1; e < 16; ++e) pw[e] = pw[e - 1] * (double)(world + 1);
-  for (int a = 0; a < n; ++a) {
-    const uint64_t* row = graph.row(a);
-    for (int w = 0; w < graph.words; ++w) {
-      uint64_t m = row[w];
-      while (m) {
-        const int64_t q = (int64_t)a * n + (w * 64 + __builtin_ctzll(m));
-        m &= m - 1;
-        packed[(size_t)(q / E)] += pw[q % E];
-      }
-    }
-  }
-}
-static void unpack_graph(const std::vector<double>& packed, int world, CamGraph& graph) {
-  const int E = graph_digits(world), n = graph.n;
-  const int64_t nbits = (int64_t)n * n;
-  for (size_t w = 0; w < packed.size(); ++w) {
-    double v = packed[w];
-    for (int e = 0; e < E && v > 0.0; ++e) {
-      const double d = std::fmod(v, (double)(world + 1));
-      v = std::floor(v / (world + 1));
-      const int64_t q = (int64_t)w * E + e;
-      if (d > 0.0 && q < nbits) graph.set((int)(q / n), (int)(q % n));
-    }
-  }
+static void level_plan_flags(const CholPlan& PL, LevelPlanDev& D) { D.valid = PL.nt >= 1 && PL.nlevels >= 1; D.use_pinv = PL.use_pinv; }
+// the ten numbers of mpsfm_ba_dense_plan; `work`: the dense workspace (only compared with NULL)
+static void dense_plan_numbers(int ncv, int nt, const CholPlan& P, const DenseOverlap& ov, const LevelPlanDev& lp, double* work, int64_t sblk, int64_t v[10]) {
+  const bool level = dense_level(&ov, &lp);
+  const bool pinv = level && dense_pinv(work, nt, &ov, &lp) != nullptr;
+  const int64_t w[10] = {ncv, nt, level ? P.nlevels : nt, P.nd_depth, pinv ? 1 : 0, (int64_t)P.items.size(), P.products, P.roles, sblk,
+                         pinv ? 1 : (level ? P.nlevels : (nt + 3) / 4 + 1)};
+  for (int i = 0; i < 10; ++i) v[i] = w[i];
 }
 
+// the tables of the level-scheduled factorisation (h->plan) to the device
 static int upload_plan(mpsfm_ba_handle* h, int64_t nblk) {
   const CholPlan& PL = h->plan;
   int rc2 = 0;
@@ -797,7 +559,7 @@ static int upload_plan(mpsfm_ba_handle* h, int64_t nblk) {
     if ((rc2 = dev_upload(&h->d_lp_live, live))) return rc2;
   }
   LevelPlanDev& D = h->lp;
-  D.valid = PL.nt >= 1 && PL.nlevels >= 1; D.use_pinv = PL.use_pinv;
+  level_plan_flags(PL, D);
   D.d_items = h->d_lp_items; D.d_srcs = h->d_lp_srcs; D.d_rows = h->d_lp_rows;
   D.d_struct_start = h->d_lp_struct_start; D.d_struct_rows = h->d_lp_struct_rows; D.d_back_cols = h->d_lp_back_cols;
   D.d_asm_tiles = h->d_lp_asm; D.d_tile_live = h->d_lp_live; D.d_col_slot = PL.slot_of_col.empty() ? nullptr : h->d_lp_col_slot; D.n_asm = (int32_t)PL.asm_tiles.size(); D.nlevels = PL.nlevels;
@@ -808,965 +570,163 @@ static int upload_plan(mpsfm_ba_handle* h, int64_t nblk) {
   return 0;
 }
 
-// Pair tables of ONE chunk for the general kernel, appended to (blk_desc, ents, blk_ent_start): the Schur pairs of its variable
-// landmarks grouped by the 6x6 destination block (counting sort, heaviest blocks first), cut into work items of at most kItemPairs
-// pairs; a dense chunk only gets its sentinel.  `rec_meta` is indexed by the global record, `pt_kv` / `pt_rec_start` / `order` by the
-// re-ordered landmark.  Shared by the host build and by the device build's general chunks.
-struct PairEnt { uint16_t key; uint32_t ent; };
-struct PairScratch {
-  std::vector<PairEnt> pe, pe_sorted;
-  std::vector<std::pair<int, int>> blk_order, items;  // (count, first index into pe)
-  std::vector<int32_t> cnt;
-};
-static void append_pair_tables(ChunkHdr& H, const uint32_t* rec_meta, const uint16_t* pt_kv, const int32_t* pt_rec_start, const int32_t* order,
-                               const uint8_t* pt_const, std::vector<uint32_t>& o_blk_desc, std::vector<uint32_t>& o_ents, std::vector<int32_t>& o_blk_ent_start,
-                               PairScratch& S) {
-  std::vector<PairEnt>&pe = S.pe, &pe_sorted = S.pe_sorted;
-  std::vector<std::pair<int, int>>&blk_order = S.blk_order, &items = S.items;
-  std::vector<int32_t>& cnt = S.cnt;
-  const int64_t c_first = H.pt0, end_pt = (int64_t)H.pt0 + H.npt;
-  pe.clear();
-  if (!H.dense) {
-    for (int64_t k = c_first; k < end_pt; ++k) {
-      const int p = order[k];
-      if (pt_const[p]) continue;
-      // Schur pairs of this landmark: records rbase .. rbase+kv-1 have variable cameras (slot-sorted)
-      const int rbase = pt_rec_start[(size_t)k] - H.rec0;
-      const int kv = (int)pt_kv[(size_t)k];
-      const uint32_t lpt = (uint32_t)(k - c_first);
-      for (int i = 0; i < kv; ++i) {
-        const uint32_t li = rec_meta[(size_t)H.rec0 + rbase + i] & 0xff;
-        for (int j = i; j < kv; ++j) {
-          const uint32_t lj = rec_meta[(size_t)H.rec0 + rbase + j] & 0xff;
-          pe.push_back(PairEnt{(uint16_t)(li | (lj << 8)), (uint32_t)(rbase + i) | ((uint32_t)(rbase + j) << 8) | (lpt << 16)});
-          // two records of one camera: the diagonal block needs B + B^T
-          if (li == lj && i != j)
-            pe.push_back(PairEnt{(uint16_t)(li | (lj << 8)), (uint32_t)(rbase + j) | ((uint32_t)(rbase + i) << 8) | (lpt << 16)});
-        }
+// ---- the table build of mpsfm_ba_create: the phases of build_host.h or the device build (devbuild.h), then the uploads ----------
+
+// the camera graph of the device build's stage 1 in the caller's slots: the device speaks provisional slots (all non-constant
+// cameras); cameras without blocks have no slot and no edges
+static void graph_from_stage1(const std::vector<uint64_t>& gbits, int words, const std::vector<int32_t>& prov, int nprov, const CameraLayout& cams,
+                              CamGraph& graph) {
+  graph.init(cams.ncv_real);
+  std::vector<int32_t> nat_of_prov((size_t)std::max(nprov, 1), -1);
+  for (size_t i = 0; i < cams.slot.size(); ++i) if (prov[i] >= 0) nat_of_prov[(size_t)prov[i]] = cams.slot[i];
+  for (int a = 0; a < nprov; ++a) {
+    const int na = nat_of_prov[(size_t)a];
+    for (int w = 0; w < words; ++w) {
+      uint64_t m = gbits[(size_t)a * words + w];
+      while (m) {
+        const int b = w * 64 + __builtin_ctzll(m);
+        m &= m - 1;
+        const int nb = nat_of_prov[(size_t)b];
+        if (na >= 0 && nb >= 0) graph.set(na, nb);
       }
     }
   }
-  // group the pairs by destination block (counting sort on li*ncam+lj); heaviest blocks first
-  {
-    const int nl = std::max(H.ncam, 1);
-    cnt.assign((size_t)nl * nl + 1, 0);
-    for (const PairEnt& e : pe) cnt[(size_t)(e.key & 0xff) * nl + (e.key >> 8) + 1]++;
-    for (size_t q = 1; q < cnt.size(); ++q) cnt[q] += cnt[q - 1];
-    pe_sorted.resize(pe.size());
-    for (const PairEnt& e : pe) pe_sorted[(size_t)cnt[(size_t)(e.key & 0xff) * nl + (e.key >> 8)]++] = e;
-    pe.swap(pe_sorted);
-  }
-  blk_order.clear();
-  for (size_t i = 0; i < pe.size();) {
-    size_t j = i;
-    while (j < pe.size() && pe[j].key == pe[i].key) ++j;
-    blk_order.emplace_back((int)(j - i), (int)i);
-    i = j;
-  }
-  std::stable_sort(blk_order.begin(), blk_order.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) { return x.first > y.first; });
-  // work items: runs of at most kItemPairs pairs of one block.  Block-major: all items of a block are
-  // neighbours, so the flush combines them (one atomic pass per block and round)
-  items.clear();
-  for (const auto& bo : blk_order)
-    for (int q = 0; q < bo.first; q += kItemPairs) items.emplace_back(std::min(kItemPairs, bo.first - q), bo.second + q);
-  H.blk0 = (int32_t)o_blk_desc.size();  // thread-local for now
-  H.ent0 = (int32_t)o_ents.size();
-  H.nent = (int32_t)pe.size();
-  H.nblk = (int32_t)items.size();
-  for (const auto& it : items) {
-    o_blk_desc.push_back(pe[(size_t)it.second].key);
-    o_blk_ent_start.push_back((int32_t)(o_ents.size() - (size_t)H.ent0));
-    for (int q = 0; q < it.first; ++q) o_ents.push_back(pe[(size_t)(it.second + q)].ent);
-  }
-  o_blk_ent_start.push_back((int32_t)(o_ents.size() - (size_t)H.ent0));  // per-chunk sentinel
 }
 
-static int build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const mpsfm_ba_state* st) {
-  const int nc = P->n_cams, npu = P->n_pts;
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (h->opt.verbose < 2) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[mpsfm_ba] build: %-28s %8.2f ms\n", what, 1e3 * std::chrono::duration<double>(now - t_prev).count());
-    t_prev = now;
-  };
-  h->nc = nc; h->np_user = npu;
-  h->loss.reproj_type = P->reproj_loss_type; h->loss.reproj_a = P->reproj_loss_scale;
-  h->loss.reproj_mag = P->reproj_loss_magnitude; h->loss.depth_type = P->depth_loss_type;
-
-  // -- Device-side table build (build_dev.hip) where it applies: one rank, at most kIndexMaxSlots non-constant cameras, no
-  //    landmark with more blocks than a chunk holds, no chunk for the general kernel.  Stage 1 runs here (block counts per camera,
-  //    blocks grouped by landmark, camera graph); the rest of this function then skips its host phases.  MPSFM_DEV_BUILD=0: host.
-  bool dev = false;
-  std::unique_ptr<DevBuilder> devb;
-  DevBuildOut DB;
-  std::vector<uint64_t> dev_gbits;
-  std::vector<int32_t> prov((size_t)std::max(nc, 1), -1);  // provisional slots of the graph stage: the non-constant cameras in order
-  int nprov = 0;
-  for (int i = 0; i < nc; ++i) if (!P->pose_const[i]) prov[(size_t)i] = nprov++;
-  const int dev_words = (nprov + 63) / 64;
-  // -- cameras of the reduced program: not constant and referenced by a residual block (any shard)
-  std::vector<double> cnt(nc + 1, 0.0);
-  const bool dev_wanted = !sharded(h) && nprov <= kIndexMaxSlots && nc <= 8192 && P->n_obs + P->n_dobs > 0 &&
-                          !(std::getenv("MPSFM_DEV_BUILD") && std::atoi(std::getenv("MPSFM_DEV_BUILD")) == 0) &&
-                          !(std::getenv("MPSFM_CHOL_GRAPH") && std::atoi(std::getenv("MPSFM_CHOL_GRAPH")) == 0);
-  if (dev_wanted) {
-    devb.reset(new DevBuilder());
-    int64_t max_blocks = 0;
-    if (int rc = devb->stage1(P, h->stream, prov, nprov, cnt, dev_gbits, dev_words, &max_blocks)) return rc;
-    dev = max_blocks <= kObsMax;  // longer block lists may be long tracks: host build
-    lap("device stage 1 (upload, group, graph)");
-  } else {
-    for (int64_t i = 0; i < P->n_obs; ++i) cnt[P->obs_cam[i]] += 1.0;
-    for (int64_t i = 0; i < P->n_dobs; ++i) cnt[P->dobs_cam[i]] += 1.0;
-    if (int rc = allreduce_host(h, cnt.data(), nc)) return rc;
+// Pair tables of a device-built handle: a sentinel per dense chunk; the general chunks (landmarks with more than kDenseCams cameras or
+// two records of one camera; they come last) get theirs from the host, which needs their record words and landmark tables back
+static int pair_tables_of_device_build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const RecTablesDev& rt, HostTables& T, const Lap& lap) {
+  std::vector<ChunkHdr>& chunks = T.chunks;
+  size_t g0 = 0;
+  while (g0 < chunks.size() && chunks[g0].dense) ++g0;
+  T.blk_ent_start.assign(g0, 0);
+  if (g0 == chunks.size()) return 0;
+  const int64_t r0 = chunks[g0].rec0, k0 = chunks[g0].pt0, nrg = T.nrec - r0, nkg = T.np_chunked - k0;
+  std::vector<uint32_t> rm((size_t)std::max<int64_t>(nrg, 1));
+  std::vector<uint16_t> kvs((size_t)std::max<int64_t>(nkg, 1));
+  std::vector<int32_t> prs((size_t)std::max<int64_t>(nkg, 1));
+  HIP_TRY(hipMemcpyAsync(rm.data(), rt.rec_meta + r0, 4 * (size_t)nrg, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(kvs.data(), rt.pt_kv + k0, 2 * (size_t)nkg, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(prs.data(), rt.pt_rec_start + k0, 4 * (size_t)nkg, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  PairScratch ps;
+  for (size_t c = g0; c < chunks.size(); ++c) {
+    if (chunks[c].dense) return fail(MPSFM_EUNSUPPORTED, "internal: dense chunks must precede the general ones");
+    // append_pair_tables indexes by the global record / re-ordered landmark: the copies start at r0 / k0
+    append_pair_tables(chunks[c], rm.data() - r0, kvs.data() - k0, prs.data() - k0, T.order.data(), P->pt_const, T.blk_desc, T.ents, T.blk_ent_start, ps);
   }
-  h->cam_slot_h.assign(nc, -1);
-  std::vector<double> cmask((size_t)nc * 6, 0.0);
-  h->ncv = 0;
-  for (int i = 0; i < nc; ++i) {
-    if (P->pose_const[i] || cnt[i] == 0.0) continue;
-    h->cam_slot_h[i] = h->ncv++;
-    for (int k = 0; k < 6; ++k) cmask[(size_t)i * 6 + k] = 1.0;
-    if (i == P->gauge_axis_cam) cmask[(size_t)i * 6 + 3] = 0.0;
-  }
-  const int ncv_real = h->ncv;
-  h->n_user = 6 * ncv_real;
-  h->n = 6 * h->ncv;
-  h->nt = (h->n + 31) / 32;
-  std::vector<int32_t>& slot = h->cam_slot_h;  // the caller's order for now; re-assigned below from the camera graph
-  // Records a DENSE chunk may hold.  A very small problem (a local bundle adjustment of a few cameras: a handful of full chunks) is
-  // cut into ~40 smaller ones: every sweep costs ONE workgroup's latency, which grows with the chunk's landmarks — measured in the
-  // single launch of local_lm.hip: 3 cameras / 300 landmarks 39 -> 34 us per iteration with 24 chunks instead of 6; beyond ~40
-  // chunks its grid barriers (~35 ns per workgroup each) take back what the sweep gains.  MPSFM_CHUNK_RECORDS overrides.
-  // landmarks of a dense chunk by the size of its camera set (dense_pts_cap): small problems, MPSFM_CHUNK_PTS_BY_CAMS overrides
-  const int pts_by_cams = [&] { const char* e = std::getenv("MPSFM_CHUNK_PTS_BY_CAMS"); return e ? (std::atoi(e) != 0 ? 1 : 0) : ((!sharded(h) && h->ncv >= 1 && h->ncv <= kLocalCams) ? 1 : 0); }();
-  int rec_cap = kObsMax;
-  constexpr int64_t kSmallChunks = 40;
-  if (const char* e = std::getenv("MPSFM_CHUNK_RECORDS")) rec_cap = std::min(std::max(std::atoi(e), 16), (int)kObsMax);
-  else if (!sharded(h) && h->ncv >= 1 && h->ncv <= kLocalCams && (int64_t)P->n_obs < kSmallChunks * kObsMax)
-    rec_cap = (int)std::min<int64_t>(kObsMax, std::max<int64_t>(64, ((int64_t)P->n_obs + kSmallChunks - 1) / kSmallChunks));
+  if (T.ents.size() > (size_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "too many Schur pairs for 32-bit entry offsets");
+  lap("pair tables of the general chunks (host)");
+  return 0;
+}
 
-  // -- residual blocks grouped by landmark and merged into records.  Every host thread owns a contiguous
-  //    landmark range: it scans the block lists for its landmarks (counting sort), orders each landmark's
-  //    blocks by camera slot and merges a reprojection and a depth block of one (camera, landmark) pair
-  //    into one record; fixed blocks (constant camera and constant landmark) are kept aside.
-  struct Rec { int32_t cam; int32_t slot; uint32_t flags; double u, v, d, m, a; };
-  auto deff = [&](int cam, int64_t src) {
-    double b = 0.0, s = 0.0;
-    if (P->shift_logscale) { b = P->shift_logscale[2 * cam]; s = P->shift_logscale[2 * cam + 1]; }
-    return P->dobs_depth[src] * std::exp(s) + b;
-  };
-  struct MergePart {
-    int p0 = 0, p1 = 0, err = 0;
-    std::vector<int64_t> pstart;  // block range of every landmark of the part
-    HostBuf<Blk> blks;   // recycled, uninitialised blocks (HostBlockCache): a few MB per part
-    HostBuf<Rec> recs;   // capacity = the part's blocks (merging only removes); nrecs filled
-    size_t nrecs = 0;
-    std::vector<Rec> fixed;
-    std::vector<int32_t> fixed_pt;
-    std::vector<int64_t> nrec_of;  // records per landmark of the range
-  };
-  const int mparts = (int)std::max<int64_t>(1, std::min<int64_t>(host_threads(), (P->n_obs + P->n_dobs) / 32768));  // starting threads only pays above ~100 k blocks
-  std::vector<MergePart> mp((size_t)mparts);
-  // Phase A (host threads over landmark ranges): the blocks of every landmark side by side (counting sort).
-  if (!dev) run_parts(mparts, [&](int t, int nparts) {
-    MergePart& M = mp[(size_t)t];
-    M.p0 = (int)((int64_t)npu * t / nparts); M.p1 = (int)((int64_t)npu * (t + 1) / nparts);
-    const int p0 = M.p0, np_loc = M.p1 - M.p0;
-    std::vector<int64_t>& pstart = M.pstart;
-    pstart.assign((size_t)np_loc + 1, 0);
-    for (int64_t i = 0; i < P->n_obs; ++i) { const unsigned q = (unsigned)(P->obs_pt[i] - p0); if (q < (unsigned)np_loc) pstart[q + 1]++; }
-    for (int64_t i = 0; i < P->n_dobs; ++i) { const unsigned q = (unsigned)(P->dobs_pt[i] - p0); if (q < (unsigned)np_loc) pstart[q + 1]++; }
-    for (int q = 0; q < np_loc; ++q) pstart[q + 1] += pstart[q];
-    M.blks.alloc((size_t)pstart[np_loc]);
-    std::vector<int64_t> fill(pstart.begin(), pstart.end() - 1);
-    for (int64_t i = 0; i < P->n_obs; ++i) {
-      const unsigned q = (unsigned)(P->obs_pt[i] - p0);
-      if (q >= (unsigned)np_loc) continue;
-      M.blks[(size_t)fill[q]++] = Blk{P->obs_cam[i], 0, 0, i};
-    }
-    for (int64_t i = 0; i < P->n_dobs; ++i) {
-      const unsigned q = (unsigned)(P->dobs_pt[i] - p0);
-      if (q >= (unsigned)np_loc) continue;
-      if (!(P->dobs_depth[i] > 0.0)) { M.err = 1; return; }
-      M.blks[(size_t)fill[q]++] = Blk{P->dobs_cam[i], 0, 1, i};
-    }
-  });
-  for (const MergePart& M : mp)
-    if (M.err == 1) return fail(MPSFM_EINVAL, "depth prior must be positive");
-  lap("group blocks by landmark (threads)");
+static void print_chunk_stats(const std::vector<ChunkHdr>& chunks) {
+  double sr = 0, sp = 0, sc = 0, sb = 0, se = 0, sd = 0; int mb = 0, mc = 0;
+  for (const ChunkHdr& H : chunks) { sr += H.nrec; sp += H.npt; sc += H.ncam; sb += H.nblk; se += H.nent; sd += H.dense; mb = std::max(mb, H.nblk); mc = std::max(mc, H.ncam); }
+  const double n = (double)chunks.size();
+  std::fprintf(stderr, "[mpsfm_ba] build: %zu chunks; per chunk: %.1f records, %.1f landmarks, %.1f cameras (max %d), %.1f work items (max %d), %.1f pairs; %.0f %% of the chunks take the dense product\n",
+               chunks.size(), sr / n, sp / n, sc / n, mc, sb / n, mb, se / n, 100.0 * sd / n);
+  int hist[kDenseCams + 2] = {0};
+  for (const ChunkHdr& H : chunks) ++hist[std::min<int>(H.ncam, kDenseCams + 1)];
+  std::fprintf(stderr, "[mpsfm_ba] build: chunks by number of variable cameras:");
+  for (int c = 0; c <= kDenseCams + 1; ++c) std::fprintf(stderr, " %s%d: %d", c > kDenseCams ? ">" : "", c > kDenseCams ? kDenseCams : c, hist[c]);
+  std::fprintf(stderr, "\n");
+}
 
-  // -- camera order.  Up to kIndexMaxSlots variable cameras: the camera graph (who shares a variable landmark with whom,
-  //    summed over the ranks) decides the slot order — nested dissection when it shortens the dependent chain of the tile
-  //    factorisation (chol_plan.h) — and which 6x6 blocks of S exist.  Beyond: the caller's order and a block skyline.
-  const bool use_graph = ncv_real > 0 && ncv_real <= kIndexMaxSlots && !(std::getenv("MPSFM_CHOL_GRAPH") && std::atoi(std::getenv("MPSFM_CHOL_GRAPH")) == 0);
-  CamGraph graph;
+// the block pattern of S and the tables of the dense factorisation (h->spat, h->plan) to the device
+static int upload_pattern(mpsfm_ba_handle* h, bool use_graph) {
   if (use_graph) {
-    graph.init(ncv_real);
-    std::vector<std::vector<uint64_t>> gb((size_t)mparts);
-    if (dev) {
-      // the device's graph speaks provisional slots (all non-constant cameras); cameras without blocks have no slot and no edges
-      std::vector<int32_t> nat_of_prov((size_t)std::max(nprov, 1), -1);
-      for (int i = 0; i < nc; ++i) if (prov[(size_t)i] >= 0) nat_of_prov[(size_t)prov[(size_t)i]] = slot[(size_t)i];
-      for (int a = 0; a < nprov; ++a) {
-        const int na = nat_of_prov[(size_t)a];
-        for (int w = 0; w < dev_words; ++w) {
-          uint64_t m = dev_gbits[(size_t)a * dev_words + w];
-          while (m) {
-            const int b = w * 64 + __builtin_ctzll(m);
-            m &= m - 1;
-            const int nb = nat_of_prov[(size_t)b];
-            if (na >= 0 && nb >= 0) graph.set(na, nb);
-          }
-        }
-      }
-    } else run_parts(mparts, [&](int t, int) {
-      const MergePart& M = mp[(size_t)t];
-      std::vector<uint64_t>& B = gb[(size_t)t];
-      B.assign(graph.bits.size(), 0);
-      std::vector<int32_t> sl;
-      for (int q = 0; q < M.p1 - M.p0; ++q) {
-        if (P->pt_const[M.p0 + q]) continue;
-        sl.clear();
-        for (int64_t r = M.pstart[(size_t)q]; r < M.pstart[(size_t)q + 1]; ++r) {
-          const int sc = slot[(size_t)M.blks[(size_t)r].cam];
-          if (sc >= 0 && std::find(sl.begin(), sl.end(), sc) == sl.end()) sl.push_back(sc);  // a handful of cameras per landmark
-        }
-        for (size_t a = 0; a < sl.size(); ++a)
-          for (size_t b = a + 1; b < sl.size(); ++b) {
-            B[(size_t)sl[a] * graph.words + (sl[b] >> 6)] |= 1ull << (sl[b] & 63);
-            B[(size_t)sl[b] * graph.words + (sl[a] >> 6)] |= 1ull << (sl[a] & 63);
-          }
-      }
-    });
-    if (!dev) for (const auto& B : gb) for (size_t w = 0; w < B.size(); ++w) graph.bits[w] |= B[w];
-    if (sharded(h)) {
-      // union over the ranks through the sum exchange (pack_graph / unpack_graph); the number of ranks comes from the
-      // exchange itself (a hook may come without world_size)
-      double ones = 1.0;
-      if (int rc = allreduce_host(h, &ones, 1)) return rc;
-      const int world = std::max((int)std::llround(ones), 1);
-      std::vector<double> packed;
-      pack_graph(graph, world, packed);
-      if (int rc = allreduce_host(h, packed.data(), (int64_t)packed.size())) return rc;
-      unpack_graph(packed, world, graph);
-    }
-    lap("camera graph");
-    int forced_depth = -2;
-    if (const char* e = std::getenv("MPSFM_CHOL_ND")) forced_depth = std::atoi(e);  // -1: caller's order, >= 0: dissection depth
-    int inv_rows = 2;
-    if (const char* e = std::getenv("MPSFM_CHOL_INVERSE")) if (std::atoi(e) == 0) inv_rows = -1;
-    plan_auto(graph, forced_depth, forced_depth >= -1, inv_rows < 0 ? 0 : dense_plain_max_tiles(), dense_inv_rows(), h->plan,
-              [](int n, void (*fn)(void*, int), void* ctx) { run_parts(n, [&](int t, int) { fn(ctx, t); }); });
-    lap("camera order + factorisation plan");
-    h->nat_slot = h->plan.slot_of_nat;
-    h->ncv = h->plan.nslots;                 // a permutation of the variable cameras
-    h->n = h->plan.n;                        // columns of the reduced system incl. the alignment padding
-    h->nt = (h->n + 31) / 32;
-    for (int i = 0; i < nc; ++i)
-      if (slot[(size_t)i] >= 0) slot[(size_t)i] = h->plan.slot_of_nat[(size_t)slot[(size_t)i]];
+    if (int rc = dev_upload(&h->d_sky_index, h->spat.sky_index)) return rc;
   } else {
-    h->nat_slot.resize((size_t)ncv_real);
-    for (int i = 0; i < ncv_real; ++i) h->nat_slot[(size_t)i] = i;
+    if (int rc = dev_upload(&h->d_sky_first, h->spat.sky_first)) return rc;
+    if (int rc = dev_upload(&h->d_sky_start, h->spat.sky_start)) return rc;
   }
+  return upload_plan(h, h->spat.nblk);
+}
 
-  // tables both builds hand to the tail of this function
-  std::vector<ChunkHdr> chunks;
-  std::vector<int32_t> chunk_cams;
-  HostBuf<int32_t> rec_cam, rec_pt;
-  std::vector<int32_t> pt_rec_start;
-  std::vector<uint32_t> blk_desc, ents;          // Schur pairs grouped by destination block, per chunk
-  std::vector<int32_t> blk_ent_start;
-  HostBuf<uint32_t> rec_meta;
-  std::vector<uint16_t> pt_kv;
-  HostBuf<double> rec_xy, rec_d, rec_m, rec_a;
-  int64_t nrec_total = 0;
-  int64_t nblk_reduced = 0;
-  double nvarpts = 0;
-  std::vector<LongHdr> lhdr;
-  int64_t wl_rows = 0;
-  std::vector<int32_t> fx_cam, fx_pt; std::vector<uint32_t> fx_meta; std::vector<double> fx_xy, fx_d, fx_m, fx_a;
-  if (dev) {
-    const bool dense_on = !(std::getenv("MPSFM_SWEEP_DENSE") && std::atoi(std::getenv("MPSFM_SWEEP_DENSE")) == 0);
-    const int rc2 = devb->stage2(slot, dense_on, rec_cap, pts_by_cams, DB);
-    if (rc2 < 0) return rc2;
-    if (rc2 == MPSFM_DEVBUILD_FALLBACK) {
-      // long tracks: the host phases run after all — Phase A first, which was skipped
-      DB.release();
-      dev = false;
-      run_parts(mparts, [&](int t, int nparts) {
-        MergePart& M = mp[(size_t)t];
-        M.p0 = (int)((int64_t)npu * t / nparts); M.p1 = (int)((int64_t)npu * (t + 1) / nparts);
-        const int p0 = M.p0, np_loc = M.p1 - M.p0;
-        std::vector<int64_t>& pstart = M.pstart;
-        pstart.assign((size_t)np_loc + 1, 0);
-        for (int64_t i = 0; i < P->n_obs; ++i) { const unsigned q = (unsigned)(P->obs_pt[i] - p0); if (q < (unsigned)np_loc) pstart[q + 1]++; }
-        for (int64_t i = 0; i < P->n_dobs; ++i) { const unsigned q = (unsigned)(P->dobs_pt[i] - p0); if (q < (unsigned)np_loc) pstart[q + 1]++; }
-        for (int q = 0; q < np_loc; ++q) pstart[q + 1] += pstart[q];
-        M.blks.alloc((size_t)pstart[np_loc]);
-        std::vector<int64_t> fill(pstart.begin(), pstart.end() - 1);
-        for (int64_t i = 0; i < P->n_obs; ++i) {
-          const unsigned q = (unsigned)(P->obs_pt[i] - p0);
-          if (q >= (unsigned)np_loc) continue;
-          M.blks[(size_t)fill[q]++] = Blk{P->obs_cam[i], 0, 0, i};
-        }
-        for (int64_t i = 0; i < P->n_dobs; ++i) {
-          const unsigned q = (unsigned)(P->dobs_pt[i] - p0);
-          if (q >= (unsigned)np_loc) continue;
-          M.blks[(size_t)fill[q]++] = Blk{P->dobs_cam[i], 0, 1, i};  // depths were validated by stage 1
-        }
-      });
-      lap("device build not applicable: host phases");
-    } else {
-      chunks.swap(DB.chunks); chunk_cams.swap(DB.chunk_cams);
-      h->perm.swap(DB.order);
-      h->np = DB.np; h->np_chunked = DB.np_chunked; h->nfixed = DB.nfixed;
-      h->nblocks_total = P->n_obs + P->n_dobs;
-      nrec_total = DB.nrec; nblk_reduced = DB.nblk_reduced; nvarpts = DB.nvarpts;
-      if (nrec_total > (int64_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "more than 2^31 records on one device");
-      h->nchunks = (int)chunks.size();
-      h->nlong = 0; h->nrec = nrec_total; h->nblocks_reduced = nblk_reduced;
-      h->nblocks_global = (double)h->nblocks_total; h->nblocks_reduced_global = (double)nblk_reduced; h->nvarpts_global = nvarpts;
-      lap("device stage 2 (order, chunks, records)");
-      // pair tables: a sentinel per dense chunk; the general chunks (landmarks with more than kDenseCams cameras or two records of one
-      // camera; they come last) get theirs from the host, which needs their record words and landmark tables back
-      size_t g0 = 0;
-      while (g0 < chunks.size() && chunks[g0].dense) ++g0;
-      blk_ent_start.assign(g0, 0);
-      if (g0 < chunks.size()) {
-        const int64_t r0 = chunks[g0].rec0, k0 = chunks[g0].pt0, nrg = nrec_total - r0, nkg = h->np_chunked - k0;
-        std::vector<uint32_t> rm((size_t)std::max<int64_t>(nrg, 1));
-        std::vector<uint16_t> kvs((size_t)std::max<int64_t>(nkg, 1));
-        std::vector<int32_t> prs((size_t)std::max<int64_t>(nkg, 1));
-        HIP_TRY(hipMemcpyAsync(rm.data(), DB.d_rec_meta + r0, 4 * (size_t)nrg, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(kvs.data(), DB.d_pt_kv + k0, 2 * (size_t)nkg, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(prs.data(), DB.d_pt_rec_start + k0, 4 * (size_t)nkg, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        PairScratch ps;
-        for (size_t c = g0; c < chunks.size(); ++c) {
-          if (chunks[c].dense) return fail(MPSFM_EUNSUPPORTED, "internal: dense chunks must precede the general ones");
-          append_pair_tables(chunks[c], rm.data() - r0, kvs.data() - k0, prs.data() - k0, h->perm.data(), P->pt_const, blk_desc, ents, blk_ent_start, ps);
-        }
-        if (ents.size() > (size_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "too many Schur pairs for 32-bit entry offsets");
-        lap("pair tables of the general chunks (host)");
-      }
-    }
-  }
-  if (!dev) {
-  // Phase B (the same host threads): every landmark's blocks ordered by (final) camera slot, a reprojection and a depth
-  // block of one (camera, landmark) pair merged into one record.
-  run_parts(mparts, [&](int t, int) {
-    MergePart& M = mp[(size_t)t];
-    const int p0 = M.p0, np_loc = M.p1 - M.p0;
-    Blk* const blks = M.blks.data();
-    for (size_t q = 0; q < M.blks.size(); ++q) blks[q].key = slot[(size_t)blks[q].cam] < 0 ? INT32_MAX : slot[(size_t)blks[q].cam];
-    M.recs.alloc(M.blks.size());
-    M.nrecs = 0;
-    M.nrec_of.assign((size_t)np_loc, 0);
-    for (int q = 0; q < np_loc; ++q) {
-      const int p = p0 + q;
-      Blk* const b0 = blks + M.pstart[(size_t)q]; Blk* const b1 = blks + M.pstart[(size_t)q + 1];
-      std::sort(b0, b1, [](const Blk& x, const Blk& y) {
-        if (x.key != y.key) return x.key < y.key;
-        if (x.cam != y.cam) return x.cam < y.cam;
-        if (x.kind != y.kind) return x.kind < y.kind;
-        return x.src < y.src;
-      });
-      const size_t before = M.nrecs;
-      for (auto it = b0; it != b1;) {
-        auto je = it;
-        while (je != b1 && je->cam == it->cam) ++je;
-        auto mid = it;
-        while (mid != je && mid->kind == 0) ++mid;
-        const int64_t nr = mid - it, nd = je - mid;
-        const bool is_fixed = (slot[it->cam] < 0) && P->pt_const[p];
-        for (int64_t k = 0; k < std::max(nr, nd); ++k) {
-          Rec r{it->cam, slot[it->cam], 0, 0, 0, 1.0, 0.0, 1.0};
-          if (k < nr) { const int64_t s = (it + k)->src; r.flags |= kRecHasReproj; r.u = P->obs_xy[2 * s]; r.v = P->obs_xy[2 * s + 1]; }
-          if (k < nd) {
-            const int64_t s = (mid + k)->src;
-            r.flags |= kRecHasDepth; r.d = deff(it->cam, s); r.m = P->dobs_magnitude[s]; r.a = P->dobs_param[s];
-            if (!(r.d > 0.0)) { M.err = 2; return; }
-            r.d = std::log(r.d);  // the residual is log Z - log d: the records carry log d (one logarithm less per evaluation)
-          }
-          if (is_fixed) { M.fixed.push_back(r); M.fixed_pt.push_back(p); }
-          else M.recs[M.nrecs++] = r;
-        }
-        it = je;
-      }
-      M.nrec_of[(size_t)q] = (int64_t)(M.nrecs - before);
-    }
-    M.blks.release();
-  });
-  for (const MergePart& M : mp)
-    if (M.err == 2) return fail(MPSFM_EINVAL, "shifted/scaled depth prior must be positive");
-  lap("sort + merge into records (threads)");
-  std::vector<int64_t> prec((size_t)npu + 1, 0);  // record range per caller landmark
-  HostBuf<Rec> recs;  // uninitialised: value-initialising tens of MB on one thread costs milliseconds
-  std::vector<Rec> fixed;
-  std::vector<int32_t> fixed_pt;
-  {
-    std::vector<int64_t> base((size_t)mparts + 1, 0);
-    for (int t = 0; t < mparts; ++t) base[(size_t)t + 1] = base[(size_t)t] + (int64_t)mp[(size_t)t].nrecs;
-    recs.alloc((size_t)base[(size_t)mparts]);
-    run_parts(mparts, [&](int t, int) {
-      MergePart& M = mp[(size_t)t];
-      std::copy(M.recs.data(), M.recs.data() + M.nrecs, recs.data() + base[(size_t)t]);
-      int64_t o = base[(size_t)t];
-      for (int q = 0; q < M.p1 - M.p0; ++q) { prec[(size_t)(M.p0 + q)] = o; o += M.nrec_of[(size_t)q]; }
-      M.recs.release();
-    });
-    prec[(size_t)npu] = base[(size_t)mparts];
-    for (MergePart& M : mp) {
-      fixed.insert(fixed.end(), M.fixed.begin(), M.fixed.end());
-      fixed_pt.insert(fixed_pt.end(), M.fixed_pt.begin(), M.fixed_pt.end());
-    }
-  }
-  h->nfixed = (int64_t)fixed.size();
-  h->nblocks_total = P->n_obs + P->n_dobs;
-  lap("merge records");
-  // -- landmark order: those with records sorted by their camera-slot list, then the rest that
-  //    are referenced by fixed blocks only
-  std::vector<int32_t> order; order.reserve(npu);
-  for (int p = 0; p < npu; ++p) if (prec[p + 1] > prec[p]) order.push_back(p);
-  {
-    // sort key: the first six camera slots of the track (16 bits each; slots beyond 65534 and constant
-    // cameras saturate), then the track length, then the landmark index — neighbours in this order share
-    // cameras, which keeps the set of S blocks a chunk touches small
-    struct Key { uint64_t k1, k2; int32_t p; };
-    std::vector<Key> keyed(order.size());
-    auto key_less = [](const Key& a, const Key& b) {
-      if (a.k1 != b.k1) return a.k1 < b.k1;
-      if (a.k2 != b.k2) return a.k2 < b.k2;
-      return a.p < b.p;
-    };
-    // sorted runs per thread, then pairwise merges (the order is total, so the result does not depend on the split)
-    const int sparts = (int)std::max<size_t>(1, std::min<size_t>((size_t)host_threads(), order.size() / 8192));
-    std::vector<size_t> cut((size_t)sparts + 1);
-    for (int t = 0; t <= sparts; ++t) cut[(size_t)t] = order.size() * (size_t)t / (size_t)sparts;
-    run_parts(sparts, [&](int t, int) {
-      for (size_t q = cut[(size_t)t]; q < cut[(size_t)t + 1]; ++q) {
-        const int pnt = order[q];
-        const int64_t n_p = prec[pnt + 1] - prec[pnt];
-        uint64_t key[2] = {0, 0};
-        for (int64_t k = 0; k < 6; ++k) {
-          uint64_t sk = 0xffff;
-          if (k < n_p && recs[prec[pnt] + k].slot >= 0) sk = (uint64_t)std::min(recs[prec[pnt] + k].slot, 0xfffe);
-          key[k / 4] = (key[k / 4] << 16) | sk;
-        }
-        key[1] = (key[1] << 32) | (uint64_t)std::min<int64_t>(n_p, 0xffffffff);
-        keyed[q] = Key{key[0], key[1], pnt};
-      }
-      std::sort(keyed.begin() + (std::ptrdiff_t)cut[(size_t)t], keyed.begin() + (std::ptrdiff_t)cut[(size_t)t + 1], key_less);
-    });
-    for (int width = 1; width < sparts; width *= 2) {
-      std::vector<int> lefts;
-      for (int t = 0; t + width < sparts; t += 2 * width) lefts.push_back(t);
-      run_parts((int)lefts.size(), [&](int j, int) {
-        const int t = lefts[(size_t)j];
-        std::inplace_merge(keyed.begin() + (std::ptrdiff_t)cut[(size_t)t], keyed.begin() + (std::ptrdiff_t)cut[(size_t)(t + width)],
-                           keyed.begin() + (std::ptrdiff_t)cut[(size_t)std::min(t + 2 * width, sparts)], key_less);
-      });
-    }
-    for (size_t q = 0; q < order.size(); ++q) order[q] = keyed[q].p;
-  }
-  lap("sort landmarks by key");
-  // landmarks whose track does not fit one chunk are swept by a workgroup of their own
-  auto is_long = [&](int p) {
-    const int64_t r_p = prec[p + 1] - prec[p];
-    if (r_p > kObsMax) return true;
-    int distinct = 0, last = -2;
-    for (int64_t r = prec[p]; r < prec[p + 1]; ++r)
-      if (recs[r].slot >= 0 && recs[r].slot != last) { ++distinct; last = recs[r].slot; }
-    return distinct > kLocalCamsMax;
-  };
-  std::vector<uint8_t> long_flag((size_t)npu + 1, 0);
-  parallel_ranges((int64_t)order.size(), 8192, [&](int64_t q0, int64_t q1) {
-    for (int64_t q = q0; q < q1; ++q) long_flag[(size_t)order[(size_t)q]] = is_long(order[(size_t)q]) ? 1 : 0;
-  });
-  auto first_long = std::stable_partition(order.begin(), order.end(), [&](int p) { return !long_flag[(size_t)p]; });
-  h->np_chunked = (int64_t)(first_long - order.begin());
-  // Landmarks the dense sweep cannot take — more than kDenseCams variable cameras, or two records of one camera for a variable
-  // landmark — go behind the others (same relative order), so that they form chunks of their own for the general kernel and
-  // every other chunk is dense by construction (the cut below keeps those within kDenseCams cameras / kDensePts landmarks).
-  const bool dense_on = !(std::getenv("MPSFM_SWEEP_DENSE") && std::atoi(std::getenv("MPSFM_SWEEP_DENSE")) == 0);
-  std::vector<uint8_t> heavy_flag((size_t)npu + 1, dense_on ? 0 : 1);
-  if (dense_on) {
-    parallel_ranges(h->np_chunked, 8192, [&](int64_t q0, int64_t q1) {
-      for (int64_t q = q0; q < q1; ++q) {
-        const int p = order[(size_t)q];
-        int distinct = 0, last = -2;
-        bool dup = false;
-        for (int64_t r = prec[p]; r < prec[p + 1]; ++r) {
-          if (recs[r].slot < 0) continue;
-          if (recs[r].slot != last) { ++distinct; last = recs[r].slot; }
-          else dup = true;  // records are slot-sorted: two of one camera are neighbours
-        }
-        heavy_flag[(size_t)p] = (distinct > kDenseCams || (dup && !P->pt_const[p])) ? 1 : 0;
-      }
-    });
-    std::stable_partition(order.begin(), first_long, [&](int p) { return !heavy_flag[(size_t)p]; });
-  }
-  const int64_t n_long = (int64_t)(order.end() - first_long);
-  {
-    std::vector<uint8_t> seen((size_t)npu + 1, 0);
-    for (int p : order) seen[p] = 1;
-    for (int32_t p : fixed_pt) if (!seen[p]) { seen[p] = 1; order.push_back(p); }
-  }
-  h->np = (int64_t)order.size();
-  h->perm = order;
-  std::vector<int32_t> inv((size_t)npu + 1, -1);
-  for (int64_t k = 0; k < h->np; ++k) inv[order[k]] = (int32_t)k;
+// the record and fixed-record tables of the host build to the device
+static int upload_record_tables(HostTables& T, RecTablesDev& rt) {
+  int rc = 0;
+  if ((rc = dev_upload(&rt.rec_cam, T.rec_cam))) return rc;
+  if ((rc = dev_upload(&rt.rec_pt, T.rec_pt))) return rc;
+  if ((rc = dev_upload(&rt.rec_meta, T.rec_meta))) return rc;
+  if ((rc = dev_upload(&rt.rec_xy, T.rec_xy))) return rc;
+  if ((rc = dev_upload(&rt.rec_d, T.rec_d))) return rc;
+  if ((rc = dev_upload(&rt.rec_m, T.rec_m))) return rc;
+  if ((rc = dev_upload(&rt.rec_a, T.rec_a))) return rc;
+  if ((rc = dev_upload(&rt.pt_rec_start, T.pt_rec_start))) return rc;
+  if ((rc = dev_upload(&rt.pt_kv, T.pt_kv))) return rc;
+  if ((rc = dev_upload(&rt.fx_cam, T.fx_cam))) return rc;
+  if ((rc = dev_upload(&rt.fx_pt, T.fx_pt))) return rc;
+  if ((rc = dev_upload(&rt.fx_meta, T.fx_meta))) return rc;
+  if ((rc = dev_upload(&rt.fx_xy, T.fx_xy))) return rc;
+  if ((rc = dev_upload(&rt.fx_d, T.fx_d))) return rc;
+  if ((rc = dev_upload(&rt.fx_m, T.fx_m))) return rc;
+  return dev_upload(&rt.fx_a, T.fx_a);
+}
 
-  lap("order landmarks");
-  // -- chunking.  Pass 1 (sequential, greedy): cut the ordered landmarks into chunks and collect each chunk's
-  //    sorted camera slots.  Pass 2 (host threads over contiguous chunk ranges): records, local camera
-  //    indices and the block-major Schur pair tables of every chunk.
-  pt_rec_start.assign((size_t)h->np + 1, 0);
-  pt_kv.assign((size_t)h->np + 1, 0xffff);
-  {
-    std::vector<int64_t> rec_off((size_t)h->np_chunked + 1, 0);  // first record of every chunked landmark
-    for (int64_t k = 0; k < h->np_chunked; ++k) rec_off[(size_t)k + 1] = rec_off[(size_t)k] + (prec[order[k] + 1] - prec[order[k]]);
-    {
-      // The greedy cut is sequential by nature; the ordered landmarks are therefore split into a FIXED number
-      // of segments (independent of the thread count, so the tables are the same on every machine), each cut
-      // greedily on its own with a forced chunk boundary at the segment ends.
-      struct Seg { std::vector<ChunkHdr> chunks; std::vector<int32_t> cams; };
-      const int nseg = (int)std::max<int64_t>(1, std::min<int64_t>(64, h->np_chunked / 4096));
-      std::vector<Seg> segs((size_t)nseg);
-      auto cut_segment = [&](int sidx) {
-        Seg& G = segs[(size_t)sidx];
-        const int64_t k0 = h->np_chunked * sidx / nseg, k1 = h->np_chunked * (sidx + 1) / nseg;
-        std::vector<int32_t> cur_cams, pc, uni;  // sorted slots of the open chunk
-        int64_t c_first = k0, c_nrec = 0;
-        auto close_chunk = [&](int64_t end_pt) {
-          if (end_pt == c_first) return;
-          ChunkHdr H{};
-          H.rec0 = (int32_t)rec_off[(size_t)c_first]; H.nrec = (int32_t)(rec_off[(size_t)end_pt] - rec_off[(size_t)c_first]);
-          H.pt0 = (int32_t)c_first; H.npt = (int32_t)(end_pt - c_first);
-          H.cam0 = (int32_t)G.cams.size(); H.ncam = (int32_t)cur_cams.size();  // segment-local for now
-          G.cams.insert(G.cams.end(), cur_cams.begin(), cur_cams.end());
-          G.chunks.push_back(H);
-          cur_cams.clear(); c_first = end_pt; c_nrec = 0;
-        };
-        for (int64_t k = k0; k < k1; ++k) {
-          const int p = order[k];
-          const int64_t r_p = prec[p + 1] - prec[p];
-          pc.clear();
-          for (int64_t r = prec[p]; r < prec[p + 1]; ++r) if (recs[r].slot >= 0) pc.push_back(recs[r].slot);
-          pc.erase(std::unique(pc.begin(), pc.end()), pc.end());  // records are slot-sorted
-          const bool subset = std::includes(cur_cams.begin(), cur_cams.end(), pc.begin(), pc.end());
-          size_t nuni = cur_cams.size();
-          if (!subset) {
-            uni.clear();
-            std::set_union(cur_cams.begin(), cur_cams.end(), pc.begin(), pc.end(), std::back_inserter(uni));
-            nuni = uni.size();
-          }
-          const bool hv = heavy_flag[(size_t)p] != 0;
-          const bool too_big = (c_nrec + r_p > (hv ? kObsMax : rec_cap)) || (k - c_first + 1 > (hv ? kPtsMax : dense_pts_cap((int)nuni, pts_by_cams))) || ((int)nuni > (hv ? kLocalCamsMax : kDenseCams)) ||
-                               (hv != (heavy_flag[(size_t)order[(size_t)c_first]] != 0));  // dense and general landmarks never share a chunk
-          if (k > c_first && too_big) {
-            close_chunk(k);
-            cur_cams = pc;
-          } else if (!subset) {
-            cur_cams.swap(uni);
-          }
-          c_nrec += r_p;
-        }
-        close_chunk(k1);
-      };
-      run_parts(std::min(host_threads(), nseg), [&](int t, int nparts) { for (int sidx = t; sidx < nseg; sidx += nparts) cut_segment(sidx); });
-      for (Seg& G : segs) {
-        const int32_t cbase = (int32_t)chunk_cams.size();
-        for (ChunkHdr& H : G.chunks) { H.cam0 += cbase; chunks.push_back(H); }
-        chunk_cams.insert(chunk_cams.end(), G.cams.begin(), G.cams.end());
-      }
-    }
-    lap("chunk boundaries");
-    const size_t nrec_chunked = (size_t)rec_off[(size_t)h->np_chunked];
-    nrec_total = (int64_t)nrec_chunked;
-    for (int64_t k = h->np_chunked; k < h->np_chunked + n_long; ++k) nrec_total += prec[order[k] + 1] - prec[order[k]];
-    if (nrec_total > (int64_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "more than 2^31 records on one device");
-    const size_t nr = (size_t)nrec_total;
-    rec_cam.alloc(nr); rec_pt.alloc(nr); rec_meta.alloc(nr); rec_xy.alloc(2 * nr); rec_d.alloc(nr); rec_m.alloc(nr); rec_a.alloc(nr);
-    lap("size record arrays");
-    struct ChunkPart {
-      std::vector<uint32_t> blk_desc, ents;
-      std::vector<int32_t> blk_ent_start;
-      int64_t nblk_reduced = 0;
-      double nvarpts = 0;
-    };
-    const int nch = (int)chunks.size();
-    const int cparts = std::max(1, std::min(host_threads(), nch / 48));
-    std::vector<ChunkPart> cp((size_t)cparts);
-    run_parts(cparts, [&](int t, int nparts) {
-      ChunkPart& C = cp[(size_t)t];
-      PairScratch ps;
-      for (int c = (int)((int64_t)nch * t / nparts); c < (int)((int64_t)nch * (t + 1) / nparts); ++c) {
-        ChunkHdr& H = chunks[(size_t)c];
-        const int32_t* cams = chunk_cams.data() + H.cam0;
-        const int64_t c_first = H.pt0, end_pt = (int64_t)H.pt0 + H.npt;
-        bool dup = false;    // two records of one camera for one variable landmark
-        int64_t w = H.rec0;  // next record
-        for (int64_t k = c_first; k < end_pt; ++k) {
-          const int p = order[k];
-          pt_rec_start[(size_t)k] = (int32_t)w;
-          const int rbase = (int)(w - H.rec0);  // chunk-relative index of this landmark's first record
-          int kv = 0;
-          for (int64_t r = prec[p]; r < prec[p + 1]; ++r, ++w) {
-            const Rec& R = recs[r];
-            uint32_t lcam = kLcamConst;
-            if (R.slot >= 0) {
-              lcam = (uint32_t)(std::lower_bound(cams, cams + H.ncam, R.slot) - cams);
-              ++kv;
-            }
-            rec_cam[(size_t)w] = R.cam; rec_pt[(size_t)w] = (int32_t)k;
-            rec_meta[(size_t)w] = lcam | ((uint32_t)(k - c_first) << 8) | R.flags;
-            rec_xy[2 * (size_t)w] = R.u; rec_xy[2 * (size_t)w + 1] = R.v; rec_d[(size_t)w] = R.d; rec_m[(size_t)w] = R.m; rec_a[(size_t)w] = R.a;
-            C.nblk_reduced += ((R.flags & kRecHasReproj) ? 1 : 0) + ((R.flags & kRecHasDepth) ? 1 : 0);
-          }
-          if (!P->pt_const[p]) {
-            pt_kv[(size_t)k] = (uint16_t)kv;
-            C.nvarpts += 1;
-            // two records of one camera for this landmark (records are slot-sorted: they are neighbours)
-            for (int i = 1; i < kv; ++i)
-              if ((rec_meta[(size_t)H.rec0 + rbase + i] & 0xff) == (rec_meta[(size_t)H.rec0 + rbase + i - 1] & 0xff)) dup = true;
-          }
-        }
-        // Chunks that form their Schur blocks as one dense product (k_track_sweep) need no pair tables at all.
-        H.dense = heavy_flag[(size_t)order[(size_t)c_first]] ? 0 : 1;  // by construction: <= kDenseCams cameras, <= kDensePts landmarks, no duplicates
-        H.slab0 = 0;
-        (void)dup;
-        append_pair_tables(H, rec_meta.data(), pt_kv.data(), pt_rec_start.data(), order.data(), P->pt_const, C.blk_desc, C.ents, C.blk_ent_start, ps);
-      }
-    });
-    lap("chunk records + pairs (threads)");
-    // concatenate the per-thread pair tables and make the chunk offsets global
-    std::vector<size_t> bbase((size_t)cparts + 1, 0), ebase((size_t)cparts + 1, 0), sbase((size_t)cparts + 1, 0);
-    for (int t = 0; t < cparts; ++t) {
-      bbase[(size_t)t + 1] = bbase[(size_t)t] + cp[(size_t)t].blk_desc.size();
-      ebase[(size_t)t + 1] = ebase[(size_t)t] + cp[(size_t)t].ents.size();
-      sbase[(size_t)t + 1] = sbase[(size_t)t] + cp[(size_t)t].blk_ent_start.size();
-      nblk_reduced += cp[(size_t)t].nblk_reduced; nvarpts += cp[(size_t)t].nvarpts;
-    }
-    if (ebase[(size_t)cparts] > (size_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "too many Schur pairs for 32-bit entry offsets");
-    blk_desc.resize(bbase[(size_t)cparts]); ents.resize(ebase[(size_t)cparts]); blk_ent_start.resize(sbase[(size_t)cparts]);
-    run_parts(cparts, [&](int t, int nparts) {
-      const ChunkPart& C = cp[(size_t)t];
-      std::copy(C.blk_desc.begin(), C.blk_desc.end(), blk_desc.begin() + (std::ptrdiff_t)bbase[(size_t)t]);
-      std::copy(C.ents.begin(), C.ents.end(), ents.begin() + (std::ptrdiff_t)ebase[(size_t)t]);
-      std::copy(C.blk_ent_start.begin(), C.blk_ent_start.end(), blk_ent_start.begin() + (std::ptrdiff_t)sbase[(size_t)t]);
-      for (int c = (int)((int64_t)nch * t / nparts); c < (int)((int64_t)nch * (t + 1) / nparts); ++c) {
-        chunks[(size_t)c].blk0 += (int32_t)bbase[(size_t)t];
-        chunks[(size_t)c].ent0 += (int32_t)ebase[(size_t)t];
-      }
-    });
-  }
-  lap("concatenate pair tables");
-  if (ents.size() > (size_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "too many Schur pairs for 32-bit entry offsets");
-  h->nchunks = (int)chunks.size();
-  {
-    size_t w = h->np_chunked > 0 ? (size_t)(pt_rec_start[(size_t)h->np_chunked - 1] + (prec[order[h->np_chunked - 1] + 1] - prec[order[h->np_chunked - 1]])) : 0;
-    for (int64_t k = h->np_chunked; k < h->np_chunked + n_long; ++k) {
-      const int p = order[k];
-      LongHdr L{};
-      L.rec0 = (int32_t)w; L.pt = (int32_t)k; L.w0 = wl_rows;
-      pt_rec_start[k] = L.rec0;
-      int kv = 0;
-      for (int64_t r = prec[p]; r < prec[p + 1]; ++r, ++w) {
-        const Rec& R = recs[r];
-        if (R.slot >= 0) ++kv;
-        rec_cam[w] = R.cam; rec_pt[w] = (int32_t)k;
-        rec_meta[w] = (R.slot >= 0 ? 0u : kLcamConst) | R.flags;
-        rec_xy[2 * w] = R.u; rec_xy[2 * w + 1] = R.v; rec_d[w] = R.d; rec_m[w] = R.m; rec_a[w] = R.a;
-        nblk_reduced += ((R.flags & kRecHasReproj) ? 1 : 0) + ((R.flags & kRecHasDepth) ? 1 : 0);
-      }
-      L.nrec = (int32_t)w - L.rec0;
-      L.kv = P->pt_const[p] ? 0 : kv;
-      if (!P->pt_const[p]) { pt_kv[k] = (uint16_t)std::min(kv, 0xfffe); nvarpts += 1; }
-      wl_rows += kv;
-      lhdr.push_back(L);
-    }
-  }
-  h->nlong = (int)lhdr.size();
-  h->nrec = nrec_total;
-  h->nblocks_reduced = nblk_reduced;
-  for (int64_t k = h->np_chunked + n_long; k <= h->np; ++k) pt_rec_start[k] = (int32_t)h->nrec;
-  {
-    double tot[3] = {(double)h->nblocks_total, (double)nblk_reduced, nvarpts};
-    if (int rc = allreduce_host(h, tot, 3)) return rc;
-    h->nblocks_global = tot[0]; h->nblocks_reduced_global = tot[1]; h->nvarpts_global = tot[2];
-  }
-  // -- fixed records (landmark index re-ordered)
-  for (size_t i = 0; i < fixed.size(); ++i) {
-    fx_cam.push_back(fixed[i].cam); fx_pt.push_back(inv[fixed_pt[i]]); fx_meta.push_back(fixed[i].flags);
-    fx_xy.push_back(fixed[i].u); fx_xy.push_back(fixed[i].v); fx_d.push_back(fixed[i].d); fx_m.push_back(fixed[i].m); fx_a.push_back(fixed[i].a);
-  }
-  }  // host phases
-
-  lap("chunks + pair tables");
-  if (h->opt.verbose >= 2 && !chunks.empty()) {
-    double sr = 0, sp = 0, sc = 0, sb = 0, se = 0, sd = 0; int mb = 0, mc = 0;
-    for (const ChunkHdr& H : chunks) { sr += H.nrec; sp += H.npt; sc += H.ncam; sb += H.nblk; se += H.nent; sd += H.dense; mb = std::max(mb, H.nblk); mc = std::max(mc, H.ncam); }
-    const double n = (double)chunks.size();
-    std::fprintf(stderr, "[mpsfm_ba] build: %zu chunks; per chunk: %.1f records, %.1f landmarks, %.1f cameras (max %d), %.1f work items (max %d), %.1f pairs; %.0f %% of the chunks take the dense product\n",
-                 chunks.size(), sr / n, sp / n, sc / n, mc, sb / n, mb, se / n, 100.0 * sd / n);
-    int hist[kDenseCams + 2] = {0};
-    for (const ChunkHdr& H : chunks) ++hist[std::min<int>(H.ncam, kDenseCams + 1)];
-    std::fprintf(stderr, "[mpsfm_ba] build: chunks by number of variable cameras:");
-    for (int c = 0; c <= kDenseCams + 1; ++c) std::fprintf(stderr, " %s%d: %d", c > kDenseCams ? ">" : "", c > kDenseCams ? kDenseCams : c, hist[c]);
-    std::fprintf(stderr, "\n");
-  }
-  // -- which 6x6 blocks of S exist, and the tables of the dense factorisation
-  if (use_graph) {
-    const int ns = h->ncv;
-    h->sky_index.assign((size_t)ns * (size_t)ns, -1);
-    int32_t nblk = 0;
-    for (int sj = 0; sj < ns; ++sj) {
-      const int j = h->plan.nat_of_slot[(size_t)sj];
-      if (j < 0) continue;
-      for (int si = 0; si <= sj; ++si) {
-        const int i = h->plan.nat_of_slot[(size_t)si];
-        if (i < 0) continue;
-        if (i == j || graph.get(i, j)) h->sky_index[(size_t)sj * ns + si] = nblk++;
-      }
-    }
-    h->sblk_blocks = nblk;
-    if (int rc2 = dev_upload(&h->d_sky_index, h->sky_index)) return rc2;
-    if (int rc2 = upload_plan(h, nblk)) return rc2;
-  } else {
-    // block skyline (DenseEnvelope): which 6x6 blocks of S can be nonzero follows from the static Schur pair tables;
-    // first_blk[c] = lowest camera slot that shares a landmark with slot c
-    const int ncv = h->ncv, nt = h->nt, n = h->n;
-    std::vector<int32_t> first_blk((size_t)std::max(ncv, 1));
-    for (int c = 0; c < ncv; ++c) first_blk[(size_t)c] = c;
-    for (const ChunkHdr& H : chunks) {
-      const int32_t* cams = chunk_cams.data() + H.cam0;
-      if (H.dense)  // no pair table: every pair of the chunk's (sorted) cameras may be coupled
-        for (int q = 1; q < H.ncam; ++q) first_blk[(size_t)cams[q]] = std::min(first_blk[(size_t)cams[q]], cams[0]);
-      for (int b = 0; b < H.nblk; ++b) {
-        const uint32_t d = blk_desc[(size_t)H.blk0 + (size_t)b];
-        const int si = cams[d & 0xff], sj = cams[(d >> 8) & 0xff];
-        const int lo = std::min(si, sj), hi = std::max(si, sj);
-        first_blk[(size_t)hi] = std::min(first_blk[(size_t)hi], lo);
-      }
-    }
-    for (const LongHdr& L : lhdr) {  // a long track couples all its variable cameras
-      int lo = INT32_MAX;
-      for (int r = 0; r < L.kv; ++r) lo = std::min(lo, slot[rec_cam[(size_t)L.rec0 + (size_t)r]]);
-      for (int r = 0; r < L.kv; ++r) { int32_t& f = first_blk[(size_t)slot[rec_cam[(size_t)L.rec0 + (size_t)r]]]; f = std::min(f, lo); }
-    }
-    const char* envs = std::getenv("MPSFM_CHOL_ENVELOPE");
-    if (envs && std::atoi(envs) == 0) std::fill(first_blk.begin(), first_blk.end(), 0);  // A/B: treat S as dense
-    if (sharded(h) && ncv > 0) {
-      // landmark shards see different camera pairs: every rank needs the UNION.  The hook only sums, so the minimum over
-      // ranks is found by bisection on indicator sums (the same number of rounds on every rank).
-      std::vector<double> lo((size_t)ncv, 0.0), hi((size_t)ncv), ind((size_t)ncv);
-      for (int c = 0; c < ncv; ++c) hi[(size_t)c] = (double)c;
-      int rounds = 1;
-      while ((1 << rounds) < ncv + 1) ++rounds;
-      for (int it = 0; it < rounds; ++it) {
-        for (int c = 0; c < ncv; ++c) ind[(size_t)c] = first_blk[(size_t)c] <= (int)std::floor(0.5 * (lo[(size_t)c] + hi[(size_t)c])) ? 1.0 : 0.0;
-        if (int rc2 = allreduce_host(h, ind.data(), ncv)) return rc2;
-        for (int c = 0; c < ncv; ++c) {
-          const double mid = std::floor(0.5 * (lo[(size_t)c] + hi[(size_t)c]));
-          if (ind[(size_t)c] > 0.0) hi[(size_t)c] = mid; else lo[(size_t)c] = std::min(mid + 1.0, hi[(size_t)c]);
-        }
-      }
-      for (int c = 0; c < ncv; ++c) first_blk[(size_t)c] = (int32_t)hi[(size_t)c];
-    }
-    h->sky_first = first_blk;
-    h->sky_start.assign((size_t)ncv + 1, 0);
-    for (int c = 0; c < ncv; ++c) h->sky_start[(size_t)c + 1] = h->sky_start[(size_t)c] + (c - first_blk[(size_t)c] + 1);
-    h->sblk_blocks = h->sky_start[(size_t)ncv];
-    if (int rc2 = dev_upload(&h->d_sky_first, h->sky_first)) return rc2;
-    if (int rc2 = dev_upload(&h->d_sky_start, h->sky_start)) return rc2;
-    std::vector<int32_t> first((size_t)nt + 1, 0);
-    for (int ti = 0; ti < nt; ++ti) {
-      int f = ti;
-      for (int r = ti * 32; r < std::min(n, ti * 32 + 32); ++r) f = std::min(f, (6 * first_blk[(size_t)(r / 6)]) / 32);
-      first[(size_t)ti] = f;
-    }
-    first[(size_t)nt] = 0;  // the right-hand-side row
-    // the factorisation plan of the skyline in the caller's order: tile (ti, tj) can be nonzero for tj >= first[ti]
-    {
-      std::vector<uint8_t> pat((size_t)nt * (size_t)nt, 0);
-      for (int ti = 0; ti < nt; ++ti)
-        for (int tj = first[(size_t)ti]; tj < ti; ++tj) pat[(size_t)ti * nt + tj] = 1;
-      CholPlan& PL = h->plan;
-      PL.ncv = ncv; PL.nslots = ncv; PL.n = n; PL.nd_depth = -1;
-      PL.slot_of_nat = h->nat_slot; PL.nat_of_slot = h->nat_slot;  // identity, no padding: slot_of_col stays empty (NULL map)
-      plan_from_pattern(pat, nt, nt <= dense_plain_max_tiles() && !(std::getenv("MPSFM_CHOL_INVERSE") && std::atoi(std::getenv("MPSFM_CHOL_INVERSE")) == 0),
-                        dense_inv_rows(), PL);
-      if (int rc2 = upload_plan(h, h->sblk_blocks)) return rc2;
-    }
-    if (h->opt.verbose >= 2) {
-      int64_t inside = 0;
-      for (int ti = 0; ti < nt; ++ti) inside += ti - first[(size_t)ti] + 1;
-      std::fprintf(stderr, "[mpsfm_ba] build: block skyline %lld of %lld tiles\n", (long long)inside, (long long)nt * (nt + 1) / 2);
-    }
-  }
-
-  // -- slabs of the dense chunks and the tables of their reduction (k_reduce_slabs): per destination — a block of S or a camera's
-  //    vectors — the slab positions that contribute, in chunk order; destinations with many sources are split into parts
-  std::vector<RedDest> red_dests;
-  std::vector<int32_t> red_srcs, diag_block;
-  bool slab_tables_on_device = false;
-  int64_t slab_units = 0;
-  {
-    h->n_dense = 0;
-    for (size_t c = 0; c < chunks.size(); ++c) {
-      ChunkHdr& H = chunks[c];
-      if (!H.dense) continue;
-      if ((int)c != h->n_dense) return fail(MPSFM_EUNSUPPORTED, "internal: dense chunks must precede the general ones");
-      H.slab0 = (int32_t)slab_units;
-      slab_units += slab_doubles(H.ncam) / 18;
-      if (slab_units > (int64_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "slabs of the dense chunks exceed 2^31 units");
-      h->n_dense = (int)c + 1;
-    }
-    const int64_t nsb = h->sblk_blocks;
-    // a device-built handle forms the tables on the device too (DevBuilder::slab_tables, behind the uploads below)
-    {
-      const char* e = std::getenv("MPSFM_SLAB_TABLES_HOST");  // 1: host loop, 0: device kernels (tests), unset: by size — below ~500
-      const int pref = e ? std::atoi(e) : -1;                  // chunks the host loop is quicker than the launches
-      slab_tables_on_device = dev && devb && h->n_dense > 0 && (pref == 0 || (pref < 0 && h->n_dense >= 512));
-    }
-    auto host_sky = [&](int si, int sj) -> int64_t {
-      return use_graph ? (int64_t)h->sky_index[(size_t)sj * (size_t)h->ncv + (size_t)si] : h->sky_start[(size_t)sj] + (si - h->sky_first[(size_t)sj]);
-    };
-    const size_t ndst = (size_t)nsb + (size_t)std::max(h->ncv, 0);
-    diag_block.assign((size_t)std::max(h->ncv, 1), -1);
-    for (int sl = 0; sl < h->ncv; ++sl) {
-      if (use_graph && h->plan.nat_of_slot[(size_t)sl] < 0) continue;
-      const int64_t b = host_sky(sl, sl);
-      if (b >= 0 && b < nsb) diag_block[(size_t)sl] = (int32_t)b;
-    }
-    std::vector<int32_t> cnt(ndst + 1, 0);
-    for (int pass = 0; pass < 2 && !slab_tables_on_device; ++pass) {  // count, then place (chunk order within a destination)
-      if (pass == 1) {
-        for (size_t d = 1; d <= ndst; ++d) cnt[d] += cnt[d - 1];
-        red_srcs.resize((size_t)cnt[ndst]);
-      }
-      for (int c = 0; c < h->n_dense; ++c) {
-        const ChunkHdr& H = chunks[(size_t)c];
-        const int32_t* cams = chunk_cams.data() + H.cam0;
-        const int nb = H.ncam * (H.ncam + 1) / 2;
-        for (int cj = 0; cj < H.ncam; ++cj) {
-          for (int ci = 0; ci <= cj; ++ci) {
-            const int64_t b = host_sky(cams[ci], cams[cj]);
-            if (b < 0) continue;  // two cameras of the chunk that share no landmark anywhere: their product is exactly zero, S has no such block
-            if (b >= nsb) return fail(MPSFM_EUNSUPPORTED, "internal: block index beyond S");
-            if (pass == 0) cnt[(size_t)b + 1]++;
-            else red_srcs[(size_t)cnt[(size_t)b]++] = H.slab0 + 2 * (cj * (cj + 1) / 2 + ci);
-          }
-          const size_t d = (size_t)nsb + (size_t)cams[cj];
-          if (pass == 0) cnt[d + 1]++;
-          else red_srcs[(size_t)cnt[d]++] = H.slab0 + 2 * nb + cj;
-        }
-      }
-    }
-    // after the placing pass cnt[d] is the END of destination d
-    std::vector<uint8_t> is_diag((size_t)nsb, 0);
-    for (int sl = 0; sl < h->ncv; ++sl) {
-      if (use_graph && h->plan.nat_of_slot[(size_t)sl] < 0) continue;
-      const int64_t b = host_sky(sl, sl);
-      if (b >= 0 && b < nsb) is_diag[(size_t)b] = 1;
-    }
-    constexpr int kPart = 16;
-    for (size_t d = 0; d < ndst && !slab_tables_on_device; ++d) {
-      const int32_t s0 = d == 0 ? 0 : cnt[d - 1], s1 = cnt[d];
-      for (int32_t q = s0; q < s1; q += kPart) {
-        RedDest R;
-        R.kind = d >= (size_t)nsb ? 2 : (is_diag[d] ? 1 : 0);
-        R.dst = d >= (size_t)nsb ? (int32_t)(d - (size_t)nsb) : (int32_t)d;
-        R.s0 = q; R.s1 = std::min(q + kPart, s1);
-        red_dests.push_back(R);
-      }
-    }
-    h->n_red_dests = (int)red_dests.size();
-    h->n_red_srcs = (int64_t)red_srcs.size(); h->n_chunk_cams = (int64_t)chunk_cams.size();
-  }
-  lap("slab reduction tables");
-
-  // -- upload
+// Everything the solve reads to the device.  `DB`: the device build's output (T is its host part) or, after a host build, empty;
+// `devb` forms the slab reduction tables on the device when `R` came without them (R.dests empty, R.diag_block set).
+static int upload_tables(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const CameraLayout& cams, DevBuildOut& DB, SlabTables& R, DevBuilder* devb,
+                         bool slab_tables_on_device) {
+  HostTables& T = DB.t;
+  const int nc = P->n_cams;
   int rc = 0;
   std::vector<double> intr(P->cam_intr, P->cam_intr + (size_t)P->n_intr * 4);
   std::vector<int32_t> intr_idx(P->cam_intr_idx, P->cam_intr_idx + nc);
   if ((rc = dev_upload(&h->d_intr, intr))) return rc;
   if ((rc = dev_upload(&h->d_intr_idx, intr_idx))) return rc;
-  if ((rc = dev_upload(&h->d_cmask, cmask))) return rc;
+  if ((rc = dev_upload(&h->d_cmask, cams.cmask))) return rc;
   if ((rc = dev_upload(&h->d_cam_slot, h->cam_slot_h))) return rc;
-  {
-    std::vector<int32_t> cam_of_slot((size_t)std::max(h->ncv, 1), 0);
-    for (int i = 0; i < nc; ++i) if (h->cam_slot_h[(size_t)i] >= 0 && h->cam_slot_h[(size_t)i] < h->ncv) cam_of_slot[(size_t)h->cam_slot_h[(size_t)i]] = i;
-    if ((rc = dev_upload(&h->d_cam_of_slot, cam_of_slot))) return rc;
-  }
-  if ((rc = dev_upload(&h->d_chunks, chunks))) return rc;
-  if ((rc = dev_upload(&h->d_chunk_cams, chunk_cams))) return rc;
+  if ((rc = dev_upload(&h->d_cam_of_slot, cam_of_slot_table(cams)))) return rc;
+  if ((rc = dev_upload(&h->d_chunks, T.chunks))) return rc;
+  if ((rc = dev_upload(&h->d_chunk_cams, T.chunk_cams))) return rc;
   if (h->np > 0 && h->np == (int64_t)h->np_user) {
     if ((rc = dev_upload(&h->d_perm, h->perm))) return rc;
     if ((rc = dev_alloc(&h->d_user_pts, (size_t)h->np * 3))) return rc;
   }
-  h->built_on_device = dev;
-  if (dev) {  // the device build's tables are where they belong
-    h->d_rec_cam = DB.d_rec_cam; h->d_rec_pt = DB.d_rec_pt; h->d_rec_meta = DB.d_rec_meta; h->d_rec_xy = DB.d_rec_xy; h->d_rec_d = DB.d_rec_d;
-    h->d_rec_m = DB.d_rec_m; h->d_rec_a = DB.d_rec_a; h->d_pt_rec_start = DB.d_pt_rec_start; h->d_pt_kv = DB.d_pt_kv;
-    h->d_fx_cam = DB.d_fx_cam; h->d_fx_pt = DB.d_fx_pt; h->d_fx_meta = DB.d_fx_meta; h->d_fx_xy = DB.d_fx_xy; h->d_fx_d = DB.d_fx_d; h->d_fx_m = DB.d_fx_m;
-    h->d_fx_a = DB.d_fx_a;
-    DB.d_rec_cam = DB.d_rec_pt = DB.d_pt_rec_start = DB.d_fx_cam = DB.d_fx_pt = nullptr; DB.d_rec_meta = DB.d_fx_meta = nullptr; DB.d_pt_kv = nullptr;
-    DB.d_rec_xy = DB.d_rec_d = DB.d_rec_m = DB.d_rec_a = DB.d_fx_xy = DB.d_fx_d = DB.d_fx_m = DB.d_fx_a = nullptr;
+  if (h->built_on_device) {  // the device build's tables are where they belong
+    h->rt = DB.rt;
+    DB.rt = RecTablesDev{};
     DB.release();  // the device copies of chunks / camera lists: the host copies (slab offsets added) are uploaded above
-  } else {
-  if ((rc = dev_upload(&h->d_rec_cam, rec_cam))) return rc;
-  if ((rc = dev_upload(&h->d_rec_pt, rec_pt))) return rc;
-  if ((rc = dev_upload(&h->d_rec_meta, rec_meta))) return rc;
-  if ((rc = dev_upload(&h->d_rec_xy, rec_xy))) return rc;
-  if ((rc = dev_upload(&h->d_rec_d, rec_d))) return rc;
-  if ((rc = dev_upload(&h->d_rec_m, rec_m))) return rc;
-  if ((rc = dev_upload(&h->d_rec_a, rec_a))) return rc;
-  if ((rc = dev_upload(&h->d_pt_rec_start, pt_rec_start))) return rc;
-  if ((rc = dev_upload(&h->d_pt_kv, pt_kv))) return rc;
-  if ((rc = dev_upload(&h->d_fx_cam, fx_cam))) return rc;
-  if ((rc = dev_upload(&h->d_fx_pt, fx_pt))) return rc;
-  if ((rc = dev_upload(&h->d_fx_meta, fx_meta))) return rc;
-  if ((rc = dev_upload(&h->d_fx_xy, fx_xy))) return rc;
-  if ((rc = dev_upload(&h->d_fx_d, fx_d))) return rc;
-  if ((rc = dev_upload(&h->d_fx_m, fx_m))) return rc;
-  if ((rc = dev_upload(&h->d_fx_a, fx_a))) return rc;
-  }
-  if ((rc = dev_upload(&h->d_lhdr, lhdr))) return rc;
-  if ((rc = dev_alloc(&h->d_wl, (size_t)std::max<int64_t>(wl_rows, 1) * 18))) return rc;
-  h->n_blk_desc = (int64_t)blk_desc.size(); h->n_blk_ent_start = (int64_t)blk_ent_start.size(); h->n_ents = (int64_t)ents.size();
-  if ((rc = dev_upload(&h->d_blk_desc, blk_desc))) return rc;
-  if ((rc = dev_upload(&h->d_blk_ent_start, blk_ent_start))) return rc;
-  if ((rc = dev_upload(&h->d_ents, ents))) return rc;
+  } else if ((rc = upload_record_tables(T, h->rt))) return rc;
+  if ((rc = dev_upload(&h->d_lhdr, T.lhdr))) return rc;
+  if ((rc = dev_alloc(&h->d_wl, (size_t)std::max<int64_t>(T.wl_rows, 1) * 18))) return rc;
+  h->n_blk_desc = (int64_t)T.blk_desc.size(); h->n_blk_ent_start = (int64_t)T.blk_ent_start.size(); h->n_ents = (int64_t)T.ents.size();
+  if ((rc = dev_upload(&h->d_blk_desc, T.blk_desc))) return rc;
+  if ((rc = dev_upload(&h->d_blk_ent_start, T.blk_ent_start))) return rc;
+  if ((rc = dev_upload(&h->d_ents, T.ents))) return rc;
   int32_t* d_diag_block = nullptr;
   if (!slab_tables_on_device) {
-    if ((rc = dev_upload(&h->d_red_dests, red_dests))) return rc;
-    if ((rc = dev_upload(&h->d_red_srcs, red_srcs))) return rc;
-  } else if ((rc = dev_upload(&d_diag_block, diag_block))) return rc;
-  if ((rc = dev_alloc(&h->d_slab, (size_t)std::max<int64_t>(slab_units, 1) * 18))) return rc;
+    if ((rc = dev_upload(&h->d_red_dests, R.dests))) return rc;
+    if ((rc = dev_upload(&h->d_red_srcs, R.srcs))) return rc;
+  } else if ((rc = dev_upload(&d_diag_block, R.diag_block))) return rc;
+  if ((rc = dev_alloc(&h->d_slab, (size_t)std::max<int64_t>(R.slab_units, 1) * 18))) return rc;
 
   if ((rc = drain_uploads())) { cached_free(d_diag_block); return rc; }
   if (slab_tables_on_device) {
     const BlockSky sky{h->d_sky_first, h->d_sky_start, h->d_sky_index, h->ncv};
     int32_t nd = 0; int64_t ns = 0;
-    rc = devb->slab_tables(h->d_chunks, h->n_dense, h->d_chunk_cams, sky, h->sblk_blocks, h->ncv, d_diag_block, &h->d_red_dests, &nd, &h->d_red_srcs, &ns);
+    rc = devb->slab_tables(h->d_chunks, h->n_dense, h->d_chunk_cams, sky, h->spat.nblk, h->ncv, d_diag_block, &h->d_red_dests, &nd, &h->d_red_srcs, &ns);
     HIP_TRY(hipStreamSynchronize(h->stream));  // d_diag_block goes back to the process-wide cache
     cached_free(d_diag_block);
     if (rc) return rc;
     h->n_red_dests = nd; h->n_red_srcs = ns;
   }
-  lap("upload tables");
-  const size_t ncs = (size_t)std::max(nc, 1), nps = (size_t)std::max<int64_t>(h->np, 1);
+  return 0;
+}
+
+// state, reduced system, dense workspace, scalars, events; the single-launch solver's buffers where it applies
+static int alloc_work_buffers(mpsfm_ba_handle* h, const BuildOptions& opt) {
+  int rc = 0;
+  const size_t ncs = (size_t)std::max(h->nc, 1), nps = (size_t)std::max<int64_t>(h->np, 1);
   for (double** p : {&h->d_q, &h->d_q2, &h->d_q0}) if ((rc = dev_alloc(p, ncs * 4))) return rc;
   for (double** p : {&h->d_t, &h->d_t2, &h->d_t0}) if ((rc = dev_alloc(p, ncs * 3))) return rc;
   for (double** p : {&h->d_pts, &h->d_pts2, &h->d_pts0, &h->d_ps, &h->d_diagV}) if ((rc = dev_alloc(p, nps * 3))) return rc;
   if ((rc = dev_alloc(&h->d_cs, ncs * 6))) return rc;
   if ((rc = dev_alloc(&h->d_camtab, ncs * kCamRec))) return rc;
   if ((rc = dev_alloc(&h->d_camtab2, ncs * kCamRec))) return rc;
-  h->sblk_count = h->sblk_blocks * 36;
+  h->sblk_count = h->spat.nblk * 36;
   h->red_count = h->sblk_count + 3 * (int64_t)h->n_user + SC_COUNT;
   if ((rc = dev_alloc(&h->d_red, (size_t)h->red_count))) return rc;
   h->d_Sblk = h->d_red; h->d_gc = h->d_red + h->sblk_count; h->d_wv = h->d_gc + h->n_user; h->d_diagU = h->d_wv + h->n_user;
@@ -1788,15 +748,7 @@ static int build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const mpsfm_ba_s
   if ((rc = dev_alloc(&h->d_fail, 1))) return rc;
   HIP_TRY(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));
   for (auto& e : h->ev) HIP_TRY(pooled_event(&e, true));
-  // tuning / test overrides of the dense factorisation, read once per handle
-  if (const char* e = std::getenv("MPSFM_CHOL_NB")) h->ov.nb = std::max(0, std::atoi(e));
-  if (const char* e = std::getenv("MPSFM_CHOL_BIG")) h->ov.big = std::atoi(e) != 0;
-  if (const char* e = std::getenv("MPSFM_CHOL_OVERLAP")) h->ov.overlap = std::atoi(e) != 0;
-  if (const char* e = std::getenv("MPSFM_CHOL_INVERSE")) h->ov.no_inverse = std::atoi(e) == 0;
-  if (const char* e = std::getenv("MPSFM_CHOL_LEVEL")) h->ov.no_level = std::atoi(e) == 0;
-  // a large reduced system without exploitable structure (every camera shares landmarks with most others): the
-  // outer-panel path with its LDS-staged 64x64 trailing update moves fewer bytes per flop than one workgroup per tile
-  else if (h->nt > dense_plain_max_tiles() && (double)h->plan.products > 0.5 * (double)h->nt * h->nt * h->nt / 6.0) h->ov.no_level = true;
+  opt.apply_dense(h->nt, h->plan, h->ov);
   if (h->nt > 64 || h->ov.nb > 0) {
     HIP_TRY(pooled_stream(&h->ov.s2));
     for (auto& e : h->ov.evF) HIP_TRY(pooled_event(&e, false));
@@ -1804,23 +756,133 @@ static int build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const mpsfm_ba_s
   }
   // Small problems (local bundle adjustment): the whole trust-region loop in one cooperative launch, one workgroup per chunk
   h->local_ok = false;
-  {
-    const char* e = std::getenv("MPSFM_LOCAL_LM");
-    const bool wanted = !(e && std::atoi(e) == 0);
-    if (wanted && !sharded(h) && h->nlong == 0 && h->nchunks > 0 && h->n_dense == h->nchunks && h->ncv >= 1 && h->ncv <= kLocalCams &&
-        h->n_user == 6 * h->ncv && h->nchunks <= local_lm_max_chunks(h->device)) {
-      h->local_log_cap = std::max(h->opt.max_num_iterations, 0) + 2;
-      if ((rc = dev_alloc(&h->d_local_acc, (size_t)2 * kLocalAccDoubles))) return rc;
-      if ((rc = dev_alloc(&h->d_local_sync, (size_t)16))) return rc;
-      if ((rc = dev_alloc(&h->d_local_log, (size_t)h->local_log_cap))) return rc;
-      h->local_ok = true;
-    }
+  if (opt.local_lm && !sharded(h) && h->nlong == 0 && h->nchunks > 0 && h->n_dense == h->nchunks && h->ncv >= 1 && h->ncv <= kLocalCams &&
+      h->n_user == 6 * h->ncv && h->nchunks <= local_lm_max_chunks(h->device)) {
+    h->local_log_cap = std::max(h->opt.max_num_iterations, 0) + 2;
+    if ((rc = dev_alloc(&h->d_local_acc, (size_t)2 * kLocalAccDoubles))) return rc;
+    if ((rc = dev_alloc(&h->d_local_sync, (size_t)16))) return rc;
+    if ((rc = dev_alloc(&h->d_local_log, (size_t)h->local_log_cap))) return rc;
+    h->local_ok = true;
   }
   HIP_TRY(hipMemsetAsync(h->d_ps, 0, nps * 3 * sizeof(double), h->stream));
   HIP_TRY(hipMemsetAsync(h->d_yc, 0, (size_t)std::max(h->n_user, 1) * sizeof(double), h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   init_tile_tables(h->stream);
-  (void)st;
+  return 0;
+}
+
+// Build the re-ordered, chunked record tables and upload everything: the list of the build's phases.
+static int build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P) {
+  const int nc = P->n_cams;
+  auto t_prev = std::chrono::steady_clock::now();
+  const Lap lap = [&](const char* what) {
+    if (h->opt.verbose < 2) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[mpsfm_ba] build: %-28s %8.2f ms\n", what, 1e3 * std::chrono::duration<double>(now - t_prev).count());
+    t_prev = now;
+  };
+  h->nc = nc; h->np_user = P->n_pts;
+  h->loss.reproj_type = P->reproj_loss_type; h->loss.reproj_a = P->reproj_loss_scale;
+  h->loss.reproj_mag = P->reproj_loss_magnitude; h->loss.depth_type = P->depth_loss_type;
+  BuildOptions opt = BuildOptions::from_environment();
+  // the exchanges of a landmark-sharded build (block counts, graph union, totals, skyline bisection) sum host values over the ranks
+  const SumExchange exchange = sharded(h) ? SumExchange([h](double* buf, int64_t count) { return allreduce_host(h, buf, count); }) : SumExchange();
+
+  // -- Device-side table build (build_dev.hip) where it applies: one rank, at most kIndexMaxSlots non-constant cameras, no
+  //    landmark with more blocks than a chunk holds.  Stage 1 runs here (block counts per camera, blocks grouped by landmark,
+  //    camera graph); stage 2 then stands in for the host phases.  MPSFM_DEV_BUILD=0: host.
+  bool dev = false;
+  std::unique_ptr<DevBuilder> devb;
+  DevBuildOut DB;
+  HostTables& T = DB.t;  // filled by either build
+  std::vector<uint64_t> dev_gbits;
+  std::vector<int32_t> prov((size_t)std::max(nc, 1), -1);  // provisional slots of the graph stage: the non-constant cameras in order
+  int nprov = 0;
+  for (int i = 0; i < nc; ++i) if (!P->pose_const[i]) prov[(size_t)i] = nprov++;
+  const int dev_words = (nprov + 63) / 64;
+  std::vector<double> cnt(nc + 1, 0.0);  // blocks per camera
+  if (!sharded(h) && nprov <= kIndexMaxSlots && nc <= 8192 && P->n_obs + P->n_dobs > 0 && opt.dev_build && opt.chol_graph) {
+    devb.reset(new DevBuilder());
+    int64_t max_blocks = 0;
+    if (int rc = devb->stage1(P, h->stream, prov, nprov, cnt, dev_gbits, dev_words, &max_blocks)) return rc;
+    dev = max_blocks <= kObsMax;  // longer block lists may be long tracks: host build
+    lap("device stage 1 (upload, group, graph)");
+  } else {
+    count_camera_blocks(P, cnt);
+    if (exchange) if (int rc = exchange(cnt.data(), nc)) return rc;
+  }
+  CameraLayout cams;
+  assign_camera_slots(P, cnt, opt, cams);
+  h->n_user = 6 * cams.ncv_real;
+  opt.set_chunk_caps(sharded(h), cams.ncv, P->n_obs);
+
+  LandmarkGroups groups;
+  if (!dev) if (int rc = group_blocks_by_landmark(P, true, groups)) return rc;
+  lap("group blocks by landmark (threads)");
+
+  // -- camera order: from the camera graph (summed over the ranks), or the caller's
+  CamGraph graph;
+  if (cams.use_graph) {
+    if (dev) graph_from_stage1(dev_gbits, dev_words, prov, nprov, cams, graph);
+    else camera_graph_from_groups(P, groups, cams, graph);
+    if (exchange) if (int rc = union_graph_over_ranks(graph, exchange)) return rc;
+    lap("camera graph");
+    plan_camera_order(graph, opt, h->plan, cams);
+    lap("camera order + factorisation plan");
+  } else keep_caller_order(cams);
+  h->cam_slot_h = cams.slot; h->nat_slot = cams.nat_slot;
+  h->ncv = cams.ncv; h->n = cams.n; h->nt = cams.nt;
+
+  // -- records, landmark order, chunks, pair tables
+  if (dev) {
+    const int rc2 = devb->stage2(cams.slot, opt.sweep_dense, opt.rec_cap, opt.pts_by_cams, DB);
+    if (rc2 < 0) return rc2;
+    if (rc2 == MPSFM_DEVBUILD_FALLBACK) {
+      // long tracks: the host phases run after all — the grouping first, which was skipped (depths were validated by stage 1)
+      DB.release();
+      dev = false;
+      if (int rc = group_blocks_by_landmark(P, false, groups)) return rc;
+      lap("device build not applicable: host phases");
+    } else {
+      if (T.nrec > (int64_t)INT32_MAX) return fail(MPSFM_EUNSUPPORTED, "more than 2^31 records on one device");
+      lap("device stage 2 (order, chunks, records)");
+      if (int rc = pair_tables_of_device_build(h, P, DB.rt, T, lap)) return rc;
+    }
+  }
+  if (!dev) if (int rc = build_record_tables(P, cams, opt, groups, T, lap)) return rc;
+  h->built_on_device = dev;
+  h->np = T.np; h->np_chunked = T.np_chunked; h->nfixed = T.nfixed; h->nrec = T.nrec;
+  h->nchunks = (int)T.chunks.size(); h->nlong = (int)T.lhdr.size();
+  h->nblocks_total = P->n_obs + P->n_dobs; h->nblocks_reduced = T.nblk_reduced;
+  {
+    double tot[3] = {(double)h->nblocks_total, (double)T.nblk_reduced, T.nvarpts};
+    if (exchange) if (int rc = exchange(tot, 3)) return rc;
+    h->nblocks_global = tot[0]; h->nblocks_reduced_global = tot[1]; h->nvarpts_global = tot[2];
+  }
+  lap("chunks + pair tables");
+  if (h->opt.verbose >= 2 && !T.chunks.empty()) print_chunk_stats(T.chunks);
+
+  // -- which 6x6 blocks of S exist, and the tables of the dense factorisation
+  if (cams.use_graph) s_pattern_index(cams, h->plan, graph, h->spat);
+  else if (int rc = s_pattern_skyline(cams, T, opt, exchange, h->opt.verbose >= 2, h->spat, h->plan)) return rc;
+  if (int rc = upload_pattern(h, cams.use_graph)) return rc;
+
+  // -- slabs of the dense chunks and the tables of their reduction; a device-built handle forms the tables on the device too
+  //    (DevBuilder::slab_tables, behind the uploads).  MPSFM_SLAB_TABLES_HOST 1: host loop, 0: device kernels (tests), unset: by
+  //    size — below ~500 chunks the host loop is quicker than the launches
+  SlabTables slabs;
+  if (int rc = assign_slabs(T.chunks, slabs)) return rc;
+  h->n_dense = slabs.n_dense;
+  const bool slab_tables_on_device = dev && h->n_dense > 0 && (opt.slab_tables_host == 0 || (opt.slab_tables_host < 0 && h->n_dense >= 512));
+  if (int rc = slab_reduction_tables(T, cams, h->plan, h->spat, !slab_tables_on_device, slabs)) return rc;
+  h->n_red_dests = (int)slabs.dests.size();
+  h->n_red_srcs = (int64_t)slabs.srcs.size(); h->n_chunk_cams = (int64_t)T.chunk_cams.size();
+  lap("slab reduction tables");
+
+  h->perm.swap(T.order);
+  if (int rc = upload_tables(h, P, cams, DB, slabs, devb.get(), slab_tables_on_device)) return rc;
+  lap("upload tables");
+  if (int rc = alloc_work_buffers(h, opt)) return rc;
   lap("allocate work buffers");
   return 0;
 }
@@ -1872,9 +934,9 @@ static int upload_state(mpsfm_ba_handle* h, const mpsfm_ba_state* st, bool as_in
 static SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr) {
   SweepArgs a{};
   a.ctl = ctl;
-  a.chunks = h->d_chunks; a.chunk_cams = h->d_chunk_cams; a.rec_cam = h->d_rec_cam; a.rec_meta = h->d_rec_meta;
-  a.rec_xy = h->d_rec_xy; a.rec_d = h->d_rec_d; a.rec_m = h->d_rec_m; a.rec_a = h->d_rec_a;
-  a.pt_rec_start = h->d_pt_rec_start; a.pt_kv = h->d_pt_kv; a.blk_desc = h->d_blk_desc; a.blk_ent_start = h->d_blk_ent_start; a.ents = h->d_ents;
+  a.chunks = h->d_chunks; a.chunk_cams = h->d_chunk_cams; a.rec_cam = h->rt.rec_cam; a.rec_meta = h->rt.rec_meta;
+  a.rec_xy = h->rt.rec_xy; a.rec_d = h->rt.rec_d; a.rec_m = h->rt.rec_m; a.rec_a = h->rt.rec_a;
+  a.pt_rec_start = h->rt.pt_rec_start; a.pt_kv = h->rt.pt_kv; a.blk_desc = h->d_blk_desc; a.blk_ent_start = h->d_blk_ent_start; a.ents = h->d_ents;
   a.camtab = h->d_camtab; a.pts = h->d_pts; a.ps = h->d_ps; a.loss = h->loss;
   a.radius = radius; a.min_diag = h->opt.min_lm_diagonal; a.max_diag = h->opt.max_lm_diagonal; a.ncv = h->ncv; a.dbg = (g_dbg_flags >> 8) & 0xff;
   a.lhdr = h->d_lhdr; a.nlong = h->nlong; a.nchunks = h->nchunks; a.cam_slot = h->d_cam_slot; a.wl = h->d_wl;
@@ -1904,7 +966,7 @@ static int cost_of_records(mpsfm_ba_handle* h, int64_t nrec, const int32_t* cam,
 static int prepare_scales(mpsfm_ba_handle* h) {
   hipStream_t s = h->stream;
   launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 0, h->d_cs, s);
-  launch_pt_scales(h->np, h->d_pt_kv, h->d_diagV, 0, h->d_ps, s);
+  launch_pt_scales(h->np, h->rt.pt_kv, h->d_diagV, 0, h->d_ps, s);
   launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, s);
   if (h->opt.jacobi_scaling) {
     HIP_TRY(hipMemsetAsync(h->d_diagU, 0, sizeof(double) * (size_t)std::max(h->n_user, 1), s));
@@ -1913,7 +975,7 @@ static int prepare_scales(mpsfm_ba_handle* h) {
     launch_track_sweep(a, h->nchunks, true, s);
     if (int rc = allreduce_dev(h, h->d_diagU, h->n_user)) return rc;
     launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 1, h->d_cs, s);
-    launch_pt_scales(h->np, h->d_pt_kv, h->d_diagV, 1, h->d_ps, s);
+    launch_pt_scales(h->np, h->rt.pt_kv, h->d_diagV, 1, h->d_ps, s);
     launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, s);
   }
   HIP_TRY(hipGetLastError());
@@ -1980,7 +1042,7 @@ static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   HIP_TRY(hipMemsetAsync(h->d_scal, 0, sizeof(double) * U_COUNT, s));
   if (h->nfixed > 0) {
     const int nb = (int)std::min<int64_t>(1024, (h->nfixed + kThreads - 1) / kThreads);
-    CostArgs c{h->nfixed, h->d_fx_cam, h->d_fx_pt, h->d_fx_meta, h->d_fx_xy, h->d_fx_d, h->d_fx_m, h->d_fx_a, h->d_camtab, h->d_pts, h->loss, h->d_costpart};
+    CostArgs c{h->nfixed, h->rt.fx_cam, h->rt.fx_pt, h->rt.fx_meta, h->rt.fx_xy, h->rt.fx_d, h->rt.fx_m, h->rt.fx_a, h->d_camtab, h->d_pts, h->loss, h->d_costpart};
     launch_cost_records(c, nb, s);
     launch_reduce_cols(h->d_costpart, nb, 4, 3, 0u, fixed_parts, s);
   }
@@ -2092,13 +1154,13 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
     HIP_TRY(hipMemsetAsync(h->d_scal, 0, sizeof(double) * U_COUNT, s));
     if (h->nfixed > 0) {
       const int nb = (int)std::min<int64_t>(1024, (h->nfixed + kThreads - 1) / kThreads);
-      CostArgs c{h->nfixed, h->d_fx_cam, h->d_fx_pt, h->d_fx_meta, h->d_fx_xy, h->d_fx_d, h->d_fx_m, h->d_fx_a, h->d_camtab, h->d_pts, h->loss, h->d_costpart};
+      CostArgs c{h->nfixed, h->rt.fx_cam, h->rt.fx_pt, h->rt.fx_meta, h->rt.fx_xy, h->rt.fx_d, h->rt.fx_m, h->rt.fx_a, h->d_camtab, h->d_pts, h->loss, h->d_costpart};
       launch_cost_records(c, nb, s);
       launch_reduce_cols(h->d_costpart, nb, 4, 3, 0u, h->d_scal + 12, s);
     }
   } else {
     double fx[3];
-    if (int rc = cost_of_records(h, h->nfixed, h->d_fx_cam, h->d_fx_pt, h->d_fx_meta, h->d_fx_xy, h->d_fx_d, h->d_fx_m, h->d_fx_a, fx)) return rc;
+    if (int rc = cost_of_records(h, h->nfixed, h->rt.fx_cam, h->rt.fx_pt, h->rt.fx_meta, h->rt.fx_xy, h->rt.fx_d, h->rt.fx_m, h->rt.fx_a, fx)) return rc;
     fixed = fx[0] + fx[1];
     if (int rc = allreduce_host(h, &fixed, 1)) return rc;
     sum->fixed_cost = fixed;
@@ -2106,7 +1168,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
 
   if (nothing_to_solve) {
     double c3[3];
-    if (int rc = cost_of_records(h, h->nrec, h->d_rec_cam, h->d_rec_pt, h->d_rec_meta, h->d_rec_xy, h->d_rec_d, h->d_rec_m, h->d_rec_a, c3)) return rc;
+    if (int rc = cost_of_records(h, h->nrec, h->rt.rec_cam, h->rt.rec_pt, h->rt.rec_meta, h->rt.rec_xy, h->rt.rec_d, h->rt.rec_m, h->rt.rec_a, c3)) return rc;
     double c = c3[0] + c3[1];
     if (int rc = allreduce_host(h, &c, 1)) return rc;
     sum->initial_cost = sum->final_cost = c + fixed;
@@ -2123,7 +1185,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
     HIP_TRY(hipMemsetAsync(h->d_gc, 0, sizeof(double) * (size_t)std::max(h->n_user, 1), s));
     launch_cam_update(h->nc, h->d_cam_slot, h->d_q, h->d_t, h->d_cs, h->d_yc, h->d_gc, h->d_q2, h->d_t2, h->d_scal, s);
     const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (h->np + kThreads - 1) / kThreads));
-    launch_pts_sqnorm(h->np, h->d_pt_kv, h->d_pts, h->d_costpart, nb, s);
+    launch_pts_sqnorm(h->np, h->rt.pt_kv, h->d_pts, h->d_costpart, nb, s);
     launch_reduce_cols(h->d_costpart, nb, 1, 1, 0u, h->d_scal + U_XN_SQ_PTS, s);
     if (!async_pre) {
       HIP_TRY(hipMemcpyAsync(h->h_scal, h->d_scal, sizeof(double) * U_COUNT, hipMemcpyDeviceToHost, s));
@@ -2298,7 +1360,7 @@ static int create_impl(const mpsfm_ba_problem* P, const mpsfm_ba_state* st, cons
     if (nrc != 0) { h->comm = nullptr; free_handle(h); return fail(MPSFM_ECOMM, std::string("ncclCommInitRank: ") + (R.GetErrorString ? R.GetErrorString(nrc) : "failed")); }
     since("ncclCommInitRank");
   }
-  int rc = build(h, P, st);
+  int rc = build(h, P);
   since("build");
   if (rc == 0 && st) rc = upload_state(h, st, true);
   since("upload_state");
@@ -2496,8 +1558,8 @@ int mpsfm_ba_eval_cost(mpsfm_ba_handle* h, double* cost_reproj, double* cost_dep
   launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, h->stream);
   h->scales_ready = false;
   double a[3], b[3];
-  if (int rc = cost_of_records(h, h->nrec, h->d_rec_cam, h->d_rec_pt, h->d_rec_meta, h->d_rec_xy, h->d_rec_d, h->d_rec_m, h->d_rec_a, a)) return rc;
-  if (int rc = cost_of_records(h, h->nfixed, h->d_fx_cam, h->d_fx_pt, h->d_fx_meta, h->d_fx_xy, h->d_fx_d, h->d_fx_m, h->d_fx_a, b)) return rc;
+  if (int rc = cost_of_records(h, h->nrec, h->rt.rec_cam, h->rt.rec_pt, h->rt.rec_meta, h->rt.rec_xy, h->rt.rec_d, h->rt.rec_m, h->rt.rec_a, a)) return rc;
+  if (int rc = cost_of_records(h, h->nfixed, h->rt.fx_cam, h->rt.fx_pt, h->rt.fx_meta, h->rt.fx_xy, h->rt.fx_d, h->rt.fx_m, h->rt.fx_a, b)) return rc;
   if (cost_reproj) *cost_reproj = a[0] + b[0];
   if (cost_depth) *cost_depth = a[1] + b[1];
   return 0;
@@ -2505,12 +1567,7 @@ int mpsfm_ba_eval_cost(mpsfm_ba_handle* h, double* cost_reproj, double* cost_dep
 
 int mpsfm_ba_dense_plan(mpsfm_ba_handle* h, int64_t info[10]) {
   if (!h || !info) return fail(MPSFM_EINVAL, "handle or info is NULL");
-  const CholPlan& P = h->plan;
-  const bool level = dense_level(&h->ov, &h->lp);
-  const bool pinv = level && dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp) != nullptr;
-  const int64_t v[10] = {h->ncv, h->nt, level ? P.nlevels : h->nt, P.nd_depth, pinv ? 1 : 0, (int64_t)P.items.size(), P.products, P.roles, h->sblk_blocks,
-                         pinv ? 1 : (level ? P.nlevels : (h->nt + 3) / 4 + 1)};
-  for (int i = 0; i < 10; ++i) info[i] = v[i];
+  dense_plan_numbers(h->ncv, h->nt, h->plan, h->ov, h->lp, h->d_dwork, h->spat.nblk, info);
   return 0;
 }
 int mpsfm_ba_reduced_dim(mpsfm_ba_handle* h) { return h ? h->n_user : MPSFM_EINVAL; }
@@ -2554,7 +1611,8 @@ int mpsfm_debug_read_trace(mpsfm_ba_handle* h, long long* out, int64_t count) {
 // table's size in bytes, or a negative error code.  which: 0 chunk headers, 1 chunk cameras, 2 rec_cam, 3 rec_pt, 4 rec_meta, 5 rec_xy,
 // 6 rec_d, 7 rec_m, 8 rec_a, 9 pt_rec_start, 10 pt_kv, 11 fx_cam, 12 fx_pt, 13 fx_meta, 14 fx_xy, 15 fx_d, 16 fx_m, 17 fx_a,
 // 18 landmark order (host), 19 reduction destinations, 20 reduction sources, 21 camera slots (host), 22: 1 byte, built on the device?,
-// 23 blk_desc, 24 blk_ent_start, 25 ents (pair tables of the general chunks)
+// 23 blk_desc, 24 blk_ent_start, 25 ents (pair tables of the general chunks), 27 long-track headers, 28 sky_index, 29 sky_first,
+// 30 sky_start (host), 31 cmask, 32 cam_of_slot, 33 the ten numbers of mpsfm_ba_dense_plan
 int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t cap) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   const void* src = nullptr;
@@ -2564,22 +1622,22 @@ int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t 
   switch (which) {
     case 0: src = h->d_chunks; bytes = (int64_t)sizeof(ChunkHdr) * h->nchunks; break;
     case 1: src = h->d_chunk_cams; bytes = 4 * h->n_chunk_cams; break;
-    case 2: src = h->d_rec_cam; bytes = 4 * nr; break;
-    case 3: src = h->d_rec_pt; bytes = 4 * nr; break;
-    case 4: src = h->d_rec_meta; bytes = 4 * nr; break;
-    case 5: src = h->d_rec_xy; bytes = 16 * nr; break;
-    case 6: src = h->d_rec_d; bytes = 8 * nr; break;
-    case 7: src = h->d_rec_m; bytes = 8 * nr; break;
-    case 8: src = h->d_rec_a; bytes = 8 * nr; break;
-    case 9: src = h->d_pt_rec_start; bytes = 4 * np1; break;
-    case 10: src = h->d_pt_kv; bytes = 2 * np1; break;
-    case 11: src = h->d_fx_cam; bytes = 4 * nf; break;
-    case 12: src = h->d_fx_pt; bytes = 4 * nf; break;
-    case 13: src = h->d_fx_meta; bytes = 4 * nf; break;
-    case 14: src = h->d_fx_xy; bytes = 16 * nf; break;
-    case 15: src = h->d_fx_d; bytes = 8 * nf; break;
-    case 16: src = h->d_fx_m; bytes = 8 * nf; break;
-    case 17: src = h->d_fx_a; bytes = 8 * nf; break;
+    case 2: src = h->rt.rec_cam; bytes = 4 * nr; break;
+    case 3: src = h->rt.rec_pt; bytes = 4 * nr; break;
+    case 4: src = h->rt.rec_meta; bytes = 4 * nr; break;
+    case 5: src = h->rt.rec_xy; bytes = 16 * nr; break;
+    case 6: src = h->rt.rec_d; bytes = 8 * nr; break;
+    case 7: src = h->rt.rec_m; bytes = 8 * nr; break;
+    case 8: src = h->rt.rec_a; bytes = 8 * nr; break;
+    case 9: src = h->rt.pt_rec_start; bytes = 4 * np1; break;
+    case 10: src = h->rt.pt_kv; bytes = 2 * np1; break;
+    case 11: src = h->rt.fx_cam; bytes = 4 * nf; break;
+    case 12: src = h->rt.fx_pt; bytes = 4 * nf; break;
+    case 13: src = h->rt.fx_meta; bytes = 4 * nf; break;
+    case 14: src = h->rt.fx_xy; bytes = 16 * nf; break;
+    case 15: src = h->rt.fx_d; bytes = 8 * nf; break;
+    case 16: src = h->rt.fx_m; bytes = 8 * nf; break;
+    case 17: src = h->rt.fx_a; bytes = 8 * nf; break;
     case 18: src = h->perm.data(); bytes = 4 * (int64_t)h->perm.size(); host = true; break;
     case 19: src = h->d_red_dests; bytes = (int64_t)sizeof(RedDest) * h->n_red_dests; break;
     case 20: src = h->d_red_srcs; bytes = 4 * h->n_red_srcs; break;
@@ -2589,6 +1647,13 @@ int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t 
     case 25: src = h->d_ents; bytes = 4 * h->n_ents; break;
     case 26: src = h->d_part; bytes = 32 * (int64_t)h->nchunks; break;
     case 22: { static uint8_t flag; flag = h->built_on_device ? 1 : 0; src = &flag; bytes = 1; host = true; break; }
+    case 27: src = h->d_lhdr; bytes = (int64_t)sizeof(LongHdr) * h->nlong; break;
+    case 28: src = h->spat.sky_index.data(); bytes = 4 * (int64_t)h->spat.sky_index.size(); host = true; break;
+    case 29: src = h->spat.sky_first.data(); bytes = 4 * (int64_t)h->spat.sky_first.size(); host = true; break;
+    case 30: src = h->spat.sky_start.data(); bytes = 8 * (int64_t)h->spat.sky_start.size(); host = true; break;
+    case 31: src = h->d_cmask; bytes = 48 * (int64_t)h->nc; break;
+    case 32: src = h->d_cam_of_slot; bytes = 4 * (int64_t)std::max(h->ncv, 1); break;
+    case 33: { static thread_local int64_t info[10]; if (int rc = mpsfm_ba_dense_plan(h, info)) return rc; src = info; bytes = 80; host = true; break; }
     default: return fail(MPSFM_EINVAL, "unknown table");
   }
   if (!out || cap < bytes) return bytes;
@@ -2597,6 +1662,93 @@ int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t 
   if (hipSetDevice(h->device) != hipSuccess) return fail(MPSFM_EHIP, "hipSetDevice failed");
   if (hipMemcpyAsync(out, src, (size_t)bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return fail(MPSFM_EHIP, "copy failed");
   if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(MPSFM_EHIP, "sync failed");
+  return bytes;
+}
+
+// Diagnostics / tests (tests/test_build_tables_cpu.py; no device involved): the host phases of the table build — the functions
+// build() calls, for a single rank — run on `P`, then table `which` copied out: numbering, arguments and return value of
+// mpsfm_debug_table (26 is a work buffer and does not exist here).  Rebuilds on every call.
+int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* out, int64_t cap) {
+  if (int rc = check_problem(P)) return rc;
+  BuildOptions opt = BuildOptions::from_environment();
+  const Lap lap = [](const char*) {};
+  const SumExchange one_rank;
+  std::vector<double> cnt((size_t)P->n_cams + 1, 0.0);
+  count_camera_blocks(P, cnt);
+  CameraLayout cams;
+  assign_camera_slots(P, cnt, opt, cams);
+  opt.set_chunk_caps(false, cams.ncv, P->n_obs);
+  LandmarkGroups groups;
+  if (int rc = group_blocks_by_landmark(P, true, groups)) return rc;
+  CamGraph graph;
+  CholPlan plan;
+  if (cams.use_graph) {
+    camera_graph_from_groups(P, groups, cams, graph);
+    plan_camera_order(graph, opt, plan, cams);
+  } else keep_caller_order(cams);
+  HostTables T;
+  if (int rc = build_record_tables(P, cams, opt, groups, T, lap)) return rc;
+  SPattern S;
+  if (cams.use_graph) s_pattern_index(cams, plan, graph, S);
+  else if (int rc = s_pattern_skyline(cams, T, opt, one_rank, false, S, plan)) return rc;
+  SlabTables slabs;
+  if (int rc = assign_slabs(T.chunks, slabs)) return rc;
+  if (int rc = slab_reduction_tables(T, cams, plan, S, true, slabs)) return rc;
+
+  const void* src = nullptr;
+  int64_t bytes = 0;
+  const int64_t nr = T.nrec, nf = T.nfixed;
+  std::vector<int32_t> cam_of_slot;
+  int64_t info[10];
+  const uint8_t on_device = 0;
+  auto vec = [&](const auto& v) { src = v.data(); bytes = (int64_t)(sizeof(v[0]) * v.size()); };
+  switch (which) {
+    case 0: vec(T.chunks); break;
+    case 1: vec(T.chunk_cams); break;
+    case 2: src = T.rec_cam.data(); bytes = 4 * nr; break;
+    case 3: src = T.rec_pt.data(); bytes = 4 * nr; break;
+    case 4: src = T.rec_meta.data(); bytes = 4 * nr; break;
+    case 5: src = T.rec_xy.data(); bytes = 16 * nr; break;
+    case 6: src = T.rec_d.data(); bytes = 8 * nr; break;
+    case 7: src = T.rec_m.data(); bytes = 8 * nr; break;
+    case 8: src = T.rec_a.data(); bytes = 8 * nr; break;
+    case 9: vec(T.pt_rec_start); break;
+    case 10: vec(T.pt_kv); break;
+    case 11: src = T.fx_cam.data(); bytes = 4 * nf; break;
+    case 12: src = T.fx_pt.data(); bytes = 4 * nf; break;
+    case 13: src = T.fx_meta.data(); bytes = 4 * nf; break;
+    case 14: src = T.fx_xy.data(); bytes = 16 * nf; break;
+    case 15: src = T.fx_d.data(); bytes = 8 * nf; break;
+    case 16: src = T.fx_m.data(); bytes = 8 * nf; break;
+    case 17: src = T.fx_a.data(); bytes = 8 * nf; break;
+    case 18: vec(T.order); break;
+    case 19: vec(slabs.dests); break;
+    case 20: vec(slabs.srcs); break;
+    case 21: vec(cams.slot); break;
+    case 22: src = &on_device; bytes = 1; break;
+    case 23: vec(T.blk_desc); break;
+    case 24: vec(T.blk_ent_start); break;
+    case 25: vec(T.ents); break;
+    case 27: vec(T.lhdr); break;
+    case 28: vec(S.sky_index); break;
+    case 29: vec(S.sky_first); break;
+    case 30: vec(S.sky_start); break;
+    case 31: vec(cams.cmask); break;
+    case 32: cam_of_slot = cam_of_slot_table(cams); vec(cam_of_slot); break;
+    case 33: {
+      DenseOverlap ov;
+      LevelPlanDev lp;
+      opt.apply_dense(cams.nt, plan, ov);
+      level_plan_flags(plan, lp);
+      double work = 0.0;
+      dense_plan_numbers(cams.ncv, cams.nt, plan, ov, lp, &work, S.nblk, info);
+      src = info; bytes = 80;
+      break;
+    }
+    default: return fail(MPSFM_EINVAL, "unknown table");
+  }
+  if (!out || cap < bytes) return bytes;
+  if (bytes > 0) std::memcpy(out, src, (size_t)bytes);
   return bytes;
 }
 
@@ -2655,7 +1807,7 @@ int mpsfm_ba_get_reduced_system(mpsfm_ba_handle* h, double* S, double* rhs, int3
   HIP_TRY(hipStreamSynchronize(h->stream));
   const double* Sb = red.data(); const double* gc = Sb + h->sblk_count; const double* wv = gc + h->n_user; const double* dU = wv + h->n_user;
   const mpsfm_ba_options& o = h->opt;
-  const BlockSky sky{h->sky_first.data(), h->sky_start.data(), h->sky_index.empty() ? nullptr : h->sky_index.data(), h->ncv};
+  const BlockSky sky{h->spat.sky_first.data(), h->spat.sky_start.data(), h->spat.sky_index.empty() ? nullptr : h->spat.sky_index.data(), h->ncv};
   for (int R = 0; R < n; ++R)
     for (int C = 0; C < n; ++C) {
       const int br = h->nat_slot[(size_t)(R / 6)], a = R % 6, bc = h->nat_slot[(size_t)(C / 6)], b = C % 6;

@@ -739,7 +739,7 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   lap("flags + three scans + sync");
   const int n_withrec = tot[0], n_fixonly = tot[1], n_fixed = tot[2];
   const int n_order = n_withrec + n_fixonly;
-  out.np = n_order; out.nfixed = n_fixed;
+  out.t.np = n_order; out.t.nfixed = n_fixed;
   // ---- landmark order (see k_candidates)
   const size_t nw = (size_t)std::max(n_withrec, 1);
   unsigned long long *kA = M.alloc<unsigned long long>(nw), *kB = M.alloc<unsigned long long>(nw), *kS = M.alloc<unsigned long long>(nw), *kG = M.alloc<unsigned long long>(nw);
@@ -781,7 +781,7 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   lap("inverse + record offsets + sync");
   const int n_long = cl[2];
   const int np_chunked = n_withrec - n_long;
-  out.np_chunked = np_chunked; out.n_long = n_long; out.nrec = nrec_total;
+  out.t.np_chunked = np_chunked; out.t.n_long = n_long; out.t.nrec = nrec_total;
   if (n_long > 0) return MPSFM_DEVBUILD_FALLBACK;  // long tracks: the host build handles them
   // ---- chunk cut
   const int nseg = (int)std::max<int64_t>(1, std::min<int64_t>(64, np_chunked / 4096));
@@ -864,14 +864,14 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
     DB_TRY(hipStreamSynchronize(M.s));
   }
   out.d_chunk_cams = (int32_t*)own(4 * (size_t)std::max(ncams, 1));
-  out.d_rec_cam = (int32_t*)own(4 * nr); out.d_rec_pt = (int32_t*)own(4 * nr); out.d_rec_meta = (uint32_t*)own(4 * nr);
-  out.d_rec_xy = (double*)own(16 * nr); out.d_rec_d = (double*)own(8 * nr); out.d_rec_m = (double*)own(8 * nr); out.d_rec_a = (double*)own(8 * nr);
-  out.d_pt_rec_start = (int32_t*)own(4 * (no + 1)); out.d_pt_kv = (uint16_t*)own(2 * (no + 1));
-  out.d_fx_cam = (int32_t*)own(4 * nf); out.d_fx_pt = (int32_t*)own(4 * nf); out.d_fx_meta = (uint32_t*)own(4 * nf);
-  out.d_fx_xy = (double*)own(16 * nf); out.d_fx_d = (double*)own(8 * nf); out.d_fx_m = (double*)own(8 * nf); out.d_fx_a = (double*)own(8 * nf);
+  out.rt.rec_cam = (int32_t*)own(4 * nr); out.rt.rec_pt = (int32_t*)own(4 * nr); out.rt.rec_meta = (uint32_t*)own(4 * nr);
+  out.rt.rec_xy = (double*)own(16 * nr); out.rt.rec_d = (double*)own(8 * nr); out.rt.rec_m = (double*)own(8 * nr); out.rt.rec_a = (double*)own(8 * nr);
+  out.rt.pt_rec_start = (int32_t*)own(4 * (no + 1)); out.rt.pt_kv = (uint16_t*)own(2 * (no + 1));
+  out.rt.fx_cam = (int32_t*)own(4 * nf); out.rt.fx_pt = (int32_t*)own(4 * nf); out.rt.fx_meta = (uint32_t*)own(4 * nf);
+  out.rt.fx_xy = (double*)own(16 * nf); out.rt.fx_d = (double*)own(8 * nf); out.rt.fx_m = (double*)own(8 * nf); out.rt.fx_a = (double*)own(8 * nf);
   unsigned long long* counters = M.alloc<unsigned long long>(2);
-  void* all[] = {out.d_chunks, out.d_chunk_cams, out.d_rec_cam, out.d_rec_pt, out.d_rec_meta, out.d_rec_xy, out.d_rec_d, out.d_rec_m, out.d_rec_a, out.d_pt_rec_start,
-                 out.d_pt_kv, out.d_fx_cam, out.d_fx_pt, out.d_fx_meta, out.d_fx_xy, out.d_fx_d, out.d_fx_m, out.d_fx_a, counters};
+  void* all[] = {out.d_chunks, out.d_chunk_cams, out.rt.rec_cam, out.rt.rec_pt, out.rt.rec_meta, out.rt.rec_xy, out.rt.rec_d, out.rt.rec_m, out.rt.rec_a, out.rt.pt_rec_start,
+                 out.rt.pt_kv, out.rt.fx_cam, out.rt.fx_pt, out.rt.fx_meta, out.rt.fx_xy, out.rt.fx_d, out.rt.fx_m, out.rt.fx_a, counters};
   for (void* p : all) if (!p) { (void)hipStreamSynchronize(M.s); out.release(); return dfail(MPSFM_ENOMEM, "hipMalloc failed"); }
   DB_TRY(hipMemsetAsync(counters, 0, 16, M.s));
   if (nchunks > 0 && jump) {
@@ -885,30 +885,30 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
     }
   } else if (nchunks > 0)
     hipLaunchKernelGGL(k_chunks_final, dim3(nseg), dim3(kT), 0, M.s, np_chunked, nseg, tmp_chunks, tmp_cams, rec_off, order, info, cbase, cambase, out.d_chunks, out.d_chunk_cams);
-  RecOut O{out.d_rec_cam, out.d_rec_pt, out.d_rec_meta, out.d_rec_xy, out.d_rec_d, out.d_rec_m, out.d_rec_a, out.d_pt_rec_start, out.d_pt_kv,
-           out.d_fx_cam, out.d_fx_pt, out.d_fx_meta, out.d_fx_xy, out.d_fx_d, out.d_fx_m, out.d_fx_a};
+  RecOut O{out.rt.rec_cam, out.rt.rec_pt, out.rt.rec_meta, out.rt.rec_xy, out.rt.rec_d, out.rt.rec_m, out.rt.rec_a, out.rt.pt_rec_start, out.rt.pt_kv,
+           out.rt.fx_cam, out.rt.fx_pt, out.rt.fx_meta, out.rt.fx_xy, out.rt.fx_d, out.rt.fx_m, out.rt.fx_a};
   if (n_order > 0)
     hipLaunchKernelGGL(k_records, dim3((unsigned)((n_order + kT - 1) / kT)), dim3(kT), 0, M.s, n_order, np_chunked, n_withrec, nrec_total, order, info, M.pstart, M.blk_cam,
                        M.blk_key, M.blk_src, rec_off, fix_off, nchunks, out.d_chunks, out.d_chunk_cams, M.pt_const, M.obs_xy, M.dobs_depth, M.dobs_mag,
                        M.dobs_par, M.shift, O, counters, M.err);
   lap("final tables: allocate, chunks, records");
   // the sentinel entry of pt_rec_start / pt_kv
-  DB_TRY(hipMemcpyAsync(out.d_pt_rec_start + n_order, &nrec_total, 4, hipMemcpyHostToDevice, M.s));
+  DB_TRY(hipMemcpyAsync(out.rt.pt_rec_start + n_order, &nrec_total, 4, hipMemcpyHostToDevice, M.s));
   const uint16_t kv_none = 0xffff;
-  DB_TRY(hipMemcpyAsync(out.d_pt_kv + n_order, &kv_none, 2, hipMemcpyHostToDevice, M.s));
+  DB_TRY(hipMemcpyAsync(out.rt.pt_kv + n_order, &kv_none, 2, hipMemcpyHostToDevice, M.s));
   // ---- to the host: chunk headers, camera lists, the landmark order, counters
-  out.chunks.resize((size_t)nchunks); out.chunk_cams.resize((size_t)ncams); out.order.resize((size_t)n_order);
+  out.t.chunks.resize((size_t)nchunks); out.t.chunk_cams.resize((size_t)ncams); out.t.order.resize((size_t)n_order);
   unsigned long long hc[2] = {0, 0};
   int32_t er[4] = {0, 0, 0, 0};
-  if (nchunks) DB_TRY(hipMemcpyAsync(out.chunks.data(), out.d_chunks, sizeof(ChunkHdr) * (size_t)nchunks, hipMemcpyDeviceToHost, M.s));
-  if (ncams) DB_TRY(hipMemcpyAsync(out.chunk_cams.data(), out.d_chunk_cams, 4 * (size_t)ncams, hipMemcpyDeviceToHost, M.s));
-  if (n_order) DB_TRY(hipMemcpyAsync(out.order.data(), order, 4 * (size_t)n_order, hipMemcpyDeviceToHost, M.s));
+  if (nchunks) DB_TRY(hipMemcpyAsync(out.t.chunks.data(), out.d_chunks, sizeof(ChunkHdr) * (size_t)nchunks, hipMemcpyDeviceToHost, M.s));
+  if (ncams) DB_TRY(hipMemcpyAsync(out.t.chunk_cams.data(), out.d_chunk_cams, 4 * (size_t)ncams, hipMemcpyDeviceToHost, M.s));
+  if (n_order) DB_TRY(hipMemcpyAsync(out.t.order.data(), order, 4 * (size_t)n_order, hipMemcpyDeviceToHost, M.s));
   DB_TRY(hipMemcpyAsync(hc, counters, 16, hipMemcpyDeviceToHost, M.s));
   DB_TRY(hipMemcpyAsync(er, M.err, 16, hipMemcpyDeviceToHost, M.s));
   DB_TRY(hipStreamSynchronize(M.s));
   lap("downloads");
   if (er[0] & 2) { out.release(); return dfail(MPSFM_EINVAL, "shifted/scaled depth prior must be positive"); }
-  out.nblk_reduced = (int64_t)hc[0]; out.nvarpts = (double)hc[1];
+  out.t.nblk_reduced = (int64_t)hc[0]; out.t.nvarpts = (double)hc[1];
   return 0;
 }
 
@@ -965,11 +965,9 @@ int DevBuilder::slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t
 }
 
 void DevBuildOut::release() {
-  void* all[] = {d_chunks, d_chunk_cams, d_rec_cam, d_rec_pt, d_rec_meta, d_rec_xy, d_rec_d, d_rec_m, d_rec_a, d_pt_rec_start, d_pt_kv,
-                 d_fx_cam, d_fx_pt, d_fx_meta, d_fx_xy, d_fx_d, d_fx_m, d_fx_a};
-  for (void* p : all) cached_free(p);
-  d_chunks = nullptr; d_chunk_cams = nullptr; d_rec_cam = d_rec_pt = nullptr; d_rec_meta = nullptr; d_rec_xy = d_rec_d = d_rec_m = d_rec_a = nullptr;
-  d_pt_rec_start = nullptr; d_pt_kv = nullptr; d_fx_cam = d_fx_pt = nullptr; d_fx_meta = nullptr; d_fx_xy = d_fx_d = d_fx_m = d_fx_a = nullptr;
+  cached_free(d_chunks); cached_free(d_chunk_cams);
+  d_chunks = nullptr; d_chunk_cams = nullptr;
+  rt.release();
 }
 
 }  // namespace mpsfm

@@ -1,26 +1,41 @@
-// Device-side table build (build_dev.hip), called from build() in ba_solver.hip.
+// Device-side table build (build_dev.hip): the stages build() in ba_solver.hip runs in place of the host phases of build_host.h.
 #pragma once
 #include <cstdint>
 #include <vector>
 
+#include "build_host.h"
 #include "common.h"
 
 namespace mpsfm {
 
 constexpr int MPSFM_DEVBUILD_FALLBACK = 1;  // stage2: the problem needs the host build (long tracks); nothing was produced
 
+// The record and fixed-record tables on the device (cached_malloc blocks): built there by the device build, uploaded by the host build.
+struct RecTablesDev {
+  int32_t *rec_cam = nullptr, *rec_pt = nullptr;
+  uint32_t* rec_meta = nullptr;
+  double *rec_xy = nullptr, *rec_d = nullptr, *rec_m = nullptr, *rec_a = nullptr;
+  int32_t* pt_rec_start = nullptr;
+  uint16_t* pt_kv = nullptr;
+  // fixed blocks (constant camera and constant landmark)
+  int32_t *fx_cam = nullptr, *fx_pt = nullptr;
+  uint32_t* fx_meta = nullptr;
+  double *fx_xy = nullptr, *fx_d = nullptr, *fx_m = nullptr, *fx_a = nullptr;
+  void release() {
+    for (void* p : {(void*)rec_cam, (void*)rec_pt, (void*)rec_meta, (void*)rec_xy, (void*)rec_d, (void*)rec_m, (void*)rec_a, (void*)pt_rec_start, (void*)pt_kv,
+                    (void*)fx_cam, (void*)fx_pt, (void*)fx_meta, (void*)fx_xy, (void*)fx_d, (void*)fx_m, (void*)fx_a})
+      cached_free(p);
+    *this = RecTablesDev{};
+  }
+};
+
 struct DevBuildOut {
   // device tables, owned by the receiver (cached_malloc blocks)
   ChunkHdr* d_chunks = nullptr;
-  int32_t *d_chunk_cams = nullptr, *d_rec_cam = nullptr, *d_rec_pt = nullptr, *d_pt_rec_start = nullptr, *d_fx_cam = nullptr, *d_fx_pt = nullptr;
-  uint32_t *d_rec_meta = nullptr, *d_fx_meta = nullptr;
-  uint16_t* d_pt_kv = nullptr;
-  double *d_rec_xy = nullptr, *d_rec_d = nullptr, *d_rec_m = nullptr, *d_rec_a = nullptr, *d_fx_xy = nullptr, *d_fx_d = nullptr, *d_fx_m = nullptr, *d_fx_a = nullptr;
-  // host copies of the small tables the rest of build() works on
-  std::vector<ChunkHdr> chunks;
-  std::vector<int32_t> chunk_cams, order;
-  int64_t np = 0, np_chunked = 0, n_long = 0, nrec = 0, nfixed = 0, nblk_reduced = 0;
-  double nvarpts = 0;
+  int32_t* d_chunk_cams = nullptr;
+  RecTablesDev rt;
+  // host copies of the small tables the rest of build() works on: chunks, chunk_cams, order and the counts
+  HostTables t;
   void release();
 };
 

@@ -1,4 +1,4 @@
-"""The device-side table build (csrc/build_dev.hip) against the host-thread build it replaces (`build()` in csrc/ba_solver.hip):
+"""The device-side table build (csrc/build_dev.hip) against the host-thread build it replaces (csrc/build_host.hip):
 every table of two handles created from the same problem — one with MPSFM_DEV_BUILD=0 — compared bit for bit (rec_d = log depth:
 within 2 ulp, the device's log is not libm's), then the solves compared."""
 

@@ -230,7 +230,7 @@ def _run_parts(nparts, reps):
 
 
 def test_table_build_worker_pool_runs_every_part_once():
-    """The persistent workers of the table build (csrc/ba_solver.hip: HostPool): every part of every job exactly once, for
+    """The persistent workers of the table build (csrc/host_parts.h: HostPool): every part of every job exactly once, for
     more parts than workers, for concurrent callers (the second finds the pool busy and starts plain threads) and in a forked
     child (which must not wait for the parent's workers)."""
     import os
@@ -258,7 +258,7 @@ def test_table_build_worker_pool_runs_every_part_once():
 
 
 def test_table_build_host_blocks_are_recycled():
-    """Large host blocks of the table build come back from the process-wide cache (csrc/ba_solver.hip: HostBlockCache);
+    """Large host blocks of the table build come back from the process-wide cache (csrc/host_parts.h: HostBlockCache);
     small ones bypass it."""
     import ctypes as C
 
