@@ -879,6 +879,63 @@ int mpsfm_thin_dense_matches(int64_t n_sparse, const double* sparse0, const doub
 int mpsfm_assign_keypoints(int64_t n_query, const double* query /* [n_query][2] */, int64_t n_kps, const double* kps /* [n_kps][2] */,
                            double max_error, int32_t device, int64_t* ids /* [n_query] */, float* ms /* may be NULL */);
 
+/* ---- descriptors to match lists: mutual nearest neighbours without the n0 x n1 similarity matrix
+ *    (reference: mpsfm/extraction/pairwise/models/nearest_neighbor.py NearestNeighbor / find_nn / mutual_check and
+ *    models/utils/featuremap.py NNs_sparse; the arithmetic contract and the tie rule: DESIGN.md section 4m).
+ *
+ *    Similarities are fp64 dot products of the fp32 (or, sampled, fp64) descriptor values, accumulated with k ascending on
+ *    the matrix pipe; every element goes through the same operation sequence wherever it sits, so identical descriptors give
+ *    bitwise identical similarities.  Nearest neighbour of a row: the maximum similarity, EQUAL SIMILARITIES GOING TO THE
+ *    LOWEST INDEX; second nearest: the maximum over the remaining columns.  Decisions in fp64, every operation rounded on
+ *    its own: dist = 2 (1 - sim); ratio test dist0 <= ratio^2 dist1 (skipped when either side holds a single descriptor);
+ *    distance test dist0 <= distance^2; scores0[i] = (sim0 + 1) / 2 where both tests passed, else 0; matches0[i] = the
+ *    nearest neighbour where both passed, else -1.  mutual_check: matches0[i] is kept only if the same tests in the other
+ *    direction give matches1[matches0[i]] == i; as in the reference scores0 is NOT zeroed for a match only the mutual check
+ *    (or the score threshold) removes.  score_threshold: matches with scores0 < score_threshold become -1 (after the mutual
+ *    check, as NNs_sparse does).  A threshold <= 0 is off.
+ *
+ *    mpsfm_match_map_descriptors: the descriptors are bilinear samples (align_corners, zero padding, fp64 with every operation
+ *    rounded on its own, the keypoint coordinates rounded to float32 first and taken as pixel coordinates) of channel-last
+ *    fp32 maps [H][W][C] at the keypoints; the confidences are sampled the same way.  The samples stay fp64 on the device.
+ *    scores0[i] = sqrt(conf0[i] * conf1[matches0[i]]) for matched rows, else 0.
+ *
+ *    inputs_on_device != 0: desc0 / desc1, or map0 / conf0 / map1 / conf1, are device pointers on `device` (checked).  The
+ *    call records an event on `stream` (a hipStream_t: the stream that produced them) and its own stream waits for it;
+ *    stream == NULL: the inputs must be complete when the call is made.  The library never works on the null stream.
+ *    Keypoints and all outputs are host memory, complete on return; nothing is retained.
+ *
+ *    MPSFM_EINVAL before any device is touched: NULL pointers, negative counts, dim / C outside 1 .. 1024, more than 2^24
+ *    descriptors on a side, H or W < 2, non-finite thresholds, non-finite values in host inputs (device inputs are scanned
+ *    by a kernel: MPSFM_EINVAL after it).  Either side empty: matches0 all -1, scores0 all 0, no device needed.
+ *    MPSFM_ENODEVICE without a device. ---- */
+typedef struct mpsfm_match_options {
+  double ratio_threshold;     /* <= 0: off */
+  double distance_threshold;  /* <= 0: off */
+  double score_threshold;     /* <= 0: off */
+  int32_t mutual_check;
+  int32_t inputs_on_device;
+  void* stream;               /* hipStream_t of the caller, read only with inputs_on_device */
+} mpsfm_match_options;
+
+typedef struct mpsfm_match_info {
+  int64_t num_matches;  /* rows with matches0 >= 0 */
+  float ms;             /* device time from the first kernel to the last (HIP events), transfers excluded */
+  int32_t column_ranges; /* workgroups that shared the columns of one strip of rows (results do not depend on it) */
+} mpsfm_match_info;
+
+/* the reference's defaults: thresholds off, mutual check on, host inputs */
+void mpsfm_match_default_options(mpsfm_match_options* opts);
+
+int mpsfm_match_descriptors(int64_t n0, int64_t n1, int32_t dim, const float* desc0 /* [n0][dim] */, const float* desc1 /* [n1][dim] */,
+                            const mpsfm_match_options* opts /* NULL: defaults */, int32_t device, int32_t* matches0 /* [n0] */,
+                            double* scores0 /* [n0] */, mpsfm_match_info* info /* may be NULL */);
+
+int mpsfm_match_map_descriptors(const float* map0 /* [H0][W0][C] */, const float* conf0 /* [H0][W0] */, int32_t H0, int32_t W0,
+                                const float* map1 /* [H1][W1][C] */, const float* conf1 /* [H1][W1] */, int32_t H1, int32_t W1, int32_t C,
+                                int64_t n0, const double* kps0 /* [n0][2] x, y; host */, int64_t n1, const double* kps1 /* [n1][2] */,
+                                const mpsfm_match_options* opts /* NULL: defaults */, int32_t device, int32_t* matches0 /* [n0] */,
+                                double* scores0 /* [n0] */, mpsfm_match_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

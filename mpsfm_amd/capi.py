@@ -27,6 +27,7 @@ EXPORTS = [
     "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_two_view_geometry", "mpsfm_two_view_geometry_batch",
     "mpsfm_two_view_default_options", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
     "mpsfm_radius_nms", "mpsfm_thin_dense_matches", "mpsfm_assign_keypoints",
+    "mpsfm_match_default_options", "mpsfm_match_descriptors", "mpsfm_match_map_descriptors",
 ]
 
 _lib = None
@@ -937,3 +938,131 @@ def assign_keypoints_ids(query, kps, max_error, device=0, return_ms=False):
     _check(L.mpsfm_assign_keypoints(len(q), q.ctypes.data, len(k), k.ctypes.data, float(max_error), int(device), ids.ctypes.data,
                                     C.addressof(ms)))
     return (ids, float(ms.value)) if return_ms else ids
+
+
+class CMatchOptions(C.Structure):
+    """mpsfm_match_options"""
+    _fields_ = [("ratio_threshold", C.c_double), ("distance_threshold", C.c_double), ("score_threshold", C.c_double),
+                ("mutual_check", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class CMatchInfo(C.Structure):
+    """mpsfm_match_info"""
+    _fields_ = [("num_matches", C.c_int64), ("ms", C.c_float), ("column_ranges", C.c_int32)]
+
+
+def _match_info(I) -> dict:
+    return dict(num_matches=int(I.num_matches), ms=float(I.ms), column_ranges=int(I.column_ranges))
+
+
+def _match_options(ratio_threshold, distance_threshold, score_threshold, do_mutual_check) -> CMatchOptions:
+    o = CMatchOptions()
+    L = lib()
+    L.mpsfm_match_default_options.restype = None
+    L.mpsfm_match_default_options.argtypes = [C.c_void_p]
+    L.mpsfm_match_default_options(C.addressof(o))
+    o.ratio_threshold = float(ratio_threshold or 0.0)
+    o.distance_threshold = float(distance_threshold or 0.0)
+    o.score_threshold = float(score_threshold or 0.0)
+    o.mutual_check = int(bool(do_mutual_check))
+    return o
+
+
+def _on_device(*xs) -> bool:
+    """True when every argument is a torch tensor in device memory (all or none: a mix is a ValueError)."""
+    flags = [type(x).__module__.startswith("torch") and bool(getattr(x, "is_cuda", False)) for x in xs]
+    if any(flags) and not all(flags):
+        raise ValueError("either all arrays are device tensors or none is")
+    return all(flags)
+
+
+def _device_inputs(o: CMatchOptions, tensors, device):
+    """float32, contiguous, on one device; the caller's stream goes into the options.  Returns (tensors, device ordinal): the
+    ordinal is the tensors' own, and a `device` argument that names another one is a ValueError."""
+    import torch
+
+    dev = tensors[0].device
+    if any(t.device != dev for t in tensors):
+        raise ValueError("device tensors on different devices")
+    ordinal = dev.index if dev.index is not None else torch.cuda.current_device()
+    if device is not None and int(device) != ordinal:
+        raise ValueError(f"device={device} but the tensors are on device {ordinal}")
+    for t in tensors:
+        if t.dtype not in (torch.float16, torch.float32):
+            raise TypeError(f"descriptors and maps must be float16 or float32, not {t.dtype}")
+    with torch.cuda.device(dev):
+        out = [t.to(torch.float32).contiguous() for t in tensors]  # enqueued on the current stream, which the call waits for
+        st = torch.cuda.current_stream(dev)
+    o.inputs_on_device = 1
+    if st.cuda_stream:
+        o.stream = st.cuda_stream
+    else:  # the legacy default stream: no stream of the library's ever synchronises with it implicitly
+        st.synchronize()
+        o.stream = None
+    return out, ordinal
+
+
+def _host_f32(a, what) -> np.ndarray:
+    if type(a).__module__.startswith("torch"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype not in (np.float16, np.float32):
+        raise TypeError(f"{what} must be float16 or float32, not {a.dtype}")
+    return np.ascontiguousarray(a, np.float32)
+
+
+_MATCH_DESC_ARGS = [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+_MATCH_MAP_ARGS = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] * 2 + [C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+
+
+def match_descriptors(desc0, desc1, ratio_threshold=None, distance_threshold=None, do_mutual_check=True, score_threshold=None,
+                      device=None, return_info=False):
+    """mpsfm_match_descriptors: desc0 [n0, dim], desc1 [n1, dim], float16 / float32 NumPy arrays, host tensors or device tensors
+    (device tensors go in as device pointers with the caller's current stream).  Returns matches0 int64 [n0] (-1: none),
+    scores0 float64 [n0][, info dict(num_matches, ms, column_ranges)].  `device`: the ordinal for host inputs (default 0); device
+    tensors run on their own device, and naming another one is a ValueError."""
+    o = _match_options(ratio_threshold, distance_threshold, score_threshold, do_mutual_check)
+    if _on_device(desc0, desc1):
+        (a, b), device = _device_inputs(o, [desc0, desc1], device)
+        pa, pb = a.data_ptr(), b.data_ptr()
+    else:
+        a, b = _host_f32(desc0, "desc0"), _host_f32(desc1, "desc1")
+        pa, pb = a.ctypes.data, b.ctypes.data
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("descriptors must be [n0, dim] and [n1, dim]")
+    n0, n1, dim = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+    m, s, I = np.full(max(n0, 1), -1, np.int32), np.zeros(max(n0, 1)), CMatchInfo()
+    L = lib()
+    L.mpsfm_match_descriptors.argtypes = _MATCH_DESC_ARGS
+    _check(L.mpsfm_match_descriptors(n0, n1, dim, pa or None, pb or None, C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data,
+                                     C.addressof(I)))
+    m, s = m[:n0].astype(np.int64), s[:n0]
+    return (m, s, _match_info(I)) if return_info else (m, s)
+
+
+def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=None, ratio_threshold=None, distance_threshold=None,
+                          do_mutual_check=True, device=None, return_info=False):
+    """mpsfm_match_map_descriptors: channel-last maps [H, W, C] and confidences [H, W] (float16 / float32; NumPy, host tensors
+    or device tensors), keypoints [n, 2] (x, y) on the host.  Returns matches0 int64 [n0], scores0 float64 [n0]
+    (sqrt(conf0 conf1) of the matched rows)[, info]."""
+    o = _match_options(ratio_threshold, distance_threshold, score_threshold, do_mutual_check)
+    if _on_device(map0, conf0, map1, conf1):
+        arrs, device = _device_inputs(o, [map0, conf0, map1, conf1], device)
+        ptrs = [t.data_ptr() for t in arrs]
+    else:
+        arrs = [_host_f32(x, w) for x, w in ((map0, "map0"), (conf0, "conf0"), (map1, "map1"), (conf1, "conf1"))]
+        ptrs = [x.ctypes.data for x in arrs]
+    m0, c0, m1, c1 = arrs
+    if m0.ndim != 3 or m1.ndim != 3 or m0.shape[2] != m1.shape[2] or tuple(c0.shape) != tuple(m0.shape[:2]) or tuple(c1.shape) != tuple(m1.shape[:2]):
+        raise ValueError("maps must be [H, W, C] with one C, confidences [H, W]")
+    k0, k1 = _xy(kps0, "kps0"), _xy(kps1, "kps1")
+    n0, n1 = len(k0), len(k1)
+    m, s, I = np.full(max(n0, 1), -1, np.int32), np.zeros(max(n0, 1)), CMatchInfo()
+    L = lib()
+    L.mpsfm_match_map_descriptors.argtypes = _MATCH_MAP_ARGS
+    _check(L.mpsfm_match_map_descriptors(ptrs[0] or None, ptrs[1] or None, int(m0.shape[0]), int(m0.shape[1]), ptrs[2] or None, ptrs[3] or None,
+                                         int(m1.shape[0]), int(m1.shape[1]), int(m0.shape[2]), n0, k0.ctypes.data, n1, k1.ctypes.data,
+                                         C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data, C.addressof(I)))
+    m, s = m[:n0].astype(np.int64), s[:n0]
+    return (m, s, _match_info(I)) if return_info else (m, s)

@@ -1,0 +1,486 @@
+// Descriptors to match lists (mpsfm_match_descriptors, mpsfm_match_map_descriptors; semantics: include/mpsfm_hip.h, the
+// arithmetic contract, the tie rule and the margin bounds: DESIGN.md section 4m).
+//
+//   k_sample_descriptors  bilinear samples of a channel-last map and of its confidence map at the keypoints, fp64
+//   k_sim_top2<T>         similarity tiles on the matrix pipe (v_mfma_f64_16x16x4_f64), a running top-2 per row in registers;
+//                         both directions in one launch, nothing of size n0 x n1 is ever written
+//   k_match_decide        ratio / distance tests, mutual check, score threshold, outputs
+//
+// k_sim_top2: a workgroup of four waves owns a strip of kStrip = 64 rows and streams the columns (all of them, or one of
+// gridDim.z ranges of column tiles when there are too few strips to fill the device) in tiles of 64 and k in
+// slices of kKS staged through LDS (slices are sized from the LDS budget: dim only sets how many there are).  Wave w holds
+// the 16 x 64 band of rows 16 w .. 16 w + 15 as four 16 x 16 accumulators, so all candidates of a row live in the 16 lanes
+// of one wave that share the row in the accumulator layout (row (lane >> 4) + 4 reg, column lane & 15).  Edge tiles are
+// padded with zeros in k, rows and columns and go through the same instructions as full ones; padded columns are never
+// offered as candidates, padded rows never written.
+//
+// Every merge (a lane's own columns, the 16 lanes of a row, column tiles) orders candidates by (value descending, index
+// ascending), a total order on distinct columns: the top-2 does not depend on the order in which candidates arrive.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "call_scope.h"
+#include "common.h"
+#include "bilinear_sample.h"  // contraction off from here on: the decisions round every operation on its own
+
+namespace mpsfm {
+
+namespace {
+constexpr int kStrip = 64;        // rows of a workgroup, columns of a tile
+constexpr int kKS = 32;           // k values of a slice
+constexpr int kLd = 80;           // doubles per k row of a slice in LDS: the four k rows of one MFMA step sit 32 banks apart
+constexpr int kMT = 256;          // threads of k_sim_top2
+constexpr int kDT = 256;          // threads of the element-wise kernels
+constexpr int32_t kMaxDim = 1024;
+constexpr int64_t kMaxDesc = 1 << 24;
+constexpr int32_t kNoIndex = INT32_MAX;
+constexpr int32_t kFillPerCU = 8; // workgroups per compute unit that fill the device: LDS for four at a time, two rounds
+
+struct Top2 { double v1, v2; int32_t i1, i2; };
+
+__device__ __forceinline__ bool before(double v, int32_t i, double w, int32_t j) { return v > w || (v == w && i < j); }
+__device__ __forceinline__ void offer(Top2& t, double v, int32_t i) {
+  if (before(v, i, t.v1, t.i1)) { t.v2 = t.v1; t.i2 = t.i1; t.v1 = v; t.i1 = i; }
+  else if (before(v, i, t.v2, t.i2)) { t.v2 = v; t.i2 = i; }
+}
+
+template <typename T> struct Vec4;
+template <> struct Vec4<float> { typedef float4 type; };
+template <> struct Vec4<double> { typedef double4 type; };
+
+// One slice: s[k][column ^ 8 (k / 4 & 7)] = X[row0 + column][k0 + k], zeros beyond the set and beyond dim.  Thread -> (row, four
+// consecutive k): eight lanes read 32 consecutive k of a row; the XOR spreads their LDS stores over all banks and is the same
+// for the four k rows an MFMA step reads, so the reads stay conflict free.
+template <typename T>
+__device__ __forceinline__ void load_slice(double* __restrict__ s, const T* __restrict__ X, int32_t nrows, int32_t row0, int32_t dim, int32_t k0,
+                                           bool vec) {
+#pragma unroll
+  for (int j = 0; j < kStrip * kKS / 4 / kMT; ++j) {
+    const int e = (int)threadIdx.x + kMT * j;
+    const int kq = e & 7, r = e >> 3;
+    const int32_t row = row0 + r, k = k0 + 4 * kq;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    if (row < nrows && k < dim) {
+      const T* p = X + (size_t)row * (size_t)dim + k;
+      if (vec) {  // dim % 4 == 0 and an aligned base: k + 3 < dim
+        const typename Vec4<T>::type q = *reinterpret_cast<const typename Vec4<T>::type*>(p);
+        v[0] = (double)q.x; v[1] = (double)q.y; v[2] = (double)q.z; v[3] = (double)q.w;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (k + c < dim) v[c] = (double)p[c];
+      }
+    }
+    const int col = r ^ (8 * kq);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s[(4 * kq + c) * kLd + col] = v[c];
+  }
+}
+
+struct SimArgs {
+  const void* X[2];   // descriptor sets 0 and 1, [n][dim]
+  int32_t n[2];
+  int32_t dim;
+  int32_t vec;        // both sets allow 4-wide loads
+  int32_t splits;     // workgroups that share a strip, each streaming its own range of column tiles (gridDim.z)
+  double* val[2];     // [n][splits][2]: top-1 and top-2 similarity of every row of direction d (rows = set d) within a range
+  int32_t* idx[2];    // [n][splits][2]: their columns (kNoIndex: the range held fewer than two)
+};
+
+template <typename T>
+__global__ __launch_bounds__(kMT) void k_sim_top2(SimArgs a) {
+  __shared__ double s_A[kKS * kLd];
+  __shared__ double s_B[kKS * kLd];
+  const int d = (int)blockIdx.y;
+  const int32_t nrows = a.n[d], ncols = a.n[1 - d];
+  const int32_t row0 = (int32_t)blockIdx.x * kStrip;
+  if (row0 >= nrows) return;  // the grid is sized for the larger set
+  const T* R = (const T*)a.X[d];
+  const T* Cc = (const T*)a.X[1 - d];
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+  const bool vec = a.vec != 0;
+
+  Top2 top[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) top[r] = Top2{-INFINITY, -INFINITY, kNoIndex, kNoIndex};
+
+  // this workgroup's range of column tiles; an empty range leaves the sentinels, which every merge ignores
+  const int32_t per = ((ncols + kStrip - 1) / kStrip + a.splits - 1) / a.splits * kStrip;
+  const int64_t cb = (int64_t)blockIdx.z * per;
+  const int32_t col_begin = (int32_t)min(cb, (int64_t)ncols), col_end = (int32_t)min(cb + per, (int64_t)ncols);
+  for (int32_t col0 = col_begin; col0 < col_end; col0 += kStrip) {
+    v4d acc[4];
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[ni] = v4d{0.0, 0.0, 0.0, 0.0};
+    for (int32_t k0 = 0; k0 < a.dim; k0 += kKS) {
+      __syncthreads();  // the previous slice has been read
+      load_slice<T>(s_A, R, nrows, row0, a.dim, k0, vec);
+      load_slice<T>(s_B, Cc, ncols, col0, a.dim, k0, vec);
+      __syncthreads();
+      const int steps = (min(a.dim - k0, kKS) + 3) >> 2;
+      for (int s = 0; s < steps; ++s) {
+        const int x = 8 * (s & 7);
+        const double* pa = s_A + (4 * s + lg) * kLd;
+        const double* pb = s_B + (4 * s + lg) * kLd;
+        const double av = pa[(16 * wave + lr) ^ x];
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, pb[(16 * ni + lr) ^ x], acc[ni], 0, 0, 0);
+      }
+    }
+    // this lane's candidates of the tile: columns col0 + 16 ni + lr, rows lg + 4 r of the band
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      const int32_t col = col0 + 16 * ni + lr;
+      if (col < ncols) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) offer(top[r], acc[ni][r], col);
+      }
+    }
+  }
+  // the 16 lanes that share a row
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) {
+      const double ov1 = __shfl_xor(top[r].v1, m), ov2 = __shfl_xor(top[r].v2, m);
+      const int32_t oi1 = __shfl_xor(top[r].i1, m), oi2 = __shfl_xor(top[r].i2, m);
+      offer(top[r], ov1, oi1);
+      offer(top[r], ov2, oi2);
+    }
+    const int32_t row = row0 + 16 * wave + lg + 4 * r;
+    if (lr == 0 && row < nrows) {
+      const size_t o = 2 * ((size_t)row * a.splits + blockIdx.z);
+      a.val[d][o] = top[r].v1;
+      a.val[d][o + 1] = top[r].v2;
+      a.idx[d][o] = top[r].i1;
+      a.idx[d][o + 1] = top[r].i2;
+    }
+  }
+}
+
+struct DecideArgs {
+  int32_t n0, n1, splits;
+  const double* val[2];
+  const int32_t* idx[2];
+  double ratio2, dist2, score_thr;
+  int32_t use_ratio, use_dist, use_score, mutual;
+  const double* conf0;  // sampled confidences (map entry) or NULL
+  const double* conf1;
+  int32_t* matches;
+  double* scores;
+};
+
+// find_nn for one row: the match or -1, and the score
+__device__ __forceinline__ int32_t nn_of(const DecideArgs& a, int d, int32_t row, double& score) {
+  // the ranges' top-2 lists merge in the same total order: the result is the top-2 over all columns, whatever the split
+  Top2 t{-INFINITY, -INFINITY, kNoIndex, kNoIndex};
+  for (int z = 0; z < a.splits; ++z) {
+    const size_t o = 2 * ((size_t)row * a.splits + z);
+    offer(t, a.val[d][o], a.idx[d][o]);
+    offer(t, a.val[d][o + 1], a.idx[d][o + 1]);
+  }
+  const double s0 = t.v1, s1 = t.v2;
+  const int32_t i0 = t.i1;
+  const int32_t ncols = d ? a.n0 : a.n1;
+  const double d0 = 2.0 * (1.0 - s0), d1 = 2.0 * (1.0 - s1);
+  bool ok = i0 >= 0 && i0 < ncols;
+  if (a.use_ratio) ok = ok && (d0 <= a.ratio2 * d1);
+  if (a.use_dist) ok = ok && (d0 <= a.dist2);
+  score = ok ? (s0 + 1.0) / 2.0 : 0.0;
+  return ok ? i0 : -1;
+}
+
+__global__ __launch_bounds__(kDT) void k_match_decide(DecideArgs a) {
+  const int32_t i = (int32_t)blockIdx.x * kDT + (int32_t)threadIdx.x;
+  if (i >= a.n0) return;
+  double score;
+  int32_t m = nn_of(a, 0, i, score);
+  if (a.mutual && m >= 0) {
+    double unused;
+    if (nn_of(a, 1, m, unused) != i) m = -1;
+  }
+  if (a.use_score && score < a.score_thr) m = -1;
+  if (a.conf0) score = m >= 0 ? sqrt(a.conf0[i] * a.conf1[m]) : 0.0;
+  a.matches[i] = m;
+  a.scores[i] = score;
+}
+
+// bilinear() of bilinear_sample.h on one channel of a channel-last map
+__device__ __forceinline__ double bilinear_channel(const float* __restrict__ map, int H, int W, int C, int c, double x, double y) {
+  const double x0f = floor(x), y0f = floor(y);
+  const double wx1 = x - x0f, wy1 = y - y0f;
+  const double wx0 = 1.0 - wx1, wy0 = 1.0 - wy1;
+  const bool fin = (x0f > -2.0) && (x0f < (double)W + 1.0) && (y0f > -2.0) && (y0f < (double)H + 1.0);
+  if (!fin) return 0.0;
+  const int x0 = (int)x0f, y0 = (int)y0f;
+  double out = 0.0;
+  const double w[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int xi = x0 + (k & 1), yi = y0 + (k >> 1);
+    if (xi >= 0 && xi < W && yi >= 0 && yi < H) {
+      const double term = w[k] * (double)map[((size_t)yi * W + xi) * C + c];
+      out = out + term;
+    }
+  }
+  return out;
+}
+
+// one thread per (keypoint, channel); channel C is the confidence map
+__global__ __launch_bounds__(kDT) void k_sample_descriptors(const float* __restrict__ map, const float* __restrict__ conf, int H, int W, int C,
+                                                            int64_t n, const double* __restrict__ kps, double* __restrict__ desc,
+                                                            double* __restrict__ cs) {
+  const int64_t t = (int64_t)blockIdx.x * kDT + (int64_t)threadIdx.x;
+  const int64_t i = t / (C + 1);
+  const int c = (int)(t - i * (C + 1));
+  if (i >= n) return;
+  const double x = (double)(float)kps[2 * i], y = (double)(float)kps[2 * i + 1];
+  if (c < C) desc[i * C + c] = bilinear_channel(map, H, W, C, c, x, y);
+  else cs[i] = bilinear_channel(conf, H, W, 1, 0, x, y);
+}
+
+__global__ __launch_bounds__(kDT) void k_scan_finite(const float* __restrict__ x, int64_t n, int32_t* __restrict__ bad) {
+  int64_t i = (int64_t)blockIdx.x * kDT + (int64_t)threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kDT;
+  bool b = false;
+  for (; i < n; i += stride) b = b || !isfinite(x[i]);
+  if (b) atomicOr(bad, 1);
+}
+
+inline dim3 blocks_of(int64_t n) { return dim3((unsigned)((n + kDT - 1) / kDT)); }
+bool all_finite(const float* a, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
+bool all_finite(const double* a, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
+// a float32 keypoint coordinate may overflow where the float64 one is finite
+bool kps_ok(const double* k, size_t n) {
+  for (size_t i = 0; i < 2 * n; ++i)
+    if (!std::isfinite(k[i]) || !std::isfinite((float)k[i])) return false;
+  return true;
+}
+
+int check_options(const mpsfm_match_options& o) {
+  if (!std::isfinite(o.ratio_threshold) || !std::isfinite(o.distance_threshold) || !std::isfinite(o.score_threshold))
+    return fail(MPSFM_EINVAL, "non-finite threshold");
+  return 0;
+}
+
+void fill_empty(int64_t n0, int32_t* matches0, double* scores0) {
+  for (int64_t i = 0; i < n0; ++i) { matches0[i] = -1; scores0[i] = 0.0; }
+}
+
+int check_device_pointer(const void* p, int32_t device, const char* what) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+    (void)hipGetLastError();
+    return fail(MPSFM_EINVAL, std::string(what) + " is not device memory of the call's device");
+  }
+  return 0;
+}
+
+// the call's stream waits for what the caller's stream has enqueued so far
+int wait_for_caller(CallScope& A, const mpsfm_match_options& o) {
+  if (!o.inputs_on_device || !o.stream) return 0;
+  hipEvent_t e = nullptr;
+  MPSFM_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t rc = hipEventRecord(e, (hipStream_t)o.stream);
+  if (rc == hipSuccess) rc = hipStreamWaitEvent(A.st, e, 0);
+  (void)hipEventDestroy(e);  // released once the recorded work is done
+  MPSFM_TRY(rc);
+  return 0;
+}
+
+int scan_device(CallScope& A, const float* x, int64_t n, int32_t* d_bad) {
+  const int64_t blocks = std::min<int64_t>((n + kDT - 1) / kDT, 4096);
+  hipLaunchKernelGGL(k_scan_finite, dim3((unsigned)blocks), dim3(kDT), 0, A.st, x, n, d_bad);
+  MPSFM_TRY(hipGetLastError());
+  return 0;
+}
+
+// top-2 in both directions, the decisions and the download; d0 / d1 on the device, conf0 / conf1 device or NULL.  d_bad (may be
+// NULL): the flag of the device scans, read with the outputs.
+template <typename T>
+int match_core(CallScope& A, int32_t device, int32_t n0, int32_t n1, int32_t dim, const T* d0, const T* d1, const double* conf0, const double* conf1,
+               const mpsfm_match_options& o, const int32_t* d_bad, int32_t* matches0, double* scores0, mpsfm_match_info* info) {
+  SimArgs s{};
+  s.X[0] = d0; s.X[1] = d1;
+  s.n[0] = n0; s.n[1] = n1;
+  s.dim = dim;
+  s.vec = (dim % 4 == 0 && ((uintptr_t)d0 % (4 * sizeof(T))) == 0 && ((uintptr_t)d1 % (4 * sizeof(T))) == 0) ? 1 : 0;
+  const int dirs = o.mutual_check ? 2 : 1;
+  const int32_t nmax = dirs == 2 ? std::max(n0, n1) : n0;
+  const int32_t strips = (nmax + kStrip - 1) / kStrip;
+  // a strip per workgroup leaves most of the device idle up to a few thousand descriptors: the column tiles of a strip are
+  // shared out until there are about kFillPerCU workgroups per compute unit
+  const int32_t col_tiles = ((dirs == 2 ? nmax : n1) + kStrip - 1) / kStrip;
+  int cus = 0;
+  MPSFM_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  const int64_t fill = (int64_t)kFillPerCU * std::max(cus, 1), wgs = (int64_t)strips * dirs;
+  s.splits = (int32_t)std::max<int64_t>(1, std::min<int64_t>(col_tiles, (fill + wgs - 1) / wgs));
+  for (int d = 0; d < dirs; ++d) {
+    s.val[d] = A.alloc<double>(2 * (size_t)s.n[d] * s.splits);
+    s.idx[d] = A.alloc<int32_t>(2 * (size_t)s.n[d] * s.splits);
+    if (!s.val[d] || !s.idx[d]) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  }
+  int32_t* d_m = A.alloc<int32_t>((size_t)n0);
+  double* d_s = A.alloc<double>((size_t)n0);
+  if (!d_m || !d_s) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  hipLaunchKernelGGL(k_sim_top2<T>, dim3((unsigned)strips, (unsigned)dirs, (unsigned)s.splits), dim3(kMT), 0, A.st, s);
+  MPSFM_TRY(hipGetLastError());
+  DecideArgs a{};
+  a.n0 = n0; a.n1 = n1; a.splits = s.splits;
+  for (int d = 0; d < 2; ++d) { a.val[d] = s.val[d]; a.idx[d] = s.idx[d]; }
+  a.use_ratio = (o.ratio_threshold > 0.0 && n0 > 1 && n1 > 1) ? 1 : 0;
+  a.use_dist = o.distance_threshold > 0.0 ? 1 : 0;
+  a.use_score = o.score_threshold > 0.0 ? 1 : 0;
+  a.ratio2 = o.ratio_threshold * o.ratio_threshold;
+  a.dist2 = o.distance_threshold * o.distance_threshold;
+  a.score_thr = o.score_threshold;
+  a.mutual = o.mutual_check ? 1 : 0;
+  a.conf0 = conf0; a.conf1 = conf1;
+  a.matches = d_m; a.scores = d_s;
+  hipLaunchKernelGGL(k_match_decide, blocks_of(n0), dim3(kDT), 0, A.st, a);
+  MPSFM_TRY(hipGetLastError());
+  if (int rc = A.end()) return rc;
+  if (d_bad) {
+    int32_t bad = 0;
+    MPSFM_TRY(A.down(&bad, d_bad, sizeof(bad)));
+    if (bad) return fail(MPSFM_EINVAL, "non-finite value in a device input");
+  }
+  MPSFM_TRY(A.down(matches0, d_m, sizeof(int32_t) * (size_t)n0));
+  MPSFM_TRY(A.down(scores0, d_s, sizeof(double) * (size_t)n0));
+  int64_t cnt = 0;
+  for (int32_t i = 0; i < n0; ++i) cnt += matches0[i] >= 0;
+  if (info) { info->num_matches = cnt; info->ms = (float)A.ms; info->column_ranges = s.splits; }
+  return 0;
+}
+}  // namespace
+
+}  // namespace mpsfm
+
+using namespace mpsfm;
+
+extern "C" void mpsfm_match_default_options(mpsfm_match_options* opts) {
+  if (!opts) return;
+  *opts = mpsfm_match_options{};
+  opts->mutual_check = 1;
+}
+
+extern "C" int mpsfm_match_descriptors(int64_t n0, int64_t n1, int32_t dim, const float* desc0, const float* desc1,
+                                       const mpsfm_match_options* opts, int32_t device, int32_t* matches0, double* scores0,
+                                       mpsfm_match_info* info) {
+  if (info) *info = mpsfm_match_info{};
+  mpsfm_match_options o;
+  mpsfm_match_default_options(&o);
+  if (opts) o = *opts;
+  if (n0 < 0 || n1 < 0) return fail(MPSFM_EINVAL, "negative size");
+  if (n0 > kMaxDesc || n1 > kMaxDesc) return fail(MPSFM_EINVAL, "more than 2^24 descriptors");
+  if (dim < 1 || dim > kMaxDim) return fail(MPSFM_EINVAL, "dim must be 1 .. 1024");
+  if ((n0 > 0 && (!desc0 || !matches0 || !scores0)) || (n1 > 0 && !desc1)) return fail(MPSFM_EINVAL, "NULL pointer");
+  if (int rc = check_options(o)) return rc;
+  if (!o.inputs_on_device && (!all_finite(desc0, (size_t)n0 * dim) || !all_finite(desc1, (size_t)n1 * dim)))
+    return fail(MPSFM_EINVAL, "non-finite descriptor value");
+  if (n0 == 0) return 0;
+  if (n1 == 0) { fill_empty(n0, matches0, scores0); return 0; }
+  if (int rc = open_device(device)) return rc;
+  CallScope A;
+  if (int rc = A.open(true)) return rc;
+  const float *d0 = desc0, *d1 = desc1;
+  int32_t* d_bad = nullptr;
+  if (o.inputs_on_device) {
+    if (int rc = check_device_pointer(desc0, device, "desc0")) return rc;
+    if (int rc = check_device_pointer(desc1, device, "desc1")) return rc;
+    if (int rc = wait_for_caller(A, o)) return rc;
+    d_bad = A.alloc<int32_t>(1);
+    if (!d_bad) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+    MPSFM_TRY(hipMemsetAsync(d_bad, 0, sizeof(int32_t), A.st));
+  } else {
+    d0 = A.put(desc0, (size_t)n0 * dim);
+    d1 = A.put(desc1, (size_t)n1 * dim);
+    if (!d0 || !d1) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  }
+  if (int rc = A.begin()) return rc;
+  if (d_bad) {
+    if (int rc = scan_device(A, d0, n0 * dim, d_bad)) return rc;
+    if (int rc = scan_device(A, d1, n1 * dim, d_bad)) return rc;
+  }
+  return match_core<float>(A, device, (int32_t)n0, (int32_t)n1, dim, d0, d1, nullptr, nullptr, o, d_bad, matches0, scores0, info);
+}
+
+extern "C" int mpsfm_match_map_descriptors(const float* map0, const float* conf0, int32_t H0, int32_t W0, const float* map1, const float* conf1,
+                                           int32_t H1, int32_t W1, int32_t C, int64_t n0, const double* kps0, int64_t n1, const double* kps1,
+                                           const mpsfm_match_options* opts, int32_t device, int32_t* matches0, double* scores0,
+                                           mpsfm_match_info* info) {
+  if (info) *info = mpsfm_match_info{};
+  mpsfm_match_options o;
+  mpsfm_match_default_options(&o);
+  if (opts) o = *opts;
+  if (n0 < 0 || n1 < 0) return fail(MPSFM_EINVAL, "negative size");
+  if (n0 > kMaxDesc || n1 > kMaxDesc) return fail(MPSFM_EINVAL, "more than 2^24 keypoints");
+  if (C < 1 || C > kMaxDim) return fail(MPSFM_EINVAL, "C must be 1 .. 1024");
+  if (H0 < 2 || W0 < 2 || H1 < 2 || W1 < 2) return fail(MPSFM_EINVAL, "a map needs at least 2 rows and 2 columns");
+  if (!map0 || !conf0 || !map1 || !conf1) return fail(MPSFM_EINVAL, "NULL pointer");
+  if ((n0 > 0 && (!kps0 || !matches0 || !scores0)) || (n1 > 0 && !kps1)) return fail(MPSFM_EINVAL, "NULL pointer");
+  if (int rc = check_options(o)) return rc;
+  if (!kps_ok(kps0, (size_t)n0) || !kps_ok(kps1, (size_t)n1)) return fail(MPSFM_EINVAL, "non-finite keypoint");
+  const size_t px0 = (size_t)H0 * (size_t)W0, px1 = (size_t)H1 * (size_t)W1;
+  if (!o.inputs_on_device && (!all_finite(map0, px0 * C) || !all_finite(conf0, px0) || !all_finite(map1, px1 * C) || !all_finite(conf1, px1)))
+    return fail(MPSFM_EINVAL, "non-finite map value");
+  if (n0 == 0) return 0;
+  if (n1 == 0) { fill_empty(n0, matches0, scores0); return 0; }
+  if (int rc = open_device(device)) return rc;
+  CallScope A;
+  if (int rc = A.open(true)) return rc;
+  const float* m[2] = {map0, map1};
+  const float* c[2] = {conf0, conf1};
+  const size_t px[2] = {px0, px1};
+  int32_t* d_bad = nullptr;
+  if (o.inputs_on_device) {
+    for (int s = 0; s < 2; ++s) {
+      if (int rc = check_device_pointer(m[s], device, s ? "map1" : "map0")) return rc;
+      if (int rc = check_device_pointer(c[s], device, s ? "conf1" : "conf0")) return rc;
+    }
+    if (int rc = wait_for_caller(A, o)) return rc;
+    d_bad = A.alloc<int32_t>(1);
+    if (!d_bad) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+    MPSFM_TRY(hipMemsetAsync(d_bad, 0, sizeof(int32_t), A.st));
+  } else {
+    for (int s = 0; s < 2; ++s) {
+      m[s] = A.put(m[s], px[s] * C);
+      c[s] = A.put(c[s], px[s]);
+      if (!m[s] || !c[s]) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+    }
+  }
+  const int64_t n[2] = {n0, n1};
+  const double* kh[2] = {kps0, kps1};
+  const int32_t H[2] = {H0, H1}, W[2] = {W0, W1};
+  double* desc[2];
+  double* cs[2];
+  const double* kd[2];
+  for (int s = 0; s < 2; ++s) {
+    kd[s] = A.put(kh[s], 2 * (size_t)n[s]);
+    desc[s] = A.alloc<double>((size_t)n[s] * C);
+    cs[s] = A.alloc<double>((size_t)n[s]);
+    if (!kd[s] || !desc[s] || !cs[s]) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  }
+  if (int rc = A.begin()) return rc;
+  for (int s = 0; s < 2; ++s) {
+    if (d_bad) {
+      if (int rc = scan_device(A, m[s], (int64_t)(px[s] * C), d_bad)) return rc;
+      if (int rc = scan_device(A, c[s], (int64_t)px[s], d_bad)) return rc;
+    }
+    hipLaunchKernelGGL(k_sample_descriptors, blocks_of(n[s] * (C + 1)), dim3(kDT), 0, A.st, m[s], c[s], H[s], W[s], C, n[s], kd[s], desc[s], cs[s]);
+    MPSFM_TRY(hipGetLastError());
+  }
+  return match_core<double>(A, device, (int32_t)n0, (int32_t)n1, C, desc[0], desc[1], cs[0], cs[1], o, d_bad, matches0, scores0, info);
+}
