@@ -936,6 +936,85 @@ int mpsfm_match_map_descriptors(const float* map0 /* [H0][W0][C] */, const float
                                 const mpsfm_match_options* opts /* NULL: defaults */, int32_t device, int32_t* matches0 /* [n0] */,
                                 double* scores0 /* [n0] */, mpsfm_match_info* info /* may be NULL */);
 
+/* ---- a dense matcher's warp to match lists: the post-network half of the reference's RoMa matcher
+ *    (mpsfm/extraction/pairwise/models/roma.py:82-124 with models/utils/warp.py simple_nms, kpids_to_matches0,
+ *    get_unique_matches, matches_to_matches0, assign_keypoints; contract, tie rule and kernels: DESIGN.md section 4n).
+ *    Every decision below is a comparison of input values or of values rounded operation by operation: results are exact
+ *    and do not depend on how the device schedules the work.
+ *
+ *    mpsfm_simple_nms: out = simple_nms(scores, radius) of a float32 map [H][W].  With pool(x)[i][j] the maximum of x over
+ *    |di| <= radius, |dj| <= radius inside the map:  m = (s == pool(s));  twice { supp = any m in the window;
+ *    ss = supp ? 0 : s;  m |= (ss == pool(ss)) & !supp };  out = m ? s : 0.  A plateau of equal values keeps all its pixels,
+ *    radius 0 keeps everything, negative scores meet the zeros of suppressed pixels as they do in the reference.  The result
+ *    is bitwise torch's.  inputs_on_device != 0: scores AND out are device pointers (overlapping ranges are MPSFM_EINVAL), else
+ *    both are host memory.
+ *
+ *    mpsfm_kpids_to_matches0: a row i is valid when ids0[i] >= 0 and ids1[i] >= 0.  A valid row is kept iff it has the
+ *    highest score among the valid rows with its ids0 AND among the valid rows with its ids1; EQUAL SCORES GO TO THE LOWEST
+ *    ROW (-0.0 counts as +0.0; the reference's choice among equal scores is an accident of an unstable np.argsort).  For
+ *    kept rows matches0[ids0] = ids1 and scores0[ids0] = score, elsewhere -1 and 0.  *n_kps0 = 1 + the largest ids0 of a
+ *    kept row, 0 when none is kept: the LENGTH OF THE REFERENCE'S OUTPUT, which is not the number of keypoints.
+ *    inputs_on_device != 0: ids0, ids1 and scores are device pointers; the outputs are host memory.
+ *
+ *    mpsfm_warp_matches: both legs of Roma._forward for one pair, selected by `mode` (MPSFM_WARP_DENSE | MPSFM_WARP_SPARSE).
+ *    certainty [H][W] and warp [H W][4] = (xA, yA, xB, yB) in normalised coordinates, float32.  Pixel coordinates are
+ *    px = fl32(fl32(W_img / 2) * fl32(x + 1)), py = fl32(fl32(H_img / 2) * fl32(y + 1)), each operation rounded on its own:
+ *    what torch computes for `W / 2 * (coords[..., 0] + 1)` on a float32 tensor.  The formula is RoMa's to_pixel_coordinates,
+ *    third-party code that is not part of the reference tree: it is TAKEN AS THE CONTRACT here, not pinned to RoMa's source.
+ *      dense leg   the rows whose simple_nms(certainty, nms_radius) value is strictly greater than fl32(sample_thresh), in
+ *                  row order: dkeypoints0 / dkeypoints1 [n_dense][2] pixels, dscores [n_dense] (capacity H W each).
+ *      sparse leg  for EVERY row id0 = the keypoint of skpts0 nearest to (fp64(px_A) scale0[0], fp64(py_A) scale0[1]) and
+ *                  strictly closer than max_error, as mpsfm_assign_keypoints decides it (lowest index among equidistant
+ *                  ones); id1 the same with skpts1, scale1 and (px_B, py_B); then mpsfm_kpids_to_matches0 with the raw
+ *                  certainty as score: smatches0 / sscores0 [n_s0], *n_kps0.
+ *    skpts* and scale* are host memory, all outputs are host memory and complete on return; nothing is retained.
+ *
+ *    inputs_on_device / stream: as for mpsfm_match_options (an event is recorded on `stream` and the call's own stream waits
+ *    for it; the library never works on the null stream).
+ *
+ *    MPSFM_EINVAL before any device is touched: NULL pointers, H or W < 1, H W or n above 2^27, negative counts, radius
+ *    outside 0 .. 64, ids >= n0 / n1 or < -1, image sizes < 1, a mode without a leg, non-finite or negative max_error,
+ *    a sample_thresh that is not finite as float32, non-finite scales, keypoints or host map / warp / score values, device
+ *    ranges of scores and out that overlap.  Device inputs are scanned by a kernel: MPSFM_EINVAL after it.  No rows, no valid row among host rows, or (sparse leg) no keypoints on a side: all -1 / 0 /
+ *    count 0 without a device.
+ *    MPSFM_ENODEVICE without a device. ---- */
+#define MPSFM_WARP_DENSE 1
+#define MPSFM_WARP_SPARSE 2
+
+typedef struct mpsfm_warp_options {
+  double sample_thresh;  /* dense leg */
+  double max_error;      /* sparse leg */
+  double scale0[2];
+  double scale1[2];
+  int32_t nms_radius;    /* dense leg */
+  int32_t inputs_on_device;
+  void* stream;          /* hipStream_t of the caller, read only with inputs_on_device */
+} mpsfm_warp_options;
+
+typedef struct mpsfm_warp_info {
+  int64_t num_dense;    /* rows the dense leg selected */
+  int64_t num_valid;    /* rows with both ids >= 0 */
+  int64_t num_matches;  /* rows kept by the unique-match rule */
+  float ms;             /* device time from the first kernel to the last (HIP events), transfers excluded */
+  int32_t reserved;
+} mpsfm_warp_info;
+
+/* the reference's default_conf: sample_thresh 0.1, nms_radius 8, max_error 2, scales 1, host inputs */
+void mpsfm_warp_default_options(mpsfm_warp_options* opts);
+
+int mpsfm_simple_nms(int32_t H, int32_t W, const float* scores /* [H][W] */, int32_t radius, int32_t inputs_on_device, void* stream,
+                     int32_t device, float* out /* [H][W] */, mpsfm_warp_info* info /* may be NULL: ms */);
+
+int mpsfm_kpids_to_matches0(int64_t n, const int64_t* ids0, const int64_t* ids1 /* [n], -1: none */, const float* scores /* [n] */,
+                            int64_t n0, int64_t n1 /* ids0 < n0, ids1 < n1 */, int32_t inputs_on_device, void* stream, int32_t device,
+                            int32_t* matches0 /* [n0] */, float* scores0 /* [n0] */, int64_t* n_kps0, mpsfm_warp_info* info /* may be NULL */);
+
+int mpsfm_warp_matches(int32_t H, int32_t W, const float* certainty /* [H][W] */, const float* warp /* [H W][4] */, int32_t H_A, int32_t W_A,
+                       int32_t H_B, int32_t W_B, int32_t mode, const mpsfm_warp_options* opts /* NULL: defaults */,
+                       int64_t n_s0, const double* skpts0 /* [n_s0][2], host */, int64_t n_s1, const double* skpts1 /* [n_s1][2], host */,
+                       int32_t device, float* dkeypoints0, float* dkeypoints1 /* [H W][2] */, float* dscores /* [H W] */, int64_t* n_dense,
+                       int32_t* smatches0 /* [n_s0] */, float* sscores0 /* [n_s0] */, int64_t* n_kps0, mpsfm_warp_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

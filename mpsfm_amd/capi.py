@@ -28,6 +28,7 @@ EXPORTS = [
     "mpsfm_two_view_default_options", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
     "mpsfm_radius_nms", "mpsfm_thin_dense_matches", "mpsfm_assign_keypoints",
     "mpsfm_match_default_options", "mpsfm_match_descriptors", "mpsfm_match_map_descriptors",
+    "mpsfm_warp_default_options", "mpsfm_simple_nms", "mpsfm_kpids_to_matches0", "mpsfm_warp_matches",
 ]
 
 _lib = None
@@ -976,8 +977,10 @@ def _on_device(*xs) -> bool:
     return all(flags)
 
 
-def _device_inputs(o: CMatchOptions, tensors, device):
-    """float32, contiguous, on one device; the caller's stream goes into the options.  Returns (tensors, device ordinal): the
+def _device_inputs(o, tensors, device):
+    """float32, contiguous, on one device; the caller's stream goes into the options `o` (CMatchOptions or CWarpOptions: both have
+    inputs_on_device and stream).  Every conversion is enqueued BEFORE the stream is taken or synchronised, so a caller that converts
+    further tensors itself does so before this call.  Returns (tensors, device ordinal): the
     ordinal is the tensors' own, and a `device` argument that names another one is a ValueError."""
     import torch
 
@@ -989,7 +992,7 @@ def _device_inputs(o: CMatchOptions, tensors, device):
         raise ValueError(f"device={device} but the tensors are on device {ordinal}")
     for t in tensors:
         if t.dtype not in (torch.float16, torch.float32):
-            raise TypeError(f"descriptors and maps must be float16 or float32, not {t.dtype}")
+            raise TypeError(f"device tensors must be float16 or float32, not {t.dtype}")
     with torch.cuda.device(dev):
         out = [t.to(torch.float32).contiguous() for t in tensors]  # enqueued on the current stream, which the call waits for
         st = torch.cuda.current_stream(dev)
@@ -1066,3 +1069,179 @@ def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=
                                          C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data, C.addressof(I)))
     m, s = m[:n0].astype(np.int64), s[:n0]
     return (m, s, _match_info(I)) if return_info else (m, s)
+
+
+class CWarpOptions(C.Structure):
+    """mpsfm_warp_options"""
+    _fields_ = [("sample_thresh", C.c_double), ("max_error", C.c_double), ("scale0", C.c_double * 2), ("scale1", C.c_double * 2),
+                ("nms_radius", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class CWarpInfo(C.Structure):
+    """mpsfm_warp_info"""
+    _fields_ = [("num_dense", C.c_int64), ("num_valid", C.c_int64), ("num_matches", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+
+def _warp_info(I) -> dict:
+    return dict(num_dense=int(I.num_dense), num_valid=int(I.num_valid), num_matches=int(I.num_matches), ms=float(I.ms))
+
+
+WARP_DENSE, WARP_SPARSE = 1, 2
+_SIMPLE_NMS_ARGS = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+_KPIDS_ARGS = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+               C.c_void_p, C.c_void_p]
+_WARP_ARGS = ([C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
+              + [C.c_void_p] * 8)
+
+
+def _warp_options(**kw) -> CWarpOptions:
+    o = CWarpOptions()
+    L = lib()
+    L.mpsfm_warp_default_options.restype = None
+    L.mpsfm_warp_default_options.argtypes = [C.c_void_p]
+    L.mpsfm_warp_default_options(C.addressof(o))
+    for k, v in kw.items():
+        if k in ("scale0", "scale1"):
+            v = np.asarray(v, np.float64).reshape(-1)
+            if v.shape != (2,):
+                raise ValueError(f"{k} must hold two values")
+            setattr(o, k, (C.c_double * 2)(float(v[0]), float(v[1])))
+        else:
+            setattr(o, k, int(v) if k == "nms_radius" else float(v))
+    return o
+
+
+def simple_nms_map(scores, radius, device=None, return_info=False):
+    """mpsfm_simple_nms: the reference's simple_nms of a 2-D float16 / float32 map, bitwise torch's.  A device tensor gives a float32
+    device tensor (the map never leaves the device), anything else a float32 NumPy array.  [, info dict(..., ms)]."""
+    o, I = CWarpOptions(), CWarpInfo()
+    L = lib()
+    L.mpsfm_simple_nms.argtypes = _SIMPLE_NMS_ARGS
+    if _on_device(scores):
+        import torch
+
+        (s,), device = _device_inputs(o, [scores], device)
+        if s.ndim != 2:
+            raise ValueError("scores must be a 2-D map")
+        if s.numel() == 0:
+            return (s.clone(), _warp_info(I)) if return_info else s.clone()
+        out = torch.empty_like(s)
+        _check(L.mpsfm_simple_nms(int(s.shape[0]), int(s.shape[1]), s.data_ptr(), int(radius), 1, o.stream, int(device), out.data_ptr(), C.addressof(I)))
+    else:
+        s = _host_f32(scores, "scores")
+        if s.ndim != 2:
+            raise ValueError("scores must be a 2-D map")
+        if s.size == 0:
+            return (s.copy(), _warp_info(I)) if return_info else s.copy()
+        out = np.empty_like(s)
+        _check(L.mpsfm_simple_nms(int(s.shape[0]), int(s.shape[1]), s.ctypes.data, int(radius), 0, None, int(device or 0), out.ctypes.data,
+                                  C.addressof(I)))
+    return (out, _warp_info(I)) if return_info else out
+
+
+def _host_scores_f32(a) -> np.ndarray:
+    """float32 [n]; float64 values are taken only when float32 holds them exactly (a rounding could create ties)"""
+    if type(a).__module__.startswith("torch"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a).reshape(-1)
+    if a.dtype == np.float64:
+        b = a.astype(np.float32)
+        if not np.array_equal(b.astype(np.float64), a, equal_nan=True):
+            raise TypeError("float64 scores that float32 does not hold exactly")
+        return np.ascontiguousarray(b)
+    if a.dtype not in (np.float16, np.float32):
+        raise TypeError(f"scores must be float16 or float32, not {a.dtype}")
+    return np.ascontiguousarray(a, np.float32)
+
+
+def _host_ids(a) -> np.ndarray:
+    """int64 [n]; anything but integers is refused (a float id would be truncated silently)"""
+    if type(a).__module__.startswith("torch"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a).reshape(-1)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"keypoint ids must be integers, not {a.dtype}")
+    return np.ascontiguousarray(a, np.int64)
+
+
+def kpids_to_matches0_arrays(ids0, ids1, scores, n0=None, n1=None, device=0, return_info=False):
+    """mpsfm_kpids_to_matches0: ids int [n] (-1: none), scores float16 / float32 [n]; host arrays, or device tensors (all three).  n0 / n1: the numbers of
+    keypoints (default: 1 + the largest id).  Returns matches0 int32 [n_kps0], scores0 float32 [n_kps0] with the reference's
+    length n_kps0 = 1 + the largest matched ids0 [, info dict(num_valid, num_matches, ms, ...)]."""
+    on_device, stream = _on_device(ids0, ids1, scores), None
+    if on_device:  # int64 ids and float32 scores, contiguous, on one device
+        import torch
+
+        if ids0.device != scores.device or ids1.device != scores.device:
+            raise ValueError("device tensors on different devices")
+        if any(t.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64) for t in (ids0, ids1)):
+            raise TypeError(f"keypoint ids must be integers, not {ids0.dtype} / {ids1.dtype}")
+        with torch.cuda.device(scores.device):  # the ids first: whatever a conversion enqueues lies in front of the point the call waits for
+            a, b = (t.reshape(-1).to(torch.int64).contiguous() for t in (ids0, ids1))
+        o = CWarpOptions()
+        (s,), device = _device_inputs(o, [scores.reshape(-1)], device or None)  # converts, then takes (or synchronises) the stream
+        stream = o.stream
+        pa, pb, ps = a.data_ptr(), b.data_ptr(), s.data_ptr()
+    else:
+        a, b = _host_ids(ids0), _host_ids(ids1)
+        s = _host_scores_f32(scores)
+        pa, pb, ps = a.ctypes.data, b.ctypes.data, s.ctypes.data
+    if not (len(a) == len(b) == len(s)):
+        raise ValueError("ids0, ids1 and scores differ in length")
+    n = len(a)
+    n0 = int(n0) if n0 is not None else (int(a.max()) + 1 if n else 0)
+    n1 = int(n1) if n1 is not None else (int(b.max()) + 1 if n else 0)
+    m, sc, nk, I = np.full(max(n0, 1), -1, np.int32), np.zeros(max(n0, 1), np.float32), C.c_int64(0), CWarpInfo()
+    L = lib()
+    L.mpsfm_kpids_to_matches0.argtypes = _KPIDS_ARGS
+    _check(L.mpsfm_kpids_to_matches0(n, pa or None, pb or None, ps or None, n0, n1, int(on_device), stream, int(device or 0), m.ctypes.data,
+                                     sc.ctypes.data, C.addressof(nk), C.addressof(I)))
+    k = int(nk.value)
+    return (m[:k], sc[:k], _warp_info(I)) if return_info else (m[:k], sc[:k])
+
+
+def warp_matches(warp, certainty, sizes, mode=WARP_DENSE | WARP_SPARSE, skpts0=None, skpts1=None, scale0=(1.0, 1.0), scale1=(1.0, 1.0),
+                 nms_radius=8, sample_thresh=0.1, max_error=2.0, device=None, return_info=False):
+    """mpsfm_warp_matches: certainty [H, W] and warp [H, W, 4] or [H W, 4] (float16 / float32; NumPy, host tensors or device tensors
+    that stay on the device), sizes = (H_A, W_A, H_B, W_B).  Returns a dict with dkeypoints0 / dkeypoints1 float32 [n, 2] and dscores
+    float32 [n] (dense leg), smatches0 int32 [n_kps0] and smatching_scores0 float32 [n_kps0] (sparse leg) [, info]."""
+    mode = int(mode)
+    o = _warp_options(scale0=scale0, scale1=scale1, nms_radius=nms_radius, sample_thresh=sample_thresh, max_error=max_error)
+    if _on_device(warp, certainty):
+        (w, c), device = _device_inputs(o, [warp, certainty], device)
+        pw, pc = w.data_ptr(), c.data_ptr()
+    else:
+        w, c = _host_f32(warp, "warp"), _host_f32(certainty, "certainty")
+        pw, pc = w.ctypes.data, c.ctypes.data
+    if c.ndim != 2 or w.shape[-1] != 4 or int(np.prod(w.shape[:-1])) != int(c.shape[0]) * int(c.shape[1]):
+        raise ValueError("certainty must be [H, W] and warp [H, W, 4] or [H W, 4]")
+    H, W = int(c.shape[0]), int(c.shape[1])
+    px = H * W
+    HA, WA, HB, WB = (int(v) for v in sizes)
+    dense, sparse = bool(mode & WARP_DENSE), bool(mode & WARP_SPARSE)
+    k0 = _xy(np.zeros((0, 2)) if skpts0 is None else skpts0, "skpts0")
+    k1 = _xy(np.zeros((0, 2)) if skpts1 is None else skpts1, "skpts1")
+    out, I = {}, CWarpInfo()
+    if px == 0:
+        if dense:
+            out.update(dkeypoints0=np.zeros((0, 2), np.float32), dkeypoints1=np.zeros((0, 2), np.float32), dscores=np.zeros(0, np.float32))
+        if sparse:
+            out.update(smatches0=np.zeros(0, np.int32), smatching_scores0=np.zeros(0, np.float32))
+        return (out, _warp_info(I)) if return_info else out
+    d0 = np.empty((px if dense else 1, 2), np.float32)
+    d1 = np.empty((px if dense else 1, 2), np.float32)
+    ds = np.empty(px if dense else 1, np.float32)
+    m, sc = np.full(max(len(k0), 1), -1, np.int32), np.zeros(max(len(k0), 1), np.float32)
+    nd, nk = C.c_int64(0), C.c_int64(0)
+    L = lib()
+    L.mpsfm_warp_matches.argtypes = _WARP_ARGS
+    _check(L.mpsfm_warp_matches(H, W, pc, pw, HA, WA, HB, WB, mode, C.addressof(o), len(k0), k0.ctypes.data, len(k1), k1.ctypes.data,
+                                int(device or 0), d0.ctypes.data, d1.ctypes.data, ds.ctypes.data, C.addressof(nd), m.ctypes.data, sc.ctypes.data,
+                                C.addressof(nk), C.addressof(I)))
+    if dense:
+        k = int(nd.value)
+        out.update(dkeypoints0=d0[:k].copy(), dkeypoints1=d1[:k].copy(), dscores=ds[:k].copy())
+    if sparse:
+        k = int(nk.value)
+        out.update(smatches0=m[:k].copy(), smatching_scores0=sc[:k].copy())
+    return (out, _warp_info(I)) if return_info else out

@@ -111,4 +111,26 @@ struct CallScope {
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+// ---- inputs that are already on the device (the inputs_on_device / stream convention of include/mpsfm_hip.h)
+inline int check_device_pointer(const void* p, int32_t device, const char* what) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+    (void)hipGetLastError();
+    return fail(MPSFM_EINVAL, std::string(what) + " is not device memory of the call's device");
+  }
+  return 0;
+}
+
+// the call's stream waits for what the caller's stream has enqueued so far (stream == NULL: the inputs are complete)
+inline int wait_for_caller(CallScope& A, void* stream) {
+  if (!stream) return 0;
+  hipEvent_t e = nullptr;
+  MPSFM_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t rc = hipEventRecord(e, (hipStream_t)stream);
+  if (rc == hipSuccess) rc = hipStreamWaitEvent(A.st, e, 0);
+  (void)hipEventDestroy(e);  // released once the recorded work is done
+  MPSFM_TRY(rc);
+  return 0;
+}
+
 }  // namespace mpsfm

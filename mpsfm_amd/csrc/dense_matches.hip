@@ -149,18 +149,7 @@ __global__ __launch_bounds__(kT) void k_thin_select(int32_t n, int32_t ns, int32
 __global__ __launch_bounds__(kT) void k_assign(PointGrid g, int64_t nq, const double* __restrict__ query, double e2, int64_t* __restrict__ ids) {
   const int64_t i = (int64_t)blockIdx.x * kT + (int64_t)threadIdx.x;
   if (i >= nq) return;
-  const double x = query[2 * i], y = query[2 * i + 1];
-  double best = e2;
-  int32_t id = -1;
-  grid_visit_query(g, x, y, [&](int32_t q) {
-    const double2 w = g.xy[q];
-    const double d2 = grid_d2(x, y, w.x, w.y);
-    if (!(d2 < e2)) return true;
-    const int32_t k = g.perm[q];
-    if (id < 0 || d2 < best || (d2 == best && k < id)) { best = d2; id = k; }
-    return true;
-  });
-  ids[i] = id;
+  ids[i] = grid_nearest(g, query[2 * i], query[2 * i + 1], e2);
 }
 
 inline dim3 blocks_of(int64_t n) { return dim3((unsigned)((n + kT - 1) / kT)); }

@@ -279,27 +279,6 @@ void fill_empty(int64_t n0, int32_t* matches0, double* scores0) {
   for (int64_t i = 0; i < n0; ++i) { matches0[i] = -1; scores0[i] = 0.0; }
 }
 
-int check_device_pointer(const void* p, int32_t device, const char* what) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
-    (void)hipGetLastError();
-    return fail(MPSFM_EINVAL, std::string(what) + " is not device memory of the call's device");
-  }
-  return 0;
-}
-
-// the call's stream waits for what the caller's stream has enqueued so far
-int wait_for_caller(CallScope& A, const mpsfm_match_options& o) {
-  if (!o.inputs_on_device || !o.stream) return 0;
-  hipEvent_t e = nullptr;
-  MPSFM_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  hipError_t rc = hipEventRecord(e, (hipStream_t)o.stream);
-  if (rc == hipSuccess) rc = hipStreamWaitEvent(A.st, e, 0);
-  (void)hipEventDestroy(e);  // released once the recorded work is done
-  MPSFM_TRY(rc);
-  return 0;
-}
-
 int scan_device(CallScope& A, const float* x, int64_t n, int32_t* d_bad) {
   const int64_t blocks = std::min<int64_t>((n + kDT - 1) / kDT, 4096);
   hipLaunchKernelGGL(k_scan_finite, dim3((unsigned)blocks), dim3(kDT), 0, A.st, x, n, d_bad);
@@ -400,7 +379,7 @@ extern "C" int mpsfm_match_descriptors(int64_t n0, int64_t n1, int32_t dim, cons
   if (o.inputs_on_device) {
     if (int rc = check_device_pointer(desc0, device, "desc0")) return rc;
     if (int rc = check_device_pointer(desc1, device, "desc1")) return rc;
-    if (int rc = wait_for_caller(A, o)) return rc;
+    if (int rc = wait_for_caller(A, o.stream)) return rc;
     d_bad = A.alloc<int32_t>(1);
     if (!d_bad) return fail(MPSFM_ENOMEM, "hipMalloc failed");
     MPSFM_TRY(hipMemsetAsync(d_bad, 0, sizeof(int32_t), A.st));
@@ -450,7 +429,7 @@ extern "C" int mpsfm_match_map_descriptors(const float* map0, const float* conf0
       if (int rc = check_device_pointer(m[s], device, s ? "map1" : "map0")) return rc;
       if (int rc = check_device_pointer(c[s], device, s ? "conf1" : "conf0")) return rc;
     }
-    if (int rc = wait_for_caller(A, o)) return rc;
+    if (int rc = wait_for_caller(A, o.stream)) return rc;
     d_bad = A.alloc<int32_t>(1);
     if (!d_bad) return fail(MPSFM_ENOMEM, "hipMalloc failed");
     MPSFM_TRY(hipMemsetAsync(d_bad, 0, sizeof(int32_t), A.st));

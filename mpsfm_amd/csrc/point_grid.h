@@ -131,7 +131,24 @@ __device__ __forceinline__ void grid_visit_point(const PointGrid& g, int32_t p, 
   }
 }
 
+// the caller's index of the point nearest to (x, y) among those at squared distance strictly below e2, the lowest index among
+// equidistant nearest ones; -1: there is none
+__device__ __forceinline__ int32_t grid_nearest(const PointGrid& g, double x, double y, double e2) {
+  double best = e2;
+  int32_t id = -1;
+  grid_visit_query(g, x, y, [&](int32_t q) {
+    const double2 w = g.xy[q];
+    const double d2 = grid_d2(x, y, w.x, w.y);
+    if (!(d2 < e2)) return true;
+    const int32_t k = g.perm[q];
+    if (id < 0 || d2 < best || (d2 == best && k < id)) { best = d2; id = k; }
+    return true;
+  });
+  return id;
+}
+
 namespace grid_detail {
+namespace {  // one copy per translation unit that includes this header
 __global__ __launch_bounds__(kGridT) void k_grid_keys(int32_t n, const double* __restrict__ pts, GridSpec sp, uint32_t* __restrict__ key,
                                                       int32_t* __restrict__ val) {
   const int32_t i = (int32_t)blockIdx.x * kGridT + (int32_t)threadIdx.x;
@@ -171,6 +188,7 @@ __global__ __launch_bounds__(kGridT) void k_grid_cells(int32_t n, const double* 
   atomicAdd(&stats[0], 1);
   atomicMax(&stats[1], r[9] - r[8]);  // k = 4 is the cell itself
 }
+}  // namespace
 }  // namespace grid_detail
 
 // Builds the grid of d_pts[n][2] (device) on the scope's stream; n >= 1.  `runs` false: keys, perm and xy only (a grid that is
