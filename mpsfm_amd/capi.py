@@ -252,6 +252,19 @@ def point_covs(prob: BAProblem, device: int = 0) -> np.ndarray:
     return covs
 
 
+def debug_panel_factor(dx: np.ndarray, waves: int = 4):
+    """Probe of the dense solve's panel factorisation: one workgroup factors the stacked 64 x 32 matrix [D; X] with `waves`
+    (1 or 4) waves.  Returns (out, ok): rows 0..31 of out hold L (lower triangle), rows 32..63 X L^-T; ok is False when a
+    pivot was not positive."""
+    dx = np.ascontiguousarray(dx, np.float64)
+    assert dx.shape == (64, 32), dx.shape
+    out, ok = np.zeros((64, 32)), C.c_int(0)
+    L = lib()
+    L.mpsfm_debug_panel_factor.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    _check(L.mpsfm_debug_panel_factor(dx.ctypes.data, int(waves), out.ctypes.data, C.byref(ok)))
+    return out, bool(ok.value)
+
+
 def triangulate_tracks(tr: Tracks, device: int = 0) -> np.ndarray:
     xyz = np.zeros((tr.n_tracks, 3))
     ct = tr.c_tracks()

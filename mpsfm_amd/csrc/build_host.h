@@ -22,6 +22,7 @@ struct BuildOptions {
   int chunk_records = 0;       // MPSFM_CHUNK_RECORDS clamped to [16, kObsMax]; 0: not set
   int chunk_pts_by_cams = -1;  // MPSFM_CHUNK_PTS_BY_CAMS as 0 / 1; -1: not set
   int chol_nb = -1, chol_big = -1, chol_overlap = -1, chol_level = -1;  // MPSFM_CHOL_NB (>= 0) / _BIG / _OVERLAP / _LEVEL; -1: not set
+  int chol_panel_waves = -1;   // MPSFM_CHOL_PANEL_WAVES: 4 or 1 waves factor a stacked panel; -1: not set
   // derived by set_chunk_caps once the variable cameras are known
   int rec_cap = kObsMax;       // records a DENSE chunk may hold
   int pts_by_cams = 0;         // landmarks of a dense chunk by the size of its camera set (dense_pts_cap)

@@ -135,6 +135,7 @@ BuildOptions BuildOptions::from_environment() {
   if (read("MPSFM_CHOL_BIG", o.chol_big)) o.chol_big = o.chol_big != 0;
   if (read("MPSFM_CHOL_OVERLAP", o.chol_overlap)) o.chol_overlap = o.chol_overlap != 0;
   if (read("MPSFM_CHOL_LEVEL", o.chol_level)) o.chol_level = o.chol_level != 0;
+  if (read("MPSFM_CHOL_PANEL_WAVES", o.chol_panel_waves)) o.chol_panel_waves = o.chol_panel_waves == 1 ? 1 : 4;
   return o;
 }
 // Records a DENSE chunk may hold.  A very small problem (a local bundle adjustment of a few cameras: a handful of full chunks) is
@@ -156,6 +157,7 @@ void BuildOptions::apply_dense(int nt, const CholPlan& plan, DenseOverlap& ov) c
   if (chol_big >= 0) ov.big = chol_big != 0;
   if (chol_overlap >= 0) ov.overlap = chol_overlap != 0;
   ov.no_inverse = !chol_inverse;
+  if (chol_panel_waves >= 0) ov.panel_waves = chol_panel_waves;
   if (chol_level >= 0) ov.no_level = chol_level == 0;
   // a large reduced system without exploitable structure (every camera shares landmarks with most others): the
   // outer-panel path with its LDS-staged 64x64 trailing update moves fewer bytes per flop than one workgroup per tile

@@ -373,6 +373,7 @@ void cached_free(void* p);
 hipError_t pooled_stream(hipStream_t* s);
 void release_stream(hipStream_t s);
 
+constexpr int kPanelWavesDefault = 4;
 // second stream + events for the outer-panel look-ahead of the dense factorisation (dense_chol.hip)
 struct DenseOverlap {
   int nb = 0;            // outer panel width in tile columns; 0: default (one panel up to 64 tile columns, else 8)
@@ -380,6 +381,7 @@ struct DenseOverlap {
   bool overlap = true;   // second-stream look-ahead
   bool no_level = false;    // per-step skyline path instead of the level-scheduled factorisation (A/B measurements)
   bool no_inverse = false;  // plain path: back substitution by groups instead of the inverse propagation (A/B measurements)
+  int panel_waves = kPanelWavesDefault;  // waves that factor the stacked panel of a tile column: 4 or 1 (MPSFM_CHOL_PANEL_WAVES)
   hipStream_t s2 = nullptr;
   hipEvent_t evF[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t evB[4] = {nullptr, nullptr, nullptr, nullptr};

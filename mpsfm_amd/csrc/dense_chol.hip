@@ -210,8 +210,8 @@ __global__ __launch_bounds__(256) void k_big_update(double* A, int nt, int j, in
 int g_dbg_flags = 0;
 extern "C" void mpsfm_debug_set(int f) { g_dbg_flags = f; }
 // Phase timeline of the factorisation (diagnostics, scripts/dbg_chol_trace.py): when a buffer is registered, the
-// workgroup that owns the diagonal tile of every step stores wall_clock64() (100 MHz) at its phase boundaries,
-// 8 stamps per wave and step.
+// workgroup that owns the diagonal tile of every step stores wall_clock64() (100 MHz) at its phase boundaries:
+// two rows of 8 stamps per step, the phases in the first, the hand-offs of the four-wave panel in the second.
 __device__ long long* g_chol_trace = nullptr;
 extern "C" int mpsfm_debug_set_chol_trace(long long* dev_buf) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_chol_trace), &dev_buf, sizeof(dev_buf));
@@ -221,8 +221,8 @@ extern "C" int mpsfm_debug_set_chol_trace(long long* dev_buf) {
 // Dense outer-panel path (reduced systems without exploitable structure, MPSFM_CHOL_NB): one step of the right-looking
 // factorisation, four waves per tile.  j = -1: factor tile column 0 only.
 //   trailing tile (tk > j+1):  A[ti][tk] -= L[ti][j] L[tk][j]^T, one quadrant per wave.
-//   panel tile (tk == j+1):    every workgroup re-derives the updated diagonal tile; wave 0 factors the stacked
-//                              [D; X] (stacked_panel); the workgroup that owns the diagonal tile stores L^-T
+//   panel tile (tk == j+1):    every workgroup re-derives the updated diagonal tile; its four waves factor the stacked
+//                              [D; X] (panel_section); the workgroup that owns the diagonal tile stores L^-T
 //                              (kept for the back substitution).
 // c0 is the first tile column whose L is applied to a trailing tile in this
 // launch (c0 == j: the plain right-looking step), tk_max the last tile column this launch touches, and
@@ -296,11 +296,59 @@ __device__ __forceinline__ void inv_role(const double* A, const double* LinvT, d
   }
 }
 
+// ---- the panel section of k_chol_step and k_chol_level, from the barrier behind s_T / s_X to the store -----------------------
+// Factors the stacked [D; X] (D in s_T, X in s_X) and stores the rows of X L^-T to x_dst (32 x 32, row-major); d_dst (the
+// probe only) receives the rows of L.  waves == kWgWaves: all four waves (stacked_panel_wg); otherwise wave 0 alone
+// (stacked_panel) and the others leave.  Every argument is workgroup-uniform and all four waves of the workgroup call this.
+// s_P: kPanelLds doubles.  fail (may be NULL) is raised when a wave met a pivot that is not positive; tr (may be NULL)
+// receives the phase stamps 2 (entry), 3 (factored: by the wave that finishes last) and 4 (stored); the four-wave path also
+// stamps its hand-offs into the step's second row (tr[8 ..], see stacked_panel_wg).
+constexpr int kPanelLds = kWgLds > kTileElems ? kWgLds : kTileElems;  // inv_role stages a tile in the same buffer
+__device__ __forceinline__ void panel_section(int waves, const double (*s_T)[kTile + 1], const double (*s_X)[kTile + 1], double* s_P, bool skip,
+                                              double* x_dst, double* d_dst, int* fail, long long* tr) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int row = lane & 31;
+  const double* sp = (lane < kTile) ? &s_T[row][0] : &s_X[row][0];
+  double* dst = (lane < kTile) ? (d_dst ? d_dst + row * kTile : nullptr) : x_dst + row * kTile;
+  if (tr && wave == 0 && lane == 0) tr[2] = wall_clock64();
+  bool ok = true;
+  if (waves == kWgWaves) {
+    double a[kSP];
+#pragma unroll
+    for (int c = 0; c < kSP; ++c) a[c] = sp[kSP * wave + c];
+    if (!skip) stacked_panel_wg(a, lane, wave, s_P, ok, tr ? tr + 8 : nullptr);
+    const bool last = wave == kWgWaves - 1;
+    if (tr && last && lane == 0) tr[3] = wall_clock64();
+    if (fail && !ok && lane == 0) atomicExch(fail, 1);
+    if (dst) {
+      double2* d2 = reinterpret_cast<double2*>(dst + kSP * wave);
+#pragma unroll
+      for (int c = 0; c < kSP; c += 2) d2[c >> 1] = make_double2(a[c], a[c + 1]);
+    }
+    if (tr && last && lane == 0) tr[4] = wall_clock64();
+    return;
+  }
+  if (wave != 0) return;
+  // stacked factorisation by wave 0: lanes 0..31 rows of D, lanes 32..63 rows of X (identity for the diagonal workgroup)
+  double a[kTile];
+#pragma unroll
+  for (int c = 0; c < kTile; ++c) a[c] = sp[c];
+  if (!skip) stacked_panel<0>(a, lane, s_P, ok);
+  if (tr && lane == 0) tr[3] = wall_clock64();
+  if (fail && !ok && lane == 0) atomicExch(fail, 1);
+  if (dst) {
+    double2* d2 = reinterpret_cast<double2*>(dst);
+#pragma unroll
+    for (int c = 0; c < kTile; c += 2) d2[c >> 1] = make_double2(a[c], a[c + 1]);
+  }
+  if (tr && lane == 0) tr[4] = wall_clock64();
+}
+
 __global__ __launch_bounds__(kStepThreads) void k_chol_step(double* A, double* LinvT, int nt, int j, int* fail, int dbg, int c0, int tk_max,
-                                                            int mode) {
+                                                            int mode, int panel_waves) {
   __shared__ double s_T[kTile][kTile + 1];
   __shared__ double s_X[kTile][kTile + 1];
-  __shared__ __attribute__((aligned(16))) double s_Lt[kTile * kTile];
+  __shared__ __attribute__((aligned(16))) double s_Lt[kPanelLds];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int mi = wave & 1, ni = wave >> 1;  // this wave's quadrant
   if (dbg & 16) return;  // ablation: the launch chain alone
@@ -323,7 +371,6 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_step(double* A, double* L
   }
   const bool own_update = (j >= 0) && !(mode & kStepNoOwnUpdate) && !(dbg & 4);
   // ---- panel column j+1 -------------------------------------------------------------------
-  const int row = lane & 31;
   const bool diag = (ti == tk);
   long long* tr = g_chol_trace ? g_chol_trace + ((size_t)(j + 1) * 2) * 8 : nullptr;
   const bool trace_on = diag && tr != nullptr && wave == 0;
@@ -353,30 +400,12 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_step(double* A, double* L
   }
   MPSFM_STAMP(1);
   __syncthreads();
-  MPSFM_STAMP(2);
-  if (wave != 0) return;
-  // stacked factorisation by wave 0: lanes 0..31 rows of D, lanes 32..63 rows of X (identity for the diagonal workgroup)
-  double a[kTile];
-  {
-    const double* src = (lane < kTile) ? &s_T[row][0] : &s_X[row][0];
-#pragma unroll
-    for (int c = 0; c < kTile; ++c) a[c] = src[c];
-  }
-  bool ok = true;
-  if (!(dbg & 1)) stacked_panel<0>(a, lane, s_Lt, ok);
-  MPSFM_STAMP(3);
   // The factored diagonal tile is NOT written back over A(tk,tk): every workgroup of this panel column loads
   // A(tk,tk) at its start, and one that is scheduled late (a busy GPU) would otherwise find L there instead of the
   // matrix.  Nothing reads L(tk,tk) from memory afterwards — the back substitution uses the stored L^-T of the
   // diagonal tiles.
-  if (diag && !ok && lane == 0) atomicExch(fail, 1);
-  if (lane >= kTile) {
-    double2* dst = diag ? reinterpret_cast<double2*>(LinvT + (size_t)tk * kTileElems + row * kTile)
-                        : reinterpret_cast<double2*>(C + row * kTile);
-#pragma unroll
-    for (int c = 0; c < kTile; c += 2) dst[c >> 1] = make_double2(a[c], a[c + 1]);
-  }
-  MPSFM_STAMP(4);
+  panel_section(panel_waves, s_T, s_X, s_Lt, (dbg & 1) != 0, diag ? LinvT + (size_t)tk * kTileElems : C, nullptr, diag ? fail : nullptr,
+                diag ? tr : nullptr);
 }
 
 
@@ -384,7 +413,7 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_step(double* A, double* L
 // The same three kinds of workgroup as a right-looking step (k_chol_step with kStepEnv), driven by an item table:
 //   panel (ti, c)   the tile's column c is at this launch's level.  The updated diagonal tile D(c) and the own tile receive
 //                   the children of c that were factored in the previous launch (sources; the rest of the subtree came
-//                   through trailing items of earlier launches), then wave 0 factors the stacked [D(c); X];
+//                   through trailing items of earlier launches), then the four waves factor the stacked [D(c); X];
 //   trail (ti, tk)  C -= sum over the source columns (all of the previous level that reach the tile: one workgroup per
 //                   tile, so independent chains never race on an ancestor's tile and the sum has a fixed order);
 //   role  (j, k)    inverse propagation for column j of the previous level and a column k of its subtree.
@@ -393,13 +422,14 @@ struct LevelArgs {
   const CholItem* items; const int32_t* srcs; const int32_t* rows;
   int* fail; int32_t nt, dbg;
   const LmCtl* ctl;
+  int32_t panel_waves;  // waves that factor a panel: kWgWaves or 1 (MPSFM_CHOL_PANEL_WAVES)
 };
 
 __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
   if (lm_over(G.ctl)) return;
   __shared__ double s_T[kTile][kTile + 1];
   __shared__ double s_X[kTile][kTile + 1];
-  __shared__ __attribute__((aligned(16))) double s_Lt[kTile * kTile];
+  __shared__ __attribute__((aligned(16))) double s_Lt[kPanelLds];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int mi = wave & 1, ni = wave >> 1;  // this wave's quadrant
   if (G.dbg & 16) return;  // ablation: the launch chain alone
@@ -428,7 +458,6 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
     return;
   }
   // ---- panel tile of column tk ---------------------------------------------------------------
-  const int row = lane & 31;
   const bool diag = (ti == tk);
   long long* tr = g_chol_trace ? g_chol_trace + ((size_t)tk * 2) * 8 : nullptr;
   const bool trace_on = diag && tr != nullptr && wave == 0;
@@ -459,27 +488,49 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
   }
   MPSFM_STAMP(1);
   __syncthreads();
-  MPSFM_STAMP(2);
-  if (wave != 0) return;
-  double a[kTile];
-  {
-    const double* sp = (lane < kTile) ? &s_T[row][0] : &s_X[row][0];
-#pragma unroll
-    for (int c = 0; c < kTile; ++c) a[c] = sp[c];
-  }
-  bool ok = true;
-  if (!(G.dbg & 1)) stacked_panel<0>(a, lane, s_Lt, ok);
-  MPSFM_STAMP(3);
   // as in k_chol_step the factored diagonal tile is not written back over A(tk,tk): its column's other workgroups may
   // still be loading it
-  if (diag && !ok && lane == 0) atomicExch(G.fail, 1);
-  if (lane >= kTile) {
-    double2* dst = diag ? reinterpret_cast<double2*>(G.LinvT + (size_t)tk * kTileElems + row * kTile)
-                        : reinterpret_cast<double2*>(C + row * kTile);
-#pragma unroll
-    for (int c = 0; c < kTile; c += 2) dst[c >> 1] = make_double2(a[c], a[c + 1]);
+  panel_section(G.panel_waves, s_T, s_X, s_Lt, (G.dbg & 1) != 0, diag ? G.LinvT + (size_t)tk * kTileElems : C, nullptr, diag ? G.fail : nullptr,
+                diag ? tr : nullptr);
+}
+
+// ---- probe: one workgroup factors a given stacked [D; X] through panel_section (tests: one wave against four) -----------------
+__global__ __launch_bounds__(kStepThreads) void k_panel_probe(const double* dx, int waves, double* out, int* fail) {
+  __shared__ double s_T[kTile][kTile + 1];
+  __shared__ double s_X[kTile][kTile + 1];
+  __shared__ __attribute__((aligned(16))) double s_Lt[kPanelLds];
+  for (int e = threadIdx.x; e < kTileElems; e += kStepThreads) {
+    s_T[e >> 5][e & 31] = dx[e];
+    s_X[e >> 5][e & 31] = dx[kTileElems + e];
   }
-  MPSFM_STAMP(4);
+  __syncthreads();
+  panel_section(waves, s_T, s_X, s_Lt, false, out + kTileElems, out, fail, nullptr);
+}
+// dx, out: host, 64 x 32 row-major (rows 0..31: D -> L, its upper triangle is not defined; rows 32..63: X -> X L^-T).
+// waves: 1 or 4.  *ok: 1 when every pivot was positive and finite.
+extern "C" int mpsfm_debug_panel_factor(const double* dx, int waves, double* out, int* ok) {
+  if (!dx || !out || !ok || (waves != 1 && waves != kWgWaves)) return MPSFM_EINVAL;
+  const size_t bytes = (size_t)2 * kTileElems * sizeof(double);
+  double* d_in = (double*)cached_malloc(bytes);
+  double* d_out = (double*)cached_malloc(bytes);
+  int* d_fail = (int*)cached_malloc(sizeof(int));
+  hipError_t e = (d_in && d_out && d_fail) ? hipSuccess : hipErrorOutOfMemory;
+  int h_fail = 0;
+  if (e == hipSuccess) e = hipMemcpy(d_in, dx, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_out, 0, bytes);
+  if (e == hipSuccess) e = hipMemset(d_fail, 0, sizeof(int));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_panel_probe, dim3(1), dim3(kStepThreads), 0, nullptr, d_in, waves, d_out, d_fail);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&h_fail, d_fail, sizeof(int), hipMemcpyDeviceToHost);
+  if (d_in) cached_free(d_in);
+  if (d_out) cached_free(d_out);
+  if (d_fail) cached_free(d_fail);
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? MPSFM_ENOMEM : MPSFM_EHIP;
+  *ok = h_fail ? 0 : 1;
+  return MPSFM_OK;
 }
 
 // Backward substitution y = L^-T z by levels, highest first (no inverse accumulators: nt > kPlainMaxTiles).  One workgroup
@@ -708,9 +759,10 @@ void launch_dense_solve(double* A, double* work, int nt, int n, double* y, int* 
   if (nt <= 0) return;
   double* LinvT = work;
   double* zbuf = work + (size_t)nt * kTileElems;
+  const int panel_waves = (ov ? ov->panel_waves : kPanelWavesDefault) == 1 ? 1 : kWgWaves;
   if (dense_level(ov, lp)) {
     double* Pinv = dense_pinv(work, nt, ov, lp);
-    LevelArgs G{A, LinvT, Pinv, nullptr, lp->d_srcs, lp->d_rows, fail, nt, g_dbg_flags, ctl};
+    LevelArgs G{A, LinvT, Pinv, nullptr, lp->d_srcs, lp->d_rows, fail, nt, g_dbg_flags, ctl, panel_waves};
     for (int l = 0; l < lp->nlevels; ++l) {
       const int grid = lp->h_launch_start[l + 1] - lp->h_launch_start[l];
       if (grid <= 0) continue;
@@ -741,16 +793,16 @@ void launch_dense_solve(double* A, double* work, int nt, int n, double* y, int* 
     const int pend = (p0 + NB - 1 < nt - 1) ? p0 + NB - 1 : nt - 1;
     // factor column p0 (its tiles already hold every earlier column); ti in [p0, nt]
     hipLaunchKernelGGL(k_chol_step, dim3(nt - p0 + 1, 1), dim3(kStepThreads), 0, s, A, LinvT, nt, p0 - 1, fail, g_dbg_flags, p0 - 1, p0,
-                       kStepNoOwnUpdate);
+                       kStepNoOwnUpdate, panel_waves);
     for (int j = p0; j <= pend - 1; ++j) {  // apply column j to columns (j, pend], factor column j+1; ti in [j+1, nt]
       const int rows = nt - j, cols = pend - j;
-      hipLaunchKernelGGL(k_chol_step, dim3(rows, cols), dim3(kStepThreads), 0, s, A, LinvT, nt, j, fail, g_dbg_flags, j, pend, 0);
+      hipLaunchKernelGGL(k_chol_step, dim3(rows, cols), dim3(kStepThreads), 0, s, A, LinvT, nt, j, fail, g_dbg_flags, j, pend, 0, panel_waves);
     }
     if (pend >= nt - 1) break;
     // columns (pend, nt-1] receive the panel p0..pend; ti in [pend+1, nt]
     if (!big_kernel) {
       hipLaunchKernelGGL(k_chol_step, dim3(nt - pend, nt - 1 - pend), dim3(kStepThreads), 0, s, A, LinvT, nt, pend, fail, g_dbg_flags, p0, nt - 1,
-                         kStepBig);
+                         kStepBig, panel_waves);
     } else if (!overlap) {
       launch_big(A, nt, pend, p0, pend + 1, nt - 1, s);
     } else {

@@ -1,5 +1,6 @@
 // Register / LDS building blocks of the tile Cholesky (dense_chol.hip), shared with the single-launch solver of small problems
-// (local_lm.hip): the stacked one-wave panel factorisation and the 16 x 16 quadrant products of v_mfma_f64_16x16x4_f64.
+// (local_lm.hip): the stacked panel factorisation by one wave and by the four waves of a workgroup, and the 16 x 16 quadrant
+// products of v_mfma_f64_16x16x4_f64.
 #pragma once
 #include "common.h"
 
@@ -132,6 +133,111 @@ __device__ __forceinline__ void stacked_panel(double (&a)[kTile], int lane, doub
       }
     }
     stacked_panel<J0 + kSP, END>(a, lane, s_P, ok);
+  }
+}
+
+// ---- the same factorisation by the FOUR waves of a workgroup ---------------------------------------------------------------
+// The one-wave panel is bound by the instruction count of its wave, and most of those instructions are rank-1 updates of
+// columns that are not on the dependent chain yet.  Here wave w holds columns 8 w .. 8 w + 7 of all 64 rows (lane = row, as
+// above: 8 doubles per lane).  For p = 0..3: wave p runs the in-panel chain of stacked_col on its columns (source lane
+// 8 p + c), writes its 8 columns of L for all 64 rows to LDS, and behind ONE workgroup barrier every wave q > p applies the
+// rank-8 update  a[c] = fma(-L[row][8p+k], L[8q+c][8p+k], a[c])  in ascending k: every element receives the operations of
+// the one-wave path with the same operands in the same order, so the two paths agree bit for bit.
+// LDS: panel p has rows of its own (none is reused, so a hand-off needs no second barrier against overwriting); a row is
+// padded to kWgLd doubles, which keeps the 16-byte pieces of neighbouring lanes in different banks.
+constexpr int kWgWaves = kTile / kSP;                  // 4
+constexpr int kWgLd = kSP + 2;                         // doubles per row of a stored panel
+constexpr int kWgPanel = 2 * kTile * kWgLd;            // doubles per stored panel
+constexpr int kWgLds = kWgWaves * kWgPanel;            // the last panel is stored too: no branch in the chain
+static_assert(kWgLd % 2 == 0, "rows of a stored panel stay 16-byte aligned");
+
+// column J of the wave's panel, d: its pivot (wave-uniform).  dst: this lane's row of the stored panel — every column of L
+// is stored as soon as it is final, so that only the last store is still in flight at the barrier.
+// The one-wave chain goes through two lane broadcasts per column (the multiplier of row J + 1, then the updated pivot).  Here
+// every lane forms the NEXT pivot itself, from the two elements of row J + 1 it depends on (broadcast before y is known, off
+// the chain) and with the operations lane J + 1 applies to them — lb = a[J] y and fma(-lb, lb, a[J+1]) — so the value is the
+// one the broadcast would have delivered, bit for bit, and the chain per column is v_rsq_f64 and seven multiply-adds.
+template <int J>
+__device__ __forceinline__ void wg_panel_col(double (&a)[kSP], int c0, double* dst, bool& ok, double d) {
+  ok = ok && (d > 0.0) && isfinite(d);
+  double vb = 0.0, a11 = 0.0;
+  if constexpr (J + 1 < kSP) {
+    vb = readlane_f64(a[J], c0 + J + 1);
+    a11 = readlane_f64(a[J + 1], c0 + J + 1);
+  }
+  const double y0 = __builtin_amdgcn_rsq(d);
+  const double h = d * y0;
+  const double e = __builtin_fma(-h, y0, 1.0);
+  const double p = __builtin_fma(0.375 * e, e, 0.5 * e);
+  const double y = __builtin_fma(y0, p, y0);
+  const double l = a[J] * y;
+  a[J] = l;
+  dst[J] = l;
+  if constexpr (J + 1 < kSP) {
+    const double lb = vb * y;                          // l of lane c0 + J + 1
+    const double dn = __builtin_fma(-lb, lb, a11);     // its a[J + 1] after this column: the next pivot
+    a[J + 1] = __builtin_fma(-l, lb, a[J + 1]);
+#pragma unroll
+    for (int c = J + 2; c < kSP; ++c) a[c] = __builtin_fma(-l, readlane_f64(l, c0 + c), a[c]);
+    wg_panel_col<J + 1>(a, c0, dst, ok, dn);
+  }
+}
+
+// A hand-off reads, per lane, the 8 own multipliers L[row][8p + k] and the 64 broadcast ones L[8 wave + c][8p + k] as 36
+// ds_read_b128, in four groups of k pairs (one own read, eight broadcast reads).  Two groups are in flight while the
+// multiply-adds of the group before run: LDS operations return in order, so a counted wait that leaves the 9 newest reads
+// outstanding has the group before them in registers.
+template <int KK>
+__device__ __forceinline__ void wg_group_load(uint32_t a_own, uint32_t a_bc, v2d (&own)[kSP / 2], v2d (&bc)[kSP / 2][kSP]) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(own[KK]) : "v"(a_own), "n"(16 * KK));
+#pragma unroll
+  for (int c = 0; c < kSP; ++c) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bc[KK][c]) : "v"(a_bc), "n"(c * kWgLd * 8 + 16 * KK));
+}
+template <int CNT>
+__device__ __forceinline__ void wg_group_wait(v2d& o, v2d (&b)[kSP]) {
+  asm volatile("s_waitcnt lgkmcnt(%9)"
+               : "+v"(o), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7])
+               : "n"(CNT));
+}
+__device__ __forceinline__ void wg_group_fma(double (&a)[kSP], const v2d& o, const v2d (&b)[kSP]) {
+#pragma unroll
+  for (int c = 0; c < kSP; ++c) a[c] = __builtin_fma(-o.x, b[c].x, a[c]);  // k = 2 KK, then k = 2 KK + 1: ascending per element
+#pragma unroll
+  for (int c = 0; c < kSP; ++c) a[c] = __builtin_fma(-o.y, b[c].y, a[c]);
+}
+
+// `wave` must be wave-uniform (a scalar); every wave of the workgroup calls this, all of them reach its three barriers.
+// s_P: kWgLds doubles, 16-byte aligned.  ok: pivots of this wave's own columns.  tr (diagnostics, may be NULL): wall_clock64 of
+// the end of panel p's chain in tr[2 p], of the end of the update of panel p + 1 by panel p in tr[2 p + 1].
+__device__ __forceinline__ void stacked_panel_wg(double (&a)[kSP], int lane, int wave, double* s_P, bool& ok, long long* tr) {
+#pragma nounroll
+  for (int p = 0; p < kWgWaves; ++p) {
+    if (wave == p) {
+      wg_panel_col<0>(a, kSP * p, s_P + p * kWgPanel + lane * kWgLd, ok, readlane_f64(a[0], kSP * p));
+      if (tr && lane == 0) tr[2 * p] = wall_clock64();
+    }
+    if (p + 1 == kWgWaves) break;
+    __syncthreads();
+    asm volatile("" ::: "memory");
+    if (wave > p) {
+      // only wave p + 1 is waited for: the waves behind it let its reads go first
+      if (wave > p + 1) __builtin_amdgcn_s_sleep(3);
+      const uint32_t a_own = lds_addr(s_P + p * kWgPanel + lane * kWgLd), a_bc = lds_addr(s_P + p * kWgPanel + kSP * wave * kWgLd);
+      v2d own[kSP / 2], bc[kSP / 2][kSP];
+      wg_group_load<0>(a_own, a_bc, own, bc);
+      wg_group_load<1>(a_own, a_bc, own, bc);
+      wg_group_wait<kSP + 1>(own[0], bc[0]);
+      wg_group_fma(a, own[0], bc[0]);
+      wg_group_load<2>(a_own, a_bc, own, bc);
+      wg_group_wait<kSP + 1>(own[1], bc[1]);
+      wg_group_fma(a, own[1], bc[1]);
+      wg_group_load<3>(a_own, a_bc, own, bc);
+      wg_group_wait<kSP + 1>(own[2], bc[2]);
+      wg_group_fma(a, own[2], bc[2]);
+      wg_group_wait<0>(own[3], bc[3]);
+      wg_group_fma(a, own[3], bc[3]);
+      if (tr && wave == p + 1 && lane == 0) tr[2 * p + 1] = wall_clock64();
+    }
   }
 }
 
