@@ -1,0 +1,334 @@
+// Test hooks, timing probes and table dumps of libmpsfm_hip: every mpsfm_debug_* entry point and the single-phase runs of the
+// bundle adjustment (one sweep, one dense solve, the reduced system).  Nothing here is on the path of a solve.
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <vector>
+
+#include "ba_handle.h"
+
+using namespace mpsfm;
+
+// the ten numbers of mpsfm_ba_dense_plan; `work`: the dense workspace (only compared with NULL)
+static void dense_plan_numbers(int ncv, int nt, const CholPlan& P, const DenseOverlap& ov, const LevelPlanDev& lp, double* work, int64_t sblk, int64_t v[10]) {
+  const bool level = dense_level(&ov, &lp);
+  const bool pinv = level && dense_pinv(work, nt, &ov, &lp) != nullptr;
+  const int64_t w[10] = {ncv, nt, level ? P.nlevels : nt, P.nd_depth, pinv ? 1 : 0, (int64_t)P.items.size(), P.products, P.roles, sblk,
+                         pinv ? 1 : (level ? P.nlevels : (nt + 3) / 4 + 1)};
+  for (int i = 0; i < 10; ++i) v[i] = w[i];
+}
+
+// Test hook (tests/test_host_cpu.py; no device involved): takes and gives back `count` host blocks of `bytes` each through
+// the block cache twice; returns how many blocks of the second round were recycled ones of the first (by address).
+extern "C" int64_t mpsfm_debug_host_cache(int64_t bytes, int32_t count) {
+  std::vector<mpsfm::HostBuf<uint8_t>> first((size_t)count), second((size_t)count);
+  std::vector<const void*> seen;
+  for (auto& b : first) { b.alloc((size_t)bytes); b[0] = 1; b[(size_t)bytes - 1] = 2; seen.push_back(b.data()); }
+  first.clear();
+  int64_t reused = 0;
+  for (auto& b : second) {
+    b.alloc((size_t)bytes);
+    b[0] = 3;
+    reused += std::find(seen.begin(), seen.end(), (const void*)b.data()) != seen.end() ? 1 : 0;
+  }
+  return reused;
+}
+
+// Test hook (tests/test_host_cpu.py; no device involved): `reps` rounds of an `nparts`-part job through the table build's
+// worker pool; returns the number of parts that did not run exactly once.
+extern "C" int64_t mpsfm_debug_run_parts(int32_t nparts, int32_t reps) {
+  int64_t bad = 0;
+  for (int r = 0; r < reps; ++r) {
+    std::vector<std::atomic<int>> hits((size_t)std::max(nparts, 1));
+    for (auto& x : hits) x.store(0);
+    mpsfm::run_parts(nparts, [&](int t, int np) {
+      if (np != std::max(nparts, 1) || t < 0 || t >= np) return;
+      volatile double acc = 0.0;
+      for (int k = 0; k < 2000; ++k) acc = acc + (double)k * 1e-9;  // a little work, so that parts overlap
+      hits[(size_t)t].fetch_add(1);
+    });
+    for (auto& x : hits) bad += x.load() == 1 ? 0 : 1;
+  }
+  return bad;
+}
+
+// Test hook (tests/test_dist_cpu.py; no device involved): the camera-graph union of a landmark-sharded run as the ranks
+// compute it — `world` adjacency matrices (n x n bytes each) packed per rank, summed like the all-reduce does, unpacked
+// into `out` (n x n bytes).  Returns the digits per double used.
+extern "C" int mpsfm_debug_graph_union(const uint8_t* adj, int32_t world, int32_t n, uint8_t* out) {
+  std::vector<double> sum;
+  for (int r = 0; r < world; ++r) {
+    mpsfm::CamGraph g;
+    g.init(n);
+    for (int a = 0; a < n; ++a)
+      for (int b = 0; b < n; ++b)
+        if (adj[((size_t)r * n + a) * n + b]) g.set(a, b);
+    std::vector<double> packed;
+    mpsfm::pack_graph(g, world, packed);
+    if (sum.empty()) sum.assign(packed.size(), 0.0);
+    for (size_t i = 0; i < packed.size(); ++i) sum[i] += packed[i];
+  }
+  mpsfm::CamGraph u;
+  u.init(n);
+  mpsfm::unpack_graph(sum, world, u);
+  for (int a = 0; a < n; ++a)
+    for (int b = 0; b < n; ++b) out[(size_t)a * n + b] = u.get(a, b) ? 1 : 0;
+  return mpsfm::graph_digits(world);
+}
+
+extern "C" {
+
+int mpsfm_ba_dense_plan(mpsfm_ba_handle* h, int64_t info[10]) {
+  if (!h || !info) return fail(MPSFM_EINVAL, "handle or info is NULL");
+  dense_plan_numbers(h->ncv, h->nt, h->plan, h->ov, h->lp, h->d_dwork, h->spat.nblk, info);
+  return 0;
+}
+
+int mpsfm_ba_sweep_once(mpsfm_ba_handle* h, double radius, float* elapsed_ms) {
+  if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
+  MPSFM_TRY(hipSetDevice(h->device));
+  if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
+  MPSFM_TRY(hipMemsetAsync(h->d_red, 0, sizeof(double) * (size_t)h->red_count, h->stream));
+  SweepArgs a = sweep_args(h, radius);
+  // the three parts of the sweep between events: dense chunks | reduction of their slabs | general chunks and long tracks
+  MPSFM_TRY(hipEventRecord(h->ev[0], h->stream));
+  launch_track_sweep_dense(a, h->n_dense, h->stream);
+  MPSFM_TRY(hipEventRecord(h->ev[1], h->stream));
+  launch_reduce_slabs(h->d_red_dests, h->n_red_dests, h->d_red_srcs, h->d_slab, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, nullptr, h->stream);
+  MPSFM_TRY(hipEventRecord(h->ev[2], h->stream));
+  a.chunk0 = h->n_dense;
+  launch_track_sweep(a, h->nchunks - h->n_dense, false, h->stream);
+  MPSFM_TRY(hipEventRecord(h->ev[3], h->stream));
+  if (h->nchunks + h->nlong > 0) launch_reduce_cols(h->d_part, h->nchunks + h->nlong, 4, 3, 1u << 2, h->d_redsc, h->stream);
+  MPSFM_TRY(hipStreamSynchronize(h->stream));
+  MPSFM_TRY(hipGetLastError());
+  h->last_radius = radius;
+  float ms = 0.f;
+  MPSFM_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[3]));
+  if (elapsed_ms) *elapsed_ms = ms;
+  return 0;
+}
+
+// Diagnostics (scripts/dbg_sweep_trace.py): the first `count` 8-byte words of the landmark-diagonal buffer, where the dense sweep leaves
+// its phase stamps under debug flag 128.
+int mpsfm_debug_read_trace(mpsfm_ba_handle* h, long long* out, int64_t count) {
+  if (!h || !out || count < 0 || count > 3 * std::max<int64_t>(h->np, 1)) return fail(MPSFM_EINVAL, "bad trace request");
+  MPSFM_TRY(hipSetDevice(h->device));
+  MPSFM_TRY(hipMemcpyAsync(out, h->d_diagV, sizeof(long long) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+  MPSFM_TRY(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// Diagnostics / tests (tests/test_gpu_devbuild.py): table `which` of the handle copied to `out` (at most `cap` bytes); returns the
+// table's size in bytes, or a negative error code.  which: 0 chunk headers, 1 chunk cameras, 2 rec_cam, 3 rec_pt, 4 rec_meta, 5 rec_xy,
+// 6 rec_d, 7 rec_m, 8 rec_a, 9 pt_rec_start, 10 pt_kv, 11 fx_cam, 12 fx_pt, 13 fx_meta, 14 fx_xy, 15 fx_d, 16 fx_m, 17 fx_a,
+// 18 landmark order (host), 19 reduction destinations, 20 reduction sources, 21 camera slots (host), 22: 1 byte, built on the device?,
+// 23 blk_desc, 24 blk_ent_start, 25 ents (pair tables of the general chunks), 27 long-track headers, 28 sky_index, 29 sky_first,
+// 30 sky_start (host), 31 cmask, 32 cam_of_slot, 33 the ten numbers of mpsfm_ba_dense_plan
+int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t cap) {
+  if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
+  const void* src = nullptr;
+  int64_t bytes = 0;
+  bool host = false;
+  const int64_t nr = h->nrec, np1 = h->np + 1, nf = h->nfixed;
+  switch (which) {
+    case 0: src = h->d_chunks; bytes = (int64_t)sizeof(ChunkHdr) * h->nchunks; break;
+    case 1: src = h->d_chunk_cams; bytes = 4 * h->n_chunk_cams; break;
+    case 2: src = h->rt.rec_cam; bytes = 4 * nr; break;
+    case 3: src = h->rt.rec_pt; bytes = 4 * nr; break;
+    case 4: src = h->rt.rec_meta; bytes = 4 * nr; break;
+    case 5: src = h->rt.rec_xy; bytes = 16 * nr; break;
+    case 6: src = h->rt.rec_d; bytes = 8 * nr; break;
+    case 7: src = h->rt.rec_m; bytes = 8 * nr; break;
+    case 8: src = h->rt.rec_a; bytes = 8 * nr; break;
+    case 9: src = h->rt.pt_rec_start; bytes = 4 * np1; break;
+    case 10: src = h->rt.pt_kv; bytes = 2 * np1; break;
+    case 11: src = h->rt.fx_cam; bytes = 4 * nf; break;
+    case 12: src = h->rt.fx_pt; bytes = 4 * nf; break;
+    case 13: src = h->rt.fx_meta; bytes = 4 * nf; break;
+    case 14: src = h->rt.fx_xy; bytes = 16 * nf; break;
+    case 15: src = h->rt.fx_d; bytes = 8 * nf; break;
+    case 16: src = h->rt.fx_m; bytes = 8 * nf; break;
+    case 17: src = h->rt.fx_a; bytes = 8 * nf; break;
+    case 18: src = h->perm.data(); bytes = 4 * (int64_t)h->perm.size(); host = true; break;
+    case 19: src = h->d_red_dests; bytes = (int64_t)sizeof(RedDest) * h->n_red_dests; break;
+    case 20: src = h->d_red_srcs; bytes = 4 * h->n_red_srcs; break;
+    case 21: src = h->cam_slot_h.data(); bytes = 4 * (int64_t)h->cam_slot_h.size(); host = true; break;
+    case 23: src = h->d_blk_desc; bytes = 4 * h->n_blk_desc; break;
+    case 24: src = h->d_blk_ent_start; bytes = 4 * h->n_blk_ent_start; break;
+    case 25: src = h->d_ents; bytes = 4 * h->n_ents; break;
+    case 26: src = h->d_part; bytes = 32 * (int64_t)h->nchunks; break;
+    case 22: { static uint8_t flag; flag = h->built_on_device ? 1 : 0; src = &flag; bytes = 1; host = true; break; }
+    case 27: src = h->d_lhdr; bytes = (int64_t)sizeof(LongHdr) * h->nlong; break;
+    case 28: src = h->spat.sky_index.data(); bytes = 4 * (int64_t)h->spat.sky_index.size(); host = true; break;
+    case 29: src = h->spat.sky_first.data(); bytes = 4 * (int64_t)h->spat.sky_first.size(); host = true; break;
+    case 30: src = h->spat.sky_start.data(); bytes = 8 * (int64_t)h->spat.sky_start.size(); host = true; break;
+    case 31: src = h->d_cmask; bytes = 48 * (int64_t)h->nc; break;
+    case 32: src = h->d_cam_of_slot; bytes = 4 * (int64_t)std::max(h->ncv, 1); break;
+    case 33: { static thread_local int64_t info[10]; if (int rc = mpsfm_ba_dense_plan(h, info)) return rc; src = info; bytes = 80; host = true; break; }
+    default: return fail(MPSFM_EINVAL, "unknown table");
+  }
+  if (!out || cap < bytes) return bytes;
+  if (bytes == 0) return 0;
+  if (host) { std::memcpy(out, src, (size_t)bytes); return bytes; }
+  if (hipSetDevice(h->device) != hipSuccess) return fail(MPSFM_EHIP, "hipSetDevice failed");
+  if (hipMemcpyAsync(out, src, (size_t)bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return fail(MPSFM_EHIP, "copy failed");
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(MPSFM_EHIP, "sync failed");
+  return bytes;
+}
+
+// Diagnostics / tests (tests/test_build_tables_cpu.py; no device involved): build_tables — the function mpsfm_ba_create runs — for
+// a single rank and without the device stages on `P`, then table `which` copied out: numbering, arguments and return value of
+// mpsfm_debug_table (26 is a work buffer and does not exist here).  Rebuilds on every call.
+int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* out, int64_t cap) {
+  if (int rc = check_problem(P)) return rc;
+  BuildOptions opt = BuildOptions::from_environment();
+  TableBuild B;
+  if (int rc = build_tables(P, opt, SumExchange(), false, 0, [](const char*) {}, nullptr, B)) return rc;
+  const CameraLayout& cams = B.cams;
+  const CholPlan& plan = B.plan;
+  const HostTables& T = B.tables.t;
+  const SPattern& S = B.spat;
+  const SlabTables& slabs = B.slabs;
+
+  const void* src = nullptr;
+  int64_t bytes = 0;
+  const int64_t nr = T.nrec, nf = T.nfixed;
+  std::vector<int32_t> cam_of_slot;
+  int64_t info[10];
+  const uint8_t on_device = 0;
+  auto vec = [&](const auto& v) { src = v.data(); bytes = (int64_t)(sizeof(v[0]) * v.size()); };
+  switch (which) {
+    case 0: vec(T.chunks); break;
+    case 1: vec(T.chunk_cams); break;
+    case 2: src = T.rec_cam.data(); bytes = 4 * nr; break;
+    case 3: src = T.rec_pt.data(); bytes = 4 * nr; break;
+    case 4: src = T.rec_meta.data(); bytes = 4 * nr; break;
+    case 5: src = T.rec_xy.data(); bytes = 16 * nr; break;
+    case 6: src = T.rec_d.data(); bytes = 8 * nr; break;
+    case 7: src = T.rec_m.data(); bytes = 8 * nr; break;
+    case 8: src = T.rec_a.data(); bytes = 8 * nr; break;
+    case 9: vec(T.pt_rec_start); break;
+    case 10: vec(T.pt_kv); break;
+    case 11: src = T.fx_cam.data(); bytes = 4 * nf; break;
+    case 12: src = T.fx_pt.data(); bytes = 4 * nf; break;
+    case 13: src = T.fx_meta.data(); bytes = 4 * nf; break;
+    case 14: src = T.fx_xy.data(); bytes = 16 * nf; break;
+    case 15: src = T.fx_d.data(); bytes = 8 * nf; break;
+    case 16: src = T.fx_m.data(); bytes = 8 * nf; break;
+    case 17: src = T.fx_a.data(); bytes = 8 * nf; break;
+    case 18: vec(T.order); break;
+    case 19: vec(slabs.dests); break;
+    case 20: vec(slabs.srcs); break;
+    case 21: vec(cams.slot); break;
+    case 22: src = &on_device; bytes = 1; break;
+    case 23: vec(T.blk_desc); break;
+    case 24: vec(T.blk_ent_start); break;
+    case 25: vec(T.ents); break;
+    case 27: vec(T.lhdr); break;
+    case 28: vec(S.sky_index); break;
+    case 29: vec(S.sky_first); break;
+    case 30: vec(S.sky_start); break;
+    case 31: vec(cams.cmask); break;
+    case 32: cam_of_slot = cam_of_slot_table(cams); vec(cam_of_slot); break;
+    case 33: {
+      DenseOverlap ov;
+      LevelPlanDev lp;
+      opt.apply_dense(cams.nt, plan, ov);
+      level_plan_flags(plan, lp);
+      double work = 0.0;
+      dense_plan_numbers(cams.ncv, cams.nt, plan, ov, lp, &work, S.nblk, info);
+      src = info; bytes = 80;
+      break;
+    }
+    default: return fail(MPSFM_EINVAL, "unknown table");
+  }
+  if (!out || cap < bytes) return bytes;
+  if (bytes > 0) std::memcpy(out, src, (size_t)bytes);
+  return bytes;
+}
+
+int mpsfm_ba_sweep_parts(mpsfm_ba_handle* h, float ms[3], int64_t info[4]) {
+  if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
+  MPSFM_TRY(hipSetDevice(h->device));
+  if (ms)
+    for (int k = 0; k < 3; ++k) MPSFM_TRY(hipEventElapsedTime(&ms[k], h->ev[k], h->ev[k + 1]));
+  if (info) { info[0] = h->n_dense; info[1] = h->nchunks - h->n_dense; info[2] = h->nlong; info[3] = h->n_red_dests; }
+  return 0;
+}
+
+// phase clocks of the last single-launch solve (local_lm.hip), 100 MHz ticks: sweep, barrier 1, dense + cameras, update, barrier 2,
+// decision, iterations, then (debug flag 64 << 8) inside the dense phase: assemble, stacked factorisations, their barrier, trailing
+// updates, back substitution (none of these while mpsfm_debug_local_skew is armed: slot 11 then sums the ticks the hook waited);
+// returns 0 when the handle does not take that path
+int mpsfm_debug_local_clocks(mpsfm_ba_handle* h, int64_t out[12]) {
+  if (!h || !h->local_ok) return 0;
+  if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return 0;
+  if (hipMemcpy(out, h->d_local_sync + 1, sizeof(int64_t) * 12, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return 1;
+}
+// test hook of the single-launch solver: in every solve launched from now on, workgroup `chunk` (negative: counted from the last;
+// reduced modulo the grid) waits `ticks` of the 100 MHz wall clock at each phase point of `phase_mask` (bits: P after barrier 0, A
+// track sweep, B after barrier 1, D update sweep, E after barrier 2); clock slot 11 of mpsfm_debug_local_clocks sums the wait.
+// (0, 0, 0): off.  At most 2 ms per point, far below the grid barrier's bounded spin.
+int mpsfm_debug_local_skew(int32_t chunk, int32_t phase_mask, int64_t ticks) {
+  if (ticks < 0 || ticks > kSkewMaxTicks) return fail(MPSFM_EINVAL, "skew ticks must lie in [0, 200000] (2 ms at 100 MHz)");
+  if (phase_mask & ~kSkewAll) return fail(MPSFM_EINVAL, "skew phase mask: bits 0-4 (P, A, B, D, E)");
+  g_local_skew = LocalSkew{chunk, phase_mask, ticks};
+  return 0;
+}
+int mpsfm_ba_dense_solve_once(mpsfm_ba_handle* h, float* elapsed_ms) {
+  if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
+  MPSFM_TRY(hipSetDevice(h->device));
+  MPSFM_TRY(hipEventRecord(h->ev[0], h->stream));
+  if (int rc = run_dense(h, h->last_radius)) return rc;
+  MPSFM_TRY(hipEventRecord(h->ev[1], h->stream));
+  MPSFM_TRY(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));  // no k_cam_update follows here to re-arm the flag
+  MPSFM_TRY(hipStreamSynchronize(h->stream));
+  MPSFM_TRY(hipGetLastError());
+  float ms = 0.f;
+  MPSFM_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+  if (elapsed_ms) *elapsed_ms = ms;
+  return 0;
+}
+
+// S and rhs of the last sweep (with the LM damping of its radius), plus the last dense solution
+// S and the right-hand side in the CALLER's camera order (6 rows per variable camera), whatever slot order the handle uses.
+int mpsfm_ba_get_reduced_system(mpsfm_ba_handle* h, double* S, double* rhs, int32_t n) {
+  if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
+  if (n != h->n_user) return fail(MPSFM_EINVAL, "n does not match the reduced dimension");
+  MPSFM_TRY(hipSetDevice(h->device));
+  std::vector<double> red((size_t)h->red_count);
+  MPSFM_TRY(hipMemcpyAsync(red.data(), h->d_red, sizeof(double) * red.size(), hipMemcpyDeviceToHost, h->stream));
+  MPSFM_TRY(hipStreamSynchronize(h->stream));
+  const double* Sb = red.data(); const double* gc = Sb + h->sblk_count; const double* wv = gc + h->n_user; const double* dU = wv + h->n_user;
+  const mpsfm_ba_options& o = h->opt;
+  const BlockSky sky{h->spat.sky_first.data(), h->spat.sky_start.data(), h->spat.sky_index.empty() ? nullptr : h->spat.sky_index.data(), h->ncv};
+  for (int R = 0; R < n; ++R)
+    for (int C = 0; C < n; ++C) {
+      const int br = h->nat_slot[(size_t)(R / 6)], a = R % 6, bc = h->nat_slot[(size_t)(C / 6)], b = C % 6;
+      double v;
+      const int lo = std::min(br, bc), hi = std::max(br, bc);
+      if (!sky_has(sky, lo, hi)) v = 0.0;
+      else if (br < bc) v = Sb[sky_block(sky, br, bc) * 36 + a * 6 + b];
+      else if (br > bc) v = Sb[sky_block(sky, bc, br) * 36 + b * 6 + a];
+      else v = Sb[sky_block(sky, br, br) * 36 + (a <= b ? a * 6 + b : b * 6 + a)];
+      if (R == C) v += std::min(std::max(dU[6 * br + a], o.min_lm_diagonal), o.max_lm_diagonal) / h->last_radius;
+      if (S) S[(size_t)R * n + C] = v;
+    }
+  if (rhs) for (int i = 0; i < n; ++i) { const int q = 6 * h->nat_slot[(size_t)(i / 6)] + i % 6; rhs[i] = wv[q] - gc[q]; }
+  return 0;
+}
+
+int mpsfm_ba_get_dense_solution(mpsfm_ba_handle* h, double* y, int32_t n) {
+  if (!h || !y) return fail(MPSFM_EINVAL, "handle or y is NULL");
+  if (n != h->n_user) return fail(MPSFM_EINVAL, "n does not match the reduced dimension");
+  MPSFM_TRY(hipSetDevice(h->device));
+  std::vector<double> ys((size_t)std::max(h->n_user, 1));
+  MPSFM_TRY(hipMemcpyAsync(ys.data(), h->d_yc, sizeof(double) * (size_t)h->n_user, hipMemcpyDeviceToHost, h->stream));
+  MPSFM_TRY(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n; ++i) y[i] = ys[(size_t)(6 * h->nat_slot[(size_t)(i / 6)] + i % 6)];
+  return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,140 @@
+// The bundle-adjustment handle and what more than one of its files needs: ba_build.hip creates and frees it, ba_comm.hip sums over
+// the ranks of a landmark-sharded run, ba_solver.hip solves on it, ba_debug.hip probes it.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <vector>
+
+#include "ba_launch.h"
+#include "build_host.h"
+#include "common.h"
+#include "dev_resources.h"
+#include "devbuild.h"
+
+struct mpsfm_ba_handle {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  void* comm = nullptr;  // ncclComm_t of a landmark-sharded run with use_rccl
+  mpsfm::DenseOverlap ov;  // second stream for the dense factorisation in outer panels (MPSFM_CHOL_NB)
+  mpsfm::SPattern spat;                    // which blocks of S exist: block skyline or index form (up to kIndexMaxSlots slots), host copies
+  int32_t* d_sky_first = nullptr;
+  int64_t* d_sky_start = nullptr;
+  int32_t* d_sky_index = nullptr;
+  mpsfm::CholPlan plan;                    // camera order, tile elimination tree and launch tables of the dense factorisation (chol_plan.h)
+  mpsfm::LevelPlanDev lp;
+  mpsfm::CholItem* d_lp_items = nullptr;
+  uint8_t* d_lp_live = nullptr;
+  int32_t* d_lp_col_slot = nullptr;
+  int32_t *d_lp_srcs = nullptr, *d_lp_rows = nullptr, *d_lp_struct_start = nullptr, *d_lp_struct_rows = nullptr, *d_lp_back_cols = nullptr, *d_lp_asm = nullptr;
+  std::vector<int32_t> nat_slot;    // variable camera in the caller's order -> slot (the accessors of S and y speak the caller's order)
+  int n_user = 0;                   // 6 x variable cameras: the reduced dimension the caller sees and the length of the slot-indexed vectors (n counts the
+                                    // system's columns incl. the alignment padding)
+  bool own_stream = false;
+  mpsfm_ba_options opt{};
+  mpsfm::LossParams loss{};
+  // sizes
+  int nc = 0, np_user = 0;
+  int64_t np = 0, np_chunked = 0;   // re-ordered landmarks (all referenced) / those inside chunks
+  int64_t nrec = 0, nfixed = 0, nblocks_total = 0, nblocks_reduced = 0;
+  double nblocks_global = 0, nblocks_reduced_global = 0, nvarpts_global = 0;
+  int ncv = 0, n = 0, nt = 0, nchunks = 0, nlong = 0;
+  int n_dense = 0;                  // chunks [0, n_dense) are swept by k_track_sweep_dense, the rest by the general kernel
+  double* d_slab = nullptr;         // slabs of the dense chunks
+  mpsfm::RedDest* d_red_dests = nullptr;   // slab reduction: destination parts and their sources
+  int32_t* d_red_srcs = nullptr;
+  int n_red_dests = 0;
+  int64_t n_red_srcs = 0, n_chunk_cams = 0, n_blk_desc = 0, n_blk_ent_start = 0, n_ents = 0;  // table sizes (diagnostics: mpsfm_debug_table)
+  bool built_on_device = false;
+  mpsfm::LongHdr* d_lhdr = nullptr;
+  double* d_wl = nullptr;
+  int64_t red_count = 0, sblk_count = 0;
+  std::vector<int32_t> perm;        // re-ordered landmark -> caller's index
+  int32_t* d_cam_of_slot = nullptr; // slot -> camera (the fused camera update of k_update_sweep)
+  int32_t* d_perm = nullptr;        // device copy, and the landmarks in the caller's order as last uploaded: the state crosses the bus
+  double* d_user_pts = nullptr;     // unpermuted and is re-ordered on the device (every landmark referenced: np == np_user)
+  std::vector<int32_t> cam_slot_h;
+  // device state
+  double *d_q = nullptr, *d_t = nullptr, *d_q2 = nullptr, *d_t2 = nullptr, *d_q0 = nullptr, *d_t0 = nullptr;
+  double *d_pts = nullptr, *d_pts2 = nullptr, *d_pts0 = nullptr;
+  double *d_intr = nullptr, *d_cmask = nullptr, *d_cs = nullptr, *d_camtab = nullptr, *d_camtab2 = nullptr;
+  int32_t *d_intr_idx = nullptr, *d_cam_slot = nullptr;
+  double *d_ps = nullptr, *d_diagV = nullptr;
+  mpsfm::ChunkHdr* d_chunks = nullptr;
+  int32_t *d_chunk_cams = nullptr, *d_blk_ent_start = nullptr;
+  uint32_t *d_blk_desc = nullptr, *d_ents = nullptr;
+  mpsfm::RecTablesDev rt;           // record and fixed-record tables
+  // reduced buffer: Sblk | gc | wv | diagU | scalars
+  double* d_red = nullptr;
+  double *d_Sblk = nullptr, *d_gc = nullptr, *d_wv = nullptr, *d_diagU = nullptr, *d_redsc = nullptr;
+  double *d_part = nullptr, *d_part2 = nullptr, *d_scal = nullptr, *d_costpart = nullptr;
+  double* h_scal = nullptr;  // pinned
+  mpsfm::LmCtl* d_ctl = nullptr;    // Levenberg-Marquardt control block (device) and the two pinned slots its copies land in
+  mpsfm::LmCtl* h_ctl = nullptr;
+  hipEvent_t ev2[4] = {nullptr, nullptr, nullptr, nullptr};  // second set of phase events (two iterations are in flight)
+  double *d_A = nullptr, *d_yc = nullptr, *d_dwork = nullptr;
+  int* d_fail = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  double last_radius = 1e4;
+  bool scales_ready = false;
+  // single-launch solver of small problems (local_lm.hip): two accumulators | barrier words + clocks | per-iteration heads
+  bool local_ok = false;
+  double* d_local_acc = nullptr;
+  int64_t* d_local_sync = nullptr;   // [0]: two 32-bit barrier words, [1..4]: phase clocks
+  mpsfm::LmHead* d_local_log = nullptr;
+  int local_log_cap = 0;
+};
+
+namespace mpsfm {
+
+inline bool sharded(const mpsfm_ba_handle* h) { return h->opt.allreduce != nullptr || h->comm != nullptr; }
+
+// ---- ba_build.hip: handle creation
+// What the phases of the table build produce.
+struct TableBuild {
+  CameraLayout cams;
+  CholPlan plan;        // camera order, tile elimination tree and launch tables of the dense factorisation
+  SPattern spat;        // which 6x6 blocks of S exist
+  DevBuildOut tables;   // .t: the host tables of either build; the rest: the device build's tables
+  SlabTables slabs;
+  double nblocks_global = 0, nblocks_reduced_global = 0, nvarpts_global = 0;  // totals over the ranks
+  bool built_on_device = false;
+  bool slab_tables_on_device = false;  // slabs holds diag_block only: DevBuilder::slab_tables forms the reduction tables behind the uploads
+};
+// The device build where it applies (devbuild.h): its builder, created by build_tables, and the stream its copies run on.
+struct DeviceStages {
+  hipStream_t stream = nullptr;
+  std::unique_ptr<DevBuilder> builder;
+};
+
+int check_problem(const mpsfm_ba_problem* P);
+// The list of the build's phases.  `opt` gets its chunk caps on the way; `exchange` sums host values over the ranks of a `sharded`
+// build (empty: one rank); `dev` NULL: host phases only.
+int build_tables(const mpsfm_ba_problem* P, BuildOptions& opt, const SumExchange& exchange, bool sharded, int verbose, const Lap& lap, DeviceStages* dev,
+                 TableBuild& out);
+void level_plan_flags(const CholPlan& PL, LevelPlanDev& D);
+
+int create_impl(const mpsfm_ba_problem* P, const mpsfm_ba_state* st, const mpsfm_ba_options* o, mpsfm_ba_handle** out);
+int upload_state(mpsfm_ba_handle* h, const mpsfm_ba_state* st, bool as_initial);
+void free_handle(mpsfm_ba_handle* h);
+
+// ---- ba_comm.hip: RCCL, loaded at run time, and the caller's all-reduce hook
+int comm_init_rank(mpsfm_ba_handle* h);  // h->comm from h->opt (use_rccl)
+void comm_destroy(void* comm);
+// sum `count` doubles over the ranks in place (one rank: nothing): complete on return / enqueued on the handle's stream
+int allreduce_host(mpsfm_ba_handle* h, double* buf, int64_t count);
+int allreduce_dev(mpsfm_ba_handle* h, double* buf, int64_t count);
+
+// ---- ba_solver.hip: the pieces of an iteration the probes of ba_debug.hip run on their own
+SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);
+// Jacobi column scales from the Jacobian at the current state (Ceres: iteration 0 only)
+int prepare_scales(mpsfm_ba_handle* h);
+// one track sweep at the current state: fills the reduced buffer and its scalar tail (inside the solve loop the prologue kernel
+// has zeroed the buffer; single-rank runs reduce the partials with the decision)
+int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool in_loop = false, bool adopt = false);
+int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);
+
+// the single-launch solver's skew hook (mpsfm_debug_local_skew): process-wide like g_dbg_flags, read when a solve is launched
+struct LocalSkew { int32_t chunk = 0, mask = 0; int64_t ticks = 0; };
+extern LocalSkew g_local_skew;
+
+}  // namespace mpsfm

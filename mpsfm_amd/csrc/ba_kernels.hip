@@ -10,6 +10,7 @@
 //   k_update_sweep  back-substitution of the landmark steps, model cost change, candidate
 //                   landmarks and the candidate cost in one pass over the same chunks.
 #include "common.h"
+#include "ba_launch.h"
 #include "sweep_common.h"
 #include "sweep_update_body.h"
 #include "lm_decide.h"
@@ -902,8 +903,6 @@ void launch_lm_pack(const double* scal, double* sums, hipStream_t s) { hipLaunch
 void launch_lm_init(LmCtl* ctl, const double* scal, const double* sums, hipStream_t s) { hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, s, ctl, scal, sums); }
 
 // ---- launch wrappers ------------------------------------------------------------------------------
-void init_tile_tables(hipStream_t) {}
-
 void launch_track_sweep(const SweepArgs& a, int nchunks, bool diag_only, hipStream_t s) {
   if (nchunks > 0) {
     if (diag_only) hipLaunchKernelGGL(k_track_sweep<MODE_DIAG>, dim3(nchunks), dim3(kThreads), 0, s, a);

@@ -1,4 +1,4 @@
-// Device-side table build of the bundle-adjustment handle (gfx950): what `build()` in ba_solver.hip does on host threads —
+// Device-side table build of the bundle-adjustment handle (gfx950): what `build_tables()` in ba_build.hip does on host threads —
 // residual blocks grouped by landmark, merged into records, landmarks ordered by their camera-slot lists, the greedy chunk cut,
 // the record arrays — as HIP kernels over the caller's raw observation lists.  The reference assembles a NEW problem for every
 // Optimizer.ba() call (mpsfm/sfm/mapper/bundle_adjustment.py:184, 285-293), so the tables are on the critical path of every call.
@@ -34,14 +34,10 @@
 #include <vector>
 
 #include "common.h"
+#include "dev_resources.h"
 #include "devbuild.h"
 
 namespace mpsfm {
-extern thread_local std::string g_err;
-int staged_upload(void* dst, const void* src, size_t bytes);
-int staged_drain();
-static int dfail(int code, const std::string& m) { g_err = m; return code; }
-#define DB_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return dfail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 namespace {
 constexpr int kT = 256;
@@ -110,7 +106,7 @@ __global__ __launch_bounds__(kT) void k_graph(int np, const int32_t* pstart, con
 }
 
 // The merge of a landmark's sorted blocks into records, shared by the counting and the writing pass: per camera the k-th
-// reprojection block and the k-th depth block form record k (host build(), "Phase B").  emit(cam, slot, flags, reproj source or
+// reprojection block and the k-th depth block form record k (host build, "Phase B").  emit(cam, slot, flags, reproj source or
 // -1, depth source or -1).
 template <class Emit>
 __device__ __forceinline__ void merge_blocks(int ps, int n, const int32_t* blk_cam, const int32_t* blk_key, const uint32_t* blk_src, Emit&& emit) {
@@ -613,10 +609,10 @@ struct DevBuilder::Impl {
   template <class F>
   int with_temp(F&& f) {
     size_t bytes = 0;
-    if (f(nullptr, bytes) != hipSuccess) return dfail(MPSFM_EHIP, "rocPRIM size query failed");
+    if (f(nullptr, bytes) != hipSuccess) return fail(MPSFM_EHIP, "rocPRIM size query failed");
     void* tmp = alloc<uint8_t>(std::max<size_t>(bytes, 16));
-    if (!tmp) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
-    return f(tmp, bytes) == hipSuccess ? 0 : dfail(MPSFM_EHIP, "rocPRIM call failed");
+    if (!tmp) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+    return f(tmp, bytes) == hipSuccess ? 0 : fail(MPSFM_EHIP, "rocPRIM call failed");
   }
   // raw input
   int32_t *obs_cam = nullptr, *obs_pt = nullptr, *dobs_cam = nullptr, *dobs_pt = nullptr;
@@ -640,7 +636,7 @@ int DevBuilder::stage1(const mpsfm_ba_problem* P, hipStream_t stream, const std:
                        std::vector<uint64_t>& graph_bits, int graph_words, int64_t* max_blocks_per_landmark) {
   Impl& M = *m;
   M.s = stream; M.nc = P->n_cams; M.np = P->n_pts; M.n_obs = P->n_obs; M.n_dobs = P->n_dobs; M.nblk = P->n_obs + P->n_dobs;
-  if (M.nblk > (int64_t)INT_MAX / 2) return dfail(MPSFM_EUNSUPPORTED, "device build: more than 2^30 residual blocks");
+  if (M.nblk > (int64_t)INT_MAX / 2) return fail(MPSFM_EUNSUPPORTED, "device build: more than 2^30 residual blocks");
   const size_t no = (size_t)M.n_obs, nd = (size_t)M.n_dobs, np = (size_t)M.np, nc = (size_t)M.nc;
   M.obs_cam = M.alloc<int32_t>(no); M.obs_pt = M.alloc<int32_t>(no); M.obs_xy = M.alloc<double>(2 * no);
   M.dobs_cam = M.alloc<int32_t>(nd); M.dobs_pt = M.alloc<int32_t>(nd); M.dobs_depth = M.alloc<double>(nd); M.dobs_mag = M.alloc<double>(nd);
@@ -650,7 +646,7 @@ int DevBuilder::stage1(const mpsfm_ba_problem* P, hipStream_t stream, const std:
   M.err = M.alloc<int32_t>(4);
   M.bits = M.alloc<unsigned long long>((size_t)std::max(ncv_real, 1) * (size_t)std::max(graph_words, 1));
   if (P->shift_logscale) M.shift = M.alloc<double>(2 * nc);
-  for (void* p : M.blocks) if (!p) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+  for (void* p : M.blocks) if (!p) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   int rc = 0;
   if (no) {
     if ((rc = staged_upload(M.obs_cam, P->obs_cam, 4 * no))) return rc;
@@ -668,11 +664,11 @@ int DevBuilder::stage1(const mpsfm_ba_problem* P, hipStream_t stream, const std:
   if (nc && (rc = staged_upload(M.nat, nat_slot.data(), 4 * nc))) return rc;
   if (M.shift && (rc = staged_upload(M.shift, P->shift_logscale, 16 * nc))) return rc;
   if ((rc = staged_drain())) return rc;
-  DB_TRY(hipMemsetAsync(M.cnt_pt, 0, 4 * (np + 1), M.s));
-  DB_TRY(hipMemsetAsync(M.cnt_cam, 0, 4 * std::max<size_t>(nc, 1), M.s));
-  DB_TRY(hipMemsetAsync(M.fill, 0, 4 * (np + 1), M.s));
-  DB_TRY(hipMemsetAsync(M.err, 0, 16, M.s));
-  DB_TRY(hipMemsetAsync(M.bits, 0, 8 * (size_t)std::max(ncv_real, 1) * (size_t)std::max(graph_words, 1), M.s));
+  MPSFM_TRY(hipMemsetAsync(M.cnt_pt, 0, 4 * (np + 1), M.s));
+  MPSFM_TRY(hipMemsetAsync(M.cnt_cam, 0, 4 * std::max<size_t>(nc, 1), M.s));
+  MPSFM_TRY(hipMemsetAsync(M.fill, 0, 4 * (np + 1), M.s));
+  MPSFM_TRY(hipMemsetAsync(M.err, 0, 16, M.s));
+  MPSFM_TRY(hipMemsetAsync(M.bits, 0, 8 * (size_t)std::max(ncv_real, 1) * (size_t)std::max(graph_words, 1), M.s));
   const int grid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (M.nblk + kT - 1) / kT));
   hipLaunchKernelGGL(k_count, dim3(grid), dim3(kT), (size_t)4 * std::max(M.nc, 1), M.s, M.n_obs, M.n_dobs, M.obs_cam, M.obs_pt, M.dobs_cam, M.dobs_pt, M.dobs_depth,
                      M.nc, M.np, M.cnt_pt, M.cnt_cam, M.err);
@@ -682,18 +678,18 @@ int DevBuilder::stage1(const mpsfm_ba_problem* P, hipStream_t stream, const std:
     hipLaunchKernelGGL(k_graph, dim3((unsigned)((np + kT - 1) / kT)), dim3(kT), 0, M.s, M.np, M.pstart, M.blk_cam, M.pt_const, M.nat, graph_words, M.bits);
   // to the host: block counts per camera, the graph, the error flags, the longest block list
   std::vector<int32_t> cc(std::max<size_t>(nc, 1)), er(4), cp(np + 1);
-  DB_TRY(hipMemcpyAsync(cc.data(), M.cnt_cam, 4 * nc, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipMemcpyAsync(er.data(), M.err, 16, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipMemcpyAsync(cc.data(), M.cnt_cam, 4 * nc, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipMemcpyAsync(er.data(), M.err, 16, hipMemcpyDeviceToHost, M.s));
   graph_bits.assign((size_t)std::max(ncv_real, 0) * (size_t)graph_words, 0);
-  if (!graph_bits.empty()) DB_TRY(hipMemcpyAsync(graph_bits.data(), M.bits, 8 * graph_bits.size(), hipMemcpyDeviceToHost, M.s));
+  if (!graph_bits.empty()) MPSFM_TRY(hipMemcpyAsync(graph_bits.data(), M.bits, 8 * graph_bits.size(), hipMemcpyDeviceToHost, M.s));
   // the longest block list: a max-reduction over the counts (rocPRIM)
   int32_t* d_max = M.alloc<int32_t>(1);
-  if (!d_max) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!d_max) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::reduce(t, b, M.cnt_pt, d_max, 0, np + 1, rocprim::maximum<int32_t>(), M.s); }))) return rc;
   int32_t mx = 0;
-  DB_TRY(hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipStreamSynchronize(M.s));
-  if (er[0] & 1) return dfail(MPSFM_EINVAL, "depth prior must be positive");
+  MPSFM_TRY(hipMemcpyAsync(&mx, d_max, 4, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipStreamSynchronize(M.s));
+  if (er[0] & 1) return fail(MPSFM_EINVAL, "depth prior must be positive");
   cam_counts.assign(nc + 1, 0.0);
   for (size_t i = 0; i < nc; ++i) cam_counts[i] = (double)cc[i];
   *max_blocks_per_landmark = mx;
@@ -718,24 +714,24 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   uint16_t* lm_slots = M.alloc<uint16_t>(np * kLmSlots + 8);
   int32_t *has_rec = M.alloc<int32_t>(np + 1), *fix_only = M.alloc<int32_t>(np + 1), *nfix = M.alloc<int32_t>(np + 1);
   int32_t *pos = M.alloc<int32_t>(np + 1), *fpos = M.alloc<int32_t>(np + 1), *fix_off = M.alloc<int32_t>(np + 1);
-  if (!d_slot || !info || !lm_slots || !has_rec || !fix_only || !nfix || !pos || !fpos || !fix_off) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!d_slot || !info || !lm_slots || !has_rec || !fix_only || !nfix || !pos || !fpos || !fix_off) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   if (nc && (rc = staged_upload(d_slot, slot_of_cam.data(), 4 * nc))) return rc;
   if ((rc = staged_drain())) return rc;
   const unsigned gnp = (unsigned)std::max<size_t>(1, (np + kT - 1) / kT);
   if (np) hipLaunchKernelGGL(k_sortmerge, dim3(gnp), dim3(kT), 0, M.s, M.np, M.pstart, M.blk_cam, M.blk_key, M.blk_src, d_slot, M.pt_const, dense_on ? 1 : 0, info, lm_slots);
   lap("allocations + sort/merge per landmark");
   if (np) hipLaunchKernelGGL(k_flags, dim3(gnp), dim3(kT), 0, M.s, M.np, info, has_rec, fix_only, nfix);
-  DB_TRY(hipMemsetAsync(has_rec + np, 0, 4, M.s));
-  DB_TRY(hipMemsetAsync(fix_only + np, 0, 4, M.s));
-  DB_TRY(hipMemsetAsync(nfix + np, 0, 4, M.s));
+  MPSFM_TRY(hipMemsetAsync(has_rec + np, 0, 4, M.s));
+  MPSFM_TRY(hipMemsetAsync(fix_only + np, 0, 4, M.s));
+  MPSFM_TRY(hipMemsetAsync(nfix + np, 0, 4, M.s));
   if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, has_rec, pos, 0, np + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
   if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, fix_only, fpos, 0, np + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
   if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, nfix, fix_off, 0, np + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
   int32_t tot[3] = {0, 0, 0};
-  DB_TRY(hipMemcpyAsync(&tot[0], pos + np, 4, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipMemcpyAsync(&tot[1], fpos + np, 4, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipMemcpyAsync(&tot[2], fix_off + np, 4, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipStreamSynchronize(M.s));
+  MPSFM_TRY(hipMemcpyAsync(&tot[0], pos + np, 4, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipMemcpyAsync(&tot[1], fpos + np, 4, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipMemcpyAsync(&tot[2], fix_off + np, 4, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipStreamSynchronize(M.s));
   lap("flags + three scans + sync");
   const int n_withrec = tot[0], n_fixonly = tot[1], n_fixed = tot[2];
   const int n_order = n_withrec + n_fixonly;
@@ -746,8 +742,8 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   int32_t *cand = M.alloc<int32_t>(nw), *cand1 = M.alloc<int32_t>(nw);
   int32_t* order = M.alloc<int32_t>((size_t)std::max(n_order, 1));
   int32_t* counts = M.alloc<int32_t>(4);
-  if (!kA || !kB || !kS || !kG || !cand || !cand1 || !order || !counts) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
-  DB_TRY(hipMemsetAsync(counts, 0, 16, M.s));
+  if (!kA || !kB || !kS || !kG || !cand || !cand1 || !order || !counts) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  MPSFM_TRY(hipMemsetAsync(counts, 0, 16, M.s));
   int32_t cl[4] = {0, 0, 0, 0};
   if (n_withrec > 0) {
     int nslots = 0;
@@ -764,20 +760,20 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
       hipLaunchKernelGGL(k_gather_keys, dim3(gw), dim3(kT), 0, M.s, n_withrec, cand1, pos, kA, kG);
       if ((rc = M.with_temp([&](void* t, size_t& sz) { return rocprim::radix_sort_pairs(t, sz, kG, kS, cand1, order, (size_t)n_withrec, 0, (unsigned)(2 + 4 * b), M.s); }))) return rc;
     }
-    DB_TRY(hipMemcpyAsync(cl, counts, 16, hipMemcpyDeviceToHost, M.s));
+    MPSFM_TRY(hipMemcpyAsync(cl, counts, 16, hipMemcpyDeviceToHost, M.s));
   }
   lap("landmark order (radix sort)");
   if (n_fixonly > 0) hipLaunchKernelGGL(k_append_fixed_only, dim3(gnp), dim3(kT), 0, M.s, M.np, fix_only, fpos, n_withrec, order);
   int32_t* inv = M.alloc<int32_t>(np + 1);
   int32_t* nrec_k = M.alloc<int32_t>((size_t)n_order + 1);
   int32_t* rec_off = M.alloc<int32_t>((size_t)n_order + 2);
-  if (!inv || !nrec_k || !rec_off) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!inv || !nrec_k || !rec_off) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   if (n_order > 0) hipLaunchKernelGGL(k_inverse, dim3((unsigned)((n_order + kT - 1) / kT)), dim3(kT), 0, M.s, n_order, order, info, inv, nrec_k, n_withrec);
-  DB_TRY(hipMemsetAsync(nrec_k + n_order, 0, 4, M.s));
+  MPSFM_TRY(hipMemsetAsync(nrec_k + n_order, 0, 4, M.s));
   if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, nrec_k, rec_off, 0, (size_t)n_order + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
   int32_t nrec_total = 0;
-  DB_TRY(hipMemcpyAsync(&nrec_total, rec_off + n_order, 4, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipStreamSynchronize(M.s));
+  MPSFM_TRY(hipMemcpyAsync(&nrec_total, rec_off + n_order, 4, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipStreamSynchronize(M.s));
   lap("inverse + record offsets + sync");
   const int n_long = cl[2];
   const int np_chunked = n_withrec - n_long;
@@ -790,7 +786,7 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   const int W = std::max(1, (nslots + 63) / 64);
   const bool jump = W <= 16;  // camera sets of up to 1024 slots: the parallel form (k_next / k_walk); beyond: one wave per segment (k_cut)
   int32_t *seg_nch = M.alloc<int32_t>(65), *seg_ncam = M.alloc<int32_t>(65), *cbase = M.alloc<int32_t>(66), *cambase = M.alloc<int32_t>(66);
-  if (!seg_nch || !seg_ncam || !cbase || !cambase) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!seg_nch || !seg_ncam || !cbase || !cambase) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   int32_t hb[2][66];
   std::memset(hb, 0, sizeof(hb));
   TmpChunk* tmp_chunks = nullptr;
@@ -804,9 +800,9 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
     hvk = M.alloc<uint8_t>((size_t)np_chunked);
     int32_t* next = M.alloc<int32_t>((size_t)np_chunked);
     starts = M.alloc<int32_t>((size_t)np_chunked);
-    if (!lmask || !rpk || !hvk || !next || !starts) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+    if (!lmask || !rpk || !hvk || !next || !starts) return fail(MPSFM_ENOMEM, "hipMalloc failed");
     const unsigned gk = (unsigned)((np_chunked + kT - 1) / kT);
-    DB_TRY(hipMemsetAsync(seg_ncam, 0, 4 * 65, M.s));
+    MPSFM_TRY(hipMemsetAsync(seg_ncam, 0, 4 * 65, M.s));
     switch (Wp) {
       case 1: hipLaunchKernelGGL(k_lm_masks<1>, dim3(gk), dim3(kT), 0, M.s, np_chunked, order, info, lm_slots, M.pstart, M.blk_key, lmask, rpk, hvk);
               hipLaunchKernelGGL(k_next<1>, dim3(gk), dim3(kT), 0, M.s, np_chunked, nseg, lmask, rpk, hvk, next, rec_cap, pts_by_cams); break;
@@ -821,18 +817,18 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
     }
     hipLaunchKernelGGL(k_walk, dim3(1), dim3(64), 0, M.s, np_chunked, nseg, next, starts, seg_nch);
     hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(64), 0, M.s, nseg, seg_nch, seg_ncam, cbase, cambase);
-    DB_TRY(hipMemcpyAsync(hb[0], cbase, 4 * (size_t)(nseg + 1), hipMemcpyDeviceToHost, M.s));
-    DB_TRY(hipStreamSynchronize(M.s));
+    MPSFM_TRY(hipMemcpyAsync(hb[0], cbase, 4 * (size_t)(nseg + 1), hipMemcpyDeviceToHost, M.s));
+    MPSFM_TRY(hipStreamSynchronize(M.s));
   } else if (np_chunked > 0) {
     tmp_chunks = M.alloc<TmpChunk>((size_t)np_chunked);
     tmp_cams = M.alloc<int32_t>((size_t)std::max(nrec_total, 1));
     int32_t* lm_chunk = M.alloc<int32_t>((size_t)np_chunked);
-    if (!tmp_chunks || !tmp_cams || !lm_chunk) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+    if (!tmp_chunks || !tmp_cams || !lm_chunk) return fail(MPSFM_ENOMEM, "hipMalloc failed");
     hipLaunchKernelGGL(k_cut, dim3(nseg), dim3(64), (size_t)64 * W * 8, M.s, np_chunked, nseg, W, order, info, lm_slots, M.pstart, M.blk_key, rec_off, tmp_chunks, tmp_cams, lm_chunk, seg_nch, seg_ncam, rec_cap);
     hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(64), 0, M.s, nseg, seg_nch, seg_ncam, cbase, cambase);
-    DB_TRY(hipMemcpyAsync(hb[0], cbase, 4 * (size_t)(nseg + 1), hipMemcpyDeviceToHost, M.s));
-    DB_TRY(hipMemcpyAsync(hb[1], cambase, 4 * (size_t)(nseg + 1), hipMemcpyDeviceToHost, M.s));
-    DB_TRY(hipStreamSynchronize(M.s));
+    MPSFM_TRY(hipMemcpyAsync(hb[0], cbase, 4 * (size_t)(nseg + 1), hipMemcpyDeviceToHost, M.s));
+    MPSFM_TRY(hipMemcpyAsync(hb[1], cambase, 4 * (size_t)(nseg + 1), hipMemcpyDeviceToHost, M.s));
+    MPSFM_TRY(hipStreamSynchronize(M.s));
   }
   lap("chunk cut");
   const int nchunks = hb[0][nseg];
@@ -841,7 +837,7 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   auto own = [&](size_t bytes) { return cached_malloc(std::max<size_t>(bytes, 8)); };
   const size_t nr = (size_t)std::max(nrec_total, 1), nf = (size_t)std::max(n_fixed, 1), no = (size_t)std::max(n_order, 1);
   out.d_chunks = (ChunkHdr*)own(sizeof(ChunkHdr) * (size_t)std::max(nchunks, 1));
-  if (!out.d_chunks) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!out.d_chunks) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   unsigned long long* csets = nullptr;
   int32_t* cam0 = nullptr;
   if (jump && nchunks > 0) {
@@ -849,7 +845,7 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
     csets = M.alloc<unsigned long long>((size_t)nchunks * Wp);
     int32_t* cncam = M.alloc<int32_t>((size_t)nchunks + 1);
     cam0 = M.alloc<int32_t>((size_t)nchunks + 1);
-    if (!csets || !cncam || !cam0) { (void)hipStreamSynchronize(M.s); out.release(); return dfail(MPSFM_ENOMEM, "hipMalloc failed"); }
+    if (!csets || !cncam || !cam0) { (void)hipStreamSynchronize(M.s); out.release(); return fail(MPSFM_ENOMEM, "hipMalloc failed"); }
     const unsigned gc = (unsigned)((nchunks + kT - 1) / kT);
     switch (Wp) {
       case 1: hipLaunchKernelGGL(k_chunk_sets<1>, dim3(gc), dim3(kT), 0, M.s, nchunks, np_chunked, nseg, cbase, starts, lmask, rec_off, hvk, out.d_chunks, cncam, csets); break;
@@ -858,10 +854,10 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
       case 8: hipLaunchKernelGGL(k_chunk_sets<8>, dim3(gc), dim3(kT), 0, M.s, nchunks, np_chunked, nseg, cbase, starts, lmask, rec_off, hvk, out.d_chunks, cncam, csets); break;
       default: hipLaunchKernelGGL(k_chunk_sets<16>, dim3(gc), dim3(kT), 0, M.s, nchunks, np_chunked, nseg, cbase, starts, lmask, rec_off, hvk, out.d_chunks, cncam, csets); break;
     }
-    DB_TRY(hipMemsetAsync(cncam + nchunks, 0, 4, M.s));
+    MPSFM_TRY(hipMemsetAsync(cncam + nchunks, 0, 4, M.s));
     if ((rc = M.with_temp([&](void* t, size_t& sz) { return rocprim::exclusive_scan(t, sz, cncam, cam0, 0, (size_t)nchunks + 1, rocprim::plus<int32_t>(), M.s); }))) { (void)hipStreamSynchronize(M.s); out.release(); return rc; }
-    DB_TRY(hipMemcpyAsync(&ncams, cam0 + nchunks, 4, hipMemcpyDeviceToHost, M.s));
-    DB_TRY(hipStreamSynchronize(M.s));
+    MPSFM_TRY(hipMemcpyAsync(&ncams, cam0 + nchunks, 4, hipMemcpyDeviceToHost, M.s));
+    MPSFM_TRY(hipStreamSynchronize(M.s));
   }
   out.d_chunk_cams = (int32_t*)own(4 * (size_t)std::max(ncams, 1));
   out.rt.rec_cam = (int32_t*)own(4 * nr); out.rt.rec_pt = (int32_t*)own(4 * nr); out.rt.rec_meta = (uint32_t*)own(4 * nr);
@@ -872,8 +868,8 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   unsigned long long* counters = M.alloc<unsigned long long>(2);
   void* all[] = {out.d_chunks, out.d_chunk_cams, out.rt.rec_cam, out.rt.rec_pt, out.rt.rec_meta, out.rt.rec_xy, out.rt.rec_d, out.rt.rec_m, out.rt.rec_a, out.rt.pt_rec_start,
                  out.rt.pt_kv, out.rt.fx_cam, out.rt.fx_pt, out.rt.fx_meta, out.rt.fx_xy, out.rt.fx_d, out.rt.fx_m, out.rt.fx_a, counters};
-  for (void* p : all) if (!p) { (void)hipStreamSynchronize(M.s); out.release(); return dfail(MPSFM_ENOMEM, "hipMalloc failed"); }
-  DB_TRY(hipMemsetAsync(counters, 0, 16, M.s));
+  for (void* p : all) if (!p) { (void)hipStreamSynchronize(M.s); out.release(); return fail(MPSFM_ENOMEM, "hipMalloc failed"); }
+  MPSFM_TRY(hipMemsetAsync(counters, 0, 16, M.s));
   if (nchunks > 0 && jump) {
     const unsigned gc = (unsigned)((nchunks + kT - 1) / kT);
     switch (Wp) {
@@ -893,21 +889,21 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
                        M.dobs_par, M.shift, O, counters, M.err);
   lap("final tables: allocate, chunks, records");
   // the sentinel entry of pt_rec_start / pt_kv
-  DB_TRY(hipMemcpyAsync(out.rt.pt_rec_start + n_order, &nrec_total, 4, hipMemcpyHostToDevice, M.s));
+  MPSFM_TRY(hipMemcpyAsync(out.rt.pt_rec_start + n_order, &nrec_total, 4, hipMemcpyHostToDevice, M.s));
   const uint16_t kv_none = 0xffff;
-  DB_TRY(hipMemcpyAsync(out.rt.pt_kv + n_order, &kv_none, 2, hipMemcpyHostToDevice, M.s));
+  MPSFM_TRY(hipMemcpyAsync(out.rt.pt_kv + n_order, &kv_none, 2, hipMemcpyHostToDevice, M.s));
   // ---- to the host: chunk headers, camera lists, the landmark order, counters
   out.t.chunks.resize((size_t)nchunks); out.t.chunk_cams.resize((size_t)ncams); out.t.order.resize((size_t)n_order);
   unsigned long long hc[2] = {0, 0};
   int32_t er[4] = {0, 0, 0, 0};
-  if (nchunks) DB_TRY(hipMemcpyAsync(out.t.chunks.data(), out.d_chunks, sizeof(ChunkHdr) * (size_t)nchunks, hipMemcpyDeviceToHost, M.s));
-  if (ncams) DB_TRY(hipMemcpyAsync(out.t.chunk_cams.data(), out.d_chunk_cams, 4 * (size_t)ncams, hipMemcpyDeviceToHost, M.s));
-  if (n_order) DB_TRY(hipMemcpyAsync(out.t.order.data(), order, 4 * (size_t)n_order, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipMemcpyAsync(hc, counters, 16, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipMemcpyAsync(er, M.err, 16, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipStreamSynchronize(M.s));
+  if (nchunks) MPSFM_TRY(hipMemcpyAsync(out.t.chunks.data(), out.d_chunks, sizeof(ChunkHdr) * (size_t)nchunks, hipMemcpyDeviceToHost, M.s));
+  if (ncams) MPSFM_TRY(hipMemcpyAsync(out.t.chunk_cams.data(), out.d_chunk_cams, 4 * (size_t)ncams, hipMemcpyDeviceToHost, M.s));
+  if (n_order) MPSFM_TRY(hipMemcpyAsync(out.t.order.data(), order, 4 * (size_t)n_order, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipMemcpyAsync(hc, counters, 16, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipMemcpyAsync(er, M.err, 16, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipStreamSynchronize(M.s));
   lap("downloads");
-  if (er[0] & 2) { out.release(); return dfail(MPSFM_EINVAL, "shifted/scaled depth prior must be positive"); }
+  if (er[0] & 2) { out.release(); return fail(MPSFM_EINVAL, "shifted/scaled depth prior must be positive"); }
   out.t.nblk_reduced = (int64_t)hc[0]; out.t.nvarpts = (double)hc[1];
   return 0;
 }
@@ -927,21 +923,21 @@ int DevBuilder::slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t
   int32_t* nparts = M.alloc<int32_t>((size_t)ndst + 1);
   int32_t* pstart = M.alloc<int32_t>((size_t)ndst + 1);
   uint8_t* is_diag = M.alloc<uint8_t>((size_t)std::max<int64_t>(nsb, 1));
-  if (!nent || !ent0 || !cnt || !start || !nparts || !pstart || !is_diag) return dfail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!nent || !ent0 || !cnt || !start || !nparts || !pstart || !is_diag) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   hipLaunchKernelGGL(k_slab_entry_counts, dim3((unsigned)((n_dense + 1 + kT - 1) / kT)), dim3(kT), 0, M.s, n_dense, d_chunks, nent);
   if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, nent, ent0, 0, (size_t)n_dense + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
   int32_t n_ent = 0;
-  DB_TRY(hipMemcpyAsync(&n_ent, ent0 + n_dense, 4, hipMemcpyDeviceToHost, M.s));
-  DB_TRY(hipMemsetAsync(cnt, 0, 4 * ((size_t)ndst + 1), M.s));
-  DB_TRY(hipMemsetAsync(is_diag, 0, (size_t)std::max<int64_t>(nsb, 1), M.s));
-  DB_TRY(hipMemsetAsync(M.err, 0, 16, M.s));
-  DB_TRY(hipStreamSynchronize(M.s));
+  MPSFM_TRY(hipMemcpyAsync(&n_ent, ent0 + n_dense, 4, hipMemcpyDeviceToHost, M.s));
+  MPSFM_TRY(hipMemsetAsync(cnt, 0, 4 * ((size_t)ndst + 1), M.s));
+  MPSFM_TRY(hipMemsetAsync(is_diag, 0, (size_t)std::max<int64_t>(nsb, 1), M.s));
+  MPSFM_TRY(hipMemsetAsync(M.err, 0, 16, M.s));
+  MPSFM_TRY(hipStreamSynchronize(M.s));
   if (n_ent <= 0) return 0;
   uint32_t* key = M.alloc<uint32_t>((size_t)n_ent);
   uint32_t* key_s = M.alloc<uint32_t>((size_t)n_ent);
   int32_t* val = M.alloc<int32_t>((size_t)n_ent);
   int32_t* val_s = (int32_t*)cached_malloc(4 * (size_t)n_ent);  // becomes the source list: owned by the caller
-  if (!key || !key_s || !val || !val_s) { cached_free(val_s); return dfail(MPSFM_ENOMEM, "hipMalloc failed"); }
+  if (!key || !key_s || !val || !val_s) { cached_free(val_s); return fail(MPSFM_ENOMEM, "hipMalloc failed"); }
   auto bail = [&](int code) { (void)hipStreamSynchronize(M.s); cached_free(val_s); return code; };
   hipLaunchKernelGGL(k_slab_entries, dim3((unsigned)n_dense), dim3(64), 0, M.s, n_dense, d_chunks, d_chunk_cams, sky, nsb, ndst, ent0, key, val, cnt, M.err);
   hipLaunchKernelGGL(k_slab_mark_diag, dim3((unsigned)((ncv + kT - 1) / kT)), dim3(kT), 0, M.s, ncv, d_diag_block, nsb, is_diag);
@@ -954,12 +950,12 @@ int DevBuilder::slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t
   int32_t tot[2] = {0, 0}, er[4] = {0, 0, 0, 0};
   if (hipMemcpyAsync(&tot[0], start + ndst, 4, hipMemcpyDeviceToHost, M.s) != hipSuccess || hipMemcpyAsync(&tot[1], pstart + ndst, 4, hipMemcpyDeviceToHost, M.s) != hipSuccess ||
       hipMemcpyAsync(er, M.err, 16, hipMemcpyDeviceToHost, M.s) != hipSuccess || hipStreamSynchronize(M.s) != hipSuccess)
-    return bail(dfail(MPSFM_EHIP, "device build: copying the slab table sizes failed"));
-  if (er[1]) return bail(dfail(MPSFM_EUNSUPPORTED, "internal: block index beyond S"));
+    return bail(fail(MPSFM_EHIP, "device build: copying the slab table sizes failed"));
+  if (er[1]) return bail(fail(MPSFM_EUNSUPPORTED, "internal: block index beyond S"));
   RedDest* dests = (RedDest*)cached_malloc(sizeof(RedDest) * (size_t)std::max(tot[1], 1));
-  if (!dests) return bail(dfail(MPSFM_ENOMEM, "hipMalloc failed"));
+  if (!dests) return bail(fail(MPSFM_ENOMEM, "hipMalloc failed"));
   hipLaunchKernelGGL(k_slab_parts, dim3((unsigned)((ndst + kT - 1) / kT)), dim3(kT), 0, M.s, ndst, nsb, cnt, start, pstart, is_diag, dests);
-  if (hipGetLastError() != hipSuccess) { cached_free(dests); return bail(dfail(MPSFM_EHIP, "device build: slab table kernels failed")); }
+  if (hipGetLastError() != hipSuccess) { cached_free(dests); return bail(fail(MPSFM_EHIP, "device build: slab table kernels failed")); }
   *d_dests = dests; *n_dests = tot[1]; *d_srcs = val_s; *n_srcs = tot[0];
   return 0;
 }

@@ -1,6 +1,6 @@
 // Host phases of the table build of mpsfm_ba_create (build_host.hip): from the caller's observation lists to the chunked record
 // tables, the block pattern of S and the slab reduction tables.  Plain C++ on host threads: no handle, no HIP call, so
-// mpsfm_debug_host_build runs them where there is no device.  build() in ba_solver.hip is the list of these phases plus the
+// mpsfm_debug_host_build runs them where there is no device.  build_tables() in ba_build.hip is the list of these phases plus the
 // device build (devbuild.h), the exchanges over ranks and the uploads.
 #pragma once
 #include <cstdint>
@@ -35,7 +35,9 @@ struct BuildOptions {
 
 // sums `count` doubles over the ranks in place, returns 0 or an error code; empty: one rank
 typedef std::function<int(double*, int64_t)> SumExchange;
-typedef std::function<void(const char*)> Lap;  // build()'s stopwatch (verbose >= 2)
+typedef std::function<void(const char*)> Lap;  // build_tables()'s stopwatch (verbose >= 2)
+// lap(what) prints `format` (what, milliseconds since the previous lap) when `on`
+Lap stopwatch(bool on, const char* format);
 
 // The tables both builds hand to the uploads.  The device build fills the small host members only (chunks, cameras, order, counts).
 struct HostTables {

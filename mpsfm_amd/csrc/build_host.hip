@@ -1,8 +1,9 @@
 // Host phases of the table build (build_host.h): plain C++ on host threads, no HIP call.
 #include "build_host.h"
 
-#include "local_lm.h"
+#include "ba_launch.h"
 
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -14,10 +15,14 @@
 
 namespace mpsfm {
 
-int dense_plain_max_tiles();  // dense_chol.hip
-int dense_inv_rows();
-
-static int fail(int code, const char* msg) { g_err = msg; return code; }
+Lap stopwatch(bool on, const char* format) {
+  return [on, format, t_prev = std::chrono::steady_clock::now()](const char* what) mutable {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, format, what, 1e3 * std::chrono::duration<double>(now - t_prev).count());
+    t_prev = now;
+  };
+}
 
 // ---- host threads and recycled host blocks (host_parts.h) ------------------------------------------------------------------
 HostBlockCache& host_cache() { static HostBlockCache c; return c; }

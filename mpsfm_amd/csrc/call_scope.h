@@ -3,24 +3,22 @@
 // included on either side of a header that sets `#pragma clang fp contract`.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "dev_resources.h"
 
 namespace mpsfm {
 
-extern thread_local std::string g_err;
-// uploads through the calling thread's pinned staging buffer (ba_solver.hip); staged_drain() completes them
-int staged_upload(void* dst, const void* src, size_t bytes);
-int staged_drain();
-
-inline int fail(int code, const std::string& m) { g_err = m; return code; }
-#define MPSFM_TRY(expr)                                                                              \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) return fail(MPSFM_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+// host arrays a call refuses when they hold a NaN or an infinity
+template <typename T>
+inline bool all_finite(const T* a, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return false;
+  return true;
+}
 
 // the device ordinal of a call: checked, then made current
 inline int open_device(int32_t device) {

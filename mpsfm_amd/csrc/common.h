@@ -262,7 +262,7 @@ __host__ __device__ inline int64_t ut_block(int64_t i, int64_t j, int64_t ncv) {
 }
 // Block-skyline storage of the upper block triangle of S: column j keeps the blocks (i, j), first[j] <= i <= j, at
 // start[j] + (i - first[j]) — first[j] is the lowest camera slot that shares a landmark with slot j on ANY rank
-// (ba_solver.hip build()), so every block a sweep can touch exists, and the buffer the ranks all-reduce holds the blocks
+// (build_tables in ba_build.hip), so every block a sweep can touch exists, and the buffer the ranks all-reduce holds the blocks
 // that can be nonzero instead of all ncv (ncv + 1) / 2 (C4: 11 MB instead of 144 MB).
 //
 // Two forms.  index != NULL (up to kIndexMaxSlots slots): index[j * ns + i], i <= j, is the block's position or -1 — exactly
@@ -364,14 +364,6 @@ struct CostArgs {
   LossParams loss;
   double* part;  // [gridDim.x][4]: reproj cost, depth cost, bad
 };
-// Caching device allocator (ba_solver.hip): hipMalloc / hipFree cost 10-300 us each and a handle makes ~60 of
-// them; freed blocks are kept per device (up to a cap) and handed out again — with whatever an earlier owner
-// left in them: every consumer initialises what it reads (MPSFM_POISON=1 fills each block with 0xFF to prove it).
-void* cached_malloc(size_t bytes);
-void cached_free(void* p);
-// recycled non-blocking streams (ba_solver.hip); a released stream must be idle
-hipError_t pooled_stream(hipStream_t* s);
-void release_stream(hipStream_t s);
 
 constexpr int kPanelWavesDefault = 4;
 // second stream + events for the outer-panel look-ahead of the dense factorisation (dense_chol.hip)

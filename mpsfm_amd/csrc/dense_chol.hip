@@ -7,7 +7,9 @@
 // the forward substitution z = L^-1 rhs falls out of the factorisation; k_backsub then solves
 // L^T y = z.
 #include "common.h"
+#include "ba_launch.h"
 #include "dense_tile.h"
+#include "dev_resources.h"
 
 namespace mpsfm {
 

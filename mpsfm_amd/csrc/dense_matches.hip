@@ -238,11 +238,6 @@ void fill_info(mpsfm_nms_info* info, const NmsRun& run, double ms) {
 }
 
 bool box_ok(const Box2& b) { return std::isfinite(b.hi[0] - b.lo[0]) && std::isfinite(b.hi[1] - b.lo[1]); }
-bool all_finite(const double* a, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(a[i])) return false;
-  return true;
-}
 int64_t count_ones(const uint8_t* k, size_t n) {
   int64_t c = 0;
   for (size_t i = 0; i < n; ++i) c += k[i] != 0;

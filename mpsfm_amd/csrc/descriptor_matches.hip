@@ -252,16 +252,6 @@ __global__ __launch_bounds__(kDT) void k_scan_finite(const float* __restrict__ x
 }
 
 inline dim3 blocks_of(int64_t n) { return dim3((unsigned)((n + kDT - 1) / kDT)); }
-bool all_finite(const float* a, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(a[i])) return false;
-  return true;
-}
-bool all_finite(const double* a, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(a[i])) return false;
-  return true;
-}
 // a float32 keypoint coordinate may overflow where the float64 one is finite
 bool kps_ok(const double* k, size_t n) {
   for (size_t i = 0; i < 2 * n; ++i)

@@ -1,4 +1,4 @@
-// What the host phases of the table build (build_host.hip) and their callers in ba_solver.hip share: host threads (run_parts on a
+// What the host phases of the table build (build_host.hip) and their callers (ba_build.hip, dev_resources.hip, ba_solver.hip) share: host threads (run_parts on a
 // persistent worker pool), recycled host blocks (HostBlockCache / HostBuf) and the pair tables of one chunk.  No device involved.
 #pragma once
 #include <algorithm>
@@ -14,10 +14,9 @@
 #include <vector>
 
 #include "common.h"
+#include "dev_resources.h"
 
 namespace mpsfm {
-
-extern thread_local std::string g_err;  // ba_solver.hip: what mpsfm_last_error returns
 
 // Large host blocks of the table build come from a process-wide cache: a fresh 40 MB block costs its page faults on first
 // touch and an munmap on release (several ms per create at C3); a recycled one costs neither.  Power-of-two buckets from

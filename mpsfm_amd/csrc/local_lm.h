@@ -1,4 +1,4 @@
-// Single-launch Levenberg-Marquardt for small problems (local bundle adjustment): interface between ba_solver.hip and local_lm.hip.
+// Single-launch Levenberg-Marquardt for small problems (local bundle adjustment): the arguments of its launch (ba_launch.h), shared by ba_solver.hip and local_lm.hip.
 #pragma once
 #include "common.h"
 
@@ -35,10 +35,5 @@ struct LocalArgs {
 // (the reduced system), before the update sweep, after barrier 2 (the partial rows and the decision)
 enum : int32_t { kSkewP = 1, kSkewA = 2, kSkewB = 4, kSkewD = 8, kSkewE = 16, kSkewAll = 31 };
 constexpr long long kSkewMaxTicks = 200000;  // 2 ms of the 100 MHz wall clock, far below a grid barrier's bounded spin
-
-// co-resident workgroups the device offers the kernel (0: cooperative launches unavailable)
-int local_lm_max_chunks(int device);
-// enqueues the solve; returns a hipError_t as int
-int launch_local_lm(const LocalArgs& a, hipStream_t s);
 
 }  // namespace mpsfm

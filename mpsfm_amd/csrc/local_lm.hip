@@ -20,6 +20,7 @@
 //
 // Every spin is bounded: a barrier that does not complete raises the abort flag, every workgroup leaves, the host reports an error.
 #include "local_lm.h"
+#include "ba_launch.h"
 #include "sweep_common.h"
 #include "sweep_dense_body.h"
 #include "sweep_update_body.h"

@@ -24,6 +24,7 @@
 // reduced buffer: 0.7 MB of atomics at C3 instead of 24 MB, and a fixed summation order per destination part.
 // LDS: 53.4 KB per workgroup = three workgroups per CU.
 #include "sweep_dense_body.h"
+#include "ba_launch.h"
 #include <algorithm>
 
 namespace mpsfm {

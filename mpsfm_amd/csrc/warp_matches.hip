@@ -231,11 +231,6 @@ int scan_device(CallScope& A, const float* x, int64_t nx, const int64_t* ids, in
   return 0;
 }
 
-bool all_finite(const float* a, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (!std::isfinite(a[i])) return false;
-  return true;
-}
 bool box_ok(const Box2& b) { return std::isfinite(b.hi[0] - b.lo[0]) && std::isfinite(b.hi[1] - b.lo[1]); }
 
 // the five pool stages of simple_nms over d_s [H][W] into d_out (both on the device, distinct)

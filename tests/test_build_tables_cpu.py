@@ -1,7 +1,7 @@
 """The host phases of the table build (csrc/build_host.hip) against the tables of the commit before they were split out of
 `build()`: tests/golden/build_tables.npz, recorded on the MI355X from handles created with MPSFM_DEV_BUILD=0
-(tests/golden/make_golden_build_tables.py).  The phases run here through mpsfm_debug_host_build — the same functions `build()`
-calls, without a device.  Every table bit for bit (dtype, length, SHA-256); rec_d / fx_d = log depth, the only values that pass
+(tests/golden/make_golden_build_tables.py).  The phases run here through mpsfm_debug_host_build, which calls build_tables()
+(csrc/ba_build.hip) — the function mpsfm_ba_create runs — for one rank and without the device stages.  Every table bit for bit (dtype, length, SHA-256); rec_d / fx_d = log depth, the only values that pass
 through libm, within 4 spacings where the golden stores them in full (the bound tests/test_gpu_devbuild.py uses between two
 implementations of log) — the cases that store digests only skip those two tables unless they hold no logarithm (case j: no
 depth priors)."""

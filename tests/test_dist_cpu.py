@@ -97,7 +97,7 @@ def test_strong_scaling_shards_reassemble_to_the_single_rank_problem():
 
 @pytest.mark.parametrize("world", [1, 2, 3, 5, 8, 64])
 def test_camera_graph_union_through_the_sum_exchange(world):
-    """What the ranks of a sharded run do at handle creation (ba_solver.hip pack_graph / unpack_graph): adjacency indicators
+    """What the ranks of a sharded run do at handle creation (build_host.hip pack_graph / unpack_graph, called by build_tables in ba_build.hip): adjacency indicators
     packed as base-(world+1) digits, summed, unpacked — equals the OR of the ranks' graphs, for every world size the summed
     digits stay exact."""
     import ctypes as C

@@ -1,4 +1,4 @@
-"""The dense reduced-camera solve (dense_chol.hip, chol_plan.hip, the dense part of ba_solver.hip) on camera graphs and sizes
+"""The dense reduced-camera solve (dense_chol.hip, chol_plan.hip, run_dense in ba_solver.hip) on camera graphs and sizes
 that no make_scene orbit reaches: every factorisation path (level schedule, per-step skyline, outer panels with the 2 x 2
 tile update and the second-stream look-ahead) and every substitution path (inverse accumulators, back levels, groups of
 four tile rows), each selected through the handle's own switches and each PROVEN selected through dense_plan().
