@@ -206,6 +206,11 @@ class BAHandle:
                 "s_blocks", "backsub_launches"]
         return dict(zip(keys, (int(x) for x in v)))
 
+    def pt_handoff(self) -> bool:
+        """True when the handle's track sweep hands the landmark factors to its update sweep, False when that sweep recomputes them."""
+        lib().mpsfm_debug_pt_handoff.argtypes = [C.c_void_p]
+        return bool(lib().mpsfm_debug_pt_handoff(self._h))
+
     def sweep_once(self, radius: float = 1e4) -> float:
         ms = C.c_float(0)
         _check(lib().mpsfm_ba_sweep_once(self._h, radius, C.byref(ms)))

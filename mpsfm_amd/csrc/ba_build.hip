@@ -21,7 +21,7 @@ void free_handle(mpsfm_ba_handle* h) {
   // handle on another stream or host thread may receive them at once.
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->ov.s2) (void)hipStreamSynchronize(h->ov.s2);
-  void* ptrs[] = {h->d_q, h->d_t, h->d_q2, h->d_t2, h->d_q0, h->d_t0, h->d_pts, h->d_pts2, h->d_pts0, h->d_intr, h->d_cmask,
+  void* ptrs[] = {h->d_q, h->d_t, h->d_q2, h->d_t2, h->d_q0, h->d_t0, h->d_pts, h->d_pts2, h->d_pts0, h->d_pt_fac, h->d_intr, h->d_cmask,
                   h->d_cs, h->d_camtab, h->d_camtab2, h->d_intr_idx, h->d_cam_slot, h->d_ps, h->d_diagV, h->d_chunks,
                   h->d_chunk_cams, h->d_blk_ent_start, h->d_blk_desc, h->d_ents, h->d_red, h->d_part, h->d_part2, h->d_scal, h->d_costpart, h->d_A, h->d_yc, h->d_dwork, h->d_fail, h->d_lhdr, h->d_wl, h->d_slab, h->d_red_dests, h->d_red_srcs,
                   h->d_sky_first, h->d_sky_start, h->d_sky_index,
@@ -212,6 +212,8 @@ static int alloc_work_buffers(mpsfm_ba_handle* h, const BuildOptions& opt) {
   for (double** p : {&h->d_q, &h->d_q2, &h->d_q0}) if ((rc = dev_alloc(p, ncs * 4))) return rc;
   for (double** p : {&h->d_t, &h->d_t2, &h->d_t0}) if ((rc = dev_alloc(p, ncs * 3))) return rc;
   for (double** p : {&h->d_pts, &h->d_pts2, &h->d_pts0, &h->d_ps, &h->d_diagV}) if ((rc = dev_alloc(p, nps * 3))) return rc;
+  // every chunk dense, no long track (fused_prologue's condition in solve_impl): the track sweep hands the landmark factors on
+  if (h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks) if ((rc = dev_alloc(&h->d_pt_fac, nps * 9))) return rc;
   if ((rc = dev_alloc(&h->d_cs, ncs * 6))) return rc;
   if ((rc = dev_alloc(&h->d_camtab, ncs * kCamRec))) return rc;
   if ((rc = dev_alloc(&h->d_camtab2, ncs * kCamRec))) return rc;

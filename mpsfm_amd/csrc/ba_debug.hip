@@ -84,6 +84,10 @@ int mpsfm_ba_dense_plan(mpsfm_ba_handle* h, int64_t info[10]) {
   return 0;
 }
 
+// 1: the handle's track sweep hands the landmark factors to its update sweep (every chunk dense, no long track; MPSFM_PT_HANDOFF=0
+// still selects the recompute form per solve), 0: its update sweep recomputes them
+int mpsfm_debug_pt_handoff(mpsfm_ba_handle* h) { return h && h->d_pt_fac != nullptr ? 1 : 0; }
+
 int mpsfm_ba_sweep_once(mpsfm_ba_handle* h, double radius, float* elapsed_ms) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   MPSFM_TRY(hipSetDevice(h->device));

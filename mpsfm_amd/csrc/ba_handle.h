@@ -59,6 +59,8 @@ struct mpsfm_ba_handle {
   double *d_intr = nullptr, *d_cmask = nullptr, *d_cs = nullptr, *d_camtab = nullptr, *d_camtab2 = nullptr;
   int32_t *d_intr_idx = nullptr, *d_cam_slot = nullptr;
   double *d_ps = nullptr, *d_diagV = nullptr;
+  double* d_pt_fac = nullptr;       // [np][9] landmark factors and gradients, track sweep -> update sweep (SweepArgs::pt_fac); NULL: the
+                                    // handle has a general chunk or a long track and its update sweep recomputes them
   mpsfm::ChunkHdr* d_chunks = nullptr;
   int32_t *d_chunk_cams = nullptr, *d_blk_ent_start = nullptr;
   uint32_t *d_blk_desc = nullptr, *d_ents = nullptr;
@@ -130,7 +132,7 @@ SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullp
 int prepare_scales(mpsfm_ba_handle* h);
 // one track sweep at the current state: fills the reduced buffer and its scalar tail (inside the solve loop the prologue kernel
 // has zeroed the buffer; single-rank runs reduce the partials with the decision)
-int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool in_loop = false, bool adopt = false);
+int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool in_loop = false, bool adopt = false, bool handoff = false);
 int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);
 
 // the single-launch solver's skew hook (mpsfm_debug_local_skew): process-wide like g_dbg_flags, read when a solve is launched

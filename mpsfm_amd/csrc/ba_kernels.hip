@@ -330,14 +330,16 @@ __global__ __launch_bounds__(kThreads) void k_track_sweep(SweepArgs A) {
 // Update sweep: y_p = -(V+D)^-1 (g_p + W^T y_c), model cost change, candidate landmarks, candidate
 // cost.  Recomputes the linearisation (cheaper than storing 240 B per record in HBM).
 #ifndef MPSFM_UPD_OCC
-#define MPSFM_UPD_OCC 4  // 102 registers without spills; LDS (12 KB) no longer limits
+#define MPSFM_UPD_OCC 4  // 107 / 109 registers without spills; LDS (6.4 / 12 KB) does not limit.  5 means 96 registers: 34 spilled, 49.7 instead of 38 us
 #endif
+// kHandoff: F and g_p of every landmark come from the track sweep of the same iteration (SweepArgs::pt_fac)
+template <bool kHandoff>
 __global__ __launch_bounds__(kThreads, MPSFM_UPD_OCC) void k_update_sweep(SweepArgs A, CamUpdArgs U) {
   if (lm_over(A.ctl)) return;
   const double lm_radius = A.ctl ? lm_radius_of(A.ctl) : A.radius;
-  __shared__ UpdLds S;
+  __shared__ UpdLdsT<kHandoff> S;
   if (U.fuse && blockIdx.x == 0) cam_update_all(U, A.yc, S.red);  // (the candidate rows of this chunk come next, like everywhere)
-  update_sweep_chunk<false>(A, blockIdx.x, lm_radius, nullptr, nullptr, A.yc, S, U, U.fuse != 0);
+  update_sweep_chunk<false, kHandoff>(A, blockIdx.x, lm_radius, nullptr, nullptr, A.yc, S, U, U.fuse != 0);
 }
 
 // decode q in [0, k(k+1)/2) -> (i, j), i <= j < k, row-major upper triangle
@@ -916,7 +918,10 @@ void launch_track_sweep(const SweepArgs& a, int nchunks, bool diag_only, hipStre
 void launch_update_sweep(const SweepArgs& a, int nchunks, hipStream_t s, const CamUpdArgs* cu) {
   CamUpdArgs u{};
   if (cu) u = *cu;
-  if (nchunks > 0) hipLaunchKernelGGL(k_update_sweep, dim3(nchunks), dim3(kThreads), 0, s, a, u);
+  if (nchunks > 0) {
+    if (a.pt_fac) hipLaunchKernelGGL(k_update_sweep<true>, dim3(nchunks), dim3(kThreads), 0, s, a, u);
+    else hipLaunchKernelGGL(k_update_sweep<false>, dim3(nchunks), dim3(kThreads), 0, s, a, u);
+  }
   if (a.nlong > 0) hipLaunchKernelGGL(k_long_update_sweep, dim3(a.nlong), dim3(kThreads), 0, s, a);
 }
 void launch_cost_records(const CostArgs& a, int nblocks, hipStream_t s) {

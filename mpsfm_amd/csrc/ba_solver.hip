@@ -87,7 +87,7 @@ static void launch_sweeps(mpsfm_ba_handle* h, SweepArgs a, hipStream_t s) {
   launch_track_sweep(a, h->nchunks - h->n_dense, false, s);
 }
 
-int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in_loop, bool adopt) {
+int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in_loop, bool adopt, bool handoff) {
   hipStream_t s = h->stream;
   if (!in_loop) launch_zero(h->d_red, h->red_count, ctl, s);
   SweepArgs a = sweep_args(h, radius, ctl);
@@ -96,6 +96,7 @@ int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in
     a.pts_rw = h->d_pts; a.q_rw = h->d_q; a.t_rw = h->d_t; a.camtab_rw = h->d_camtab; a.q2 = h->d_q2; a.t2 = h->d_t2;
     a.red = h->d_red; a.nred = h->red_count;
   }
+  if (handoff) a.pt_fac = h->d_pt_fac;
   launch_sweeps(h, a, s);
   if (h->nchunks + h->nlong > 0 && !(in_loop && !sharded(h)))
     launch_reduce_cols(h->d_part, h->nchunks + h->nlong, 4, 3, 1u << 2, h->d_redsc, s, sharded(h) ? nullptr : h->d_scal + U_X_COST,
@@ -166,6 +167,9 @@ static int summary_from_ctl(mpsfm_ba_handle* h, const LmCtl& last, mpsfm_ba_summ
 // host synchronisation before the end — the loop is ONE cooperative launch (local_lm.hip).  Returns kLocalRefused when the launch
 // is not accepted (nothing has changed the state then: the launch chain takes over).
 constexpr int kLocalRefused = 1;
+// MPSFM_PT_HANDOFF=0: the update sweep recomputes the landmark factors everywhere (the comparison path); read per solve
+static bool pt_handoff_enabled() { const char* e = std::getenv("MPSFM_PT_HANDOFF"); return !(e && std::atoi(e) == 0); }
+
 static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   hipStream_t s = h->stream;
   const mpsfm_ba_options& o = h->opt;
@@ -181,6 +185,7 @@ static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   MPSFM_TRY(hipMemsetAsync(h->d_local_sync, 0, sizeof(int64_t) * 16, s));
   LocalArgs la{};
   la.A = sweep_args(h, 0.0, nullptr);
+  if (pt_handoff_enabled()) la.A.pt_fac = h->d_pt_fac;  // phase A -> phase D of the chunk's own workgroup
   la.ctl = h->d_ctl;
   la.o = lm_opts_of(o);
   la.log = o.verbose > 0 ? h->d_local_log : nullptr;
@@ -285,6 +290,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   const double no_radius = 0.0;  // inside the loop the kernels read the radius from the control block
   const bool fuse_prologue = [] { const char* e = std::getenv("MPSFM_FUSE_PROLOGUE"); return !(e && std::atoi(e) == 0); }();
   const bool fuse_cam = [] { const char* e = std::getenv("MPSFM_FUSE_CAM"); return !(e && std::atoi(e) == 0); }();
+  const bool pt_handoff = pt_handoff_enabled() && h->d_pt_fac != nullptr;  // (allocated where all chunks are dense and no track is long)
   auto enqueue_iteration = [&](int it) -> int {
     hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
     MPSFM_TRY(hipEventRecord(ev[0], s));
@@ -293,7 +299,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
     const bool fused_prologue = fuse_prologue && h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks;
     if (!fused_prologue)
       launch_lm_prologue(h->d_ctl, h->d_red, h->red_count, h->nc, h->np, h->d_q, h->d_t, h->d_camtab, h->d_pts, h->d_q2, h->d_t2, h->d_camtab2, h->d_pts2, s);
-    if (int rc = run_track_sweep(h, no_radius, ctl, true, fused_prologue)) return rc;
+    if (int rc = run_track_sweep(h, no_radius, ctl, true, fused_prologue, pt_handoff)) return rc;
     if (int rc = allreduce_dev(h, h->d_red, h->red_count)) return rc;
     MPSFM_TRY(hipEventRecord(ev[1], s));
     if (int rc = run_dense(h, no_radius, ctl)) return rc;
@@ -307,6 +313,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
                         h->d_intr, h->d_intr_idx, h->d_camtab2, h->d_fail, ctl);
     {
       SweepArgs a = sweep_args(h, no_radius, ctl);
+      if (pt_handoff) a.pt_fac = h->d_pt_fac;
       launch_update_sweep(a, h->nchunks, s, fused_cam ? &cu : nullptr);
     }
     if (!sharded(h)) {

@@ -342,6 +342,10 @@ struct SweepArgs {
   double* pts_rw; double* q_rw; double* t_rw; double* camtab_rw;
   const double* q2; const double* t2;
   double* red; int64_t nred;
+  // hand-off of the landmark factors from the dense track sweep to the update sweep of the same iteration (all chunks dense, no
+  // long tracks; NULL: the update sweep forms V_p, its factor and g_p again): 9 doubles per landmark, F = chol(V + D)^-1 as
+  // spd3_inv_factor packs it, then g_p.  F[0] == 0 marks a failed factorisation; the slot of a constant landmark is never written
+  double* pt_fac;
 };
 // k_update_sweep with the camera update in front (all chunks dense): every workgroup forms the candidate rows of ITS chunk's
 // cameras in LDS, workgroup 0 also does what k_cam_update does for all cameras (candidate poses and table, step and state norms,

@@ -13,7 +13,8 @@
 //      with the stored L(j,j)^-T) — redundant, but it saves the barrier a single solving workgroup would need
 //   C  candidate cameras in LDS (each workgroup keeps the variable cameras' state and table rows itself)
 //   D  update sweep of the chunk (update_sweep_chunk, the body of k_update_sweep): candidate landmarks, model cost change,
-//      candidate cost; the other accumulator is zeroed for the next iteration
+//      candidate cost; the other accumulator is zeroed for the next iteration.  The landmark factors and gradients of A reach it
+//      through SweepArgs::pt_fac as in the launch chain (written and read by the chunk's own workgroup)
 //   -- grid barrier 2 --
 //   E  every workgroup sums the chunks' partial rows in the same order and takes the same decision (lm_decide.h); an accepted
 //      candidate becomes the state (cameras in LDS, the chunk's own landmarks in HBM)
@@ -43,7 +44,8 @@ struct DenseSolveLds {
 };
 union PhaseLds {
   DenseLds sweep;
-  UpdLds upd;
+  UpdLdsT<false> upd;
+  UpdLdsT<true> upd_fac;
   DenseSolveLds dense;
 };
 constexpr int kPer3Decl = (kLocalCams * (kLocalCams + 1) / 2 * 36 + kThreads - 1) / kThreads;
@@ -416,7 +418,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_local_lm(LocalArgs G) {
 
     // ---- D: update sweep of the chunk; the other accumulator starts the next iteration from zero --------------------------------------
     skew_point(G, kSkewD, cix, nwg);
-    update_sweep_chunk<true>(A, cix, lm_radius, S.tab, S.tab2, S.y, U.upd, CamUpdArgs{}, false);
+    // (hand-off: phase A of this workgroup wrote the chunk's factors; barrier 1 waited for the stores and invalidated the CU's cache)
+    if (A.pt_fac) update_sweep_chunk<true, true>(A, cix, lm_radius, S.tab, S.tab2, S.y, U.upd_fac, CamUpdArgs{}, false);
+    else update_sweep_chunk<true, false>(A, cix, lm_radius, S.tab, S.tab2, S.y, U.upd, CamUpdArgs{}, false);
     {
       double* other = G.acc[par ^ 1];
       for (int e = cix * kThreads + tid; e < kLocalAccDoubles; e += nwg * kThreads) other[e] = 0.0;

@@ -184,15 +184,37 @@ __device__ __forceinline__ double record_cost(const double* __restrict__ cam, co
   return cost;
 }
 
+// Wave-wide sum and maximum on the vector pipe (DPP), valid in EVERY lane: row shifts sum along the 16-lane rows, row_bcast:15 and
+// row_bcast:31 carry the row totals on, lane 63 holds the result and is read back through a scalar register.  Lanes without a
+// source keep `old`: zero for the sum, the lane's own value for the maximum.  Call them with all 64 lanes active (lane 63 is read);
+// six ds_bpermute_b32 round trips per value on the LDS pipe before (round 5: -1 us per sweep, -2.4 us in k_lm_reduce_decide).
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double dpp_or_zero(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROWS, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROWS, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double dpp_or_self(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), CTRL, ROWS, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, ROWS, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double lane63(double v) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
 __device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
+  v += dpp_or_zero<0x111, 0xf>(v); v += dpp_or_zero<0x112, 0xf>(v); v += dpp_or_zero<0x114, 0xf>(v); v += dpp_or_zero<0x118, 0xf>(v);  // row_shr:1,2,4,8
+  v += dpp_or_zero<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
+  v += dpp_or_zero<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
+  return lane63(v);
 }
 __device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-  return v;
+  v = fmax(v, dpp_or_self<0x111, 0xf>(v)); v = fmax(v, dpp_or_self<0x112, 0xf>(v)); v = fmax(v, dpp_or_self<0x114, 0xf>(v));
+  v = fmax(v, dpp_or_self<0x118, 0xf>(v));
+  v = fmax(v, dpp_or_self<0x142, 0xa>(v));
+  v = fmax(v, dpp_or_self<0x143, 0xc>(v));
+  return lane63(v);
 }
 
 // camera table row of a record: the table in HBM, or (kLocal: single-launch solver) the workgroup's own LDS copy of the variable
@@ -205,12 +227,12 @@ __device__ __forceinline__ const double* camera_row(const double* tab, const dou
 
 // One step of the segmented scan along the lanes of a 16-lane row: adds the values of the lane SH to the left (DPP row_shr) when
 // it belongs to the same landmark.  Lanes without such a neighbour in the row receive landmark -1.
-template <int SH>
-__device__ __forceinline__ void seg_step(int my_lpt, double (&v)[9]) {
+template <int SH, int N>
+__device__ __forceinline__ void seg_step(int my_lpt, double (&v)[N]) {
   constexpr int ctrl = 0x110 | SH;
   const bool same = __builtin_amdgcn_update_dpp(-1, my_lpt, ctrl, 0xf, 0xf, false) == my_lpt;
 #pragma unroll
-  for (int k = 0; k < 9; ++k) {
+  for (int k = 0; k < N; ++k) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v[k]), ctrl, 0xf, 0xf, false);
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v[k]), ctrl, 0xf, 0xf, false);
     v[k] += same ? __hiloint2double(hi, lo) : 0.0;

@@ -390,6 +390,12 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
         if (!okf) my_bad = 1;
         const double p0 = A.ps[3 * (H.pt0 + lpt)], p1 = A.ps[3 * (H.pt0 + lpt) + 1], p2 = A.ps[3 * (H.pt0 + lpt) + 2];
         my_gmax = fmax(fabs(g0 / p0), fmax(fabs(g1 / p1), fabs(g2 / p2)));
+        if (A.pt_fac) {  // the update sweep of this iteration starts from F and g_p (F[0] == 0: not factored)
+          double* o = A.pt_fac + (size_t)9 * (H.pt0 + lpt);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) o[k] = F[k];
+          o[6] = g0; o[7] = g1; o[8] = g2;
+        }
       }
       if (lcam != (int)kLcamConst) {
         double* w = &S.W[tid * kWStride];

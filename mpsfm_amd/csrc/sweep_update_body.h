@@ -6,10 +6,11 @@
 
 namespace mpsfm {
 
-// LDS of one chunk's update sweep (12 KB)
-struct UpdLds {
-  double V[kPtsMax * 6];
-  double g[kPtsMax * 3];   // g_p + W^T y_c
+// LDS of one chunk's update sweep: 12 KB, 6.4 KB with the hand-off (no V)
+template <bool kHandoff>
+struct UpdLdsT {
+  double V[kHandoff ? 1 : kPtsMax * 6];
+  double g[kPtsMax * 3];   // g_p + W^T y_c (hand-off: W^T y_c alone)
   int32_t slot[kLocalCamsMax];
   double red[5 * (kThreads / 64)];
   uint8_t lpt[kThreads];   // landmark of every record (the first record of a landmark writes its candidate)
@@ -23,13 +24,19 @@ struct UpdLds {
 //   2  EVERY record solves its landmark's 3x3 system itself (the ~5 records of a landmark repeat ~80 operations) instead of one
 //      thread per landmark between two barriers: y_p, the candidate landmark — written by the landmark's first record —, the
 //      model cost change and the candidate cost follow in the same registers
-template <bool kLocal>
+// kHandoff: the dense track sweep of the same iteration — same state, same radius — has left the factor F and g_p of every
+// variable landmark in A.pt_fac.  Step 1 then only sums W^T y_c (three values through the scan and the LDS adds, no V), and step 2
+// starts from the nine doubles of the record's landmark, requested behind the linearisation and in front of the scan and the first
+// barrier (beside the record loads they are 12 more registers at the pressure peak: 119 against 107, and 0.6 us); F[0] > 0 marks a
+// valid factor.
+template <bool kLocal, bool kHandoff>
 __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, double lm_radius, const double* l_tab, const double* l_tab2,
-                                                   const double* yc, UpdLds& S, const CamUpdArgs& U, bool fuse) {
+                                                   const double* yc, UpdLdsT<kHandoff>& S, const CamUpdArgs& U, bool fuse) {
+  constexpr int NV = kHandoff ? 3 : 9;  // sums per record: [V_p (6),] g (3)
   const int tid = thread_index<kLocal>();
   const ChunkHdr H = A.chunks[cix];
   const int nrec = H.nrec, npt = H.npt, ncam = H.ncam;
-  for (int i = tid; i < npt * 6; i += kThreads) S.V[i] = 0.0;
+  if constexpr (!kHandoff) for (int i = tid; i < npt * 6; i += kThreads) S.V[i] = 0.0;
   for (int i = tid; i < npt * 3; i += kThreads) S.g[i] = 0.0;
   if (tid < ncam) {
     const int slot = A.chunk_cams[H.cam0 + tid];
@@ -58,7 +65,10 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
   double d = 1.0, m = 0.0, a = 1.0;
   double X[3] = {0, 0, 0}, psc[3] = {0, 0, 0};
   bool ok = true, variable = false;
-  double Vg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double Vg[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) Vg[k] = 0.0;
+  double fac[kHandoff ? 9 : 1] = {};  // the landmark's F and g_p
   if (tid < nrec) {
     const int rix = H.rec0 + tid;
     meta = A.rec_meta[rix];
@@ -74,13 +84,19 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
     linearize_update(camera_row<kLocal>(A.camtab, l_tab, S.slot, cam, lcam), X, psc, meta, xy.x, xy.y, d, m, a, A.loss,
                      lcam != (int)kLcamConst ? yc + (size_t)S.slot[lcam] * 6 : nullptr, L);
     ok = L.ok;
+    if constexpr (kHandoff) {
+      if (variable) {  // (a constant landmark's slot is never written)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) fac[k] = A.pt_fac[(size_t)9 * (H.pt0 + lpt) + k];
+      }
+    }
     if (L.ok && psc[0] != 0.0) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
         const double j0 = L.Jp[3 * r], j1 = L.Jp[3 * r + 1], j2 = L.Jp[3 * r + 2];
-        Vg[0] += j0 * j0; Vg[1] += j0 * j1; Vg[2] += j0 * j2; Vg[3] += j1 * j1; Vg[4] += j1 * j2; Vg[5] += j2 * j2;
-        const double rr = L.r[r] + L.mrow[r];
-        Vg[6] += j0 * rr; Vg[7] += j1 * rr; Vg[8] += j2 * rr;
+        if constexpr (!kHandoff) { Vg[0] += j0 * j0; Vg[1] += j0 * j1; Vg[2] += j0 * j2; Vg[3] += j1 * j1; Vg[4] += j1 * j2; Vg[5] += j2 * j2; }
+        const double rr = kHandoff ? L.mrow[r] : L.r[r] + L.mrow[r];  // (hand-off: J_p^T r is in g_p already)
+        Vg[NV - 3] += j0 * rr; Vg[NV - 2] += j1 * rr; Vg[NV - 1] += j2 * rr;
       }
     }
   }
@@ -89,10 +105,12 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
     seg_step<1>(lpt, Vg); seg_step<2>(lpt, Vg); seg_step<4>(lpt, Vg); seg_step<8>(lpt, Vg);
     const int nlpt = __builtin_amdgcn_update_dpp(-1, lpt, 0x101, 0xf, 0xf, false);  // row_shl:1: the right neighbour's landmark
     if (nlpt != lpt && lpt < npt) {  // last lane of its run inside the row (lane 15 of a row sees -1)
+      if constexpr (!kHandoff) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) if (Vg[k] != 0.0) atomicAdd(&S.V[lpt * 6 + k], Vg[k]);
+        for (int k = 0; k < 6; ++k) if (Vg[k] != 0.0) atomicAdd(&S.V[lpt * 6 + k], Vg[k]);
+      }
 #pragma unroll
-      for (int k = 0; k < 3; ++k) if (Vg[6 + k] != 0.0) atomicAdd(&S.g[lpt * 3 + k], Vg[6 + k]);
+      for (int k = 0; k < 3; ++k) if (Vg[NV - 3 + k] != 0.0) atomicAdd(&S.g[lpt * 3 + k], Vg[NV - 3 + k]);
     }
   }
   __syncthreads();
@@ -103,16 +121,26 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
     double yp[3] = {0, 0, 0}, X2[3] = {X[0], X[1], X[2]};
     const bool first = tid == 0 || S.lpt[tid - 1] != (uint8_t)lpt;
     if (variable) {
-      double V[6], F[6];
+      double F[6];
+      bool okf;
+      double g0 = S.g[lpt * 3], g1 = S.g[lpt * 3 + 1], g2 = S.g[lpt * 3 + 2];
+      if constexpr (kHandoff) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) V[k] = S.V[lpt * 6 + k];
-      V[0] += fmin(fmax(V[0], A.min_diag), A.max_diag) / lm_radius;
-      V[3] += fmin(fmax(V[3], A.min_diag), A.max_diag) / lm_radius;
-      V[5] += fmin(fmax(V[5], A.min_diag), A.max_diag) / lm_radius;
-      if (!spd3_inv_factor(V, F)) {  // F = chol(V + D)^-1, the factor the track sweep forms for the same block
+        for (int k = 0; k < 6; ++k) F[k] = fac[k];
+        okf = F[0] > 0.0;  // the track sweep zeroes the factor of a block it could not factor
+        g0 = fac[6] + g0; g1 = fac[7] + g1; g2 = fac[8] + g2;
+      } else {
+        double V[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) V[k] = S.V[lpt * 6 + k];
+        V[0] += fmin(fmax(V[0], A.min_diag), A.max_diag) / lm_radius;
+        V[3] += fmin(fmax(V[3], A.min_diag), A.max_diag) / lm_radius;
+        V[5] += fmin(fmax(V[5], A.min_diag), A.max_diag) / lm_radius;
+        okf = spd3_inv_factor(V, F);  // F = chol(V + D)^-1, the factor the track sweep forms for the same block
+      }
+      if (!okf) {
         ok = false;  // (every record of the landmark reports it: the count only has to be non-zero)
       } else {
-        const double g0 = S.g[lpt * 3], g1 = S.g[lpt * 3 + 1], g2 = S.g[lpt * 3 + 2];
         const double v0 = F[0] * g0, v1 = F[1] * g0 + F[2] * g1, v2 = F[3] * g0 + F[4] * g1 + F[5] * g2;  // F g
         yp[0] = -(F[0] * v0 + F[1] * v1 + F[3] * v2); yp[1] = -(F[2] * v1 + F[4] * v2); yp[2] = -(F[5] * v2);  // -F^T F g
 #pragma unroll
