@@ -1,0 +1,152 @@
+"""Bundle-adjustment problems from an explicit visibility list, built so that the chunks of the track sweep sit on the caps of
+csrc/common.h: kDenseCams = 16 and kDensePts = 96 (dense chunks), kObsMax = 252 and kPtsMax = 126 (all chunks), kTileCams = 16,
+kItemPairs = 64 and kEntStage = 1024 (general chunks), more than 252 records (long tracks).  Shared by test_chunk_caps_cpu.py,
+which asserts from the device-free table build that every scene reaches what it is named for, and test_gpu_chunk_caps.py, which
+compares the kernels with the CPU oracle on them.
+
+Small problems get 64-record chunks whose landmark cap shrinks with the camera set (BuildOptions::set_chunk_caps); the scenes
+marked CAPS are built under the two existing switches that lift both."""
+
+import functools
+
+import numpy as np
+
+from mpsfm_amd.problem import BAProblem
+from mpsfm_amd.synthetic import CX, CY, FX, FY, R_from_quat, make_scene
+
+CAPS = {"MPSFM_CHUNK_RECORDS": "252", "MPSFM_CHUNK_PTS_BY_CAMS": "0"}
+SIGMA_L = 0.0263  # make_scene's log-depth noise
+
+
+def scene(n_cams, tracks, seed, const_cams=(0,), every_depth=False):
+    """Cameras, their perturbation and the loss settings of make_scene(n_cams, ...); landmark j uniform in +-1.5 and seen by the
+    cameras of tracks[j] (a camera named twice gives two blocks), each projected from the truth with 1 px noise; log-depth priors
+    as in make_scene (3 % gross, 10 % dropped — none dropped with `every_depth`)."""
+    base, truth = make_scene(n_cams, 2, True, seed=seed)
+    rng = np.random.default_rng([seed, 7])
+    n_pts = len(tracks)
+    X = rng.uniform(-1.5, 1.5, (n_pts, 3))
+    obs_cam = np.array([c for t in tracks for c in t], np.int32)
+    obs_pt = np.repeat(np.arange(n_pts, dtype=np.int32), [len(t) for t in tracks])
+    n_obs = len(obs_cam)
+    Xc = np.einsum("nij,nj->ni", R_from_quat(truth["cam_quat"])[obs_cam], X[obs_pt]) + truth["cam_t"][obs_cam]
+    z = Xc[:, 2]
+    assert (z > 0.5).all(), z.min()
+    xy = np.stack([FX * Xc[:, 0] / z + CX, FY * Xc[:, 1] / z + CY], axis=1) + rng.normal(0.0, 1.0, (n_obs, 2))
+    xy = xy.astype(np.float16).astype(np.float64)
+    d = z * np.exp(rng.normal(0.0, SIGMA_L, n_obs))
+    d[rng.uniform(size=n_obs) < 0.03] *= 1.5
+    valid = np.ones(n_obs, bool) if every_depth else rng.uniform(size=n_obs) >= 0.10
+    var = np.maximum((SIGMA_L * d) ** 2, 0.02**2)
+    pose_const = np.zeros(n_cams, np.uint8)
+    pose_const[list(const_cams)] = 1
+    return BAProblem(
+        cam_quat=base.cam_quat, cam_t=base.cam_t, pts=X + rng.normal(0.0, 0.05, (n_pts, 3)), cam_intr=base.cam_intr,
+        cam_intr_idx=base.cam_intr_idx, pose_const=pose_const, pt_const=np.zeros(n_pts, np.uint8), obs_cam=obs_cam, obs_pt=obs_pt,
+        obs_xy=xy, gauge_axis_cam=base.gauge_axis_cam, reproj_loss_type=base.reproj_loss_type, reproj_loss_scale=base.reproj_loss_scale,
+        reproj_loss_magnitude=base.reproj_loss_magnitude, dobs_cam=obs_cam[valid], dobs_pt=obs_pt[valid], dobs_depth=d[valid],
+        dobs_magnitude=(d**2 / np.clip(var, 1e-6, None))[valid], dobs_param=(2.0 * np.sqrt(var) / d)[valid],
+        depth_loss_type=base.depth_loss_type)
+
+
+def _random_tracks(rng, n, cams, kmin, kmax):
+    """n tracks of kmin..kmax distinct cameras out of `cams`."""
+    return [tuple(sorted(rng.choice(cams, size=int(rng.integers(kmin, kmax + 1)), replace=False).tolist())) for _ in range(n)]
+
+
+def _windows(rng, n, n_cams, k=3):
+    """n tracks of k consecutive cameras (wrapping around, camera 0 included): every camera gets its share."""
+    return [tuple(sorted((int(s) + i) % n_cams for i in range(k))) for s in rng.integers(0, n_cams, n)]
+
+
+def _two_view():
+    pairs = [(1, 2), (2, 3), (1, 3), (0, 1), (0, 3)]
+    return scene(4, [pairs[j % 5] for j in range(600)], seed=31)
+
+
+def _pairs16():
+    rng = np.random.default_rng(32)
+    return scene(17, _random_tracks(rng, 500, np.arange(1, 17), 2, 2), seed=32)
+
+
+def _mixed16():
+    rng = np.random.default_rng(37)  # a seed whose greedy cut closes two 16-camera chunks at exactly 252 records
+    return scene(17, _random_tracks(rng, 300, np.arange(1, 17), 2, 16) + [tuple(range(1, 17))] * 15, seed=37)
+
+
+def _one_var():
+    shapes = [(0, 1), (1, 2), (1, 3), (0, 1, 2)]
+    prob = scene(4, [shapes[j % 4] for j in range(240)], seed=34, const_cams=(0, 2, 3))
+    prob.pt_const[::7] = 1
+    return prob
+
+
+def _g17_40():
+    rng = np.random.default_rng(35)
+    return scene(45, [tuple(range(1, 18))] * 30 + [tuple(range(1, 41))] * 12 + _windows(rng, 200, 45), seed=35)
+
+
+def _dup_aab():
+    rng = np.random.default_rng(36)
+    return scene(5, [(1, 1, 2)] * 200 + _random_tracks(rng, 150, np.arange(5), 2, 4), seed=36, every_depth=True)
+
+
+def _dup_aa():
+    rng = np.random.default_rng(37)
+    fill = [(0, 1, 4), (0, 2, 3, 4)] * 20 + _random_tracks(rng, 110, np.arange(5), 2, 4)
+    return scene(5, [(1, 1)] * 300 + fill, seed=37, every_depth=True)
+
+
+def _r252_253():
+    rng = np.random.default_rng(38)
+    big = [tuple(range(1, 253)), tuple(range(1, 254)), tuple(range(2, 257))]
+    return scene(260, big + _windows(rng, 600, 260), seed=38)
+
+
+# name -> (maker, environment the handles are created under)
+SCENES = {
+    "two_view": (_two_view, CAPS),
+    "pairs16": (_pairs16, CAPS),
+    "mixed16": (_mixed16, CAPS),
+    "one_var": (_one_var, {}),
+    "g17_40": (_g17_40, {}),
+    "dup_aab": (_dup_aab, {}),
+    "dup_aa": (_dup_aa, {}),
+    "r252_253": (_r252_253, {}),
+}
+ALL_DENSE = ("two_view", "pairs16", "mixed16", "one_var")  # no general chunk, no long track: the hand-off runs; <= 16 variable cameras too
+
+
+@functools.lru_cache(maxsize=None)
+def _problem(name):
+    return SCENES[name][0]()
+
+
+def problem(name):
+    """A fresh copy of the named scene's problem (built once per process)."""
+    return _problem(name).copy()
+
+
+def environment_of(name):
+    return dict(SCENES[name][1])
+
+
+def shapes(t):
+    """What the tables `t` of a build (build_table_cases.host_tables / handle_tables) say about its chunks: `dense` and `general`,
+    the (nrec, npt, ncam, nent) rows of either kind; `items`, per general chunk the pair counts of its work items; `split`, the
+    number of work items that continue the block of the item before them; `long`, the (nrec, kv) of every long track."""
+    ch = t["chunks"].reshape(-1, 12)          # ChunkHdr: rec0 nrec pt0 npt cam0 ncam blk0 nblk ent0 nent dense slab0
+    rows = lambda c: [tuple(int(x) for x in r[[1, 3, 5, 9]]) for r in c]  # noqa: E731
+    items, split = [], 0
+    for ci, H in enumerate(ch):
+        if H[10]:
+            assert H[7] == 0 and H[9] == 0
+            continue
+        start = t["blk_ent_start"][H[6] + ci: H[6] + ci + H[7] + 1]   # every chunk before this one left a sentinel
+        assert start[0] == 0 and start[-1] == H[9]
+        items.append(np.diff(start))
+        desc = t["blk_desc"][H[6]: H[6] + H[7]]
+        split += int((desc[1:] == desc[:-1]).sum())
+    lh = t["lhdr"].reshape(-1, 6)             # LongHdr: rec0 nrec pt kv w0 (64 bits)
+    return dict(dense=rows(ch[ch[:, 10] == 1]), general=rows(ch[ch[:, 10] == 0]), items=items, split=split,
+                long=[(int(r[1]), int(r[3])) for r in lh])
