@@ -1015,6 +1015,118 @@ int mpsfm_warp_matches(int32_t H, int32_t W, const float* certainty /* [H][W] */
                        int32_t device, float* dkeypoints0, float* dkeypoints1 /* [H W][2] */, float* dscores /* [H W] */, int64_t* n_dense,
                        int32_t* smatches0 /* [n_s0] */, float* sscores0 /* [n_s0] */, int64_t* n_kps0, mpsfm_warp_info* info /* may be NULL */);
 
+/* ---- monocular depth and normal priors of many images in one call (reference mpsfm/sfm/scene/image/depth.py:34-130
+ *    Depth._init, image/utils.py:6-36 get_continuity_mask, image/normals.py:12-246 Normals._init; looped per image by
+ *    reconstruction/mixins/init_utils.py:53-64 initialize_mono_maps).  Images of one call may differ in source size, target
+ *    size and in which optional inputs they carry; the configuration is per call.  Value maps are float64, or float32 with
+ *    is_float32 (upcast on load: arithmetic is fp64, except the continuity test, which runs in the map's own precision);
+ *    masks are one byte per pixel, non-zero = true.  Value outputs are float64, mask outputs uint8 (0 / 1).
+ *    Resizing (OpenCV is restated): bilinear samples at (i + 0.5) (n_src / n_dst) - 0.5 per axis with a
+ *    replicated border and the fraction rounded to float32, rows first, then columns; equal sizes copy; a mask resized
+ *    bilinearly and tested == 1 is true iff every tap of non-zero weight is true; nearest takes source index
+ *    min(floor(i n_src / n_dst), n_src - 1).  n_images == 0 is a no-op.  No input array is modified. ---- */
+typedef struct mpsfm_depth_prior_conf { /* Depth.default_conf */
+  double inherent_noise;
+  double std_multiplier;
+  double prior_std_multiplier;
+  double max_std;               /* read with has_max_std */
+  double depth_lim;             /* read with has_depth_lim */
+  double fixed_uncertainty_val;
+  double depth_uncertainty;     /* read with has_depth_uncertainty */
+  int32_t has_max_std, has_depth_lim, has_depth_uncertainty; /* 0: the setting is None */
+  int32_t use_continuity, fixed_uncertainty, prior_uncertainty, flip_consistency;
+  int32_t reserved;
+} mpsfm_depth_prior_conf;
+
+typedef struct mpsfm_depth_prior_problem {
+  int32_t height, width;           /* of depth, depth2, the variances, valid, valid2            */
+  int32_t int_height, int_width;   /* camera.int_height / int_width: size of the outputs        */
+  int32_t mask_height, mask_width; /* of mask (ignored when mask is NULL)                       */
+  int32_t is_float32;              /* depth, depth2 and the variances are float32               */
+  int32_t n_kps;
+  const void* depth;               /* required                                                  */
+  const void* depth2;              /* NULL: absent (required by flip_consistency)               */
+  const void* depth_variance;      /* NULL: absent (required by prior_uncertainty)              */
+  const void* depth_variance2;     /* NULL: absent (required by both together)                  */
+  const uint8_t* valid;            /* NULL: absent                                              */
+  const uint8_t* valid2;           /* NULL: absent                                              */
+  const uint8_t* mask;             /* NULL: absent; [mask_height][mask_width]                   */
+  const double* kps;               /* [n_kps][2] image coordinates; may be NULL with n_kps == 0 */
+  double sx, sy;                   /* camera.sx / sy (keypoint -> map coordinates)              */
+} mpsfm_depth_prior_problem;
+
+typedef struct mpsfm_depth_prior_output {
+  double* data_prior;         /* [int_height][int_width] */
+  double* uncertainty;        /* [int_height][int_width] */
+  uint8_t* valid;             /* [int_height][int_width] */
+  uint8_t* continuity_mask;   /* [int_height][int_width]; all 1 without use_continuity */
+  double* uncertainty_update; /* [n_kps]: the finished uncertainty at the keypoints (PriorUtils.uncertainty_at_kps) */
+} mpsfm_depth_prior_output;
+
+typedef struct mpsfm_normal_prior_conf { /* Normals.default_conf */
+  double inherent_polar_noise;
+  double std_multiplier;
+  double lc_std_multiplier;
+  double prior_std_multiplier;
+  double downscale_factor;
+  int32_t flip_consistency;
+  int32_t reserved;
+} mpsfm_normal_prior_conf;
+
+typedef struct mpsfm_normal_prior_problem {
+  int32_t height, width;           /* of normals, normals2 and the variances                    */
+  int32_t int_height, int_width;   /* H, W of the full-size outputs                             */
+  int32_t mask_height, mask_width; /* of mask (ignored when mask is NULL)                       */
+  int32_t half_height, half_width; /* Hd, Wd the caller sized the half-size outputs for: checked */
+  int32_t is_float32;              /* normals and variances are float32                         */
+  int32_t reserved;
+  const void* normals;             /* [height][width][3], required                              */
+  const void* normals2;            /* NULL: absent (required by flip_consistency)               */
+  const void* normals_variance;    /* [height][width], required                                 */
+  const void* normals2_variance;   /* NULL: absent (required by flip_consistency)               */
+  const uint8_t* mask;             /* NULL: absent; [mask_height][mask_width]                   */
+  const uint8_t* continuity_mask;  /* NULL: absent; [int_height][int_width]                     */
+} mpsfm_normal_prior_problem;
+
+typedef struct mpsfm_normal_prior_output { /* Hd = int(H // downscale_factor), Wd = int(W // downscale_factor): Python's floor
+                                            * division (fmod based, 77 // 1.1 == 69), not floor(H / f); a problem whose
+                                            * half_height / half_width differ from that is refused                         */
+  double* data;                   /* [H][W][3]      */
+  double* uncertainty;            /* [H][W][3][3]   */
+  double* data_downscaled;        /* [Hd][Wd][3]    */
+  double* uncertainty_downscaled; /* [Hd][Wd][3][3] */
+} mpsfm_normal_prior_output;
+
+typedef struct mpsfm_prior_summary {
+  float ms;          /* device time of the launches (HIP events), transfers excluded */
+  int32_t n_images;
+  int64_t n_pixels;  /* destination pixels over all images (full size) */
+} mpsfm_prior_summary;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_depth_prior_conf) == 88 && offsetof(mpsfm_depth_prior_conf, has_max_std) == 56 &&
+                  offsetof(mpsfm_depth_prior_conf, flip_consistency) == 80,
+              "ABI of mpsfm_depth_prior_conf");
+static_assert(sizeof(mpsfm_depth_prior_problem) == 112 && offsetof(mpsfm_depth_prior_problem, depth) == 32 &&
+                  offsetof(mpsfm_depth_prior_problem, kps) == 88 && offsetof(mpsfm_depth_prior_problem, sy) == 104,
+              "ABI of mpsfm_depth_prior_problem");
+static_assert(sizeof(mpsfm_depth_prior_output) == 40, "ABI of mpsfm_depth_prior_output");
+static_assert(sizeof(mpsfm_normal_prior_conf) == 48 && offsetof(mpsfm_normal_prior_conf, flip_consistency) == 40,
+              "ABI of mpsfm_normal_prior_conf");
+static_assert(sizeof(mpsfm_normal_prior_problem) == 88 && offsetof(mpsfm_normal_prior_problem, half_height) == 24 &&
+                  offsetof(mpsfm_normal_prior_problem, normals) == 40 && offsetof(mpsfm_normal_prior_problem, continuity_mask) == 80,
+              "ABI of mpsfm_normal_prior_problem");
+static_assert(sizeof(mpsfm_normal_prior_output) == 32, "ABI of mpsfm_normal_prior_output");
+static_assert(sizeof(mpsfm_prior_summary) == 16 && offsetof(mpsfm_prior_summary, n_pixels) == 8, "ABI of mpsfm_prior_summary");
+#endif
+
+int mpsfm_depth_priors(int32_t n_images, const mpsfm_depth_prior_problem* problems /* [n_images] */,
+                       const mpsfm_depth_prior_conf* conf, int32_t device, const mpsfm_depth_prior_output* outputs /* [n_images] */,
+                       mpsfm_prior_summary* summary /* may be NULL */);
+
+int mpsfm_normal_priors(int32_t n_images, const mpsfm_normal_prior_problem* problems /* [n_images] */,
+                        const mpsfm_normal_prior_conf* conf, int32_t device, const mpsfm_normal_prior_output* outputs /* [n_images] */,
+                        mpsfm_prior_summary* summary /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ EXPORTS = [
     "mpsfm_radius_nms", "mpsfm_thin_dense_matches", "mpsfm_assign_keypoints",
     "mpsfm_match_default_options", "mpsfm_match_descriptors", "mpsfm_match_map_descriptors",
     "mpsfm_warp_default_options", "mpsfm_simple_nms", "mpsfm_kpids_to_matches0", "mpsfm_warp_matches",
+    "mpsfm_depth_priors", "mpsfm_normal_priors",
 ]
 
 _lib = None
@@ -1263,3 +1264,189 @@ def warp_matches(warp, certainty, sizes, mode=WARP_DENSE | WARP_SPARSE, skpts0=N
         k = int(nk.value)
         out.update(smatches0=m[:k].copy(), smatching_scores0=sc[:k].copy())
     return (out, _warp_info(I)) if return_info else out
+
+
+# ---- monocular depth / normal priors (csrc/mono_priors.hip) --------------------------------------------------------------
+class CDepthPriorConf(C.Structure):
+    _fields_ = [("inherent_noise", C.c_double), ("std_multiplier", C.c_double), ("prior_std_multiplier", C.c_double),
+                ("max_std", C.c_double), ("depth_lim", C.c_double), ("fixed_uncertainty_val", C.c_double),
+                ("depth_uncertainty", C.c_double), ("has_max_std", C.c_int32), ("has_depth_lim", C.c_int32),
+                ("has_depth_uncertainty", C.c_int32), ("use_continuity", C.c_int32), ("fixed_uncertainty", C.c_int32),
+                ("prior_uncertainty", C.c_int32), ("flip_consistency", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CDepthPriorProblem(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("int_height", C.c_int32), ("int_width", C.c_int32),
+                ("mask_height", C.c_int32), ("mask_width", C.c_int32), ("is_float32", C.c_int32), ("n_kps", C.c_int32),
+                ("depth", C.c_void_p), ("depth2", C.c_void_p), ("depth_variance", C.c_void_p), ("depth_variance2", C.c_void_p),
+                ("valid", C.c_void_p), ("valid2", C.c_void_p), ("mask", C.c_void_p), ("kps", C.c_void_p),
+                ("sx", C.c_double), ("sy", C.c_double)]
+
+
+class CDepthPriorOutput(C.Structure):
+    _fields_ = [("data_prior", C.c_void_p), ("uncertainty", C.c_void_p), ("valid", C.c_void_p), ("continuity_mask", C.c_void_p),
+                ("uncertainty_update", C.c_void_p)]
+
+
+class CNormalPriorConf(C.Structure):
+    _fields_ = [("inherent_polar_noise", C.c_double), ("std_multiplier", C.c_double), ("lc_std_multiplier", C.c_double),
+                ("prior_std_multiplier", C.c_double), ("downscale_factor", C.c_double), ("flip_consistency", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class CNormalPriorProblem(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("int_height", C.c_int32), ("int_width", C.c_int32),
+                ("mask_height", C.c_int32), ("mask_width", C.c_int32), ("half_height", C.c_int32), ("half_width", C.c_int32),
+                ("is_float32", C.c_int32), ("reserved", C.c_int32), ("normals", C.c_void_p), ("normals2", C.c_void_p), ("normals_variance", C.c_void_p),
+                ("normals2_variance", C.c_void_p), ("mask", C.c_void_p), ("continuity_mask", C.c_void_p)]
+
+
+class CNormalPriorOutput(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("uncertainty", C.c_void_p), ("data_downscaled", C.c_void_p),
+                ("uncertainty_downscaled", C.c_void_p)]
+
+
+class CPriorSummary(C.Structure):
+    _fields_ = [("ms", C.c_float), ("n_images", C.c_int32), ("n_pixels", C.c_int64)]
+
+
+def _prior_values(item, names, shape_tail=()):
+    """The value maps of one image in ONE precision: float32 when every present map is float32, float64 otherwise.
+    Returns (is_float32, {name: C-contiguous array or None})."""
+    present = [np.asarray(item[k]) for k in names if item.get(k) is not None]
+    f32 = bool(present) and all(a.dtype == np.float32 for a in present)
+    dt = np.float32 if f32 else np.float64
+    out = {}
+    for k in names:
+        a = item.get(k)
+        out[k] = None if a is None else np.ascontiguousarray(a, dt)
+    shape = out[names[0]].shape if out[names[0]] is not None else None
+    for k, a in out.items():
+        if a is not None and shape is not None and a.shape[:2] != shape[:2]:
+            raise ValueError(f"{k} and {names[0]} differ in shape")
+    return f32, out
+
+
+def _prior_mask(a):
+    """bool / numeric mask -> C-contiguous uint8 (non-zero = true), None stays None"""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.ndim != 2:
+        raise ValueError("masks are [H, W]")
+    return np.ascontiguousarray(a != 0 if a.dtype != np.bool_ else a).view(np.uint8)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def depth_priors(items, conf, device=0, return_summary=False):
+    """mpsfm_depth_priors: the depth priors of all `items` in one call.
+
+    `items`: list of dicts with depth [h,w] (float32 or float64), optional depth2, depth_variance, depth_variance2,
+    valid, valid2 [h,w], optional mask (any shape), size = (int_height, int_width), kps [n,2], sx, sy.  `conf`: mapping with
+    the keys of Depth.default_conf.  Nothing passed in is modified.
+    Returns a list of dicts(data_prior, uncertainty float64 [H,W]; valid, continuity_mask bool [H,W]; uncertainty_update [n])."""
+    n = len(items)
+    P = (CDepthPriorProblem * max(n, 1))()
+    O = (CDepthPriorOutput * max(n, 1))()
+    keep, outs = [], []
+    for k, it in enumerate(items):
+        f32, v = _prior_values(it, ("depth", "depth2", "depth_variance", "depth_variance2"))
+        if v["depth"] is None or v["depth"].ndim != 2:
+            raise ValueError("depth must be an [h, w] map")
+        h, w = v["depth"].shape
+        masks = {m: _prior_mask(it.get(m)) for m in ("valid", "valid2", "mask")}
+        for m in ("valid", "valid2"):
+            if masks[m] is not None and masks[m].shape != (h, w):
+                raise ValueError(f"{m} and depth differ in shape")
+        kps = np.ascontiguousarray(np.asarray(it.get("kps", np.zeros((0, 2))), np.float64).reshape(-1, 2))
+        H, W = (int(x) for x in it["size"])
+        e = P[k]
+        e.height, e.width, e.int_height, e.int_width = h, w, H, W
+        e.mask_height, e.mask_width = masks["mask"].shape if masks["mask"] is not None else (0, 0)
+        e.is_float32, e.n_kps = int(f32), len(kps)
+        e.depth, e.depth2, e.depth_variance, e.depth_variance2 = (_ptr(v[m]) for m in ("depth", "depth2", "depth_variance", "depth_variance2"))
+        e.valid, e.valid2, e.mask = _ptr(masks["valid"]), _ptr(masks["valid2"]), _ptr(masks["mask"])
+        e.kps = kps.ctypes.data if len(kps) else None
+        e.sx, e.sy = float(it["sx"]), float(it["sy"])
+        ok = H > 0 and W > 0
+        shape = (H, W) if ok else (0, 0)  # every entry is written by the call
+        o = dict(data_prior=np.empty(shape), uncertainty=np.empty(shape), valid=np.empty(shape, np.uint8),
+                 continuity_mask=np.empty(shape, np.uint8), uncertainty_update=np.empty(len(kps)))
+        O[k].data_prior, O[k].uncertainty, O[k].valid = o["data_prior"].ctypes.data, o["uncertainty"].ctypes.data, o["valid"].ctypes.data
+        O[k].continuity_mask, O[k].uncertainty_update = o["continuity_mask"].ctypes.data, o["uncertainty_update"].ctypes.data
+        keep.append((v, masks, kps))
+        outs.append(o)
+    cf = CDepthPriorConf()
+    for name in ("inherent_noise", "std_multiplier", "prior_std_multiplier", "fixed_uncertainty_val"):
+        setattr(cf, name, float(conf[name]))
+    for name in ("max_std", "depth_lim", "depth_uncertainty"):
+        val = conf[name]
+        setattr(cf, "has_" + name, int(val is not None))
+        setattr(cf, name, 0.0 if val is None else float(val))
+    for name in ("use_continuity", "fixed_uncertainty", "prior_uncertainty", "flip_consistency"):
+        setattr(cf, name, int(bool(conf[name])))
+    S = CPriorSummary()
+    L = lib()
+    L.mpsfm_depth_priors.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_depth_priors(n, C.addressof(P), C.addressof(cf), int(device), C.addressof(O), C.addressof(S)))
+    for o in outs:
+        o["valid"], o["continuity_mask"] = o["valid"].view(np.bool_), o["continuity_mask"].view(np.bool_)
+    return (outs, dict(ms=S.ms, n_images=S.n_images, n_pixels=S.n_pixels)) if return_summary else outs
+
+
+def normal_priors(items, conf, device=0, return_summary=False):
+    """mpsfm_normal_priors: the normal priors of all `items` in one call.
+
+    `items`: list of dicts with normals [h,w,3], normals_variance [h,w] (float32 or float64), optional normals2,
+    normals2_variance, optional mask (any shape), optional continuity_mask [H,W], size = (H, W).  `conf`: mapping with the
+    keys of Normals.default_conf.  Nothing passed in is modified.
+    Returns a list of dicts(data [H,W,3], uncertainty [H,W,3,3], data_downscaled [Hd,Wd,3], uncertainty_downscaled [Hd,Wd,3,3])."""
+    n = len(items)
+    P = (CNormalPriorProblem * max(n, 1))()
+    O = (CNormalPriorOutput * max(n, 1))()
+    f = conf["downscale_factor"]
+    keep, outs = [], []
+    for k, it in enumerate(items):
+        f32, v = _prior_values(it, ("normals", "normals2", "normals_variance", "normals2_variance"))
+        nm = v["normals"]
+        if nm is None or nm.ndim != 3 or nm.shape[2] != 3:
+            raise ValueError("normals must be an [h, w, 3] map")
+        if v["normals2"] is not None and v["normals2"].shape != nm.shape:
+            raise ValueError("normals2 and normals differ in shape")
+        for m in ("normals_variance", "normals2_variance"):
+            if v[m] is not None and v[m].shape != nm.shape[:2]:
+                raise ValueError(f"{m} must be [h, w]")
+        h, w = nm.shape[:2]
+        H, W = (int(x) for x in it["size"])
+        mask, cont = _prior_mask(it.get("mask")), _prior_mask(it.get("continuity_mask"))
+        if cont is not None and cont.shape != (H, W):
+            raise ValueError("continuity_mask must have the target size")
+        e = P[k]
+        e.height, e.width, e.int_height, e.int_width = h, w, H, W
+        e.mask_height, e.mask_width = mask.shape if mask is not None else (0, 0)
+        e.is_float32 = int(f32)
+        e.normals, e.normals2, e.normals_variance, e.normals2_variance = (_ptr(v[m]) for m in ("normals", "normals2", "normals_variance", "normals2_variance"))
+        e.mask, e.continuity_mask = _ptr(mask), _ptr(cont)
+        ok = H > 0 and W > 0 and f > 0
+        Hd, Wd = (max(int(H // f), 0), max(int(W // f), 0)) if ok else (0, 0)
+        e.half_height, e.half_width = Hd, Wd
+        if not ok:
+            H = W = 0
+        o = dict(data=np.empty((H, W, 3)), uncertainty=np.empty((H, W, 3, 3)), data_downscaled=np.empty((Hd, Wd, 3)),
+                 uncertainty_downscaled=np.empty((Hd, Wd, 3, 3)))  # every entry is written by the call
+        O[k].data, O[k].uncertainty = o["data"].ctypes.data, o["uncertainty"].ctypes.data
+        O[k].data_downscaled, O[k].uncertainty_downscaled = o["data_downscaled"].ctypes.data, o["uncertainty_downscaled"].ctypes.data
+        keep.append((v, mask, cont))
+        outs.append(o)
+    cf = CNormalPriorConf()
+    for name in ("inherent_polar_noise", "std_multiplier", "lc_std_multiplier", "prior_std_multiplier", "downscale_factor"):
+        setattr(cf, name, float(conf[name]))
+    cf.flip_consistency = int(bool(conf["flip_consistency"]))
+    S = CPriorSummary()
+    L = lib()
+    L.mpsfm_normal_priors.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    _check(L.mpsfm_normal_priors(n, C.addressof(P), C.addressof(cf), int(device), C.addressof(O), C.addressof(S)))
+    return (outs, dict(ms=S.ms, n_images=S.n_images, n_pixels=S.n_pixels)) if return_summary else outs
