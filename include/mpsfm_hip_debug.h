@@ -1,0 +1,57 @@
+/*
+ * mpsfm_hip_debug.h - test and diagnostic hooks of libmpsfm_hip.so.
+ *
+ * These entry points are OUTSIDE the stable ABI of mpsfm_hip.h: the tests and the scripts under scripts/ call them, nothing
+ * else should.  They may change or disappear without a change of MPSFM_ABI_VERSION.  The files that define them
+ * (csrc/ba_debug.hip, csrc/dense_chol.hip, csrc/chol_plan.hip) include this header, so every definition is checked
+ * against its declaration; mpsfm_amd/abi.py declares the same signatures for ctypes (tests/test_abi_cpu.py compares).
+ */
+#ifndef MPSFM_HIP_DEBUG_H
+#define MPSFM_HIP_DEBUG_H
+
+#include "mpsfm_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct mpsfm_plan_handle mpsfm_plan_handle;
+
+/* process-wide ablation flags: bits 0-7 dense solve, bits 8-15 track sweep; 0: off */
+void mpsfm_debug_set(int f);
+/* registers a device buffer for the phase timeline of the factorisation (100 MHz stamps, 2 x 8 per step); NULL: off */
+int mpsfm_debug_set_chol_trace(long long* dev_buf);
+/* one workgroup factors the stacked host matrix dx [64][32] = [D; X] with `waves` (1 or 4) waves; out: L, X L^-T; *ok: every pivot positive */
+int mpsfm_debug_panel_factor(const double* dx, int waves, double* out, int* ok);
+
+/* the Cholesky plan of a camera graph, no device involved; adj: n x n bytes; depth -2: choose, >= -1: that order; NULL on bad arguments */
+mpsfm_plan_handle* mpsfm_debug_plan_create(const uint8_t* adj, int32_t n, int32_t depth, int32_t pinv_max_tiles, int32_t inv_rows);
+/* frees a plan of mpsfm_debug_plan_create; NULL is allowed */
+void mpsfm_debug_plan_destroy(mpsfm_plan_handle* h);
+/* table `what` (0 header ... 13 col_of_slot, see csrc/chol_plan.hip) of a plan; returns its length, copies min(length, cap) entries */
+int64_t mpsfm_debug_plan_get(const mpsfm_plan_handle* h, int32_t what, int32_t* out, int64_t cap);
+
+/* no device involved: `count` host blocks of `bytes` through the block cache twice; returns how many of the second round were recycled */
+int64_t mpsfm_debug_host_cache(int64_t bytes, int32_t count);
+/* no device involved: `reps` rounds of an `nparts`-part job through the table build's worker pool; returns the parts that did not run exactly once */
+int64_t mpsfm_debug_run_parts(int32_t nparts, int32_t reps);
+/* no device involved: the camera-graph union of `world` ranks (adj: world x n x n bytes) as the all-reduce computes it; out: n x n bytes; returns the digits per double */
+int mpsfm_debug_graph_union(const uint8_t* adj, int32_t world, int32_t n, uint8_t* out);
+
+/* 1: the handle's track sweep hands the landmark factors to its update sweep, 0: the update sweep recomputes them */
+int mpsfm_debug_pt_handoff(mpsfm_ba_handle* h);
+/* the first `count` 8-byte words of the landmark-diagonal buffer, where the dense sweep leaves its phase stamps under debug flag 128 */
+int mpsfm_debug_read_trace(mpsfm_ba_handle* h, long long* out, int64_t count);
+/* table `which` (numbering in csrc/ba_debug.hip) of the handle copied to `out` (at most `cap` bytes); returns its size in bytes or a negative error code */
+int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t cap);
+/* no device involved: builds the tables of `P` as mpsfm_ba_create does for a single rank, then as mpsfm_debug_table; rebuilds on every call */
+int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* out, int64_t cap);
+/* phase clocks of the last single-launch solve, 100 MHz ticks; returns 0 when the handle does not take that path */
+int mpsfm_debug_local_clocks(mpsfm_ba_handle* h, int64_t out[12]);
+/* in every single-launch solve from now on workgroup `chunk` waits `ticks` (at most 200000) at each phase point of `phase_mask` (bits 0-4); (0, 0, 0): off */
+int mpsfm_debug_local_skew(int32_t chunk, int32_t phase_mask, int64_t ticks);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* MPSFM_HIP_DEBUG_H */

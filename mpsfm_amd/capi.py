@@ -1,4 +1,4 @@
-"""ctypes binding of libmpsfm_hip.so (include/mpsfm_hip.h).
+"""Python wrappers over libmpsfm_hip.so (include/mpsfm_hip.h); abi.py declares the structs, the signatures and the loader.
 
 This is the only door between the Python host layer and the HIP kernels.  There is no CPU
 fallback: every call fails loudly when the library is missing or no gfx950 device is visible.
@@ -7,75 +7,25 @@ fallback: every call fails loudly when the library is missing or no gfx950 devic
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
-from .problem import ALLREDUCE_FN, BAProblem, COptions, CProblem, CState, CSummary, CTracks, Tracks
+from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
+    ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CDcImage, CDcSummary, CDepthGather, CDepthPriorConf,
+    CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchInfo, CMatchOptions, CNmsInfo,
+    CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRegImage,
+    CRelPoseOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
+    CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
+)
+from .problem import BAProblem, Tracks
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libmpsfm_hip.so")
-
-EXPORTS = [
-    "mpsfm_abi_version", "mpsfm_last_error", "mpsfm_device_count", "mpsfm_ba_default_options",
-    "mpsfm_ba_solve", "mpsfm_ba_create", "mpsfm_ba_set_state", "mpsfm_ba_reset_state",
-    "mpsfm_ba_solve_resident", "mpsfm_ba_get_state", "mpsfm_ba_destroy", "mpsfm_ba_eval_cost",
-    "mpsfm_ba_sweep_once", "mpsfm_ba_get_reduced_system", "mpsfm_ba_reduced_dim",
-    "mpsfm_ba_get_dense_solution", "mpsfm_ba_dense_solve_once", "mpsfm_ba_dense_plan", "mpsfm_point_covs",
-    "mpsfm_triangulate_tracks", "mpsfm_filter_tracks", "mpsfm_integrate_depth", "mpsfm_integrate_depth_batch",
-    "mpsfm_integration_variances", "mpsfm_depth_blocks", "mpsfm_comm_unique_id", "mpsfm_depth_consistency",
-    "mpsfm_abs_pose_estimate", "mpsfm_rel_pose_estimate", "mpsfm_two_view_geometry", "mpsfm_two_view_geometry_batch",
-    "mpsfm_two_view_default_options", "mpsfm_registration_pairs", "mpsfm_init_pair_candidates",
-    "mpsfm_radius_nms", "mpsfm_thin_dense_matches", "mpsfm_assign_keypoints",
-    "mpsfm_match_default_options", "mpsfm_match_descriptors", "mpsfm_match_map_descriptors",
-    "mpsfm_warp_default_options", "mpsfm_simple_nms", "mpsfm_kpids_to_matches0", "mpsfm_warp_matches",
-    "mpsfm_depth_priors", "mpsfm_normal_priors",
-]
-
-_lib = None
-
-
-class MpsfmHipError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"libmpsfm_hip error {code}: {msg}")
-        self.code = code
-
-
-def lib():
-    """Loads libmpsfm_hip.so (building it is __graft_entry__.build()'s job, not ours)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise MpsfmHipError(-2, f"{LIB_PATH} is missing: run `python -m mpsfm_amd.build` (hipcc, gfx950)")
-        try:
-            # torch wheels bundle their own libamdhip64; if ours (linked against /opt/rocm) is loaded
-            # first the process ends up with two HIP runtimes and torch.cuda reports no devices.
-            # Importing torch first makes its runtime the process-wide one (same soname).
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        L.mpsfm_last_error.restype = C.c_char_p
-        L.mpsfm_ba_destroy.restype = None
-        L.mpsfm_ba_default_options.restype = None
-        L.mpsfm_ba_sweep_once.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_float)]
-        L.mpsfm_ba_dense_solve_once.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.mpsfm_ba_get_reduced_system.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-        L.mpsfm_ba_get_dense_solution.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-        L.mpsfm_ba_eval_cost.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        for name in ("mpsfm_ba_set_state", "mpsfm_ba_get_state", "mpsfm_ba_solve_resident"):
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-        L.mpsfm_ba_reset_state.argtypes = [C.c_void_p]
-        L.mpsfm_ba_reduced_dim.argtypes = [C.c_void_p]
-        L.mpsfm_ba_dense_plan.argtypes = [C.c_void_p, C.c_void_p]
-        L.mpsfm_ba_destroy.argtypes = [C.c_void_p]
-        L.mpsfm_ba_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
-        L.mpsfm_ba_solve.argtypes = [C.c_void_p] * 4
-        L.mpsfm_point_covs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-        L.mpsfm_triangulate_tracks.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        L.mpsfm_filter_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib = L
-    return _lib
+EXPORTS = list(SIGNATURES)  # every function of include/mpsfm_hip.h
+# names that callers outside the package have read from here; they are the table's own lists, not second declarations
+_MATCH_DESC_ARGS = SIGNATURES["mpsfm_match_descriptors"][1]
+_MATCH_MAP_ARGS = SIGNATURES["mpsfm_match_map_descriptors"][1]
+_SIMPLE_NMS_ARGS = SIGNATURES["mpsfm_simple_nms"][1]
+_KPIDS_ARGS = SIGNATURES["mpsfm_kpids_to_matches0"][1]
+_WARP_ARGS = SIGNATURES["mpsfm_warp_matches"][1]
 
 
 def _check(rc: int):
@@ -98,9 +48,7 @@ def default_options(**kw) -> COptions:
 def comm_unique_id() -> bytes:
     """128 bytes for COptions.comm_id (ncclGetUniqueId of the RCCL library in the process)."""
     buf = (C.c_uint8 * 128)()
-    L = lib()
-    L.mpsfm_comm_unique_id.argtypes = [C.c_void_p]
-    _check(L.mpsfm_comm_unique_id(C.addressof(buf)))
+    _check(lib().mpsfm_comm_unique_id(C.addressof(buf)))
     return bytes(buf)
 
 
@@ -209,7 +157,6 @@ class BAHandle:
 
     def pt_handoff(self) -> bool:
         """True when the handle's track sweep hands the landmark factors to its update sweep, False when that sweep recomputes them."""
-        lib().mpsfm_debug_pt_handoff.argtypes = [C.c_void_p]
         return bool(lib().mpsfm_debug_pt_handoff(self._h))
 
     def sweep_once(self, radius: float = 1e4) -> float:
@@ -220,7 +167,6 @@ class BAHandle:
     def sweep_parts(self) -> dict:
         """HIP-event times of the parts of the last sweep_once and the chunk counts behind them."""
         ms, info = (C.c_float * 3)(), (C.c_int64 * 4)()
-        lib().mpsfm_ba_sweep_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _check(lib().mpsfm_ba_sweep_parts(self._h, ms, info))
         return dict(dense_ms=ms[0], reduce_ms=ms[1], general_ms=ms[2], dense_chunks=int(info[0]), general_chunks=int(info[1]),
                     long_tracks=int(info[2]), reduce_parts=int(info[3]))
@@ -265,9 +211,7 @@ def debug_panel_factor(dx: np.ndarray, waves: int = 4):
     dx = np.ascontiguousarray(dx, np.float64)
     assert dx.shape == (64, 32), dx.shape
     out, ok = np.zeros((64, 32)), C.c_int(0)
-    L = lib()
-    L.mpsfm_debug_panel_factor.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-    _check(L.mpsfm_debug_panel_factor(dx.ctypes.data, int(waves), out.ctypes.data, C.byref(ok)))
+    _check(lib().mpsfm_debug_panel_factor(dx.ctypes.data, int(waves), out.ctypes.data, C.byref(ok)))
     return out, bool(ok.value)
 
 
@@ -284,16 +228,6 @@ def filter_tracks(tr: Tracks, xyz: np.ndarray, device: int = 0):
     ct = tr.c_tracks()
     _check(lib().mpsfm_filter_tracks(C.byref(ct), xyz.ctypes.data, device, ang.ctypes.data, err.ctypes.data, front.ctypes.data))
     return ang, err, front.astype(bool)
-
-
-class CDepthGather(C.Structure):
-    _fields_ = [
-        ("n_images", C.c_int32), ("map_h", C.c_void_p), ("map_w", C.c_void_p), ("depth_map", C.c_void_p), ("valid_map", C.c_void_p),
-        ("sx", C.c_void_p), ("sy", C.c_void_p), ("cam_quat_xyzw", C.c_void_p), ("cam_t", C.c_void_p),
-        ("n_obs", C.c_int64), ("obs_img", C.c_void_p), ("obs_xy", C.c_void_p), ("obs_var", C.c_void_p), ("obs_pt", C.c_void_p),
-        ("n_pts", C.c_int32), ("pts", C.c_void_p),
-        ("scale_filter", C.c_int32), ("scale_filter_factor", C.c_double), ("gross_outliers", C.c_int32), ("multiplier", C.c_double),
-    ]
 
 
 def depth_blocks(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts, scale_filter_factor=1.5,
@@ -323,10 +257,8 @@ def depth_blocks(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_x
     G.scale_filter, G.scale_filter_factor, G.gross_outliers, G.multiplier = 1, float(scale_filter_factor), 0, float(multiplier)
     out = {k: np.zeros(n) for k in ("depth", "depth3d", "magnitude", "param", "whitened")}
     out["flags"] = np.zeros(n, np.uint8)
-    L = lib()
-    L.mpsfm_depth_blocks.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
-    _check(L.mpsfm_depth_blocks(C.byref(G), device, out["flags"].ctypes.data, out["depth"].ctypes.data, out["depth3d"].ctypes.data,
-                                out["magnitude"].ctypes.data, out["param"].ctypes.data, out["whitened"].ctypes.data))
+    _check(lib().mpsfm_depth_blocks(C.byref(G), device, out["flags"].ctypes.data, out["depth"].ctypes.data, out["depth3d"].ctypes.data,
+                                    out["magnitude"].ctypes.data, out["param"].ctypes.data, out["whitened"].ctypes.data))
     return out
 
 
@@ -339,8 +271,6 @@ INT_DEFAULT_CONF = dict(
 def _int_problem(depth_prior, depth_uncertainty, valid, normals, normals_var, depth_init, K, kps, depth3d, zvars3d, conf,
                  init=True, integrated=False, energy_old=0.0, wu=None, wv=None):
     """Fills a CIntProblem; returns (P, keepalive tuple, (H, W), wu, wv)."""
-    from .problem import CIntProblem
-
     c = dict(INT_DEFAULT_CONF)
     c.update(conf or {})
     f64 = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
@@ -374,15 +304,11 @@ def _int_problem(depth_prior, depth_uncertainty, valid, normals, normals_var, de
 def integrate_depth(depth_prior, depth_uncertainty, valid, normals, normals_var, depth_init, K, kps, depth3d, zvars3d,
                     conf=None, init=True, integrated=False, energy_old=0.0, wu=None, wv=None, device=0):
     """mpsfm_integrate_depth.  Returns (depth map or None, summary dict, wu, wv)."""
-    from .problem import CIntSummary
-
     P, _keep, (H, W), wu, wv = _int_problem(depth_prior, depth_uncertainty, valid, normals, normals_var, depth_init, K, kps,
                                             depth3d, zvars3d, conf, init, integrated, energy_old, wu, wv)
     out = np.zeros((H, W))
     S = CIntSummary()
-    L = lib()
-    L.mpsfm_integrate_depth.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_integrate_depth(C.byref(P), device, out.ctypes.data, C.byref(S)))
+    _check(lib().mpsfm_integrate_depth(C.byref(P), device, out.ctypes.data, C.byref(S)))
     n = S.irls_iterations
     summary = dict(changed=bool(S.changed), irls_iterations=n, cg_iterations_total=S.cg_iterations_total,
                    integrated=bool(S.integrated_out), energy_old=S.energy_old_out, energy_initial=S.energy_initial,
@@ -404,8 +330,6 @@ def integrate_depth_batch(items, conf=None, device=0):
     (depth_prior, depth_uncertainty, valid, normals, normals_var, depth_init, K, kps, depth3d, zvars3d and
     optionally init, integrated, energy_old, wu, wv); all maps of one size.  Returns a list of
     (depth map or None, summary dict, wu, wv) in the same order."""
-    from .problem import CIntProblem, CIntSummary
-
     n = len(items)
     if n == 0:
         return []
@@ -423,9 +347,7 @@ def integrate_depth_batch(items, conf=None, device=0):
         wus.append(wu)
         wvs.append(wv)
     ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-    L = lib()
-    L.mpsfm_integrate_depth_batch.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_integrate_depth_batch(n, C.byref(Ps), device, C.byref(ptrs), C.byref(Ss)))
+    _check(lib().mpsfm_integrate_depth_batch(n, C.byref(Ps), device, C.byref(ptrs), C.byref(Ss)))
     return [((outs[i] if Ss[i].changed else None), _int_summary_dict(Ss[i]), wus[i], wvs[i]) for i in range(n)]
 
 
@@ -434,8 +356,6 @@ def integration_variances(depth_prior, depth_uncertainty, valid, normals, normal
                           device=0, return_field=False):
     """mpsfm_integration_variances: var(log depth) propagated through the integration at integer pixels
     `query_xy` [n,2] (x, y).  Returns (variances [n], summary dict[, field [H,W]])."""
-    from .problem import CIntSummary
-
     empty = np.zeros((0, 2), np.int64)
     P, _keep, (H, W), _, _ = _int_problem(depth_prior, depth_uncertainty, valid, normals, normals_var, depth_checkpoint, K,
                                           empty if kps is None else kps, [] if depth3d is None else depth3d,
@@ -445,21 +365,12 @@ def integration_variances(depth_prior, depth_uncertainty, valid, normals, normal
     out = np.zeros(len(q))
     field = np.zeros((H, W)) if return_field else None
     S = CIntSummary()
-    L = lib()
-    L.mpsfm_integration_variances.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
-                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_integration_variances(C.byref(P), device, int(bool(use_sparse)), len(q), qx.ctypes.data if len(q) else None,
-                                         qy.ctypes.data if len(q) else None, float(rtol), int(max_iter),
-                                         out.ctypes.data if len(q) else None, field.ctypes.data if return_field else None,
-                                         C.byref(S)))
+    _check(lib().mpsfm_integration_variances(C.byref(P), device, int(bool(use_sparse)), len(q), qx.ctypes.data if len(q) else None,
+                                             qy.ctypes.data if len(q) else None, float(rtol), int(max_iter),
+                                             out.ctypes.data if len(q) else None, field.ctypes.data if return_field else None,
+                                             C.byref(S)))
     summary = dict(converged=bool(S.changed), cg_iterations=S.cg_iterations_total, ms=S.ms)
     return (out, summary, field) if return_field else (out, summary)
-
-
-class CTriCandidates(C.Structure):
-    _fields_ = [("n_candidates", C.c_int64), ("cand_start", C.c_void_p), ("view_cam_from_world", C.c_void_p), ("view_intr", C.c_void_p),
-                ("view_xy", C.c_void_p), ("min_tri_angle", C.c_double), ("max_error", C.c_double), ("residual_type", C.c_int32),
-                ("min_num_trials", C.c_void_p)]
 
 
 def tri_estimate_batch(cand_start, view_cam_from_world, view_intr, view_xy, min_tri_angle, max_error, residual_type=0,
@@ -479,20 +390,8 @@ def tri_estimate_batch(cand_start, view_cam_from_world, view_intr, view_xy, min_
     c = CTriCandidates(n, cs.ctypes.data, P.ctypes.data, K.ctypes.data, xy.ctypes.data, float(min_tri_angle), float(max_error),
                        int(residual_type), None if mt is None else mt.ctypes.data)
     xyz, ok, inl = np.zeros((max(n, 0), 3)), np.zeros(max(n, 0), np.uint8), np.zeros(len(P), np.uint8)
-    L = lib()
-    L.mpsfm_tri_estimate_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_tri_estimate_batch(C.byref(c), device, xyz.ctypes.data, ok.ctypes.data, inl.ctypes.data))
+    _check(lib().mpsfm_tri_estimate_batch(C.byref(c), device, xyz.ctypes.data, ok.ctypes.data, inl.ctypes.data))
     return xyz, ok.astype(bool), inl.astype(bool)
-
-
-class CDcImage(C.Structure):
-    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("depth", C.c_void_p), ("variance", C.c_void_p),
-                ("prior_std_multiplier", C.c_double), ("intr_scaled", C.c_double * 4), ("intr", C.c_double * 4),
-                ("cam_from_world", C.c_double * 12)]
-
-
-class CDcSummary(C.Structure):
-    _fields_ = [("ms", C.c_float), ("n_legs", C.c_int32), ("n_pixels", C.c_int64)]
 
 
 DC_IN, DC_SURFACE, DC_OCCL, DC_INVALID = 1, 2, 4, 8  # code bits of depth_consistency(return_codes=True)
@@ -536,24 +435,11 @@ def depth_consistency(images, pairs, c=15.0, score_thresh=0.6, device=0, return_
             codes.append((np.zeros(sa, np.uint8), np.zeros(sb, np.uint8)))
         cptr = (C.c_void_p * max(2 * n_pairs, 1))(*[m.ctypes.data for cd in codes for m in cd])
     S = CDcSummary()
-    L = lib()
-    L.mpsfm_depth_consistency.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_depth_consistency(n_img, C.addressof(arr), n_pairs, pa.ctypes.data, pb.ctypes.data, float(c),
-                                     float(score_thresh), int(device), counts.ctypes.data,
-                                     C.addressof(cptr) if cptr is not None else None, C.byref(S)))
+    _check(lib().mpsfm_depth_consistency(n_img, C.addressof(arr), n_pairs, pa.ctypes.data, pb.ctypes.data, float(c),
+                                         float(score_thresh), int(device), counts.ctypes.data,
+                                         C.addressof(cptr) if cptr is not None else None, C.byref(S)))
     summary = dict(ms=S.ms, n_legs=S.n_legs, n_pixels=S.n_pixels)
     return (counts, summary, codes) if return_codes else (counts, summary)
-
-
-class CRansacOptions(C.Structure):
-    """mpsfm_ransac_options: the options of both LO-RANSAC estimators."""
-    _fields_ = [("max_error", C.c_double), ("min_inlier_ratio", C.c_double), ("confidence", C.c_double),
-                ("dyn_num_trials_multiplier", C.c_double), ("min_num_trials", C.c_int64), ("max_num_trials", C.c_int64),
-                ("seed", C.c_uint64), ("batch_trials", C.c_int32), ("reserved", C.c_int32)]
-
-
-CAbsPoseOptions = CRelPoseOptions = CRansacOptions
 
 
 def _ransac_options(defaults: dict, options: dict) -> CRansacOptions:
@@ -574,11 +460,6 @@ def _ransac_report(R, mask: np.ndarray, n: int) -> dict:
                 num_batches=int(R.num_batches), ms=float(R.ms))
 
 
-class CAbsPoseResult(C.Structure):
-    _fields_ = [("cam_from_world", C.c_double * 12), ("num_inliers", C.c_int64), ("num_trials", C.c_int64), ("max_num_trials", C.c_int64),
-                ("num_models", C.c_int64), ("success", C.c_int32), ("lo_rounds", C.c_int32), ("num_batches", C.c_int32), ("ms", C.c_float)]
-
-
 ABS_POSE_DEFAULTS = dict(max_error=12.0, min_inlier_ratio=0.25, confidence=0.99999, dyn_num_trials_multiplier=3.0, min_num_trials=100,
                          max_num_trials=10000, seed=0, batch_trials=0)
 
@@ -596,17 +477,9 @@ def abs_pose_estimate(points2D, points3D, intr, device=0, **options) -> dict:
     n = len(p2)
     mask = np.zeros(max(n, 1), np.uint8)
     R = CAbsPoseResult()
-    L = lib()
-    L.mpsfm_abs_pose_estimate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_abs_pose_estimate(n, p2.ctypes.data, p3.ctypes.data, K.ctypes.data, C.byref(opt), int(device), mask.ctypes.data,
-                                     C.byref(R)))
+    _check(lib().mpsfm_abs_pose_estimate(n, p2.ctypes.data, p3.ctypes.data, K.ctypes.data, C.byref(opt), int(device), mask.ctypes.data,
+                                         C.byref(R)))
     return dict(_ransac_report(R, mask, n), cam_from_world=np.array(R.cam_from_world[:]).reshape(3, 4))
-
-
-class CRelPoseResult(C.Structure):
-    _fields_ = [("E", C.c_double * 9), ("cam2_from_cam1", C.c_double * 12), ("num_inliers", C.c_int64), ("num_trials", C.c_int64),
-                ("max_num_trials", C.c_int64), ("num_models", C.c_int64), ("lo_rounds", C.c_int64), ("num_batches", C.c_int64),
-                ("num_cheirality_points", C.c_int64), ("success", C.c_int32), ("ms", C.c_float)]
 
 
 # pycolmap 3.11 RANSACOptions() as recalled
@@ -628,31 +501,10 @@ def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> di
     n = len(p1)
     mask = np.zeros(max(n, 1), np.uint8)
     R = CRelPoseResult()
-    L = lib()
-    L.mpsfm_rel_pose_estimate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                          C.c_void_p]
-    _check(L.mpsfm_rel_pose_estimate(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, C.byref(opt), int(device),
-                                     mask.ctypes.data, C.byref(R)))
+    _check(lib().mpsfm_rel_pose_estimate(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, C.byref(opt), int(device),
+                                         mask.ctypes.data, C.byref(R)))
     return dict(_ransac_report(R, mask, n), E=np.array(R.E[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4),
                 num_cheirality_points=int(R.num_cheirality_points))
-
-
-class CTwoViewOptions(C.Structure):
-    _fields_ = [("ransac", CRansacOptions), ("min_num_inliers", C.c_int64), ("min_E_F_inlier_ratio", C.c_double),
-                ("max_H_inlier_ratio", C.c_double), ("watermark_min_inlier_ratio", C.c_double), ("watermark_border_size", C.c_double),
-                ("detect_watermark", C.c_int32), ("compute_relative_pose", C.c_int32)]
-
-
-class CTwoViewLeg(C.Structure):
-    _fields_ = [("num_inliers", C.c_int64), ("num_trials", C.c_int64), ("max_num_trials", C.c_int64), ("lo_rounds", C.c_int64),
-                ("num_batches", C.c_int64), ("success", C.c_int32), ("reserved", C.c_int32)]
-
-
-class CTwoViewResult(C.Structure):
-    _fields_ = [("E", C.c_double * 9), ("F", C.c_double * 9), ("H", C.c_double * 9), ("cam2_from_cam1", C.c_double * 12),
-                ("tri_angle", C.c_double), ("leg", CTwoViewLeg * 4), ("num_inliers", C.c_int64), ("num_cheirality_points", C.c_int64),
-                ("num_border_inliers", C.c_int64), ("config", C.c_int32), ("success", C.c_int32), ("watermark", C.c_int32),
-                ("ms", C.c_float)]
 
 
 # COLMAP 3.11 TwoViewGeometryOptions as recalled (mpsfm_two_view_default_options)
@@ -661,11 +513,6 @@ TWO_VIEW_DEFAULTS = dict(max_error=4.0, min_inlier_ratio=0.25, confidence=0.999,
                          max_H_inlier_ratio=0.8, watermark_min_inlier_ratio=0.7, watermark_border_size=0.1, detect_watermark=True,
                          compute_relative_pose=False)
 TWO_VIEW_LEGS = ("E", "F", "H", "T")  # T: the translation of the watermark test
-
-
-class CTwoViewBatchReport(C.Structure):
-    """mpsfm_two_view_batch_report"""
-    _fields_ = [("num_groups", C.c_int64), ("num_syncs", C.c_int64), ("num_launches", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
 
 
 def _two_view_options(options: dict) -> CTwoViewOptions:
@@ -712,10 +559,8 @@ def two_view_geometry(points1, points2, intr1, intr2, size1, size2, device=0, **
     n = len(p1)
     mask = np.zeros(max(n, 1), np.uint8)
     R = CTwoViewResult()
-    L = lib()
-    L.mpsfm_two_view_geometry.argtypes = [C.c_int64] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_two_view_geometry(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, s1.ctypes.data, s2.ctypes.data,
-                                     C.byref(opt), int(device), mask.ctypes.data, C.byref(R)))
+    _check(lib().mpsfm_two_view_geometry(n, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data, s1.ctypes.data, s2.ctypes.data,
+                                         C.byref(opt), int(device), mask.ctypes.data, C.byref(R)))
     return _two_view_result(R, mask[:n])
 
 
@@ -742,20 +587,13 @@ def two_view_geometry_batch(pairs, device=0, pairs_per_group=0, return_report=Fa
     mask = np.zeros(max(N, 1), np.uint8)
     R = (CTwoViewResult * max(P, 1))()
     rep = CTwoViewBatchReport()
-    L = lib()
-    L.mpsfm_two_view_geometry_batch.argtypes = [C.c_int64] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3
-    _check(L.mpsfm_two_view_geometry_batch(P, start.ctypes.data, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data,
-                                           s1.ctypes.data, s2.ctypes.data, C.byref(opt), int(pairs_per_group), int(device),
-                                           mask.ctypes.data, R, C.byref(rep)))
+    _check(lib().mpsfm_two_view_geometry_batch(P, start.ctypes.data, p1.ctypes.data, p2.ctypes.data, K1.ctypes.data, K2.ctypes.data,
+                                               s1.ctypes.data, s2.ctypes.data, C.byref(opt), int(pairs_per_group), int(device),
+                                               mask.ctypes.data, R, C.byref(rep)))
     out = [_two_view_result(R[k], mask[start[k]:start[k + 1]]) for k in range(P)]
     if return_report:
         return out, dict(num_groups=int(rep.num_groups), num_syncs=int(rep.num_syncs), num_launches=int(rep.num_launches), ms=float(rep.ms))
     return out
-
-
-class CRegImage(C.Structure):
-    _fields_ = [("map_h", C.c_int32), ("map_w", C.c_int32), ("depth_map", C.c_void_p), ("sx", C.c_double), ("sy", C.c_double),
-                ("intr", C.c_double * 4), ("quat_xyzw", C.c_double * 4), ("t", C.c_double * 3)]
 
 
 REG_DROPPED, REG_TRIANGULATED, REG_LIFTED = 0, 1, 2  # `kind` of registration_pairs
@@ -800,26 +638,10 @@ def registration_pairs(refs, match_ref, ref_xy, match_pt, pts, pt_risky=None, li
         e.quat_xyzw = (C.c_double * 4)(*[float(v) for v in np.asarray(r["quat_xyzw"], np.float64).reshape(4)])
         e.t = (C.c_double * 3)(*[float(v) for v in np.asarray(r["t"], np.float64).reshape(3)])
     xyz, kind, ms = np.zeros((n, 3)), np.zeros(n, np.uint8), C.c_float(0)
-    L = lib()
-    L.mpsfm_registration_pairs.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_registration_pairs(n_refs, C.addressof(arr), n, match_ref.ctypes.data, ref_xy.ctypes.data, match_pt.ctypes.data,
-                                      None if risky is None else risky.ctypes.data, n_pts, pts.ctypes.data,
-                                      int(bool(lifted_registration)), int(device), xyz.ctypes.data, kind.ctypes.data, C.addressof(ms)))
+    _check(lib().mpsfm_registration_pairs(n_refs, C.addressof(arr), n, match_ref.ctypes.data, ref_xy.ctypes.data, match_pt.ctypes.data,
+                                          None if risky is None else risky.ctypes.data, n_pts, pts.ctypes.data,
+                                          int(bool(lifted_registration)), int(device), xyz.ctypes.data, kind.ctypes.data, C.addressof(ms)))
     return (xyz, kind, float(ms.value)) if return_ms else (xyz, kind)
-
-
-class CInitPair(C.Structure):
-    _fields_ = [("n_matches", C.c_int64), ("xy1", C.c_void_p), ("xy2", C.c_void_p), ("select", C.c_void_p),
-                ("intr1", C.c_double * 4), ("intr2", C.c_double * 4), ("cam2_from_cam1", C.c_double * 12),
-                ("map_h", C.c_int32), ("map_w", C.c_int32), ("prior_map", C.c_void_p), ("valid_map", C.c_void_p),
-                ("sx", C.c_double), ("sy", C.c_double), ("rescale", C.c_double), ("tri_min_angle", C.c_double),
-                ("tri_max_error", C.c_double), ("what", C.c_int32), ("reserved", C.c_int32)]
-
-
-class CInitCandidates(C.Structure):
-    _fields_ = [("flags", C.c_void_p), ("tri_xyz", C.c_void_p), ("tri_angle_deg", C.c_void_p), ("lift_xyz", C.c_void_p),
-                ("lift_angle_deg", C.c_void_p), ("d_prior", C.c_void_p), ("ms", C.c_float)]
 
 
 INIT_TRIANGULATE, INIT_LIFT = 1, 2
@@ -870,19 +692,11 @@ def init_pair_candidates(xy1, xy2, intr1, intr2, cam2_from_cam1, prior_map=None,
                                      ("d_prior", n))}
     O = CInitCandidates(flags.ctypes.data, o["tri_xyz"].ctypes.data, o["tri_angle_deg"].ctypes.data, o["lift_xyz"].ctypes.data,
                         o["lift_angle_deg"].ctypes.data, o["d_prior"].ctypes.data, 0.0)
-    L = lib()
-    L.mpsfm_init_pair_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    _check(L.mpsfm_init_pair_candidates(C.byref(P), int(device), C.byref(O)))
+    _check(lib().mpsfm_init_pair_candidates(C.byref(P), int(device), C.byref(O)))
     for bit, name in enumerate(("tri_ok", "tri_posdepth1", "tri_posdepth2", "valid", "lift_posdepth1", "lift_posdepth2")):
         o[name] = (flags >> bit & 1).astype(bool)
     o["ms"] = float(O.ms)
     return o
-
-
-class CNmsInfo(C.Structure):
-    """mpsfm_nms_info"""
-    _fields_ = [("rounds", C.c_int32), ("launches", C.c_int32), ("cells", C.c_int32), ("max_cell_points", C.c_int32), ("ms", C.c_float),
-                ("reserved", C.c_int32)]
 
 
 def _nms_info(I) -> dict:
@@ -914,10 +728,8 @@ def radius_nms(points, scores, radius, order=None, device=0, return_info=False):
         if len(o) != n:
             raise ValueError("order must have one entry per point")
     keep, kept, I = np.zeros(max(n, 1), np.uint8), C.c_int64(0), CNmsInfo()
-    L = lib()
-    L.mpsfm_radius_nms.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_radius_nms(n, p.ctypes.data, s.ctypes.data, None if o is None else o.ctypes.data, float(radius), int(device),
-                              keep.ctypes.data, C.addressof(kept), C.addressof(I)))
+    _check(lib().mpsfm_radius_nms(n, p.ctypes.data, s.ctypes.data, None if o is None else o.ctypes.data, float(radius), int(device),
+                                  keep.ctypes.data, C.addressof(kept), C.addressof(I)))
     keep = keep[:n].astype(bool)
     assert int(kept.value) == int(keep.sum())
     return (keep, _nms_info(I)) if return_info else keep
@@ -938,12 +750,9 @@ def thin_dense_matches_mask(dense0, dense1, dscores, sparse0=None, sparse1=None,
     if len(s0) != len(s1):
         raise ValueError("sparse0 and sparse1 differ in length")
     keep, kept, I = np.zeros(max(nd, 1), np.uint8), C.c_int64(0), CNmsInfo()
-    L = lib()
-    L.mpsfm_thin_dense_matches.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_thin_dense_matches(len(s0), s0.ctypes.data, s1.ctypes.data, nd, d0.ctypes.data, d1.ctypes.data, sc.ctypes.data,
-                                      float(radius), int(bool(reference_slice)), int(device), keep.ctypes.data, C.addressof(kept),
-                                      C.addressof(I)))
+    _check(lib().mpsfm_thin_dense_matches(len(s0), s0.ctypes.data, s1.ctypes.data, nd, d0.ctypes.data, d1.ctypes.data, sc.ctypes.data,
+                                          float(radius), int(bool(reference_slice)), int(device), keep.ctypes.data, C.addressof(kept),
+                                          C.addressof(I)))
     keep = keep[:nd].astype(bool)
     return (keep, _nms_info(I)) if return_info else keep
 
@@ -953,22 +762,9 @@ def assign_keypoints_ids(query, kps, max_error, device=0, return_ms=False):
     ones) or -1.  Returns ids int64 [n_query][, device ms]."""
     q, k = _xy(query, "query"), _xy(kps, "kps")
     ids, ms = np.full(len(q), -1, np.int64), C.c_float(0)
-    L = lib()
-    L.mpsfm_assign_keypoints.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_assign_keypoints(len(q), q.ctypes.data, len(k), k.ctypes.data, float(max_error), int(device), ids.ctypes.data,
-                                    C.addressof(ms)))
+    _check(lib().mpsfm_assign_keypoints(len(q), q.ctypes.data, len(k), k.ctypes.data, float(max_error), int(device), ids.ctypes.data,
+                                        C.addressof(ms)))
     return (ids, float(ms.value)) if return_ms else ids
-
-
-class CMatchOptions(C.Structure):
-    """mpsfm_match_options"""
-    _fields_ = [("ratio_threshold", C.c_double), ("distance_threshold", C.c_double), ("score_threshold", C.c_double),
-                ("mutual_check", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
-
-
-class CMatchInfo(C.Structure):
-    """mpsfm_match_info"""
-    _fields_ = [("num_matches", C.c_int64), ("ms", C.c_float), ("column_ranges", C.c_int32)]
 
 
 def _match_info(I) -> dict:
@@ -977,10 +773,7 @@ def _match_info(I) -> dict:
 
 def _match_options(ratio_threshold, distance_threshold, score_threshold, do_mutual_check) -> CMatchOptions:
     o = CMatchOptions()
-    L = lib()
-    L.mpsfm_match_default_options.restype = None
-    L.mpsfm_match_default_options.argtypes = [C.c_void_p]
-    L.mpsfm_match_default_options(C.addressof(o))
+    lib().mpsfm_match_default_options(C.addressof(o))
     o.ratio_threshold = float(ratio_threshold or 0.0)
     o.distance_threshold = float(distance_threshold or 0.0)
     o.score_threshold = float(score_threshold or 0.0)
@@ -1033,11 +826,6 @@ def _host_f32(a, what) -> np.ndarray:
     return np.ascontiguousarray(a, np.float32)
 
 
-_MATCH_DESC_ARGS = [C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-_MATCH_MAP_ARGS = ([C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] * 2 + [C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
-
-
 def match_descriptors(desc0, desc1, ratio_threshold=None, distance_threshold=None, do_mutual_check=True, score_threshold=None,
                       device=None, return_info=False):
     """mpsfm_match_descriptors: desc0 [n0, dim], desc1 [n1, dim], float16 / float32 NumPy arrays, host tensors or device tensors
@@ -1055,10 +843,8 @@ def match_descriptors(desc0, desc1, ratio_threshold=None, distance_threshold=Non
         raise ValueError("descriptors must be [n0, dim] and [n1, dim]")
     n0, n1, dim = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
     m, s, I = np.full(max(n0, 1), -1, np.int32), np.zeros(max(n0, 1)), CMatchInfo()
-    L = lib()
-    L.mpsfm_match_descriptors.argtypes = _MATCH_DESC_ARGS
-    _check(L.mpsfm_match_descriptors(n0, n1, dim, pa or None, pb or None, C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data,
-                                     C.addressof(I)))
+    _check(lib().mpsfm_match_descriptors(n0, n1, dim, pa or None, pb or None, C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data,
+                                         C.addressof(I)))
     m, s = m[:n0].astype(np.int64), s[:n0]
     return (m, s, _match_info(I)) if return_info else (m, s)
 
@@ -1081,24 +867,11 @@ def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=
     k0, k1 = _xy(kps0, "kps0"), _xy(kps1, "kps1")
     n0, n1 = len(k0), len(k1)
     m, s, I = np.full(max(n0, 1), -1, np.int32), np.zeros(max(n0, 1)), CMatchInfo()
-    L = lib()
-    L.mpsfm_match_map_descriptors.argtypes = _MATCH_MAP_ARGS
-    _check(L.mpsfm_match_map_descriptors(ptrs[0] or None, ptrs[1] or None, int(m0.shape[0]), int(m0.shape[1]), ptrs[2] or None, ptrs[3] or None,
-                                         int(m1.shape[0]), int(m1.shape[1]), int(m0.shape[2]), n0, k0.ctypes.data, n1, k1.ctypes.data,
-                                         C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data, C.addressof(I)))
+    _check(lib().mpsfm_match_map_descriptors(ptrs[0] or None, ptrs[1] or None, int(m0.shape[0]), int(m0.shape[1]), ptrs[2] or None, ptrs[3] or None,
+                                             int(m1.shape[0]), int(m1.shape[1]), int(m0.shape[2]), n0, k0.ctypes.data, n1, k1.ctypes.data,
+                                             C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data, C.addressof(I)))
     m, s = m[:n0].astype(np.int64), s[:n0]
     return (m, s, _match_info(I)) if return_info else (m, s)
-
-
-class CWarpOptions(C.Structure):
-    """mpsfm_warp_options"""
-    _fields_ = [("sample_thresh", C.c_double), ("max_error", C.c_double), ("scale0", C.c_double * 2), ("scale1", C.c_double * 2),
-                ("nms_radius", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
-
-
-class CWarpInfo(C.Structure):
-    """mpsfm_warp_info"""
-    _fields_ = [("num_dense", C.c_int64), ("num_valid", C.c_int64), ("num_matches", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
 
 
 def _warp_info(I) -> dict:
@@ -1106,19 +879,11 @@ def _warp_info(I) -> dict:
 
 
 WARP_DENSE, WARP_SPARSE = 1, 2
-_SIMPLE_NMS_ARGS = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-_KPIDS_ARGS = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-               C.c_void_p, C.c_void_p]
-_WARP_ARGS = ([C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
-              + [C.c_void_p] * 8)
 
 
 def _warp_options(**kw) -> CWarpOptions:
     o = CWarpOptions()
-    L = lib()
-    L.mpsfm_warp_default_options.restype = None
-    L.mpsfm_warp_default_options.argtypes = [C.c_void_p]
-    L.mpsfm_warp_default_options(C.addressof(o))
+    lib().mpsfm_warp_default_options(C.addressof(o))
     for k, v in kw.items():
         if k in ("scale0", "scale1"):
             v = np.asarray(v, np.float64).reshape(-1)
@@ -1135,7 +900,6 @@ def simple_nms_map(scores, radius, device=None, return_info=False):
     device tensor (the map never leaves the device), anything else a float32 NumPy array.  [, info dict(..., ms)]."""
     o, I = CWarpOptions(), CWarpInfo()
     L = lib()
-    L.mpsfm_simple_nms.argtypes = _SIMPLE_NMS_ARGS
     if _on_device(scores):
         import torch
 
@@ -1211,10 +975,8 @@ def kpids_to_matches0_arrays(ids0, ids1, scores, n0=None, n1=None, device=0, ret
     n0 = int(n0) if n0 is not None else (int(a.max()) + 1 if n else 0)
     n1 = int(n1) if n1 is not None else (int(b.max()) + 1 if n else 0)
     m, sc, nk, I = np.full(max(n0, 1), -1, np.int32), np.zeros(max(n0, 1), np.float32), C.c_int64(0), CWarpInfo()
-    L = lib()
-    L.mpsfm_kpids_to_matches0.argtypes = _KPIDS_ARGS
-    _check(L.mpsfm_kpids_to_matches0(n, pa or None, pb or None, ps or None, n0, n1, int(on_device), stream, int(device or 0), m.ctypes.data,
-                                     sc.ctypes.data, C.addressof(nk), C.addressof(I)))
+    _check(lib().mpsfm_kpids_to_matches0(n, pa or None, pb or None, ps or None, n0, n1, int(on_device), stream, int(device or 0), m.ctypes.data,
+                                         sc.ctypes.data, C.addressof(nk), C.addressof(I)))
     k = int(nk.value)
     return (m[:k], sc[:k], _warp_info(I)) if return_info else (m[:k], sc[:k])
 
@@ -1252,11 +1014,9 @@ def warp_matches(warp, certainty, sizes, mode=WARP_DENSE | WARP_SPARSE, skpts0=N
     ds = np.empty(px if dense else 1, np.float32)
     m, sc = np.full(max(len(k0), 1), -1, np.int32), np.zeros(max(len(k0), 1), np.float32)
     nd, nk = C.c_int64(0), C.c_int64(0)
-    L = lib()
-    L.mpsfm_warp_matches.argtypes = _WARP_ARGS
-    _check(L.mpsfm_warp_matches(H, W, pc, pw, HA, WA, HB, WB, mode, C.addressof(o), len(k0), k0.ctypes.data, len(k1), k1.ctypes.data,
-                                int(device or 0), d0.ctypes.data, d1.ctypes.data, ds.ctypes.data, C.addressof(nd), m.ctypes.data, sc.ctypes.data,
-                                C.addressof(nk), C.addressof(I)))
+    _check(lib().mpsfm_warp_matches(H, W, pc, pw, HA, WA, HB, WB, mode, C.addressof(o), len(k0), k0.ctypes.data, len(k1), k1.ctypes.data,
+                                    int(device or 0), d0.ctypes.data, d1.ctypes.data, ds.ctypes.data, C.addressof(nd), m.ctypes.data, sc.ctypes.data,
+                                    C.addressof(nk), C.addressof(I)))
     if dense:
         k = int(nd.value)
         out.update(dkeypoints0=d0[:k].copy(), dkeypoints1=d1[:k].copy(), dscores=ds[:k].copy())
@@ -1267,49 +1027,6 @@ def warp_matches(warp, certainty, sizes, mode=WARP_DENSE | WARP_SPARSE, skpts0=N
 
 
 # ---- monocular depth / normal priors (csrc/mono_priors.hip) --------------------------------------------------------------
-class CDepthPriorConf(C.Structure):
-    _fields_ = [("inherent_noise", C.c_double), ("std_multiplier", C.c_double), ("prior_std_multiplier", C.c_double),
-                ("max_std", C.c_double), ("depth_lim", C.c_double), ("fixed_uncertainty_val", C.c_double),
-                ("depth_uncertainty", C.c_double), ("has_max_std", C.c_int32), ("has_depth_lim", C.c_int32),
-                ("has_depth_uncertainty", C.c_int32), ("use_continuity", C.c_int32), ("fixed_uncertainty", C.c_int32),
-                ("prior_uncertainty", C.c_int32), ("flip_consistency", C.c_int32), ("reserved", C.c_int32)]
-
-
-class CDepthPriorProblem(C.Structure):
-    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("int_height", C.c_int32), ("int_width", C.c_int32),
-                ("mask_height", C.c_int32), ("mask_width", C.c_int32), ("is_float32", C.c_int32), ("n_kps", C.c_int32),
-                ("depth", C.c_void_p), ("depth2", C.c_void_p), ("depth_variance", C.c_void_p), ("depth_variance2", C.c_void_p),
-                ("valid", C.c_void_p), ("valid2", C.c_void_p), ("mask", C.c_void_p), ("kps", C.c_void_p),
-                ("sx", C.c_double), ("sy", C.c_double)]
-
-
-class CDepthPriorOutput(C.Structure):
-    _fields_ = [("data_prior", C.c_void_p), ("uncertainty", C.c_void_p), ("valid", C.c_void_p), ("continuity_mask", C.c_void_p),
-                ("uncertainty_update", C.c_void_p)]
-
-
-class CNormalPriorConf(C.Structure):
-    _fields_ = [("inherent_polar_noise", C.c_double), ("std_multiplier", C.c_double), ("lc_std_multiplier", C.c_double),
-                ("prior_std_multiplier", C.c_double), ("downscale_factor", C.c_double), ("flip_consistency", C.c_int32),
-                ("reserved", C.c_int32)]
-
-
-class CNormalPriorProblem(C.Structure):
-    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("int_height", C.c_int32), ("int_width", C.c_int32),
-                ("mask_height", C.c_int32), ("mask_width", C.c_int32), ("half_height", C.c_int32), ("half_width", C.c_int32),
-                ("is_float32", C.c_int32), ("reserved", C.c_int32), ("normals", C.c_void_p), ("normals2", C.c_void_p), ("normals_variance", C.c_void_p),
-                ("normals2_variance", C.c_void_p), ("mask", C.c_void_p), ("continuity_mask", C.c_void_p)]
-
-
-class CNormalPriorOutput(C.Structure):
-    _fields_ = [("data", C.c_void_p), ("uncertainty", C.c_void_p), ("data_downscaled", C.c_void_p),
-                ("uncertainty_downscaled", C.c_void_p)]
-
-
-class CPriorSummary(C.Structure):
-    _fields_ = [("ms", C.c_float), ("n_images", C.c_int32), ("n_pixels", C.c_int64)]
-
-
 def _prior_values(item, names, shape_tail=()):
     """The value maps of one image in ONE precision: float32 when every present map is float32, float64 otherwise.
     Returns (is_float32, {name: C-contiguous array or None})."""
@@ -1389,9 +1106,7 @@ def depth_priors(items, conf, device=0, return_summary=False):
     for name in ("use_continuity", "fixed_uncertainty", "prior_uncertainty", "flip_consistency"):
         setattr(cf, name, int(bool(conf[name])))
     S = CPriorSummary()
-    L = lib()
-    L.mpsfm_depth_priors.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_depth_priors(n, C.addressof(P), C.addressof(cf), int(device), C.addressof(O), C.addressof(S)))
+    _check(lib().mpsfm_depth_priors(n, C.addressof(P), C.addressof(cf), int(device), C.addressof(O), C.addressof(S)))
     for o in outs:
         o["valid"], o["continuity_mask"] = o["valid"].view(np.bool_), o["continuity_mask"].view(np.bool_)
     return (outs, dict(ms=S.ms, n_images=S.n_images, n_pixels=S.n_pixels)) if return_summary else outs
@@ -1446,7 +1161,5 @@ def normal_priors(items, conf, device=0, return_summary=False):
         setattr(cf, name, float(conf[name]))
     cf.flip_consistency = int(bool(conf["flip_consistency"]))
     S = CPriorSummary()
-    L = lib()
-    L.mpsfm_normal_priors.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    _check(L.mpsfm_normal_priors(n, C.addressof(P), C.addressof(cf), int(device), C.addressof(O), C.addressof(S)))
+    _check(lib().mpsfm_normal_priors(n, C.addressof(P), C.addressof(cf), int(device), C.addressof(O), C.addressof(S)))
     return (outs, dict(ms=S.ms, n_images=S.n_images, n_pixels=S.n_pixels)) if return_summary else outs

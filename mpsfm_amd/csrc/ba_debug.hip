@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/mpsfm_hip_debug.h"
 #include "ba_handle.h"
 
 using namespace mpsfm;

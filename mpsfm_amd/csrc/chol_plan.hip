@@ -8,7 +8,7 @@
 #include <map>
 #include <utility>
 
-#include "../../include/mpsfm_hip.h"
+#include "../../include/mpsfm_hip_debug.h"
 
 namespace mpsfm {
 namespace {

@@ -6,6 +6,7 @@
 // row-major inside a tile.  Tile row `nt` (one extra) carries the right-hand side in its row 0, so
 // the forward substitution z = L^-1 rhs falls out of the factorisation; k_backsub then solves
 // L^T y = z.
+#include "../../include/mpsfm_hip_debug.h"
 #include "common.h"
 #include "ba_launch.h"
 #include "dense_tile.h"

@@ -1,4 +1,4 @@
-"""Flat bundle-adjustment problem descriptor and its ctypes mirror of include/mpsfm_hip.h.
+"""Flat bundle-adjustment problem descriptor (its ctypes mirrors of include/mpsfm_hip.h are declared in abi.py).
 
 The descriptor is exactly what ``Optimizer.__build_problem`` gathers before it hands the
 problem to Ceres (reference mpsfm/sfm/mapper/bundle_adjustment.py:67-185): poses with gauge
@@ -12,144 +12,12 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from .abi import (  # noqa: F401 - the ctypes mirrors live in abi.py; these names stay importable from here
+    ALLREDUCE_FN, INT_MAX_IRLS, MAX_TRACE, TERMINATION_NAMES, CIntProblem, CIntSummary, COptions, CProblem, CState, CSummary, CTracks,
+)
+
 LOSS_TRIVIAL, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2
 LOSS_BY_NAME = {"trivial": LOSS_TRIVIAL, "softl1": LOSS_SOFT_L1, "soft_l1": LOSS_SOFT_L1, "cauchy": LOSS_CAUCHY}
-
-MAX_TRACE = 64
-
-TERMINATION_NAMES = {
-    0: "function_tolerance",
-    1: "gradient_tolerance",
-    2: "parameter_tolerance",
-    3: "max_iterations",
-    4: "min_radius",
-    5: "invalid_steps",
-    6: "no_variables",
-}
-
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_void_p)
-
-
-class CProblem(C.Structure):
-    _fields_ = [
-        ("n_cams", C.c_int32),
-        ("n_pts", C.c_int32),
-        ("n_intr", C.c_int32),
-        ("cam_intr", C.c_void_p),
-        ("cam_intr_idx", C.c_void_p),
-        ("pose_const", C.c_void_p),
-        ("gauge_axis_cam", C.c_int32),
-        ("pt_const", C.c_void_p),
-        ("n_obs", C.c_int64),
-        ("obs_cam", C.c_void_p),
-        ("obs_pt", C.c_void_p),
-        ("obs_xy", C.c_void_p),
-        ("reproj_loss_type", C.c_int32),
-        ("reproj_loss_scale", C.c_double),
-        ("reproj_loss_magnitude", C.c_double),
-        ("n_dobs", C.c_int64),
-        ("dobs_cam", C.c_void_p),
-        ("dobs_pt", C.c_void_p),
-        ("dobs_depth", C.c_void_p),
-        ("dobs_magnitude", C.c_void_p),
-        ("dobs_param", C.c_void_p),
-        ("depth_loss_type", C.c_int32),
-        ("shift_logscale", C.c_void_p),
-    ]
-
-
-class CState(C.Structure):
-    _fields_ = [("cam_quat_xyzw", C.c_void_p), ("cam_t", C.c_void_p), ("pts", C.c_void_p)]
-
-
-class COptions(C.Structure):
-    _fields_ = [
-        ("max_num_iterations", C.c_int32),
-        ("function_tolerance", C.c_double),
-        ("gradient_tolerance", C.c_double),
-        ("parameter_tolerance", C.c_double),
-        ("initial_trust_region_radius", C.c_double),
-        ("max_trust_region_radius", C.c_double),
-        ("min_trust_region_radius", C.c_double),
-        ("min_relative_decrease", C.c_double),
-        ("min_lm_diagonal", C.c_double),
-        ("max_lm_diagonal", C.c_double),
-        ("max_num_consecutive_invalid_steps", C.c_int32),
-        ("jacobi_scaling", C.c_int32),
-        ("device", C.c_int32),
-        ("stream", C.c_void_p),
-        ("verbose", C.c_int32),
-        ("allreduce", ALLREDUCE_FN),
-        ("allreduce_user", C.c_void_p),
-        ("world_size", C.c_int32),
-        ("rank", C.c_int32),
-        ("use_rccl", C.c_int32),
-        ("comm_id", C.c_uint8 * 128),
-    ]
-
-
-class CSummary(C.Structure):
-    _fields_ = [
-        ("initial_cost", C.c_double),
-        ("final_cost", C.c_double),
-        ("fixed_cost", C.c_double),
-        ("num_iterations", C.c_int32),
-        ("num_successful_steps", C.c_int32),
-        ("num_unsuccessful_steps", C.c_int32),
-        ("termination", C.c_int32),
-        ("num_residual_blocks", C.c_int64),
-        ("num_residual_evals", C.c_int64),
-        ("num_jacobian_evals", C.c_int64),
-        ("reduced_dim", C.c_int32),
-        ("final_radius", C.c_double),
-        ("time_total_s", C.c_double),
-        ("time_linearize_s", C.c_double),
-        ("time_dense_s", C.c_double),
-        ("time_update_s", C.c_double),
-        ("trace_len", C.c_int32),
-        ("trace_cost", C.c_double * MAX_TRACE),
-        ("trace_radius", C.c_double * MAX_TRACE),
-        ("trace_accepted", C.c_uint8 * MAX_TRACE),
-    ]
-
-    def to_dict(self) -> dict:
-        n = self.trace_len
-        return {
-            "initial_cost": self.initial_cost,
-            "final_cost": self.final_cost,
-            "fixed_cost": self.fixed_cost,
-            "num_iterations": self.num_iterations,
-            "num_successful_steps": self.num_successful_steps,
-            "num_unsuccessful_steps": self.num_unsuccessful_steps,
-            "termination": TERMINATION_NAMES.get(self.termination, str(self.termination)),
-            "num_residual_blocks": self.num_residual_blocks,
-            "num_residual_evals": self.num_residual_evals,
-            "num_jacobian_evals": self.num_jacobian_evals,
-            "reduced_dim": self.reduced_dim,
-            "final_radius": self.final_radius,
-            "time_total_s": self.time_total_s,
-            "time_linearize_s": self.time_linearize_s,
-            "time_dense_s": self.time_dense_s,
-            "time_update_s": self.time_update_s,
-            "trace_cost": [self.trace_cost[i] for i in range(n)],
-            "trace_radius": [self.trace_radius[i] for i in range(n)],
-            "trace_accepted": [int(self.trace_accepted[i]) for i in range(n)],
-        }
-
-
-class CTracks(C.Structure):
-    _fields_ = [
-        ("n_cams", C.c_int32),
-        ("n_tracks", C.c_int32),
-        ("n_intr", C.c_int32),
-        ("cam_quat_xyzw", C.c_void_p),
-        ("cam_t", C.c_void_p),
-        ("cam_intr", C.c_void_p),
-        ("cam_intr_idx", C.c_void_p),
-        ("track_start", C.c_void_p),
-        ("el_cam", C.c_void_p),
-        ("el_xy", C.c_void_p),
-    ]
 
 
 def _arr(a, dtype, shape=None):
@@ -336,29 +204,3 @@ class Tracks:
         t.cam_intr, t.cam_intr_idx = _ptr(self.cam_intr), _ptr(self.cam_intr_idx)
         t.track_start, t.el_cam, t.el_xy = _ptr(self.track_start), _ptr(self.el_cam), _ptr(self.el_xy)
         return t
-
-
-INT_MAX_IRLS = 16
-
-
-class CIntProblem(C.Structure):
-    _fields_ = [
-        ("H", C.c_int32), ("W", C.c_int32),
-        ("depth_prior", C.c_void_p), ("depth_uncertainty", C.c_void_p), ("valid", C.c_void_p), ("normals", C.c_void_p),
-        ("normals_var", C.c_void_p), ("depth_init", C.c_void_p), ("K", C.c_double * 4),
-        ("n_sparse", C.c_int32), ("sparse_x", C.c_void_p), ("sparse_y", C.c_void_p), ("sparse_depth3d", C.c_void_p),
-        ("sparse_zvar", C.c_void_p),
-        ("large_number", C.c_double), ("tol", C.c_double), ("step_size", C.c_double), ("cg_tol", C.c_double),
-        ("lambda1", C.c_double), ("lambda2", C.c_double), ("k", C.c_double), ("depth_magnitude_multiplier", C.c_double),
-        ("normals_magnitude_multiplier", C.c_double), ("scale_filter_factor", C.c_double),
-        ("max_iter", C.c_int32), ("cg_max_iter", C.c_int32), ("scale_filter", C.c_int32),
-        ("init", C.c_int32), ("integrated", C.c_int32), ("energy_old", C.c_double), ("wu", C.c_void_p), ("wv", C.c_void_p),
-    ]
-
-
-class CIntSummary(C.Structure):
-    _fields_ = [
-        ("changed", C.c_int32), ("irls_iterations", C.c_int32), ("cg_iterations_total", C.c_int32), ("integrated_out", C.c_int32),
-        ("energy_initial", C.c_double), ("energy_final", C.c_double), ("energy_old_out", C.c_double),
-        ("cg_iters", C.c_int32 * INT_MAX_IRLS), ("energies", C.c_double * (INT_MAX_IRLS + 1)), ("ms", C.c_float),
-    ]

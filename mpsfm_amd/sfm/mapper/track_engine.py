@@ -18,28 +18,12 @@ import ctypes as C
 import numpy as np
 
 from ... import capi
+from ...abi import CTriGraph, CTriOptions, CTriState  # noqa: F401 - declared in abi.py, importable from here as before
 from .bundle_adjustment import pinhole_params
 
 _OPT_FIELDS = ("max_transitivity", "create_max_angle_error", "continue_max_angle_error", "merge_max_reproj_error",
                "complete_max_reproj_error", "complete_max_transitivity", "re_max_angle_error", "re_min_ratio", "re_max_trials",
                "min_angle", "ignore_two_view_tracks")
-
-
-class CTriOptions(C.Structure):
-    _fields_ = [("max_transitivity", C.c_int32), ("create_max_angle_error", C.c_double), ("continue_max_angle_error", C.c_double),
-                ("merge_max_reproj_error", C.c_double), ("complete_max_reproj_error", C.c_double), ("complete_max_transitivity", C.c_int32),
-                ("re_max_angle_error", C.c_double), ("re_min_ratio", C.c_double), ("re_max_trials", C.c_int32), ("min_angle", C.c_double),
-                ("ignore_two_view_tracks", C.c_int32)]
-
-
-class CTriGraph(C.Structure):
-    _fields_ = [("n_images", C.c_int32), ("kp_start", C.c_void_p), ("kp_xy", C.c_void_p), ("cam_intr", C.c_void_p),
-                ("corr_start", C.c_void_p), ("corr_kp", C.c_void_p)]
-
-
-class CTriState(C.Structure):
-    _fields_ = [("registered", C.c_void_p), ("cam_quat_xyzw", C.c_void_p), ("cam_t", C.c_void_p), ("kp_point", C.c_void_p),
-                ("n_points", C.c_int64), ("xyz", C.c_void_p)]
 
 
 def tri_options(options) -> CTriOptions:
@@ -114,7 +98,6 @@ def state_arrays(mpsfm_rec, image_ids, kp_start):
 
 class HipIncrementalTriangulator:
     def __init__(self, correspondence_graph, mpsfm_rec, device: int = 0):
-        L = capi.lib()
         self.rec, self.cg, self.device = mpsfm_rec, correspondence_graph, device
         ga = graph_arrays(correspondence_graph, mpsfm_rec)
         for k, v in ga.items():
@@ -123,23 +106,8 @@ class HipIncrementalTriangulator:
                       self.corr_start.ctypes.data, self.corr_kp.ctypes.data)
         self._image_ids_arr = np.asarray(self.image_ids)
         self._h = C.c_void_p(None)
-        L.mpsfm_triangulator_create.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
-        capi._check(L.mpsfm_triangulator_create(C.byref(g), device, C.byref(self._h)))
+        capi._check(capi.lib().mpsfm_triangulator_create(C.byref(g), device, C.byref(self._h)))
         capi._track(self)  # closed before the interpreter's exit handlers give way to the C runtime's
-        for name in ("triangulate_image", "complete_image"):
-            getattr(L, "mpsfm_triangulator_" + name).argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
-        for name in ("complete_tracks", "merge_tracks"):
-            getattr(L, "mpsfm_triangulator_" + name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-        L.mpsfm_triangulator_retriangulate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
-        L.mpsfm_triangulator_set_state.argtypes = [C.c_void_p, C.c_void_p]
-        L.mpsfm_triangulator_get_ops.argtypes = [C.c_void_p] * 5
-        L.mpsfm_triangulator_get_op_elements.argtypes = [C.c_void_p, C.c_void_p]
-        for name in ("num_ops", "num_points", "num_op_elements"):
-            getattr(L, "mpsfm_triangulator_" + name).argtypes = [C.c_void_p]
-            getattr(L, "mpsfm_triangulator_" + name).restype = C.c_int64
-        L.mpsfm_triangulator_destroy.argtypes = [C.c_void_p]
-        L.mpsfm_triangulator_destroy.restype = None
-        L.mpsfm_triangulator_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
         self.last_ops = None
 
     def close(self):

@@ -14,7 +14,6 @@ h.sweep_once(1e4)
 L=capi.lib()
 nt=h.dense_plan()["tile_columns"]
 buf=torch.zeros((nt+1)*2*8, dtype=torch.int64, device="cuda")
-L.mpsfm_debug_set_chol_trace.argtypes=[C.c_void_p]
 for _ in range(3): h.dense_solve_once()
 assert L.mpsfm_debug_set_chol_trace(buf.data_ptr())==0
 ms=h.dense_solve_once()

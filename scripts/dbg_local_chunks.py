@@ -7,8 +7,6 @@ from mpsfm_amd.synthetic import make_scene
 ncam, npts = int(sys.argv[1]), int(sys.argv[2])
 prob, _ = make_scene(ncam, npts, True, seed=3)
 L = capi.lib()
-L.mpsfm_debug_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
-L.mpsfm_debug_table.restype = C.c_int64
 L.mpsfm_debug_set(64 << 8)
 h = capi.BAHandle(prob)
 for _ in range(2):

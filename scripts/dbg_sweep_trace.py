@@ -14,7 +14,6 @@ L.mpsfm_debug_set(128 << 8)
 h.sweep_once(1e4)
 n = h.sweep_parts()["dense_chunks"]
 buf = np.zeros(n * 64, np.int64)
-L.mpsfm_debug_read_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 capi._check(L.mpsfm_debug_read_trace(h._h, buf.ctypes.data, len(buf)))
 L.mpsfm_debug_set(0)
 t = buf.reshape(n, 4, 16)[:, :, :10].astype(np.float64)

@@ -7,15 +7,12 @@ from mpsfm_amd.synthetic import make_scene
 prob, _ = make_scene(int(sys.argv[1]), int(sys.argv[2]), True, seed=3)
 h = capi.BAHandle(prob)
 L = capi.lib()
-L.mpsfm_debug_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
-L.mpsfm_debug_table.restype = C.c_int64
 for _ in range(3):
     h.sweep_once(1e4)
 L.mpsfm_debug_set(128 << 8)
 h.sweep_once(1e4)
 n = h.sweep_parts()["dense_chunks"]
 buf = np.zeros(n * 64, np.int64)
-L.mpsfm_debug_read_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 capi._check(L.mpsfm_debug_read_trace(h._h, buf.ctypes.data, len(buf)))
 L.mpsfm_debug_set(0)
 nb = L.mpsfm_debug_table(h._h, 0, None, 0)

@@ -6,7 +6,6 @@ from mpsfm_amd import capi
 from mpsfm_amd.synthetic import make_scene
 from oracle import cpu_oracle as O
 L = capi.lib()
-L.mpsfm_debug_local_clocks.argtypes = [C.c_void_p, C.c_void_p]; L.mpsfm_debug_local_clocks.restype = C.c_int
 def problem(seed):
     rng = np.random.default_rng(5000 + seed)
     n_cams = int(rng.integers(2, 20)); n_pts = int(rng.integers(20, 6000)); depth = bool(rng.integers(0, 2))

@@ -104,8 +104,6 @@ def _read(call):
 def handle_tables(prob):
     """Every table of a handle created from `prob` under the current environment."""
     L = capi.lib()
-    L.mpsfm_debug_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
-    L.mpsfm_debug_table.restype = C.c_int64
     with capi.BAHandle(prob.copy()) as h:
         return _read(lambda which, out, cap: L.mpsfm_debug_table(h._h, which, out, cap))
 
@@ -113,8 +111,6 @@ def handle_tables(prob):
 def host_tables(prob):
     """The same tables from the host phases alone (mpsfm_debug_host_build: no device involved)."""
     L = capi.lib()
-    L.mpsfm_debug_host_build.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
-    L.mpsfm_debug_host_build.restype = C.c_int64
     cp = prob.c_problem()
     return _read(lambda which, out, cap: L.mpsfm_debug_host_build(C.byref(cp), which, out, cap))
 

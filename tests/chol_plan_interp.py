@@ -15,11 +15,6 @@ T = 32
 
 def _plan(adj, depth=-2, pinv_max_tiles=64, inv_rows=2):
     L = capi.lib()
-    L.mpsfm_debug_plan_create.restype = C.c_void_p
-    L.mpsfm_debug_plan_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    L.mpsfm_debug_plan_get.restype = C.c_int64
-    L.mpsfm_debug_plan_get.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
-    L.mpsfm_debug_plan_destroy.argtypes = [C.c_void_p]
     a = np.ascontiguousarray(adj, dtype=np.uint8)
     h = L.mpsfm_debug_plan_create(a.ctypes.data, a.shape[0], depth, pinv_max_tiles, inv_rows)
     assert h

@@ -56,7 +56,6 @@ def test_sampler_draws_distinct_indices_in_range():
 
 def _call(n, p2, p3, K, o=None, mask=True, res=True):
     L = capi.lib()
-    L.mpsfm_abs_pose_estimate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     if o is None:
         o = capi.CAbsPoseOptions(12.0, 0.25, 0.99999, 3.0, 100, 10000, 0, 0, 0)
     m = np.zeros(max(n, 1), np.uint8)

@@ -49,7 +49,6 @@ def test_restatement_alive_mask_is_the_compacted_problem():
 
 def _nms(n, pts, sc, order, radius, keep, kept, info=None, device=0):
     L = capi.lib()
-    L.mpsfm_radius_nms.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     return L.mpsfm_radius_nms(n, p(pts), p(sc), p(order), radius, device, p(keep), p(kept), info)
 
@@ -82,9 +81,6 @@ def test_radius_nms_checks_arguments_before_any_device():
 
 def test_thin_and_assign_check_arguments_before_any_device():
     L = capi.lib()
-    L.mpsfm_thin_dense_matches.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.mpsfm_assign_keypoints.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
     s, d, sc = np.zeros((2, 2)), np.arange(8.0).reshape(4, 2), np.ones(4)
     keep, kept = np.zeros(4, np.uint8), np.zeros(1, np.int64)
     P = lambda a: None if a is None else a.ctypes.data  # noqa: E731

@@ -104,8 +104,6 @@ def _raw(images, pa, pb, counts=None, n_images=None, n_pairs=None):
     pb = np.ascontiguousarray(pb, np.int32)
     cnt = np.zeros((max(len(pa), 1), 2, 4), np.int64) if counts is None else counts
     L = capi.lib()
-    L.mpsfm_depth_consistency.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     return L.mpsfm_depth_consistency(len(images) if n_images is None else n_images, C.addressof(arr),
                                      len(pa) if n_pairs is None else n_pairs, pa.ctypes.data, pb.ctypes.data, 15.0, 0.6, 0,
                                      cnt.ctypes.data if counts is not False else None, None, None)

@@ -82,10 +82,6 @@ def test_restatement_sampling_is_the_pixel_on_pixels_and_zero_outside():
 
 def _lib():
     L = capi.lib()
-    L.mpsfm_match_default_options.restype = None
-    L.mpsfm_match_default_options.argtypes = [C.c_void_p]
-    L.mpsfm_match_descriptors.argtypes = capi._MATCH_DESC_ARGS
-    L.mpsfm_match_map_descriptors.argtypes = capi._MATCH_MAP_ARGS
     return L
 
 

@@ -105,7 +105,6 @@ def test_camera_graph_union_through_the_sum_exchange(world):
     from mpsfm_amd import capi
 
     L = capi.lib()
-    L.mpsfm_debug_graph_union.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     rng = np.random.default_rng(world)
     for n in (1, 7, 67, 130):
         adj = (rng.uniform(size=(world, n, n)) < 0.15).astype(np.uint8)

@@ -156,8 +156,6 @@ def test_refinement_takes_the_single_launch_solver():
     ap = AbsolutePose()
     prob = ap.refinement_problem(np.c_[R, t], p2, X, K)
     L = capi.lib()
-    L.mpsfm_debug_local_clocks.argtypes = [C.c_void_p, C.c_void_p]
-    L.mpsfm_debug_local_clocks.restype = C.c_int
     with capi.BAHandle(prob, ap.solver_options()) as h:
         s = h.solve()
         clk = (C.c_int64 * 12)()

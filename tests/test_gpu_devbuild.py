@@ -23,8 +23,6 @@ TABLES = {0: ("chunks", np.int32), 1: ("chunk_cams", np.int32), 2: ("rec_cam", n
 
 def tables(h):
     L = capi.lib()
-    L.mpsfm_debug_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
-    L.mpsfm_debug_table.restype = C.c_int64
     out = {}
     for which, (name, dt) in TABLES.items():
         n = L.mpsfm_debug_table(h._h, which, None, 0)

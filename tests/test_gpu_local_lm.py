@@ -18,8 +18,6 @@ pytestmark = pytest.mark.gpu
 def local_iterations(h) -> int:
     """Iterations the handle's last solve ran inside the single launch; -1: the handle does not take that path."""
     L = capi.lib()
-    L.mpsfm_debug_local_clocks.argtypes = [C.c_void_p, C.c_void_p]
-    L.mpsfm_debug_local_clocks.restype = C.c_int
     clk = (C.c_int64 * 12)()
     return int(clk[6]) if L.mpsfm_debug_local_clocks(h._h, clk) else -1
 

@@ -23,8 +23,6 @@ SHAPES = [(3, 300, True), (7, 900, False), (12, 4000, True), (16, 6000, True)]  
 
 def set_skew(chunk, mask, ticks) -> int:
     L = capi.lib()
-    L.mpsfm_debug_local_skew.argtypes = [C.c_int32, C.c_int32, C.c_int64]
-    L.mpsfm_debug_local_skew.restype = C.c_int
     return L.mpsfm_debug_local_skew(chunk, mask, ticks)
 
 
@@ -42,15 +40,12 @@ def skew():
 def local_clocks(h):
     """The phase clocks of the handle's last single-launch solve: [6] iterations, [11] ticks the skew hook waited; None: the chain."""
     L = capi.lib()
-    L.mpsfm_debug_local_clocks.argtypes = [C.c_void_p, C.c_void_p]
-    L.mpsfm_debug_local_clocks.restype = C.c_int
     clk = (C.c_int64 * 12)()
     return [int(x) for x in clk] if L.mpsfm_debug_local_clocks(h._h, clk) else None
 
 
 def dense_chunks(h) -> int:
     L = capi.lib()
-    L.mpsfm_ba_sweep_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     info = (C.c_int64 * 4)()
     assert L.mpsfm_ba_sweep_parts(h._h, None, info) == 0
     return int(info[0])

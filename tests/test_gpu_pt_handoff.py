@@ -30,8 +30,6 @@ def gpu_solve(prob, monkeypatch, options=None, **env):
         monkeypatch.setenv("MPSFM_" + k, v)
     out = prob.copy()
     L = capi.lib()
-    L.mpsfm_debug_local_clocks.argtypes = [C.c_void_p, C.c_void_p]
-    L.mpsfm_debug_local_clocks.restype = C.c_int
     with capi.BAHandle(prob.copy(), options=options) as h:
         s = h.solve()
         h.get_state(out)

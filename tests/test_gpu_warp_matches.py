@@ -123,7 +123,6 @@ def test_simple_nms_in_place_on_the_device_is_refused():
     import torch
 
     L = capi.lib()
-    L.mpsfm_simple_nms.argtypes = capi._SIMPLE_NMS_ARGS
     t = torch.rand(80, 70, device="cuda")
     u = torch.empty(81, 70, device="cuda")
     torch.cuda.synchronize()

@@ -224,8 +224,6 @@ def _run_parts(nparts, reps):
     from mpsfm_amd import capi
 
     L = capi.lib()
-    L.mpsfm_debug_run_parts.restype = C.c_int64
-    L.mpsfm_debug_run_parts.argtypes = [C.c_int32, C.c_int32]
     return int(L.mpsfm_debug_run_parts(nparts, reps))
 
 
@@ -265,8 +263,6 @@ def test_table_build_host_blocks_are_recycled():
     from mpsfm_amd import capi
 
     L = capi.lib()
-    L.mpsfm_debug_host_cache.restype = C.c_int64
-    L.mpsfm_debug_host_cache.argtypes = [C.c_int64, C.c_int32]
     assert L.mpsfm_debug_host_cache(3 << 20, 4) == 4      # 3 MB blocks (4 MB buckets): all four recycled
     assert L.mpsfm_debug_host_cache(3 << 20, 4) == 4      # and again from the same cache
     assert L.mpsfm_debug_host_cache(5 << 20, 2) == 2      # another bucket

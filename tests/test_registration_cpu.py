@@ -351,9 +351,6 @@ def test_wrappers_check_arguments_before_the_library_is_touched(monkeypatch):
 
 def test_entry_points_validate_on_the_host_and_need_a_device():
     L = capi.lib()
-    L.mpsfm_registration_pairs.argtypes = [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                           C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.mpsfm_init_pair_candidates.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     ref = capi.CRegImage()
     m = np.ones((4, 4))
     ref.map_h, ref.map_w, ref.depth_map, ref.sx, ref.sy = 4, 4, m.ctypes.data, 1.0, 1.0

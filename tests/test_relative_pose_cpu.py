@@ -90,8 +90,6 @@ def test_decomposition_picks_the_physical_candidate():
 
 def _call(n, p1, p2, K1, K2, o=None, mask=True, res=True):
     L = capi.lib()
-    L.mpsfm_rel_pose_estimate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                          C.c_void_p]
     if o is None:
         o = capi.CRelPoseOptions(4.0, 0.01, 0.9999, 3.0, 1000, 100000, 0, 0, 0)
     m = np.zeros(max(n, 1), np.uint8)

@@ -261,8 +261,6 @@ def test_geometric_verification_masks_equal_the_references_isin_expression():
 # ---- the entry point's argument checks ------------------------------------------------------------------------------------
 def _default_options():
     L = capi.lib()
-    L.mpsfm_two_view_default_options.restype = None
-    L.mpsfm_two_view_default_options.argtypes = [C.c_void_p]
     o = capi.CTwoViewOptions()
     L.mpsfm_two_view_default_options(C.byref(o))
     return o
@@ -270,7 +268,6 @@ def _default_options():
 
 def _call(n, p1, p2, K1, K2, s1=(1280, 960), s2=(1200, 1000), o=None, mask=True, res=True):
     L = capi.lib()
-    L.mpsfm_two_view_geometry.argtypes = [C.c_int64] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_void_p]
     if o is None:
         o = _default_options()
     m = np.zeros(max(n, 1) if n < 2**20 else 1, np.uint8)
@@ -293,7 +290,6 @@ def test_default_options_are_colmaps():
         assert getattr(o, k) == d[k]
     assert (d["max_error"], d["min_inlier_ratio"], d["confidence"], d["min_num_trials"], d["max_num_trials"]) == (4.0, 0.25, 0.999, 100, 10000)
     assert (d["min_num_inliers"], d["min_E_F_inlier_ratio"], d["max_H_inlier_ratio"]) == (15, 0.95, 0.8)
-    assert C.sizeof(capi.CTwoViewOptions) == 112 and C.sizeof(capi.CTwoViewResult) == 552 and C.sizeof(capi.CTwoViewLeg) == 48
     assert {k: v for k, v in TV.DEFAULT_OPTIONS.items()} == {k: v for k, v in d.items() if k != "batch_trials"}
 
 
@@ -368,7 +364,6 @@ def test_tri_estimate_batch_rejects_a_first_offset_other_than_zero():
         c = capi.CTriCandidates(2, cs_.ctypes.data, P.ctypes.data, K.ctypes.data, xy.ctypes.data, 0.0, 0.03, 0, None)
         xyz, ok, inl = np.zeros((2, 3)), np.zeros(2, np.uint8), np.zeros(4, np.uint8)
         L = capi.lib()
-        L.mpsfm_tri_estimate_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         assert L.mpsfm_tri_estimate_batch(C.byref(c), 0, xyz.ctypes.data, ok.ctypes.data, inl.ctypes.data) == -1
         assert b"cand_start[0]" in L.mpsfm_last_error()
 

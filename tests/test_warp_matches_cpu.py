@@ -86,11 +86,6 @@ def test_restatement_empty_and_radius_zero_branches():
 # ---- the C ABI without a device -------------------------------------------------------------------------------------------
 def _lib():
     L = capi.lib()
-    L.mpsfm_warp_default_options.restype = None
-    L.mpsfm_warp_default_options.argtypes = [C.c_void_p]
-    L.mpsfm_simple_nms.argtypes = capi._SIMPLE_NMS_ARGS
-    L.mpsfm_kpids_to_matches0.argtypes = capi._KPIDS_ARGS
-    L.mpsfm_warp_matches.argtypes = capi._WARP_ARGS
     return L
 
 
