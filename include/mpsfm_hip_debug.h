@@ -19,7 +19,7 @@ typedef struct mpsfm_plan_handle mpsfm_plan_handle;
 
 /* process-wide ablation flags: bits 0-7 dense solve, bits 8-15 track sweep; 0: off */
 void mpsfm_debug_set(int f);
-/* registers a device buffer for the phase timeline of the factorisation (100 MHz stamps, 2 x 8 per step); NULL: off */
+/* registers a device buffer for the phase timeline of the factorisation (100 MHz stamps, 2 x 8 per step) with the solves launched from now on; NULL: off */
 int mpsfm_debug_set_chol_trace(long long* dev_buf);
 /* one workgroup factors the stacked host matrix dx [64][32] = [D; X] with `waves` (1 or 4) waves; out: L, X L^-T; *ok: every pivot positive */
 int mpsfm_debug_panel_factor(const double* dx, int waves, double* out, int* ok);
@@ -28,7 +28,7 @@ int mpsfm_debug_panel_factor(const double* dx, int waves, double* out, int* ok);
 mpsfm_plan_handle* mpsfm_debug_plan_create(const uint8_t* adj, int32_t n, int32_t depth, int32_t pinv_max_tiles, int32_t inv_rows);
 /* frees a plan of mpsfm_debug_plan_create; NULL is allowed */
 void mpsfm_debug_plan_destroy(mpsfm_plan_handle* h);
-/* table `what` (0 header ... 13 col_of_slot, see csrc/chol_plan.hip) of a plan; returns its length, copies min(length, cap) entries */
+/* table `what` (0 header ... 13 col_of_slot, 14 the launch records as int32, 16 per item: see csrc/chol_plan.hip) of a plan; returns its length, copies min(length, cap) entries */
 int64_t mpsfm_debug_plan_get(const mpsfm_plan_handle* h, int32_t what, int32_t* out, int64_t cap);
 
 /* no device involved: `count` host blocks of `bytes` through the block cache twice; returns how many of the second round were recycled */
@@ -40,6 +40,8 @@ int mpsfm_debug_graph_union(const uint8_t* adj, int32_t world, int32_t n, uint8_
 
 /* 1: the handle's track sweep hands the landmark factors to its update sweep, 0: the update sweep recomputes them */
 int mpsfm_debug_pt_handoff(mpsfm_ba_handle* h);
+/* mpsfm_ba_dense_solve_once on the given system (S n x n and rhs in the caller's camera order, zero outside the handle's block pattern) instead of the last sweep's; *failed: a pivot was not positive */
+int mpsfm_debug_dense_solve_given(mpsfm_ba_handle* h, const double* S, const double* rhs, int32_t n, int32_t* failed);
 /* the first `count` 8-byte words of the landmark-diagonal buffer, where the dense sweep leaves its phase stamps under debug flag 128 */
 int mpsfm_debug_read_trace(mpsfm_ba_handle* h, long long* out, int64_t count);
 /* table `which` (numbering in csrc/ba_debug.hip) of the handle copied to `out` (at most `cap` bytes); returns its size in bytes or a negative error code */

@@ -176,6 +176,16 @@ class BAHandle:
         _check(lib().mpsfm_ba_dense_solve_once(self._h, C.byref(ms)))
         return ms.value
 
+    def dense_solve_given(self, S: np.ndarray, rhs: np.ndarray) -> bool:
+        """dense_solve_once on the given system (caller's camera order, zero outside the handle's block pattern) instead of the last
+        sweep's; True when the factorisation met a pivot that is not positive.  Needs one sweep_once before it."""
+        n = self.reduced_dim
+        S, rhs = np.ascontiguousarray(S, np.float64), np.ascontiguousarray(rhs, np.float64)
+        assert S.shape == (n, n) and rhs.shape == (n,)
+        failed = C.c_int32(0)
+        _check(lib().mpsfm_debug_dense_solve_given(self._h, S.ctypes.data, rhs.ctypes.data, n, C.byref(failed)))
+        return bool(failed.value)
+
     def reduced_system(self):
         n = self.reduced_dim
         S, rhs = np.zeros((n, n)), np.zeros(n)

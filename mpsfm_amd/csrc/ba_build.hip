@@ -26,7 +26,7 @@ void free_handle(mpsfm_ba_handle* h) {
                   h->d_chunk_cams, h->d_blk_ent_start, h->d_blk_desc, h->d_ents, h->d_red, h->d_part, h->d_part2, h->d_scal, h->d_costpart, h->d_A, h->d_yc, h->d_dwork, h->d_fail, h->d_lhdr, h->d_wl, h->d_slab, h->d_red_dests, h->d_red_srcs,
                   h->d_sky_first, h->d_sky_start, h->d_sky_index,
                   h->d_local_acc, h->d_local_sync, h->d_local_log, h->d_perm, h->d_user_pts, h->d_cam_of_slot,
-                  h->d_lp_items, h->d_lp_srcs, h->d_lp_rows, h->d_lp_struct_start, h->d_lp_struct_rows, h->d_lp_back_cols, h->d_lp_asm, h->d_lp_live, h->d_lp_col_slot};
+                  h->d_lp_items, h->d_lp_heads, h->d_lp_srcs, h->d_lp_rows, h->d_lp_struct_start, h->d_lp_struct_rows, h->d_lp_back_cols, h->d_lp_asm, h->d_lp_live, h->d_lp_col_slot};
   for (void* p : ptrs) cached_free(p);
   h->rt.release();
   comm_destroy(h->comm);
@@ -78,13 +78,13 @@ static int upload_pattern(mpsfm_ba_handle* h, bool use_graph) {
     return rc;
   std::vector<uint8_t> live((size_t)(PL.nt + 1) * (size_t)(PL.nt + 2) / 2, 0);
   for (int32_t id : PL.asm_tiles) live[(size_t)id] = 1;
-  if (int rc = dev_upload(&h->d_lp_items, PL.items, &h->d_lp_srcs, PL.srcs, &h->d_lp_rows, PL.rows, &h->d_lp_struct_start, PL.struct_start,
+  if (int rc = dev_upload(&h->d_lp_items, PL.items, &h->d_lp_heads, PL.heads, &h->d_lp_srcs, PL.srcs, &h->d_lp_rows, PL.rows, &h->d_lp_struct_start, PL.struct_start,
                           &h->d_lp_struct_rows, PL.struct_rows, &h->d_lp_back_cols, PL.back_cols, &h->d_lp_asm, PL.asm_tiles,
                           &h->d_lp_col_slot, PL.slot_of_col, &h->d_lp_live, live))
     return rc;
   LevelPlanDev& D = h->lp;
   level_plan_flags(PL, D);
-  D.d_items = h->d_lp_items; D.d_srcs = h->d_lp_srcs; D.d_rows = h->d_lp_rows;
+  D.d_items = h->d_lp_items; D.d_heads = h->d_lp_heads; D.d_srcs = h->d_lp_srcs; D.d_rows = h->d_lp_rows;
   D.d_struct_start = h->d_lp_struct_start; D.d_struct_rows = h->d_lp_struct_rows; D.d_back_cols = h->d_lp_back_cols;
   D.d_asm_tiles = h->d_lp_asm; D.d_tile_live = h->d_lp_live; D.d_col_slot = PL.slot_of_col.empty() ? nullptr : h->d_lp_col_slot; D.n_asm = (int32_t)PL.asm_tiles.size(); D.nlevels = PL.nlevels;
   D.h_launch_start = PL.launch_start.data(); D.h_back_start = PL.back_start.data();

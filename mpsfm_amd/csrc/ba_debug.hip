@@ -285,6 +285,7 @@ int mpsfm_debug_local_skew(int32_t chunk, int32_t phase_mask, int64_t ticks) {
 int mpsfm_ba_dense_solve_once(mpsfm_ba_handle* h, float* elapsed_ms) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   MPSFM_TRY(hipSetDevice(h->device));
+  h->ov.entry_list = chol_entry_list();
   MPSFM_TRY(hipEventRecord(h->ev[0], h->stream));
   if (int rc = run_dense(h, h->last_radius)) return rc;
   MPSFM_TRY(hipEventRecord(h->ev[1], h->stream));
@@ -294,6 +295,47 @@ int mpsfm_ba_dense_solve_once(mpsfm_ba_handle* h, float* elapsed_ms) {
   float ms = 0.f;
   MPSFM_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
   if (elapsed_ms) *elapsed_ms = ms;
+  return 0;
+}
+
+// Test hook (tests/test_gpu_level_entry.py): mpsfm_ba_dense_solve_once on a GIVEN system instead of the last sweep's.  S (n x n, both
+// triangles) and rhs in the caller's camera order, n the reduced dimension; entries outside the handle's block pattern must be zero
+// (they have no tile).  The solution is read with mpsfm_ba_get_dense_solution; *failed: the factorisation met a pivot that is not
+// positive.  Needs one mpsfm_ba_sweep_once before it (the assemble launch runs first: it zeroes what the solve accumulates into).
+int mpsfm_debug_dense_solve_given(mpsfm_ba_handle* h, const double* S, const double* rhs, int32_t n, int32_t* failed) {
+  if (!h || !S || !rhs || !failed) return fail(MPSFM_EINVAL, "handle, S, rhs or failed is NULL");
+  if (n != h->n_user || h->n <= 0) return fail(MPSFM_EINVAL, "n does not match the reduced dimension");
+  MPSFM_TRY(hipSetDevice(h->device));
+  h->ov.entry_list = chol_entry_list();
+  run_assemble(h, h->last_radius);
+  const int nt = h->nt, N = nt * 32;
+  std::vector<int32_t> cam_of_slot((size_t)std::max(h->ncv, 1), -1);
+  for (size_t i = 0; i < h->nat_slot.size(); ++i) cam_of_slot[(size_t)h->nat_slot[i]] = (int32_t)i;
+  std::vector<int32_t> user((size_t)N, -1);  // column of the system -> row of S, -1: padding
+  for (int C = 0; C < N; ++C) {
+    const int v = vec_index(h->plan.slot_of_col.empty() ? nullptr : h->plan.slot_of_col.data(), C, h->n);
+    if (v >= 0 && cam_of_slot[(size_t)(v / 6)] >= 0) user[(size_t)C] = 6 * cam_of_slot[(size_t)(v / 6)] + v % 6;
+  }
+  std::vector<double> A((size_t)(nt + 1) * (size_t)(nt + 2) / 2 * 1024, 0.0);
+  for (int ti = 0; ti <= nt; ++ti)
+    for (int tj = 0; tj <= ti && tj < nt; ++tj) {
+      double* T = A.data() + (size_t)lt_tile(ti, tj) * 1024;
+      for (int r = 0; r < 32; ++r)
+        for (int c = 0; c < 32; ++c) {
+          const int uc = user[(size_t)(tj * 32 + c)];
+          if (ti == nt) { T[r * 32 + c] = (r == 0 && uc >= 0) ? rhs[uc] : 0.0; continue; }
+          const int R = ti * 32 + r, C = tj * 32 + c, ur = user[(size_t)R];
+          T[r * 32 + c] = (ur >= 0 && uc >= 0) ? S[(size_t)ur * n + uc] : (R == C ? 1.0 : 0.0);
+        }
+    }
+  MPSFM_TRY(hipMemcpyAsync(h->d_A, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice, h->stream));
+  launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, h->stream, &h->ov, &h->lp, nullptr);
+  int flag = 0;
+  MPSFM_TRY(hipMemcpyAsync(&flag, h->d_fail, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  MPSFM_TRY(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));  // no k_cam_update follows here to re-arm the flag
+  MPSFM_TRY(hipStreamSynchronize(h->stream));
+  MPSFM_TRY(hipGetLastError());
+  *failed = flag ? 1 : 0;
   return 0;
 }
 

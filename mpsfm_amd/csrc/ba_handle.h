@@ -23,6 +23,7 @@ struct mpsfm_ba_handle {
   mpsfm::CholPlan plan;                    // camera order, tile elimination tree and launch tables of the dense factorisation (chol_plan.h)
   mpsfm::LevelPlanDev lp;
   mpsfm::CholItem* d_lp_items = nullptr;
+  mpsfm::LevelHead* d_lp_heads = nullptr;
   uint8_t* d_lp_live = nullptr;
   int32_t* d_lp_col_slot = nullptr;
   int32_t *d_lp_srcs = nullptr, *d_lp_rows = nullptr, *d_lp_struct_start = nullptr, *d_lp_struct_rows = nullptr, *d_lp_back_cols = nullptr, *d_lp_asm = nullptr;
@@ -133,7 +134,9 @@ int prepare_scales(mpsfm_ba_handle* h);
 // one track sweep at the current state: fills the reduced buffer and its scalar tail (inside the solve loop the prologue kernel
 // has zeroed the buffer; single-rank runs reduce the partials with the decision)
 int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool in_loop = false, bool adopt = false, bool handoff = false);
+void run_assemble(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);  // the first launch of run_dense (h->n > 0)
 int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);
+bool chol_entry_list();  // MPSFM_CHOL_ENTRY=list, read per solve into DenseOverlap::entry_list
 
 // the single-launch solver's skew hook (mpsfm_debug_local_skew): process-wide like g_dbg_flags, read when a solve is launched
 struct LocalSkew { int32_t chunk = 0, mask = 0; int64_t ticks = 0; };

@@ -106,19 +106,22 @@ int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in
   return 0;
 }
 
+void run_assemble(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
+  // the level-scheduled factorisation without inverse accumulators only touches the tiles of its plan
+  const bool level = dense_level(&h->ov, &h->lp);
+  double* pinv = dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp);
+  const bool listed = level && !pinv;
+  AssembleArgs as{BlockSky{h->d_sky_first, h->d_sky_start, h->d_sky_index, h->ncv}, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, h->ncv, h->n, h->nt, radius,
+                  h->opt.min_lm_diagonal, h->opt.max_lm_diagonal, h->d_A, pinv, listed ? h->lp.d_asm_tiles : nullptr, listed ? h->lp.n_asm : 0,
+                  h->lp.d_col_slot, h->n_user, (level && pinv) ? h->d_yc : nullptr, (level && pinv) ? h->lp.d_tile_live : nullptr, ctl};
+  launch_assemble(as, h->stream);
+}
+
 int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
-  hipStream_t s = h->stream;
   // d_fail is zero here: cleared at creation and re-armed by k_cam_update after every read
   if (h->n > 0) {
-    // the level-scheduled factorisation without inverse accumulators only touches the tiles of its plan
-    const bool level = dense_level(&h->ov, &h->lp);
-    double* pinv = dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp);
-    const bool listed = level && !pinv;
-    AssembleArgs as{BlockSky{h->d_sky_first, h->d_sky_start, h->d_sky_index, h->ncv}, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, h->ncv, h->n, h->nt, radius,
-                    h->opt.min_lm_diagonal, h->opt.max_lm_diagonal, h->d_A, pinv, listed ? h->lp.d_asm_tiles : nullptr, listed ? h->lp.n_asm : 0,
-                    h->lp.d_col_slot, h->n_user, (level && pinv) ? h->d_yc : nullptr, (level && pinv) ? h->lp.d_tile_live : nullptr, ctl};
-    launch_assemble(as, s);
-    launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, s, &h->ov, &h->lp, ctl);
+    run_assemble(h, radius, ctl);
+    launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, h->stream, &h->ov, &h->lp, ctl);
   }
   return 0;
 }
@@ -168,6 +171,9 @@ static int summary_from_ctl(mpsfm_ba_handle* h, const LmCtl& last, mpsfm_ba_summ
 // is not accepted (nothing has changed the state then: the launch chain takes over).
 constexpr int kLocalRefused = 1;
 // MPSFM_PT_HANDOFF=0: the update sweep recomputes the landmark factors everywhere (the comparison path); read per solve
+// MPSFM_CHOL_ENTRY=list: the level launches walk item -> source list -> operands instead of reading launch records (the comparison
+// path of dense_chol.hip); read per solve like the switch above
+bool chol_entry_list() { const char* e = std::getenv("MPSFM_CHOL_ENTRY"); return e && std::strcmp(e, "list") == 0; }
 static bool pt_handoff_enabled() { const char* e = std::getenv("MPSFM_PT_HANDOFF"); return !(e && std::atoi(e) == 0); }
 
 static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
@@ -291,6 +297,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   const bool fuse_prologue = [] { const char* e = std::getenv("MPSFM_FUSE_PROLOGUE"); return !(e && std::atoi(e) == 0); }();
   const bool fuse_cam = [] { const char* e = std::getenv("MPSFM_FUSE_CAM"); return !(e && std::atoi(e) == 0); }();
   const bool pt_handoff = pt_handoff_enabled() && h->d_pt_fac != nullptr;  // (allocated where all chunks are dense and no track is long)
+  h->ov.entry_list = chol_entry_list();
   auto enqueue_iteration = [&](int it) -> int {
     hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
     MPSFM_TRY(hipEventRecord(ev[0], s));

@@ -26,6 +26,20 @@ static_assert(sizeof(CholItem) == 16, "CholItem is read as one 16-byte scalar lo
 constexpr uint16_t kItemPanel = 0, kItemTrail = 1, kItemRole = 2;
 constexpr int32_t kSrcX = 1 << 16;  // panel source flag: the source column also reaches the item's own tile (ti in struct(src))
 
+// Launch record of an item (device only, beside the three tables above): everything a workgroup of k_chol_level needs before it can
+// request its first tile, in ONE 64-byte scalar load — the item, the head of its source list and a role's row list — so that no
+// load of the entry waits for another one.  Built from items / srcs / rows (level_heads), which stay the tables of record.
+constexpr int kInlineSrc = 8;  // sources held in the record; longer lists continue in srcs at `over`
+constexpr int kHeadRows = 4;   // rows of a role held in the record; longer lists continue in rows at `over`
+struct alignas(64) LevelHead {
+  uint16_t type, ti, tk, nsrc;  // as CholItem
+  int32_t src[kInlineSrc];      // panel / trail: the first min(nsrc, kInlineSrc) sources, kSrcX kept; unused entries 0
+  int32_t row[kHeadRows];       // role: the first min(nsrc, kHeadRows) rows; unused entries 0
+  uint32_t over;                // offset in srcs (panel, trail) or rows (role) of the first entry that is not held here
+  uint32_t pad_;
+};
+static_assert(sizeof(LevelHead) == 64, "LevelHead is read as one 64-byte scalar load");
+
 struct CamGraph {  // symmetric adjacency of the variable cameras in the caller's order, one bit row per camera
   int n = 0, words = 0;
   std::vector<uint64_t> bits;
@@ -48,7 +62,8 @@ struct CholPlan {
   std::vector<CholItem> items;
   std::vector<int32_t> launch_start;  // [nlevels + 1] item range of every launch
   std::vector<int32_t> srcs, rows;
-  std::vector<int32_t> asm_tiles;     // packed ids (lt_tile) of the tiles the factorisation touches
+  std::vector<LevelHead> heads;       // [items.size()] launch records
+  std::vector<int32_t> asm_tiles;    // packed ids (lt_tile) of the tiles the factorisation touches
   std::vector<int32_t> back_cols, back_start;  // backward substitution: columns by level, highest level first
   int64_t products = 0, roles = 0;
   double est_us = 0.0;
@@ -57,6 +72,8 @@ struct CholPlan {
 // Tile pattern: nt x nt bytes, pat[ti * nt + tj] != 0 for ti > tj: tile (ti, tj) of S can be nonzero.
 // tables = false: symbolic factorisation, levels and the cost estimate only (plan_auto compares candidates that way)
 void plan_from_pattern(const std::vector<uint8_t>& pat, int nt, bool use_pinv, int inv_rows, CholPlan& P, bool tables = true);
+// P.heads from P.items, P.srcs and P.rows (plan_from_pattern calls it when it builds the tables)
+void level_heads(CholPlan& P);
 // slot order from the camera graph.  depth < 0: caller's order; depth >= 0: nested dissection of that depth (0: components + RCM)
 // move_up: a segment that exceeds a whole number of tiles by at most this many cameras hands them to its parent's separator
 void order_cameras(const CamGraph& g, int depth, int move_up, std::vector<int32_t>& slot_of_nat, std::vector<int32_t>& col_of_slot, int& n_cols);

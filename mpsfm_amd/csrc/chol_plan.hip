@@ -231,11 +231,27 @@ void tile_pattern(const CamGraph& g, const std::vector<int32_t>& slot_of_nat, co
   }
 }
 
+void level_heads(CholPlan& P) {
+  P.heads.assign(P.items.size(), LevelHead{});
+  for (size_t q = 0; q < P.items.size(); ++q) {
+    const CholItem& it = P.items[q];
+    LevelHead& H = P.heads[q];
+    H.type = it.type; H.ti = it.ti; H.tk = it.tk; H.nsrc = it.nsrc;
+    if (it.type == kItemRole) {
+      for (int r = 0; r < std::min<int>(it.nsrc, kHeadRows); ++r) H.row[r] = P.rows[(size_t)it.aux + r];
+      H.over = it.aux + kHeadRows;
+    } else {
+      for (int r = 0; r < std::min<int>(it.nsrc, kInlineSrc); ++r) H.src[r] = P.srcs[(size_t)it.src + r];
+      H.over = it.src + kInlineSrc;
+    }
+  }
+}
+
 void plan_from_pattern(const std::vector<uint8_t>& pat, int nt, bool use_pinv, int inv_rows, CholPlan& P, bool tables) {
   P.nt = nt; P.use_pinv = use_pinv;
   P.struct_start.assign((size_t)nt + 1, 0); P.struct_rows.clear();
   P.parent.assign((size_t)nt, -1); P.level.assign((size_t)nt, 0);
-  P.items.clear(); P.launch_start.clear(); P.srcs.clear(); P.rows.clear(); P.asm_tiles.clear();
+  P.items.clear(); P.launch_start.clear(); P.srcs.clear(); P.rows.clear(); P.heads.clear(); P.asm_tiles.clear();
   P.back_cols.clear(); P.back_start.clear();
   P.products = 0; P.roles = 0; P.nlevels = 0;
   if (nt <= 0) { P.launch_start.push_back(0); P.back_start.push_back(0); return; }
@@ -363,6 +379,7 @@ void plan_from_pattern(const std::vector<uint8_t>& pat, int nt, bool use_pinv, i
     for (int j : by_level[(size_t)l]) P.back_cols.push_back(j);
   }
   P.back_start.push_back((int32_t)P.back_cols.size());
+  level_heads(P);
   // launch-cost model (measured on MI355X: a dependent launch ~9.5 us whatever it holds up to a few hundred workgroups)
   P.est_us = 9.5 * P.nlevels + 0.02 * (double)P.products + 0.004 * (double)P.roles + (use_pinv ? 10.0 : 6.5 * P.nlevels);
 }
@@ -437,7 +454,8 @@ mpsfm_plan_handle* mpsfm_debug_plan_create(const uint8_t* adj, int32_t n, int32_
 void mpsfm_debug_plan_destroy(mpsfm_plan_handle* h) { delete h; }
 // what: 0 header {ncv, nslots, n, nt, nlevels, nd_depth, use_pinv, n_items, products, roles}; 1 slot_of_nat; 2 struct_start; 3 struct_rows;
 // 4 parent; 5 level; 6 items (4 int32 each: type | ti << 16, tk | nsrc << 16, src, aux); 7 launch_start; 8 srcs; 9 rows; 10 asm_tiles;
-// 11 back_cols; 12 back_start; 13 col_of_slot.  Returns the length; copies min(length, cap) entries.
+// 11 back_cols; 12 back_start; 13 col_of_slot; 14 heads (the launch records as they go to the device, 16 int32 each: type | ti << 16,
+// tk | nsrc << 16, kInlineSrc sources, kHeadRows rows, overflow offset, 0).  Returns the length; copies min(length, cap) entries.
 int64_t mpsfm_debug_plan_get(const mpsfm_plan_handle* h, int32_t what, int32_t* out, int64_t cap) {
   if (!h) return -1;
   const mpsfm::CholPlan& P = h->P;
@@ -463,6 +481,11 @@ int64_t mpsfm_debug_plan_get(const mpsfm_plan_handle* h, int32_t what, int32_t* 
     case 11: v = &P.back_cols; break;
     case 12: v = &P.back_start; break;
     case 13: v = &P.col_of_slot; break;
+    case 14:
+      static_assert(sizeof(mpsfm::LevelHead) == 16 * sizeof(int32_t), "heads are handed out as int32");
+      tmp.resize(P.heads.size() * 16);
+      if (!P.heads.empty()) std::memcpy(tmp.data(), P.heads.data(), sizeof(int32_t) * tmp.size());
+      break;
     default: return -1;
   }
   if (out) std::memcpy(out, v->data(), sizeof(int32_t) * (size_t)std::min<int64_t>(cap, (int64_t)v->size()));

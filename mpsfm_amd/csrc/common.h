@@ -128,6 +128,30 @@ struct LmOpts {
 };
 __device__ inline bool lm_over(const LmCtl* c) { return c != nullptr && __hip_atomic_load(&c->term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kLmRunning; }
 __device__ inline double lm_radius_of(const LmCtl* c) { return __hip_atomic_load(&c->radius, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The agent-scope atomic of lm_over() is what a reader needs whose writer runs in the SAME launch (local_lm.hip).  In the launch chain
+// the writer of `term` and `radius` (k_lm_decide) is an earlier launch of the same stream: the launch boundary publishes its stores
+// and nothing writes the block while a later kernel runs, so a plain load is sufficient there, and the kernels of the dense solve
+// use one (lm_term_chain / lm_radius_chain).  The block was written by another compute die a moment ago, so the load goes all the
+// way to memory; as a vector load it is counted with the kernel's first operand loads: requested in front of them, tested behind
+// them and before the first store, its trip runs under theirs instead of in front of them.  (A scalar load would do as well, but
+// scalar loads return out of order: the wait for the item's launch record, which hits in L2, would wait for this one too.)
+#define MPSFM_CONST_AS __attribute__((address_space(4)))
+template <typename T>
+__device__ __forceinline__ T load_const(const T* p) { return *reinterpret_cast<const MPSFM_CONST_AS T*>(reinterpret_cast<uintptr_t>(p)); }
+__device__ __forceinline__ int32_t lm_term_chain(const LmCtl* c) {
+  return c != nullptr ? __hip_atomic_load(&c->term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : kLmRunning;
+}
+// the test of a value of lm_term_chain, at the place where it stands: the empty asm keeps the compiler from moving the test, and
+// with it the wait for the load, to the front of the requests it was written behind
+__device__ __forceinline__ bool lm_over_chain(int32_t term) { asm volatile("" : "+v"(term)); return __builtin_amdgcn_readfirstlane(term) != kLmRunning; }
+// the same request without a branch in front of it, so that the kernel's arguments can all be fetched in one batch: without a
+// control block it reads `readable` (any readable word) and the caller does not look at the value (c != nullptr && lm_over_chain(v))
+__device__ __forceinline__ int32_t lm_term_chain(const LmCtl* c, const void* readable) {
+  return __hip_atomic_load(c != nullptr ? &c->term : static_cast<const int32_t*>(readable), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ double lm_radius_chain(const LmCtl* c, double fallback) {
+  return c != nullptr ? __hip_atomic_load(&c->radius, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : fallback;
+}
 
 // ---- small device math -------------------------------------------------------------------
 // Reciprocal, square root and reciprocal square root in a handful of instructions: the hardware estimate (v_rcp_f64 / v_rsq_f64,
@@ -378,6 +402,8 @@ struct DenseOverlap {
   bool no_level = false;    // per-step skyline path instead of the level-scheduled factorisation (A/B measurements)
   bool no_inverse = false;  // plain path: back substitution by groups instead of the inverse propagation (A/B measurements)
   int panel_waves = kPanelWavesDefault;  // waves that factor the stacked panel of a tile column: 4 or 1 (MPSFM_CHOL_PANEL_WAVES)
+  bool entry_list = false;  // k_chol_level walks item -> srcs / rows -> operands instead of reading launch records (MPSFM_CHOL_ENTRY=list,
+                            // the comparison path; read per solve)
   hipStream_t s2 = nullptr;
   hipEvent_t evF[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t evB[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -387,6 +413,7 @@ struct DenseOverlap {
 struct LevelPlanDev {
   bool valid = false, use_pinv = false;
   const CholItem* d_items = nullptr;
+  const LevelHead* d_heads = nullptr;  // one launch record per item (chol_plan.h)
   const int32_t* d_srcs = nullptr;
   const int32_t* d_rows = nullptr;
   const int32_t* d_struct_start = nullptr;

@@ -60,32 +60,36 @@ __device__ __forceinline__ void assemble_quad(const AssembleArgs& P, double lm_r
   }
 }
 // one workgroup (256 threads): tile (ti, tj) of the system and / or a zero for its inverse accumulator
-__device__ __forceinline__ void assemble_tile(const AssembleArgs& P, double lm_radius, int ti, int tj, bool write) {
+// v: the thread's four elements from assemble_quad (rows (e >> 5) + 8 k, column e & 31 for e = threadIdx.x), read when `write`
+__device__ __forceinline__ void assemble_tile(const AssembleArgs& P, int ti, int tj, bool write, const double (&v)[4]) {
   const int64_t id = lt_tile(ti, tj);
   if (P.Pinv && ti < P.nt && tj < ti)
     for (int e = threadIdx.x; e < kTileElems; e += 256) P.Pinv[id * kTileElems + e] = 0.0;
   if (!write) return;
   double* T = P.A + id * kTileElems;
-  const int e = threadIdx.x;  // elements e + 256 k: rows (e >> 5) + 8 k, column e & 31
-  double v[4];
-  assemble_quad(P, lm_radius, ti, tj, e >> 5, 8, e & 31, v);
+  const int e = threadIdx.x;  // elements e + 256 k
 #pragma unroll
   for (int k = 0; k < 4; ++k) T[e + 256 * k] = v[k];
 }
 
 // one workgroup per lower tile (including the rhs tile row)
 __global__ __launch_bounds__(256) void k_assemble(AssembleArgs P) {
-  if (lm_over(P.ctl)) return;
-  const double lm_radius = P.ctl ? lm_radius_of(P.ctl) : P.radius;
+  // `term`, the radius and the tile id are requested together; `term` is tested in front of the first store (lm_term_chain)
+  const int32_t term = lm_term_chain(P.ctl);
+  const double lm_radius = lm_radius_chain(P.ctl, P.radius);
   // decode tile id -> (ti, tj), ti >= tj, ti in [0, nt], tj in [0, nt-1]
   const int64_t id = P.tile_list ? (int64_t)P.tile_list[blockIdx.x] : (int64_t)blockIdx.x;
   int ti = (int)((sqrt(8.0 * (double)id + 1.0) - 1.0) * 0.5);
   while ((int64_t)ti * (ti + 1) / 2 > id) --ti;
   while ((int64_t)(ti + 1) * (ti + 2) / 2 <= id) ++ti;
   const int tj = (int)(id - (int64_t)ti * (ti + 1) / 2);
+  const bool write = !(P.live && !P.live[id]);
+  double v[4];
+  if (write) assemble_quad(P, lm_radius, ti, tj, threadIdx.x >> 5, 8, threadIdx.x & 31, v);  // loads only
+  if (lm_over_chain(term)) return;
   if (P.y && blockIdx.x == 0)  // the solution vector is accumulated with atomics (k_inv_y): start from zero
     for (int e = threadIdx.x; e < P.n_vec; e += 256) P.y[e] = 0.0;
-  assemble_tile(P, lm_radius, ti, tj, !(P.live && !P.live[id]));
+  assemble_tile(P, ti, tj, write, v);
 }
 
 // C(32x32, C-layout accumulators) -= A(32x32) * B(32x32)^T, A/B row-major tiles in global memory.
@@ -214,10 +218,12 @@ int g_dbg_flags = 0;
 extern "C" void mpsfm_debug_set(int f) { g_dbg_flags = f; }
 // Phase timeline of the factorisation (diagnostics, scripts/dbg_chol_trace.py): when a buffer is registered, the
 // workgroup that owns the diagonal tile of every step stores wall_clock64() (100 MHz) at its phase boundaries:
-// two rows of 8 stamps per step, the phases in the first, the hand-offs of the four-wave panel in the second.
-__device__ long long* g_chol_trace = nullptr;
+// two rows of 8 stamps per step, the phases in the first, the hand-offs of the four-wave panel in the second.  The pointer is
+// kept on the host and travels in the kernels' arguments: a device global would cost every workgroup a load of its own.
+static long long* g_chol_trace = nullptr;
 extern "C" int mpsfm_debug_set_chol_trace(long long* dev_buf) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_chol_trace), &dev_buf, sizeof(dev_buf));
+  g_chol_trace = dev_buf;
+  return 0;
 }
 #define MPSFM_STAMP(k) do { if (trace_on && lane == 0) tr[(k)] = wall_clock64(); } while (0)
 
@@ -248,8 +254,10 @@ constexpr int kStepNoOwnUpdate = 1, kStepBig = 2;
 #endif
 constexpr int kInvRows = MPSFM_INV_ROWS;  // rows i handled by one inverse-role workgroup (X(j,k) is formed once for all of them)
 constexpr int kStepThreads = 256;         // four waves: one 16 x 16 quadrant of a tile each
-__device__ __forceinline__ void inv_role(const double* A, const double* LinvT, double* Pinv, int nt, int j, const int* irow, int ni_rows, int k,
-                                         double (*s_B)[kTile + 1], double* s_C) {
+// irow: the rows of this workgroup, entries from ni_rows on repeat the last one (their loads go nowhere new, their products are skipped)
+// term (has_ctl): `term` of the control block, requested by the caller (lm_term_chain) and looked at here behind the first loads
+__device__ __forceinline__ void inv_role(const double* A, const double* LinvT, double* Pinv, int nt, int j, const int (&irow)[kInvRows], int ni_rows, int k,
+                                         int32_t term, bool has_ctl, double (*s_B)[kTile + 1], double* s_C) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int mi = wave & 1, ni = wave >> 1;
   const int m16 = lane & 15, kg = lane >> 4;
@@ -261,12 +269,13 @@ __device__ __forceinline__ void inv_role(const double* A, const double* LinvT, d
   double aop[kInvRows][8];
 #pragma unroll
   for (int r = 0; r < kInvRows; ++r) {
-    const int i = irow[min(r, ni_rows - 1)];
+    const int i = irow[r];
     quad_load(Pinv + lt_tile(i, k) * kTileElems, kTile, lane, mi, ni, acc[r]);
     const double* arow = A + lt_tile(i, j) * kTileElems + (16 * mi + m16) * kTile + kg;
 #pragma unroll
     for (int s = 0; s < 8; ++s) aop[r][s] = arow[4 * s];
   }
+  if (has_ctl && lm_over_chain(term)) return;
   for (int e = tid; e < kTileElems; e += kStepThreads) {
     const int r = e >> 5, c = e & 31;
     s_B[r][c] = Li[e];
@@ -348,7 +357,7 @@ __device__ __forceinline__ void panel_section(int waves, const double (*s_T)[kTi
 }
 
 __global__ __launch_bounds__(kStepThreads) void k_chol_step(double* A, double* LinvT, int nt, int j, int* fail, int dbg, int c0, int tk_max,
-                                                            int mode, int panel_waves) {
+                                                            int mode, int panel_waves, long long* trace) {
   __shared__ double s_T[kTile][kTile + 1];
   __shared__ double s_X[kTile][kTile + 1];
   __shared__ __attribute__((aligned(16))) double s_Lt[kPanelLds];
@@ -375,7 +384,7 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_step(double* A, double* L
   const bool own_update = (j >= 0) && !(mode & kStepNoOwnUpdate) && !(dbg & 4);
   // ---- panel column j+1 -------------------------------------------------------------------
   const bool diag = (ti == tk);
-  long long* tr = g_chol_trace ? g_chol_trace + ((size_t)(j + 1) * 2) * 8 : nullptr;
+  long long* tr = trace ? trace + ((size_t)(j + 1) * 2) * 8 : nullptr;
   const bool trace_on = diag && tr != nullptr && wave == 0;
   MPSFM_STAMP(0);
   {
@@ -423,65 +432,236 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_step(double* A, double* L
 struct LevelArgs {
   double* A; double* LinvT; double* Pinv;
   const CholItem* items; const int32_t* srcs; const int32_t* rows;
+  const LevelHead* heads;  // launch records of this launch's items (chol_plan.h)
   int* fail; int32_t nt, dbg;
   const LmCtl* ctl;
+  long long* trace;     // phase timeline (mpsfm_debug_set_chol_trace), NULL: off
   int32_t panel_waves;  // waves that factor a panel: kWgWaves or 1 (MPSFM_CHOL_PANEL_WAVES)
 };
 
+// The entry of a level launch.  Every workgroup is a chain of latencies before its first tile is on its way, and the launch ends
+// with its slowest workgroup.  Behind the kernel arguments the entry makes one trip for the item's launch record (64 bytes, one
+// scalar load: item, sources, rows; a table every launch reads: it hits in L2) and one for the tiles; `term`, which comes from
+// memory (lm_term_chain), is requested first and looked at behind the tile requests, and the trace pointer is an argument.  With
+// the sources in registers the first sources (a panel item's through LDS, below; a trailing item's as operands) are requested together
+// with the tiles they update, and every further source while the products of the one before run.  The products themselves keep their
+// order (ascending source, same k-steps),
+// so the factor is bit for bit what the list-walking entry (kList: item -> srcs / rows -> operands, MPSFM_CHOL_ENTRY=list) gives.
+typedef int32_t v16i __attribute__((ext_vector_type(16)));
+static_assert(kInvRows <= kHeadRows, "a role's rows must fit its launch record");
+constexpr int kHeadSrc0 = 2, kHeadRow0 = kHeadSrc0 + kInlineSrc, kHeadOver = kHeadRow0 + kHeadRows;  // words of a LevelHead
+constexpr int kPanelBatch = 2;  // sources of a panel item staged and requested in front of the first wait (C3: panels have at most two)
+constexpr int kTrailBatch = 4;  // the same for a trailing item (C3: at most three, C4 / C5: four)
+
+// source q of an item: from the record, beyond kInlineSrc from the list (a dependent load, no scene of the benchmark gets there)
+__device__ __forceinline__ int head_src(const v16i& w, const int32_t* srcs, int q) {
+  if (q >= kInlineSrc) return srcs[(uint32_t)w[kHeadOver] + (uint32_t)(q - kInlineSrc)];
+  int e = w[kHeadSrc0];
+#pragma unroll
+  for (int r = 1; r < kInlineSrc; ++r) e = (q == r) ? w[kHeadSrc0 + r] : e;
+  return e;
+}
+struct PanelOps { double am[8], bn[8], ax[8]; };
+struct TrailOps { double a[8], b[8]; };
+// operands of source e for the panel item (ti, tk): L(tk, c) for both quadrant operands, L(ti, c) where the source reaches the own tile
+__device__ __forceinline__ void panel_request(const double* A, int ti, int tk, int e, bool diag, int lane, int mi, int ni, PanelOps& o) {
+  const int c = e & 0xffff;
+  const double* Lk = A + lt_tile(tk, c) * kTileElems;
+  quad_operand(Lk, lane, mi, o.am);
+  quad_operand(Lk, lane, ni, o.bn);
+  if (!diag && (e & kSrcX)) quad_operand(A + lt_tile(ti, c) * kTileElems, lane, mi, o.ax);
+}
+__device__ __forceinline__ void panel_apply(const PanelOps& o, int e, bool diag, v4d& dacc, v4d& xacc) {
+  quad_gemm_sub(o.am, o.bn, dacc);
+  if (!diag && (e & kSrcX)) quad_gemm_sub(o.ax, o.bn, xacc);
+}
+__device__ __forceinline__ void trail_request(const double* A, int ti, int tk, int c, int lane, int mi, int ni, TrailOps& o) {
+  quad_operand(A + lt_tile(ti, c) * kTileElems, lane, mi, o.a);
+  quad_operand(A + lt_tile(tk, c) * kTileElems, lane, ni, o.b);
+}
+
+// The source tiles of a panel item go through LDS.  Read straight into the operand layout (quad_operand: lane l takes 64 bytes of
+// row l & 15) the sixteen lanes of a quarter wave sit in sixteen different cache lines, a wave touches 64 lines per load
+// instruction, and the workgroup's 48 instructions per source tile pair keep the CU's one tag lookup per cycle busy for ~1.3 us:
+// that, not a chain of dependent loads, is what a source costs (launches 6 and 9 of C3, the two with two-source panels, stood
+// out by 1.4 us before and after the sources moved into the launch record).  Staged, the workgroup fetches a tile as 512
+// consecutive 16-byte pieces, two per thread (8 lines per instruction), parks them with the row stride of k_big_update's staging
+// and reads the operands back in the same layout: the values and the order of the products are unchanged.
+constexpr int kStageTile = kTile * kLdsLd;  // doubles of a staged tile
+static_assert(kPanelLds >= 2 * kStageTile, "the first source of a panel item is staged in the panel's LDS buffer");
+__device__ __forceinline__ void stage_fetch(const double* __restrict__ T, double2& p0, double2& p1) {
+  p0 = reinterpret_cast<const double2*>(T)[threadIdx.x];
+  p1 = reinterpret_cast<const double2*>(T)[threadIdx.x + kStepThreads];
+}
+__device__ __forceinline__ void stage_park(const double2& p0, const double2& p1, double* S) {
+  const int r = threadIdx.x >> 4, c2 = threadIdx.x & 15;  // row, 16-byte piece of the row; the second piece sits 16 rows below
+  *reinterpret_cast<double2*>(S + r * kLdsLd + 2 * c2) = p0;
+  *reinterpret_cast<double2*>(S + (r + 16) * kLdsLd + 2 * c2) = p1;
+}
+// quad_operand on a staged tile
+__device__ __forceinline__ void quad_operand_lds(const double* S, int lane, int b, double (&o)[8]) {
+  const double2* p = reinterpret_cast<const double2*>(S + (16 * b + (lane & 15)) * kLdsLd + 8 * (lane >> 4));
+#pragma unroll
+  for (int s = 0; s < 4; ++s) { const double2 x = p[s]; o[2 * s] = x.x; o[2 * s + 1] = x.y; }
+}
+
+template <bool kList>
 __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
-  if (lm_over(G.ctl)) return;
   __shared__ double s_T[kTile][kTile + 1];
   __shared__ double s_X[kTile][kTile + 1];
   __shared__ __attribute__((aligned(16))) double s_Lt[kPanelLds];
+  __shared__ __attribute__((aligned(16))) double s_S1[kList ? 2 : 2 * kStageTile];  // staging of a panel item's second source
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int mi = wave & 1, ni = wave >> 1;  // this wave's quadrant
-  if (G.dbg & 16) return;  // ablation: the launch chain alone
-  const CholItem it = G.items[blockIdx.x];
   double* A = G.A;
-  if (it.type == kItemRole) {
-    if (G.dbg & 8) return;
-    inv_role(A, G.LinvT, G.Pinv, G.nt, it.ti, G.rows + it.aux, it.nsrc, it.tk, s_T, s_Lt);
-    return;
+  int type, ti, tk, nsrc;
+  int32_t term = kLmRunning;
+  const bool has_ctl = !kList && G.ctl != nullptr;  // `term` holds the control block's word
+  v16i w = {};
+  const int32_t* src = nullptr;
+  if constexpr (kList) {
+    if (lm_over(G.ctl)) return;
+    if (G.dbg & 16) return;  // ablation: the launch chain alone
+    const CholItem it = G.items[blockIdx.x];
+    type = it.type; ti = it.ti; tk = it.tk; nsrc = it.nsrc;
+    src = G.srcs + it.src;
+    if (type == kItemRole) {
+      if (G.dbg & 8) return;
+      int irow[kInvRows];
+#pragma unroll
+      for (int r = 0; r < kInvRows; ++r) irow[r] = G.rows[it.aux + min(r, nsrc - 1)];
+      inv_role(A, G.LinvT, G.Pinv, G.nt, ti, irow, nsrc, tk, kLmRunning, false, s_T, s_Lt);
+      return;
+    }
+  } else {
+    // `term` is requested here and looked at behind the operand requests, in front of the first store
+    term = lm_term_chain(G.ctl, G.heads);
+    w = load_const(reinterpret_cast<const v16i*>(G.heads + blockIdx.x));
+    type = w[0] & 0xffff; ti = (uint32_t)w[0] >> 16; tk = w[1] & 0xffff; nsrc = (uint32_t)w[1] >> 16;
+    if (G.dbg & 16) return;
+    if ((G.dbg & 4) && type != kItemRole) nsrc = 0;  // ablation: no updates (one place for the tile loads: a second one costs waits)
+    if (type == kItemRole) {
+      if (G.dbg & 8) return;
+      int irow[kInvRows];
+      irow[0] = w[kHeadRow0];
+#pragma unroll
+      for (int r = 1; r < kInvRows; ++r) irow[r] = r < nsrc ? w[kHeadRow0 + r] : irow[r - 1];
+      inv_role(A, G.LinvT, G.Pinv, G.nt, ti, irow, nsrc, tk, term, has_ctl, s_T, s_Lt);
+      return;
+    }
   }
-  const int ti = it.ti, tk = it.tk, nsrc = it.nsrc;
-  const int32_t* src = G.srcs + it.src;
   double* C = A + lt_tile(ti, tk) * kTileElems;
-  if (it.type == kItemTrail) {
+  if (type == kItemTrail) {
     v4d acc;
-    quad_load(C, kTile, lane, mi, ni, acc);
-    if (!(G.dbg & 4))
-      for (int q = 0; q < nsrc; ++q) {
-        const int c = src[q];
-        double a[8], b[8];
-        quad_operand(A + lt_tile(ti, c) * kTileElems, lane, mi, a);
-        quad_operand(A + lt_tile(tk, c) * kTileElems, lane, ni, b);
-        quad_gemm_sub(a, b, acc);
+    if constexpr (kList) quad_load(C, kTile, lane, mi, ni, acc);
+    if (kList ? !(G.dbg & 4) : true) {
+      if constexpr (kList) {
+        for (int q = 0; q < nsrc; ++q) {
+          const int c = src[q];
+          double a[8], b[8];
+          quad_operand(A + lt_tile(ti, c) * kTileElems, lane, mi, a);
+          quad_operand(A + lt_tile(tk, c) * kTileElems, lane, ni, b);
+          quad_gemm_sub(a, b, acc);
+        }
+      } else {
+        TrailOps o[kTrailBatch], cur;
+#pragma unroll
+        for (int q = 0; q < kTrailBatch; ++q)
+          if (q < nsrc) trail_request(A, ti, tk, w[kHeadSrc0 + q], lane, mi, ni, o[q]);
+        if (nsrc > kTrailBatch) trail_request(A, ti, tk, head_src(w, G.srcs, kTrailBatch), lane, mi, ni, cur);
+        quad_load(C, kTile, lane, mi, ni, acc);  // behind the operands: the compiler waits for an accumulator where it is loaded
+#pragma unroll
+        for (int q = 0; q < kTrailBatch; ++q)
+          if (q < nsrc) quad_gemm_sub(o[q].a, o[q].b, acc);
+        for (int q = kTrailBatch; q < nsrc; ++q) {  // source q + 1 is on its way while the products of q run
+          TrailOps nxt;
+          const bool more = q + 1 < nsrc;
+          if (more) trail_request(A, ti, tk, head_src(w, G.srcs, q + 1), lane, mi, ni, nxt);
+          quad_gemm_sub(cur.a, cur.b, acc);
+          if (more) cur = nxt;
+        }
       }
+    }
+    if (has_ctl && lm_over_chain(term)) return;
     quad_store(C, kTile, lane, mi, ni, acc);
     return;
   }
   // ---- panel tile of column tk ---------------------------------------------------------------
   const bool diag = (ti == tk);
-  long long* tr = g_chol_trace ? g_chol_trace + ((size_t)tk * 2) * 8 : nullptr;
+  long long* tr = G.trace ? G.trace + ((size_t)tk * 2) * 8 : nullptr;
   const bool trace_on = diag && tr != nullptr && wave == 0;
   MPSFM_STAMP(0);
   {
     v4d dacc, xacc;
-    quad_load(A + lt_tile(tk, tk) * kTileElems, kTile, lane, mi, ni, dacc);
-    if (!diag) quad_load(C, kTile, lane, mi, ni, xacc);
-    if (!(G.dbg & 4))
-      for (int q = 0; q < nsrc; ++q) {
-        const int e = src[q], c = e & 0xffff;
-        const double* Lk = A + lt_tile(tk, c) * kTileElems;
-        double am[8], bn[8];
-        quad_operand(Lk, lane, mi, am);
-        quad_operand(Lk, lane, ni, bn);
-        quad_gemm_sub(am, bn, dacc);
-        if (!diag && (e & kSrcX)) {
-          quad_operand(A + lt_tile(ti, c) * kTileElems, lane, mi, am);
-          quad_gemm_sub(am, bn, xacc);
+    const double* D = A + lt_tile(tk, tk) * kTileElems;
+    if constexpr (kList) {
+      quad_load(D, kTile, lane, mi, ni, dacc);
+      if (!diag) quad_load(C, kTile, lane, mi, ni, xacc);
+    }
+    if (kList ? !(G.dbg & 4) : true) {
+      if constexpr (kList) {
+        for (int q = 0; q < nsrc; ++q) {
+          const int e = src[q], c = e & 0xffff;
+          const double* Lk = A + lt_tile(tk, c) * kTileElems;
+          double am[8], bn[8];
+          quad_operand(Lk, lane, mi, am);
+          quad_operand(Lk, lane, ni, bn);
+          quad_gemm_sub(am, bn, dacc);
+          if (!diag && (e & kSrcX)) {
+            quad_operand(A + lt_tile(ti, c) * kTileElems, lane, mi, am);
+            quad_gemm_sub(am, bn, xacc);
+          }
+        }
+      } else {
+        // the first two sources through LDS (above), requested with D and X in front of the first wait
+        static_assert(kPanelBatch == 2, "two staged sources, written out (an indexed array of pieces ends up in scratch)");
+        const int e0 = w[kHeadSrc0], e1 = w[kHeadSrc0 + 1];
+        const bool s0 = nsrc > 0, s1 = nsrc > 1, x0 = s0 && !diag && (e0 & kSrcX), x1 = s1 && !diag && (e1 & kSrcX);
+        double2 k0a = {}, k0b = {}, x0a = {}, x0b = {}, k1a = {}, k1b = {}, x1a = {}, x1b = {};
+        PanelOps cur;
+        int e_cur = 0;
+        if (s0) stage_fetch(A + lt_tile(tk, e0 & 0xffff) * kTileElems, k0a, k0b);
+        if (x0) stage_fetch(A + lt_tile(ti, e0 & 0xffff) * kTileElems, x0a, x0b);
+        if (s1) stage_fetch(A + lt_tile(tk, e1 & 0xffff) * kTileElems, k1a, k1b);
+        if (x1) stage_fetch(A + lt_tile(ti, e1 & 0xffff) * kTileElems, x1a, x1b);
+        if (nsrc > kPanelBatch) { e_cur = head_src(w, G.srcs, kPanelBatch); panel_request(A, ti, tk, e_cur, diag, lane, mi, ni, cur); }
+        quad_load(D, kTile, lane, mi, ni, dacc);
+        if (!diag) quad_load(C, kTile, lane, mi, ni, xacc);
+        if (has_ctl && lm_over_chain(term)) return;
+        if (s0) {
+          stage_park(k0a, k0b, s_Lt);
+          if (x0) stage_park(x0a, x0b, s_Lt + kStageTile);
+          if (s1) stage_park(k1a, k1b, s_S1);
+          if (x1) stage_park(x1a, x1b, s_S1 + kStageTile);
+          __syncthreads();
+          double am[8], bn[8];
+          quad_operand_lds(s_Lt, lane, mi, am);
+          quad_operand_lds(s_Lt, lane, ni, bn);
+          quad_gemm_sub(am, bn, dacc);
+          if (x0) {
+            quad_operand_lds(s_Lt + kStageTile, lane, mi, am);
+            quad_gemm_sub(am, bn, xacc);
+          }
+          if (s1) {
+            quad_operand_lds(s_S1, lane, mi, am);
+            quad_operand_lds(s_S1, lane, ni, bn);
+            quad_gemm_sub(am, bn, dacc);
+            if (x1) {
+              quad_operand_lds(s_S1 + kStageTile, lane, mi, am);
+              quad_gemm_sub(am, bn, xacc);
+            }
+          }
+        }
+        for (int q = kPanelBatch; q < nsrc; ++q) {  // source q + 1 is on its way while the products of q run
+          PanelOps nxt;
+          const bool more = q + 1 < nsrc;
+          const int e_nxt = more ? head_src(w, G.srcs, q + 1) : 0;
+          if (more) panel_request(A, ti, tk, e_nxt, diag, lane, mi, ni, nxt);
+          panel_apply(cur, e_cur, diag, dacc, xacc);
+          if (more) { cur = nxt; e_cur = e_nxt; }
         }
       }
+    }
     quad_store(&s_T[0][0], kTile + 1, lane, mi, ni, dacc);
     if (diag) {  // identity: x L^-T = row of L^-T
 #pragma unroll
@@ -543,7 +723,7 @@ __global__ __launch_bounds__(256) void k_back_level(const double* A, const doubl
                                                     const int32_t* struct_rows, int nt, int n, double* ybuf, double* y, const int32_t* col_slot, const LmCtl* ctl) {
   __shared__ double s_part[8][kTile];
   __shared__ double s_v[kTile];
-  if (lm_over(ctl)) return;
+  const int32_t term = lm_term_chain(ctl);  // requested with the column's tables, tested in front of the first barrier
   const int j = cols[blockIdx.x];
   const int c = threadIdx.x & 31, part = threadIdx.x >> 5;
   const int r0 = struct_start[j], r1 = struct_start[j + 1] - 1;  // the last entry is the right-hand-side row
@@ -555,6 +735,7 @@ __global__ __launch_bounds__(256) void k_back_level(const double* A, const doubl
 #pragma unroll 8
     for (int r = 0; r < kTile; ++r) sacc = __builtin_fma(Tl[r * kTile], yi[r], sacc);
   }
+  if (lm_over_chain(term)) return;
   s_part[part][c] = sacc;
   __syncthreads();
   if (part == 0) {
@@ -680,11 +861,12 @@ __global__ __launch_bounds__(256) void k_backsub_group(const double* A, const do
 // are cut into kInvSplit workgroups (i = k+1+s mod kInvSplit); every workgroup first forms the w_i it needs itself (a
 // 32 x 32 product each — cheaper than a launch of its own for them), split 0 also w_k.  y starts from zero (k_assemble).
 constexpr int kInvSplit = 4;
+constexpr int kInvPre = 8;  // accumulator tiles of a workgroup requested in front of its barrier (C3: at most 10 per workgroup)
 __global__ __launch_bounds__(256) void k_inv_y(const double* A, const double* LinvT, const double* Pinv, int nt, int n, double* y,
                                                const int32_t* col_slot, const LmCtl* ctl) {
   __shared__ double s_w[(kPlainMaxTiles / kInvSplit + 2) * kTile];
   __shared__ double s_part[8][kTile];
-  if (lm_over(ctl)) return;
+  const int32_t term = lm_term_chain(ctl);  // requested with the first operands, tested in front of the first barrier
   const int k = blockIdx.x, sp = blockIdx.y, c = threadIdx.x & 31, part = threadIdx.x >> 5;
   const int first = k + 1 + sp;
   const int m = first < nt ? (nt - first + kInvSplit - 1) / kInvSplit : 0;  // tiles i = first + kInvSplit j
@@ -700,9 +882,26 @@ __global__ __launch_bounds__(256) void k_inv_y(const double* A, const double* Li
     for (int q = 0; q < kTile; ++q) sacc = __builtin_fma(Li[q], z[q], sacc);
     s_w[idx] = sacc;
   }
+  // the accumulators of the first kInvPre tiles do not depend on s_w: requested in front of the barrier that publishes it
+  double pv[kInvPre][4];
+#pragma unroll
+  for (int j = 0; j < kInvPre; ++j)
+    if (j < m) {
+      const double* Pt = Pinv + lt_tile(first + kInvSplit * j, k) * kTileElems;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pv[j][r] = Pt[(4 * part + r) * kTile + c];
+    }
+  if (lm_over_chain(term)) return;
   __syncthreads();
   double sacc = 0.0;
-  for (int j = 0; j < m; ++j) {
+#pragma unroll
+  for (int j = 0; j < kInvPre; ++j)
+    if (j < m) {
+      const double* w = s_w + (j + own) * kTile;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sacc += pv[j][r] * w[4 * part + r];
+    }
+  for (int j = kInvPre; j < m; ++j) {
     const double* Pt = Pinv + lt_tile(first + kInvSplit * j, k) * kTileElems;
     const double* w = s_w + (j + own) * kTile;
 #pragma unroll
@@ -765,12 +964,15 @@ void launch_dense_solve(double* A, double* work, int nt, int n, double* y, int* 
   const int panel_waves = (ov ? ov->panel_waves : kPanelWavesDefault) == 1 ? 1 : kWgWaves;
   if (dense_level(ov, lp)) {
     double* Pinv = dense_pinv(work, nt, ov, lp);
-    LevelArgs G{A, LinvT, Pinv, nullptr, lp->d_srcs, lp->d_rows, fail, nt, g_dbg_flags, ctl, panel_waves};
+    LevelArgs G{A, LinvT, Pinv, nullptr, lp->d_srcs, lp->d_rows, nullptr, fail, nt, g_dbg_flags, ctl, g_chol_trace, panel_waves};
+    const bool list = ov && ov->entry_list;
     for (int l = 0; l < lp->nlevels; ++l) {
       const int grid = lp->h_launch_start[l + 1] - lp->h_launch_start[l];
       if (grid <= 0) continue;
       G.items = lp->d_items + lp->h_launch_start[l];
-      hipLaunchKernelGGL(k_chol_level, dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
+      G.heads = lp->d_heads + lp->h_launch_start[l];
+      if (list) hipLaunchKernelGGL(k_chol_level<true>, dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
+      else hipLaunchKernelGGL(k_chol_level<false>, dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
     }
     if (Pinv) {
       hipLaunchKernelGGL(k_inv_y, dim3(nt, kInvSplit), dim3(256), 0, s, A, LinvT, Pinv, nt, n, y, lp->d_col_slot, ctl);
@@ -796,16 +998,16 @@ void launch_dense_solve(double* A, double* work, int nt, int n, double* y, int* 
     const int pend = (p0 + NB - 1 < nt - 1) ? p0 + NB - 1 : nt - 1;
     // factor column p0 (its tiles already hold every earlier column); ti in [p0, nt]
     hipLaunchKernelGGL(k_chol_step, dim3(nt - p0 + 1, 1), dim3(kStepThreads), 0, s, A, LinvT, nt, p0 - 1, fail, g_dbg_flags, p0 - 1, p0,
-                       kStepNoOwnUpdate, panel_waves);
+                       kStepNoOwnUpdate, panel_waves, g_chol_trace);
     for (int j = p0; j <= pend - 1; ++j) {  // apply column j to columns (j, pend], factor column j+1; ti in [j+1, nt]
       const int rows = nt - j, cols = pend - j;
-      hipLaunchKernelGGL(k_chol_step, dim3(rows, cols), dim3(kStepThreads), 0, s, A, LinvT, nt, j, fail, g_dbg_flags, j, pend, 0, panel_waves);
+      hipLaunchKernelGGL(k_chol_step, dim3(rows, cols), dim3(kStepThreads), 0, s, A, LinvT, nt, j, fail, g_dbg_flags, j, pend, 0, panel_waves, g_chol_trace);
     }
     if (pend >= nt - 1) break;
     // columns (pend, nt-1] receive the panel p0..pend; ti in [pend+1, nt]
     if (!big_kernel) {
       hipLaunchKernelGGL(k_chol_step, dim3(nt - pend, nt - 1 - pend), dim3(kStepThreads), 0, s, A, LinvT, nt, pend, fail, g_dbg_flags, p0, nt - 1,
-                         kStepBig, panel_waves);
+                         kStepBig, panel_waves, g_chol_trace);
     } else if (!overlap) {
       launch_big(A, nt, pend, p0, pend + 1, nt - 1, s);
     } else {
