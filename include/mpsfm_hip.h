@@ -936,6 +936,73 @@ int mpsfm_match_map_descriptors(const float* map0 /* [H0][W0][C] */, const float
                                 const mpsfm_match_options* opts /* NULL: defaults */, int32_t device, int32_t* matches0 /* [n0] */,
                                 double* scores0 /* [n0] */, mpsfm_match_info* info /* may be NULL */);
 
+/* ---- dense reciprocal matches from descriptor maps: the dense leg of the reference's MASt3R matcher
+ *    (mpsfm/extraction/pairwise/models/mast3r.py:119-170 merge_corres, extract_correspondences, with MASt3R's
+ *    fast_reciprocal_NNs; the contract, the kernels and the measurements: DESIGN.md section 4p).
+ *
+ *    One search (A [H1][W1][C], B [H2][W2][C], subsample S, max_iter), channel-last float32 maps.  The descent rule is MASt3R's
+ *    fast_nn.py (int subsample, pixel_tol 0, ret_basin False, dist "dot"), which is NOT part of the reference tree: the rule
+ *    is INFERRED AND FROZEN BY TESTS.  Seeds are the pixels (y, x) with y = S/2, S/2 + S, ... < H1 and x = S/2, ... < W1,
+ *    y-major; xy1 = y W1 + x, xy2 = -1, old1 = xy1, old2 = xy2, all seeds active.  While a seed is active:
+ *      1. active seeds: xy2 = NN_B(A[xy1])            2. seeds with xy2 == old2 become inactive
+ *      3. still active seeds: xy1 = NN_A(B[xy2])      4. seeds with xy1 == old1 become inactive
+ *      5. one iteration is counted; at max_iter the loop ends   6. otherwise old1 = xy1, old2 = xy2
+ *    The seeds inactive at the end have converged; the result is their (xy1, xy2), unique and sorted by (xy1, xy2) ascending.
+ *    NN_X(d): the pixel of X with the largest fp64 dot product with d, accumulated with k ascending on the matrix pipe, every
+ *    element through the same operation sequence (section 4m's contract); EQUAL SIMILARITIES GO TO THE LOWEST INDEX.  The
+ *    result is a function of the inputs alone: bitwise the same from run to run and from host or device inputs.
+ *
+ *    mpsfm_recip_seed_count: the number of seeds of an H x W map, 0 for arguments below 1.
+ *    mpsfm_reciprocal_nns: one search; idx1 / idx2 [capacity] receive *n_out pairs; capacity >= the seed count of (H1, W1).
+ *    mpsfm_dense_correspondences: extract_correspondences.  The searches (feat11 -> feat21), (feat21 -> feat11),
+ *    (feat12 -> feat22), (feat22 -> feat12) run in lockstep; per pair of searches idx1 = [fwd.xy1, bwd.xy2],
+ *    idx2 = [fwd.xy2, bwd.xy1] with the float32 confidences QA[idx1], QB[idx2], (QA, QB) = (qonf11, qonf21), then
+ *    (qonf12, qonf22); the two pairs are concatenated and made unique by (idx1 major, idx2 minor) ascending; a kept row's
+ *    score is that of its FIRST occurrence, sqrtf(q1 * q2) in float32 with each operation rounded on its own.
+ *    xy1 [n][2] = (idx1 % W1, idx1 / W1), xy2 likewise with W2.  feat11, feat12, qonf11, qonf12 are [H1][W1]([C]), the
+ *    others [H2][W2]([C]).  capacity >= 2 (seeds of (H1, W1) + seeds of (H2, W2)).
+ *    info of the four searches: counts summed, iterations the largest.
+ *
+ *    inputs_on_device / stream: as for mpsfm_match_options (maps and confidences are device pointers, checked; an event is
+ *    recorded on `stream` and the call's own stream waits for it; the library never works on the null stream).  Outputs are
+ *    host memory, complete on return; nothing is retained.
+ *
+ *    MPSFM_EINVAL before any device is touched: NULL pointers, C outside 1 .. 1024, H or W < 1, more than 2^24 pixels in a
+ *    map, subsample < 1, max_iter outside 1 .. 1024, a capacity below the bound above, non-finite values in host inputs
+ *    (device inputs are scanned by a kernel: MPSFM_EINVAL after it).  No seed (S/2 >= H or W on every seeded map): *n_out = 0,
+ *    no device needed.  MPSFM_ENODEVICE without a device. ---- */
+typedef struct mpsfm_recip_options {
+  int32_t subsample;
+  int32_t max_iter;
+  int32_t inputs_on_device;
+  void* stream;              /* hipStream_t of the caller, read only with inputs_on_device */
+} mpsfm_recip_options;
+
+typedef struct mpsfm_recip_info {
+  int64_t n_seeds;
+  int64_t n_converged;    /* seeds inactive at the end (before the pairs are made unique) */
+  int64_t nn_queries;     /* nearest-neighbour queries: the active seeds summed over all half-steps */
+  int32_t iterations;     /* iterations at whose start a seed was active */
+  int32_t column_ranges;  /* workgroups that shared the columns of one strip of rows (results do not depend on it) */
+  float ms;               /* device time from the first kernel to the last (HIP events), transfers excluded */
+  int32_t reserved;
+} mpsfm_recip_info;
+
+/* the reference's use: subsample 8, max_iter 10, host inputs */
+void mpsfm_recip_default_options(mpsfm_recip_options* opts);
+
+int64_t mpsfm_recip_seed_count(int32_t H, int32_t W, int32_t subsample);
+
+int mpsfm_reciprocal_nns(const float* A /* [H1][W1][C] */, int32_t H1, int32_t W1, const float* B /* [H2][W2][C] */, int32_t H2, int32_t W2,
+                         int32_t C, const mpsfm_recip_options* opts /* NULL: defaults */, int32_t device, int64_t capacity,
+                         int32_t* idx1 /* [capacity] */, int32_t* idx2 /* [capacity] */, int64_t* n_out, mpsfm_recip_info* info /* may be NULL */);
+
+int mpsfm_dense_correspondences(const float* feat11, const float* feat21, const float* feat22, const float* feat12,
+                                const float* qonf11, const float* qonf21, const float* qonf22, const float* qonf12,
+                                int32_t H1, int32_t W1, int32_t H2, int32_t W2, int32_t C, const mpsfm_recip_options* opts /* NULL: defaults */,
+                                int32_t device, int64_t capacity, int32_t* xy1 /* [capacity][2] x, y */, int32_t* xy2 /* [capacity][2] */,
+                                float* scores /* [capacity] */, int64_t* n_out, mpsfm_recip_info* info /* may be NULL */);
+
 /* ---- a dense matcher's warp to match lists: the post-network half of the reference's RoMa matcher
  *    (mpsfm/extraction/pairwise/models/roma.py:82-124 with models/utils/warp.py simple_nms, kpids_to_matches0,
  *    get_unique_matches, matches_to_matches0, assign_keypoints; contract, tie rule and kernels: DESIGN.md section 4n).

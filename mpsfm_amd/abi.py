@@ -269,6 +269,17 @@ class CMatchInfo(C.Structure):
     _fields_ = [("num_matches", C.c_int64), ("ms", C.c_float), ("column_ranges", C.c_int32)]
 
 
+class CRecipOptions(C.Structure):
+    _c_name_ = "mpsfm_recip_options"
+    _fields_ = [("subsample", C.c_int32), ("max_iter", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class CRecipInfo(C.Structure):
+    _c_name_ = "mpsfm_recip_info"
+    _fields_ = [("n_seeds", C.c_int64), ("n_converged", C.c_int64), ("nn_queries", C.c_int64), ("iterations", C.c_int32),
+                ("column_ranges", C.c_int32), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+
 class CWarpOptions(C.Structure):
     _c_name_ = "mpsfm_warp_options"
     _fields_ = [("sample_thresh", C.c_double), ("max_error", C.c_double), ("scale0", C.c_double * 2), ("scale1", C.c_double * 2),
@@ -394,6 +405,10 @@ SIGNATURES = {
     "mpsfm_match_default_options": (None, [P]),
     "mpsfm_match_descriptors": (C.c_int, [I64, I64, I32, P, P, P, I32, P, P, P]),
     "mpsfm_match_map_descriptors": (C.c_int, [P, P, I32, I32, P, P, I32, I32, I32, I64, P, I64, P, P, I32, P, P, P]),
+    "mpsfm_recip_default_options": (None, [P]),
+    "mpsfm_recip_seed_count": (I64, [I32, I32, I32]),
+    "mpsfm_reciprocal_nns": (C.c_int, [P, I32, I32, P, I32, I32, I32, P, I32, I64, P, P, P, P]),
+    "mpsfm_dense_correspondences": (C.c_int, [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, I32, I64, P, P, P, P, P]),
     "mpsfm_warp_default_options": (None, [P]),
     "mpsfm_simple_nms": (C.c_int, [I32, I32, P, I32, I32, P, I32, P, P]),
     "mpsfm_kpids_to_matches0": (C.c_int, [I64, P, P, P, I64, I64, I32, P, I32, P, P, P, P]),

@@ -13,8 +13,8 @@ import numpy as np
 from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
     ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CDcImage, CDcSummary, CDepthGather, CDepthPriorConf,
     CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchInfo, CMatchOptions, CNmsInfo,
-    CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRegImage,
-    CRelPoseOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
+    CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
+    CRecipOptions, CRegImage, CRelPoseOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
     CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
 )
 from .problem import BAProblem, Tracks
@@ -882,6 +882,70 @@ def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=
                                              C.addressof(o), int(device or 0), m.ctypes.data, s.ctypes.data, C.addressof(I)))
     m, s = m[:n0].astype(np.int64), s[:n0]
     return (m, s, _match_info(I)) if return_info else (m, s)
+
+
+def _recip_info(I) -> dict:
+    return dict(n_seeds=int(I.n_seeds), n_converged=int(I.n_converged), iterations=int(I.iterations), nn_queries=int(I.nn_queries),
+                column_ranges=int(I.column_ranges), ms=float(I.ms))
+
+
+def _recip_options(subsample, max_iter) -> CRecipOptions:
+    o = CRecipOptions()
+    lib().mpsfm_recip_default_options(C.addressof(o))
+    o.subsample, o.max_iter = int(subsample), int(max_iter)
+    return o
+
+
+def recip_seed_count(H, W, subsample) -> int:
+    """mpsfm_recip_seed_count: the seeds of an H x W map (pixels S/2, S/2 + S, ... along both axes)."""
+    return int(lib().mpsfm_recip_seed_count(int(H), int(W), int(subsample)))
+
+
+def _recip_maps(o, arrays, names, device):
+    """The maps of a reciprocal-matching call as (arrays kept alive, pointers, device ordinal): device tensors go in as device pointers
+    with the caller's current stream, everything else as float32 host arrays."""
+    if _on_device(*arrays):
+        arrs, device = _device_inputs(o, list(arrays), device)
+        return arrs, [t.data_ptr() for t in arrs], device
+    arrs = [_host_f32(x, w) for x, w in zip(arrays, names)]
+    return arrs, [x.ctypes.data for x in arrs], device
+
+
+def reciprocal_nns(A, B, subsample=8, max_iter=10, device=None, return_info=False):
+    """mpsfm_reciprocal_nns: one descent from the seed grid of A [H1, W1, C] into B [H2, W2, C] (float16 / float32; NumPy, host
+    tensors or device tensors).  Returns the converged pairs as linear indices idx1, idx2 int32, unique and sorted by
+    (idx1, idx2)[, info dict(n_seeds, n_converged, iterations, nn_queries, column_ranges, ms)]."""
+    o = _recip_options(subsample, max_iter)
+    (a, b), (pa, pb), device = _recip_maps(o, (A, B), ("A", "B"), device)
+    if a.ndim != 3 or b.ndim != 3 or a.shape[2] != b.shape[2]:
+        raise ValueError("maps must be [H, W, C] with one C")
+    cap = max(recip_seed_count(a.shape[0], a.shape[1], o.subsample), 1)
+    i1, i2, n, I = np.zeros(cap, np.int32), np.zeros(cap, np.int32), C.c_int64(0), CRecipInfo()
+    _check(lib().mpsfm_reciprocal_nns(pa or None, int(a.shape[0]), int(a.shape[1]), pb or None, int(b.shape[0]), int(b.shape[1]), int(a.shape[2]),
+                                      C.addressof(o), int(device or 0), cap, i1.ctypes.data, i2.ctypes.data, C.addressof(n), C.addressof(I)))
+    i1, i2 = i1[:n.value].copy(), i2[:n.value].copy()
+    return (i1, i2, _recip_info(I)) if return_info else (i1, i2)
+
+
+def dense_correspondences(feats, qonfs, subsample=8, max_iter=10, device=None, return_info=False):
+    """mpsfm_dense_correspondences: feats = (feat11, feat21, feat22, feat12) [H, W, C], qonfs = (qonf11, qonf21, qonf22, qonf12) [H, W], the
+    order of the reference's extract_correspondences.  Returns xy1, xy2 int64 [n, 2] (x, y) and scores float32 [n][, info]."""
+    o = _recip_options(subsample, max_iter)
+    names = ["feat11", "feat21", "feat22", "feat12", "qonf11", "qonf21", "qonf22", "qonf12"]
+    arrs, ptrs, device = _recip_maps(o, tuple(feats) + tuple(qonfs), names, device)
+    f, q = arrs[:4], arrs[4:]
+    if any(x.ndim != 3 for x in f) or len({int(x.shape[2]) for x in f}) != 1:
+        raise ValueError("maps must be [H, W, C] with one C")
+    s1, s2 = tuple(f[0].shape[:2]), tuple(f[1].shape[:2])
+    if [tuple(x.shape[:2]) for x in f] != [s1, s2, s2, s1] or [tuple(x.shape) for x in q] != [s1, s2, s2, s1]:
+        raise ValueError("feat11, feat12, qonf11, qonf12 share one [H1, W1], feat21, feat22, qonf21, qonf22 one [H2, W2]")
+    cap = max(2 * (recip_seed_count(*s1, o.subsample) + recip_seed_count(*s2, o.subsample)), 1)
+    xy1, xy2, sc, n, I = np.zeros((cap, 2), np.int32), np.zeros((cap, 2), np.int32), np.zeros(cap, np.float32), C.c_int64(0), CRecipInfo()
+    _check(lib().mpsfm_dense_correspondences(*[p or None for p in ptrs], int(s1[0]), int(s1[1]), int(s2[0]), int(s2[1]), int(f[0].shape[2]),
+                                             C.addressof(o), int(device or 0), cap, xy1.ctypes.data, xy2.ctypes.data, sc.ctypes.data,
+                                             C.addressof(n), C.addressof(I)))
+    xy1, xy2, sc = xy1[:n.value].astype(np.int64), xy2[:n.value].astype(np.int64), sc[:n.value].copy()
+    return (xy1, xy2, sc, _recip_info(I)) if return_info else (xy1, xy2, sc)
 
 
 def _warp_info(I) -> dict:

@@ -24,60 +24,19 @@
 
 #include "call_scope.h"
 #include "common.h"
+#include "sim_tile.h"
 #include "bilinear_sample.h"  // contraction off from here on: the decisions round every operation on its own
 
 namespace mpsfm {
 
 namespace {
-constexpr int kStrip = 64;        // rows of a workgroup, columns of a tile
-constexpr int kKS = 32;           // k values of a slice
-constexpr int kLd = 80;           // doubles per k row of a slice in LDS: the four k rows of one MFMA step sit 32 banks apart
-constexpr int kMT = 256;          // threads of k_sim_top2
-constexpr int kDT = 256;          // threads of the element-wise kernels
-constexpr int32_t kMaxDim = 1024;
-constexpr int64_t kMaxDesc = 1 << 24;
-constexpr int32_t kNoIndex = INT32_MAX;
-constexpr int32_t kFillPerCU = 8; // workgroups per compute unit that fill the device: LDS for four at a time, two rounds
+using namespace sim;  // the tile geometry, before(), load_slice() and the device scan: sim_tile.h
 
 struct Top2 { double v1, v2; int32_t i1, i2; };
 
-__device__ __forceinline__ bool before(double v, int32_t i, double w, int32_t j) { return v > w || (v == w && i < j); }
 __device__ __forceinline__ void offer(Top2& t, double v, int32_t i) {
   if (before(v, i, t.v1, t.i1)) { t.v2 = t.v1; t.i2 = t.i1; t.v1 = v; t.i1 = i; }
   else if (before(v, i, t.v2, t.i2)) { t.v2 = v; t.i2 = i; }
-}
-
-template <typename T> struct Vec4;
-template <> struct Vec4<float> { typedef float4 type; };
-template <> struct Vec4<double> { typedef double4 type; };
-
-// One slice: s[k][column ^ 8 (k / 4 & 7)] = X[row0 + column][k0 + k], zeros beyond the set and beyond dim.  Thread -> (row, four
-// consecutive k): eight lanes read 32 consecutive k of a row; the XOR spreads their LDS stores over all banks and is the same
-// for the four k rows an MFMA step reads, so the reads stay conflict free.
-template <typename T>
-__device__ __forceinline__ void load_slice(double* __restrict__ s, const T* __restrict__ X, int32_t nrows, int32_t row0, int32_t dim, int32_t k0,
-                                           bool vec) {
-#pragma unroll
-  for (int j = 0; j < kStrip * kKS / 4 / kMT; ++j) {
-    const int e = (int)threadIdx.x + kMT * j;
-    const int kq = e & 7, r = e >> 3;
-    const int32_t row = row0 + r, k = k0 + 4 * kq;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    if (row < nrows && k < dim) {
-      const T* p = X + (size_t)row * (size_t)dim + k;
-      if (vec) {  // dim % 4 == 0 and an aligned base: k + 3 < dim
-        const typename Vec4<T>::type q = *reinterpret_cast<const typename Vec4<T>::type*>(p);
-        v[0] = (double)q.x; v[1] = (double)q.y; v[2] = (double)q.z; v[3] = (double)q.w;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (k + c < dim) v[c] = (double)p[c];
-      }
-    }
-    const int col = r ^ (8 * kq);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s[(4 * kq + c) * kLd + col] = v[c];
-  }
 }
 
 struct SimArgs {
@@ -243,14 +202,6 @@ __global__ __launch_bounds__(kDT) void k_sample_descriptors(const float* __restr
   else cs[i] = bilinear_channel(conf, H, W, 1, 0, x, y);
 }
 
-__global__ __launch_bounds__(kDT) void k_scan_finite(const float* __restrict__ x, int64_t n, int32_t* __restrict__ bad) {
-  int64_t i = (int64_t)blockIdx.x * kDT + (int64_t)threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * kDT;
-  bool b = false;
-  for (; i < n; i += stride) b = b || !isfinite(x[i]);
-  if (b) atomicOr(bad, 1);
-}
-
 inline dim3 blocks_of(int64_t n) { return dim3((unsigned)((n + kDT - 1) / kDT)); }
 // a float32 keypoint coordinate may overflow where the float64 one is finite
 bool kps_ok(const double* k, size_t n) {
@@ -267,13 +218,6 @@ int check_options(const mpsfm_match_options& o) {
 
 void fill_empty(int64_t n0, int32_t* matches0, double* scores0) {
   for (int64_t i = 0; i < n0; ++i) { matches0[i] = -1; scores0[i] = 0.0; }
-}
-
-int scan_device(CallScope& A, const float* x, int64_t n, int32_t* d_bad) {
-  const int64_t blocks = std::min<int64_t>((n + kDT - 1) / kDT, 4096);
-  hipLaunchKernelGGL(k_scan_finite, dim3((unsigned)blocks), dim3(kDT), 0, A.st, x, n, d_bad);
-  MPSFM_TRY(hipGetLastError());
-  return 0;
 }
 
 // top-2 in both directions, the decisions and the download; d0 / d1 on the device, conf0 / conf1 device or NULL.  d_bad (may be
