@@ -936,6 +936,65 @@ int mpsfm_match_map_descriptors(const float* map0 /* [H0][W0][C] */, const float
                                 const mpsfm_match_options* opts /* NULL: defaults */, int32_t device, int32_t* matches0 /* [n0] */,
                                 double* scores0 /* [n0] */, mpsfm_match_info* info /* may be NULL */);
 
+/* ---- descriptors to match lists for MANY image pairs in one call (reference mpsfm/extraction/pairwise/match_sparse.py
+ *    match_from_paths, the loop over all retrieved pairs of a scene).  The descriptor sets of all images are
+ *    given once, concatenated: image i owns the rows [image_start[i], image_start[i + 1]) of desc.  Pair k matches image
+ *    pair_image0[k] (rows) against image pair_image1[k] (columns) and owns the rows [match_start[k], match_start[k + 1]) of
+ *    matches0 / scores0, as many as its first image has descriptors.  One set of options serves all pairs.
+ *
+ *    Pair k's slice of matches0 / scores0 is IDENTICAL, matches equal and scores bitwise equal, to what mpsfm_match_descriptors
+ *    returns for (image pair_image0[k], image pair_image1[k]) alone with the same options, whatever the other pairs, their
+ *    order, the order of the images, column_ranges and pairs_per_group: both calls run the same device code on every element
+ *    (csrc/sim_top2.h), and a row's top-2 is a function of the SET of its candidates under one total order.  The ratio test is
+ *    skipped per pair when either of ITS sides holds a single descriptor.  (i, i) is allowed, and so is any pair listed twice;
+ *    (i, j) and (j, i) are two pairs.  A pair whose first image is empty owns zero rows; a pair whose second image is empty gets
+ *    -1 / 0; both take part in no launch, and if no other pair is left no device is touched.
+ *
+ *    The pairs that are launched are processed in GROUPS of consecutive launched pairs: per group one launch forms the top-2 of every
+ *    strip of 64 rows of every pair in both directions from a host-built table of work items, one launch decides every output row.
+ *    pairs_per_group 0: consecutive pairs while the group's top-2 tables (24 B per row and column range, both directions) stay
+ *    under 256 MiB; an explicit value is used as given up to 4096.  column_ranges 0: per group, every strip's column tiles are
+ *    shared out over ceil(8 CUs / (strips of the group, both directions)) workgroups, at most one per column tile, so a batch of
+ *    many pairs runs with one workgroup per strip; an explicit value asks for that many per strip, clamped the same way.  Results
+ *    depend on neither.  All groups are enqueued back to back on one stream and reuse the same tables in stream order; the
+ *    descriptors of all images are uploaded once, matches and scores of the whole batch come down once, and the host waits
+ *    ONCE per call (report->num_syncs == 1).  A batch whose descriptors do not fit the device returns MPSFM_ENOMEM: chunking a
+ *    scene over images is the caller's business.
+ *
+ *    opts->inputs_on_device != 0: desc is a device pointer on `device` (checked), the event is recorded on opts->stream as
+ *    in the single call, non-finite values are found by a kernel and reported as MPSFM_EINVAL after it.  image_start, the
+ *    pair arrays, match_start and all outputs are host memory, complete on return; nothing is retained.
+ *
+ *    MPSFM_EINVAL before any HIP call, the message naming the image or pair: NULL pointers (opts, pair_num_matches and report
+ *    may be NULL), negative counts, image_start[0] != 0 or a decreasing offset, an image of more than 2^24 descriptors, dim
+ *    outside 1 .. 1024, a pair index outside [0, num_images), match_start[0] != 0 or a slice whose length is not its first
+ *    image's size, negative column_ranges or pairs_per_group, non-finite thresholds, a non-finite host descriptor value.
+ *    num_pairs == 0 returns 0 and touches nothing.  MPSFM_ENODEVICE without a device, but only when a pair needs one. ---- */
+typedef struct mpsfm_match_batch_report {
+  int64_t num_matches;     /* rows with matches0 >= 0, all pairs */
+  int64_t num_groups;
+  int64_t num_launches;    /* kernel launches of the call */
+  int64_t num_syncs;       /* stream synchronisations of the call */
+  int64_t num_workgroups;  /* workgroups of all similarity launches */
+  float ms;                /* device time, first kernel to last (HIP events) */
+  int32_t reserved;
+} mpsfm_match_batch_report;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_match_batch_report) == 48 && offsetof(mpsfm_match_batch_report, num_groups) == 8 &&
+                  offsetof(mpsfm_match_batch_report, num_launches) == 16 && offsetof(mpsfm_match_batch_report, num_syncs) == 24 &&
+                  offsetof(mpsfm_match_batch_report, num_workgroups) == 32 && offsetof(mpsfm_match_batch_report, ms) == 40,
+              "ABI of mpsfm_match_batch_report");
+#endif
+
+int mpsfm_match_descriptors_batch(int32_t num_images, const int64_t* image_start /* [num_images + 1], image_start[0] == 0 */, int32_t dim,
+                                  const float* desc /* [image_start[num_images]][dim]: the images' descriptor sets, concatenated */,
+                                  int64_t num_pairs, const int32_t* pair_image0, const int32_t* pair_image1 /* [num_pairs] image indices */,
+                                  const int64_t* match_start /* [num_pairs + 1], match_start[0] == 0 */,
+                                  const mpsfm_match_options* opts /* NULL: defaults */, int32_t column_ranges /* 0: default rule */,
+                                  int32_t pairs_per_group /* 0: default rule */, int32_t device,
+                                  int32_t* matches0, double* scores0 /* [match_start[num_pairs]] */,
+                                  int64_t* pair_num_matches /* [num_pairs], may be NULL */, mpsfm_match_batch_report* report /* may be NULL */);
+
 /* ---- dense reciprocal matches from descriptor maps: the dense leg of the reference's MASt3R matcher
  *    (mpsfm/extraction/pairwise/models/mast3r.py:119-170 merge_corres, extract_correspondences, with MASt3R's
  *    fast_reciprocal_NNs; the contract, the kernels and the measurements: DESIGN.md section 4p).

@@ -12,7 +12,7 @@ import numpy as np
 
 from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
     ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CDcImage, CDcSummary, CDepthGather, CDepthPriorConf,
-    CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchInfo, CMatchOptions, CNmsInfo,
+    CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
     CRecipOptions, CRegImage, CRelPoseOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
     CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
@@ -857,6 +857,62 @@ def match_descriptors(desc0, desc1, ratio_threshold=None, distance_threshold=Non
                                          C.addressof(I)))
     m, s = m[:n0].astype(np.int64), s[:n0]
     return (m, s, _match_info(I)) if return_info else (m, s)
+
+
+def match_descriptors_batch(descs, pairs, ratio_threshold=None, distance_threshold=None, do_mutual_check=True, score_threshold=None,
+                            device=None, column_ranges=0, pairs_per_group=0, return_info=False):
+    """mpsfm_match_descriptors_batch: the match lists of many image pairs in one call.  `descs`: a sequence of [n_i, dim] float16 /
+    float32 arrays, one per image (NumPy, host tensors, or device tensors all on one device: those are concatenated on the device and
+    go in as one device pointer with the caller's current stream).  `pairs`: a sequence of (i, j) image indices, rows = image i,
+    columns = image j.  Returns a list of matches0 int64 [n_i] and a list of scores0 float64 [n_i], one entry per pair, each what
+    match_descriptors returns for that pair alone[, info dict(num_matches, num_groups, num_launches, num_syncs, num_workgroups, ms,
+    pair_num_matches int64 [num_pairs])].  `column_ranges` / `pairs_per_group` 0: the library's default rules; results depend on
+    neither."""
+    o = _match_options(ratio_threshold, distance_threshold, score_threshold, do_mutual_check)
+    descs = list(descs)
+    for d in descs:
+        if getattr(d, "ndim", None) != 2:
+            raise ValueError("every descriptor set must be [n, dim]")
+    if len({int(d.shape[1]) for d in descs}) > 1:
+        raise ValueError("descriptor sets of different dim")
+    dim = int(descs[0].shape[1]) if descs else 1
+    image_start = np.zeros(len(descs) + 1, np.int64)
+    if descs:
+        image_start[1:] = np.cumsum([int(d.shape[0]) for d in descs])
+    if descs and _on_device(*descs):
+        import torch
+
+        tensors, device = _device_inputs(o, descs, device)
+        with torch.cuda.device(tensors[0].device):
+            cat = torch.cat(tensors)  # on the current stream, which the call waits for (or which _device_inputs synchronised)
+            if not o.stream:
+                torch.cuda.current_stream().synchronize()
+        ptr = cat.data_ptr()
+    else:
+        host = [_host_f32(d, "descs") for d in descs]
+        cat = np.ascontiguousarray(np.concatenate(host)) if host else np.zeros((0, dim), np.float32)
+        ptr = cat.ctypes.data
+    pr = np.asarray(list(pairs), np.int64).reshape(-1, 2)
+    if len(pr) and (pr.min() < 0 or pr.max() >= len(descs)):
+        raise ValueError("a pair names an image that is not in descs")
+    p0, p1 = np.ascontiguousarray(pr[:, 0], np.int32), np.ascontiguousarray(pr[:, 1], np.int32)
+    sizes = np.diff(image_start)
+    match_start = np.zeros(len(pr) + 1, np.int64)
+    match_start[1:] = np.cumsum(sizes[p0])
+    rows = int(match_start[-1])
+    m, s = np.full(max(rows, 1), -1, np.int32), np.zeros(max(rows, 1))
+    cnt, R = np.zeros(max(len(pr), 1), np.int64), CMatchBatchReport()
+    _check(lib().mpsfm_match_descriptors_batch(len(descs), image_start.ctypes.data, dim, ptr or None, len(pr), p0.ctypes.data, p1.ctypes.data,
+                                               match_start.ctypes.data, C.addressof(o), int(column_ranges), int(pairs_per_group),
+                                               int(device or 0), m.ctypes.data, s.ctypes.data, cnt.ctypes.data, C.addressof(R)))
+    m = m.astype(np.int64)
+    ms = [m[match_start[k]:match_start[k + 1]] for k in range(len(pr))]
+    ss = [s[match_start[k]:match_start[k + 1]] for k in range(len(pr))]
+    if not return_info:
+        return ms, ss
+    info = dict(num_matches=int(R.num_matches), num_groups=int(R.num_groups), num_launches=int(R.num_launches), num_syncs=int(R.num_syncs),
+                num_workgroups=int(R.num_workgroups), ms=float(R.ms), pair_num_matches=cnt[:len(pr)])
+    return ms, ss, info
 
 
 def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=None, ratio_threshold=None, distance_threshold=None,

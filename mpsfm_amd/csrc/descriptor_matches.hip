@@ -7,15 +7,8 @@
 //   k_match_decide        ratio / distance tests, mutual check, score threshold, outputs
 //
 // k_sim_top2: a workgroup of four waves owns a strip of kStrip = 64 rows and streams the columns (all of them, or one of
-// gridDim.z ranges of column tiles when there are too few strips to fill the device) in tiles of 64 and k in
-// slices of kKS staged through LDS (slices are sized from the LDS budget: dim only sets how many there are).  Wave w holds
-// the 16 x 64 band of rows 16 w .. 16 w + 15 as four 16 x 16 accumulators, so all candidates of a row live in the 16 lanes
-// of one wave that share the row in the accumulator layout (row (lane >> 4) + 4 reg, column lane & 15).  Edge tiles are
-// padded with zeros in k, rows and columns and go through the same instructions as full ones; padded columns are never
-// offered as candidates, padded rows never written.
-//
-// Every merge (a lane's own columns, the 16 lanes of a row, column tiles) orders candidates by (value descending, index
-// ascending), a total order on distinct columns: the top-2 does not depend on the order in which candidates arrive.
+// gridDim.z ranges of column tiles when there are too few strips to fill the device).  The strip itself, the running top-2 and
+// the decisions of a row are the bodies of sim_top2.h, which the batched matcher (descriptor_matches_batch.hip) calls too.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -26,18 +19,12 @@
 #include "common.h"
 #include "sim_tile.h"
 #include "bilinear_sample.h"  // contraction off from here on: the decisions round every operation on its own
+#include "sim_top2.h"
 
 namespace mpsfm {
 
 namespace {
-using namespace sim;  // the tile geometry, before(), load_slice() and the device scan: sim_tile.h
-
-struct Top2 { double v1, v2; int32_t i1, i2; };
-
-__device__ __forceinline__ void offer(Top2& t, double v, int32_t i) {
-  if (before(v, i, t.v1, t.i1)) { t.v2 = t.v1; t.i2 = t.i1; t.v1 = v; t.i1 = i; }
-  else if (before(v, i, t.v2, t.i2)) { t.v2 = v; t.i2 = i; }
-}
+using namespace sim;  // the tile geometry, before(), load_slice() and the device scan: sim_tile.h; Top2, the strip and the decisions: sim_top2.h
 
 struct SimArgs {
   const void* X[2];   // descriptor sets 0 and 1, [n][dim]
@@ -57,68 +44,12 @@ __global__ __launch_bounds__(kMT) void k_sim_top2(SimArgs a) {
   const int32_t nrows = a.n[d], ncols = a.n[1 - d];
   const int32_t row0 = (int32_t)blockIdx.x * kStrip;
   if (row0 >= nrows) return;  // the grid is sized for the larger set
-  const T* R = (const T*)a.X[d];
-  const T* Cc = (const T*)a.X[1 - d];
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  const int lr = lane & 15, lg = lane >> 4;
-  const bool vec = a.vec != 0;
-
-  Top2 top[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) top[r] = Top2{-INFINITY, -INFINITY, kNoIndex, kNoIndex};
-
   // this workgroup's range of column tiles; an empty range leaves the sentinels, which every merge ignores
   const int32_t per = ((ncols + kStrip - 1) / kStrip + a.splits - 1) / a.splits * kStrip;
   const int64_t cb = (int64_t)blockIdx.z * per;
   const int32_t col_begin = (int32_t)min(cb, (int64_t)ncols), col_end = (int32_t)min(cb + per, (int64_t)ncols);
-  for (int32_t col0 = col_begin; col0 < col_end; col0 += kStrip) {
-    v4d acc[4];
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[ni] = v4d{0.0, 0.0, 0.0, 0.0};
-    for (int32_t k0 = 0; k0 < a.dim; k0 += kKS) {
-      __syncthreads();  // the previous slice has been read
-      load_slice<T>(s_A, R, nrows, row0, a.dim, k0, vec);
-      load_slice<T>(s_B, Cc, ncols, col0, a.dim, k0, vec);
-      __syncthreads();
-      const int steps = (min(a.dim - k0, kKS) + 3) >> 2;
-      for (int s = 0; s < steps; ++s) {
-        const int x = 8 * (s & 7);
-        const double* pa = s_A + (4 * s + lg) * kLd;
-        const double* pb = s_B + (4 * s + lg) * kLd;
-        const double av = pa[(16 * wave + lr) ^ x];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, pb[(16 * ni + lr) ^ x], acc[ni], 0, 0, 0);
-      }
-    }
-    // this lane's candidates of the tile: columns col0 + 16 ni + lr, rows lg + 4 r of the band
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      const int32_t col = col0 + 16 * ni + lr;
-      if (col < ncols) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) offer(top[r], acc[ni][r], col);
-      }
-    }
-  }
-  // the 16 lanes that share a row
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) {
-      const double ov1 = __shfl_xor(top[r].v1, m), ov2 = __shfl_xor(top[r].v2, m);
-      const int32_t oi1 = __shfl_xor(top[r].i1, m), oi2 = __shfl_xor(top[r].i2, m);
-      offer(top[r], ov1, oi1);
-      offer(top[r], ov2, oi2);
-    }
-    const int32_t row = row0 + 16 * wave + lg + 4 * r;
-    if (lr == 0 && row < nrows) {
-      const size_t o = 2 * ((size_t)row * a.splits + blockIdx.z);
-      a.val[d][o] = top[r].v1;
-      a.val[d][o + 1] = top[r].v2;
-      a.idx[d][o] = top[r].i1;
-      a.idx[d][o + 1] = top[r].i2;
-    }
-  }
+  sim_top2_strip<T>(s_A, s_B, (const T*)a.X[d], nrows, row0, (const T*)a.X[1 - d], ncols, col_begin, col_end, a.dim, a.vec != 0, a.splits,
+                    (int32_t)blockIdx.z, a.val[d], a.idx[d]);
 }
 
 struct DecideArgs {
@@ -133,36 +64,13 @@ struct DecideArgs {
   double* scores;
 };
 
-// find_nn for one row: the match or -1, and the score
-__device__ __forceinline__ int32_t nn_of(const DecideArgs& a, int d, int32_t row, double& score) {
-  // the ranges' top-2 lists merge in the same total order: the result is the top-2 over all columns, whatever the split
-  Top2 t{-INFINITY, -INFINITY, kNoIndex, kNoIndex};
-  for (int z = 0; z < a.splits; ++z) {
-    const size_t o = 2 * ((size_t)row * a.splits + z);
-    offer(t, a.val[d][o], a.idx[d][o]);
-    offer(t, a.val[d][o + 1], a.idx[d][o + 1]);
-  }
-  const double s0 = t.v1, s1 = t.v2;
-  const int32_t i0 = t.i1;
-  const int32_t ncols = d ? a.n0 : a.n1;
-  const double d0 = 2.0 * (1.0 - s0), d1 = 2.0 * (1.0 - s1);
-  bool ok = i0 >= 0 && i0 < ncols;
-  if (a.use_ratio) ok = ok && (d0 <= a.ratio2 * d1);
-  if (a.use_dist) ok = ok && (d0 <= a.dist2);
-  score = ok ? (s0 + 1.0) / 2.0 : 0.0;
-  return ok ? i0 : -1;
-}
-
 __global__ __launch_bounds__(kDT) void k_match_decide(DecideArgs a) {
   const int32_t i = (int32_t)blockIdx.x * kDT + (int32_t)threadIdx.x;
   if (i >= a.n0) return;
+  const Top2Table dir0{a.val[0], a.idx[0], a.splits, a.n1}, dir1{a.val[1], a.idx[1], a.splits, a.n0};
+  const MatchRule rule{a.ratio2, a.dist2, a.score_thr, a.use_ratio, a.use_dist, a.use_score, a.mutual};
   double score;
-  int32_t m = nn_of(a, 0, i, score);
-  if (a.mutual && m >= 0) {
-    double unused;
-    if (nn_of(a, 1, m, unused) != i) m = -1;
-  }
-  if (a.use_score && score < a.score_thr) m = -1;
+  const int32_t m = match_of(dir0, dir1, rule, i, score);
   if (a.conf0) score = m >= 0 ? sqrt(a.conf0[i] * a.conf1[m]) : 0.0;
   a.matches[i] = m;
   a.scores[i] = score;
@@ -208,16 +116,6 @@ bool kps_ok(const double* k, size_t n) {
   for (size_t i = 0; i < 2 * n; ++i)
     if (!std::isfinite(k[i]) || !std::isfinite((float)k[i])) return false;
   return true;
-}
-
-int check_options(const mpsfm_match_options& o) {
-  if (!std::isfinite(o.ratio_threshold) || !std::isfinite(o.distance_threshold) || !std::isfinite(o.score_threshold))
-    return fail(MPSFM_EINVAL, "non-finite threshold");
-  return 0;
-}
-
-void fill_empty(int64_t n0, int32_t* matches0, double* scores0) {
-  for (int64_t i = 0; i < n0; ++i) { matches0[i] = -1; scores0[i] = 0.0; }
 }
 
 // top-2 in both directions, the decisions and the download; d0 / d1 on the device, conf0 / conf1 device or NULL.  d_bad (may be
@@ -300,7 +198,7 @@ extern "C" int mpsfm_match_descriptors(int64_t n0, int64_t n1, int32_t dim, cons
   if (n0 > kMaxDesc || n1 > kMaxDesc) return fail(MPSFM_EINVAL, "more than 2^24 descriptors");
   if (dim < 1 || dim > kMaxDim) return fail(MPSFM_EINVAL, "dim must be 1 .. 1024");
   if ((n0 > 0 && (!desc0 || !matches0 || !scores0)) || (n1 > 0 && !desc1)) return fail(MPSFM_EINVAL, "NULL pointer");
-  if (int rc = check_options(o)) return rc;
+  if (int rc = check_match_options(o)) return rc;
   if (!o.inputs_on_device && (!all_finite(desc0, (size_t)n0 * dim) || !all_finite(desc1, (size_t)n1 * dim)))
     return fail(MPSFM_EINVAL, "non-finite descriptor value");
   if (n0 == 0) return 0;
@@ -344,7 +242,7 @@ extern "C" int mpsfm_match_map_descriptors(const float* map0, const float* conf0
   if (H0 < 2 || W0 < 2 || H1 < 2 || W1 < 2) return fail(MPSFM_EINVAL, "a map needs at least 2 rows and 2 columns");
   if (!map0 || !conf0 || !map1 || !conf1) return fail(MPSFM_EINVAL, "NULL pointer");
   if ((n0 > 0 && (!kps0 || !matches0 || !scores0)) || (n1 > 0 && !kps1)) return fail(MPSFM_EINVAL, "NULL pointer");
-  if (int rc = check_options(o)) return rc;
+  if (int rc = check_match_options(o)) return rc;
   if (!kps_ok(kps0, (size_t)n0) || !kps_ok(kps1, (size_t)n1)) return fail(MPSFM_EINVAL, "non-finite keypoint");
   const size_t px0 = (size_t)H0 * (size_t)W0, px1 = (size_t)H1 * (size_t)W1;
   if (!o.inputs_on_device && (!all_finite(map0, px0 * C) || !all_finite(conf0, px0) || !all_finite(map1, px1 * C) || !all_finite(conf1, px1)))
