@@ -330,16 +330,15 @@ __global__ __launch_bounds__(kThreads) void k_track_sweep(SweepArgs A) {
 // Update sweep: y_p = -(V+D)^-1 (g_p + W^T y_c), model cost change, candidate landmarks, candidate
 // cost.  Recomputes the linearisation (cheaper than storing 240 B per record in HBM).
 #ifndef MPSFM_UPD_OCC
-#define MPSFM_UPD_OCC 4  // 107 / 109 registers without spills; LDS (6.4 / 12 KB) does not limit.  5 means 96 registers: 34 spilled, 49.7 instead of 38 us
+#define MPSFM_UPD_OCC 4  // 117 / 119 registers without spills; LDS (6.4 / 12 KB) does not limit.  5 means 96 registers: 34 spilled, 49.7 instead of 38 us
 #endif
 // kHandoff: F and g_p of every landmark come from the track sweep of the same iteration (SweepArgs::pt_fac)
 template <bool kHandoff>
 __global__ __launch_bounds__(kThreads, MPSFM_UPD_OCC) void k_update_sweep(SweepArgs A, CamUpdArgs U) {
-  if (lm_over(A.ctl)) return;
-  const double lm_radius = A.ctl ? lm_radius_of(A.ctl) : A.radius;
   __shared__ UpdLdsT<kHandoff> S;
-  if (U.fuse && blockIdx.x == 0) cam_update_all(U, A.yc, S.red);  // (the candidate rows of this chunk come next, like everywhere)
-  update_sweep_chunk<false, kHandoff>(A, blockIdx.x, lm_radius, nullptr, nullptr, A.yc, S, U, U.fuse != 0);
+  // The body requests the control block itself, beside the chunk header (the radius given here is what it uses without one), tests
+  // `term` in front of the first store, and lets workgroup 0 run cam_update_all when the camera update is fused.
+  update_sweep_chunk<false, kHandoff>(A, blockIdx.x, A.radius, nullptr, nullptr, A.yc, S, U, U.fuse != 0);
 }
 
 // decode q in [0, k(k+1)/2) -> (i, j), i <= j < k, row-major upper triangle

@@ -153,6 +153,17 @@ __device__ __forceinline__ double lm_radius_chain(const LmCtl* c, double fallbac
   return c != nullptr ? __hip_atomic_load(&c->radius, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : fallback;
 }
 
+// `accepted` and `radius` the same way for the sweeps of the launch chain, which request the control block in one batch with their
+// chunk header: no branch in front of the requests; without a control block the value read from `readable` (8 readable bytes,
+// 8-aligned) is replaced by `fallback` where it is used.
+__device__ __forceinline__ int32_t lm_accepted_chain(const LmCtl* c, const void* readable) {
+  return __hip_atomic_load(c != nullptr ? &c->accepted : static_cast<const int32_t*>(readable), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ double lm_radius_chain(const LmCtl* c, const void* readable, double fallback) {
+  const double r = __hip_atomic_load(c != nullptr ? &c->radius : static_cast<const double*>(readable), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  return c != nullptr ? r : fallback;
+}
+
 // ---- small device math -------------------------------------------------------------------
 // Reciprocal, square root and reciprocal square root in a handful of instructions: the hardware estimate (v_rcp_f64 / v_rsq_f64,
 // ~2^-22 relative) refined by two Newton steps (error ~ e^4: below one ulp; the last bit may differ from the IEEE-rounded quotient

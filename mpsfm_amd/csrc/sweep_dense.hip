@@ -6,8 +6,12 @@
 // has at most kDenseCams (16) variable cameras, kDensePts (96) landmarks, kObsMax (252) merged records and one record per
 // (camera, variable landmark).
 //
-//   P0  clear the LDS accumulators, request the landmark data of P2
-//   P1  one thread per record: residuals, analytic Jacobians, robust weights (sweep_common.h);
+//   entry  two batches of loads instead of a chain of dependent trips: the control block (term, accepted, radius: vector loads)
+//       beside the chunk header, then, from the header alone, the chunk's records; `term` is tested behind these requests
+//       and in front of the first global store
+//   P0  while the records are in flight: adoption of an accepted candidate, clear the LDS accumulators
+//   P1  one thread per record: the loads indexed by the record (landmark, scales, pt_kv, depth triple, camera row) in one batch —
+//       pt_kv and the scales stay in registers for P2 —, residuals, analytic Jacobians, robust weights (sweep_common.h);
 //       V_p, g_p per landmark and U_c (upper triangle), g_c per camera by ds_add_f64 — the camera accumulators in 4 (up to 8
 //       cameras) or 2 copies chosen by the landmark, because neighbouring lanes are the records of one landmark and would
 //       otherwise add ~13-fold to one address; W = Jc^T Jp stays in registers
@@ -30,13 +34,12 @@
 namespace mpsfm {
 
 __global__ __launch_bounds__(kThreads, 3) void k_track_sweep_dense(SweepArgs A) {
-  if (lm_over(A.ctl)) return;
-  const double lm_radius = A.ctl ? lm_radius_of(A.ctl) : A.radius;
   __shared__ DenseLds S;
   // One workgroup per chunk.  Persistent workgroups (3 per CU taking chunks from a cost-sorted list through a shared counter) were
   // measured and dropped: the slots stay full, but every chunk then takes longer (wave life 21.5 -> 24.7 us at C3: the sweep is
   // bound by the CU's shared pipes, not by the 22 % of slot time the dispatcher leaves empty) — 0.118 against 0.111 ms.
-  dense_sweep_chunk<false>(A, blockIdx.x + A.chunk0, lm_radius, nullptr, S, A.part);
+  // (the body requests the control block itself, beside the chunk header: the radius given here is what it uses without one)
+  dense_sweep_chunk<false>(A, blockIdx.x + A.chunk0, A.radius, nullptr, S, A.part);
 }
 
 // One wave per destination part: sums the part's slab sources in table order and adds the sum into the (zeroed) reduced buffer.

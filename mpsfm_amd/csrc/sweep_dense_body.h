@@ -250,17 +250,40 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
 #define MPSFM_STAMP(k) do { if (trace) trace[k] = (long long)clock64(); } while (0)
   MPSFM_STAMP(0);
   if (trace) trace[12] = (long long)wall_clock64();  // 100 MHz reference, to calibrate the shader clock
+  // ---- entry: what the chunk needs from memory, requested in two batches instead of one trip after the other ---------------------
+  // batch 0: the chunk header, and behind it (vector loads return in order: the header must not wait for a block that comes all the
+  // way from memory) the control block (launch chain only, see lm_term_chain)
   const ChunkHdr H = A.chunks[cix];
+  [[maybe_unused]] int32_t term = kLmRunning, accepted = 0;
+  if constexpr (!kLocal) {
+    term = lm_term_chain(A.ctl, A.chunks);
+    accepted = lm_accepted_chain(A.ctl, A.chunks);
+    lm_radius = lm_radius_chain(A.ctl, A.chunks, lm_radius);
+  }
   const int nrec = H.nrec, npt = H.npt, ncam = H.ncam;
   const int ncopy = ncam <= 8 ? 4 : 2, cstride = ncam <= 8 ? 8 : 16;  // accumulator copies x cameras per copy = 32
+  // batch 1, from the header alone: the chunk's records (and the camera list, which only the single-launch form reads: camera_row).
+  // A lane without a record (camera) keeps its guard but takes no branch: it reads the head of the chunk table, which is always
+  // readable, and drops the value behind the barrier.  With a branch around the requests the compiler counts the loads in flight
+  // for the path that skips them, and the wait for `term` below becomes a wait for the records.
+  const bool has_rec = tid < nrec;
+  uint32_t my_meta = *(has_rec ? &A.rec_meta[H.rec0 + tid] : reinterpret_cast<const uint32_t*>(A.chunks));
+  int cam = *(has_rec ? &A.rec_cam[H.rec0 + tid] : reinterpret_cast<const int32_t*>(A.chunks));
+  double2 xy = *(has_rec ? &reinterpret_cast<const double2*>(A.rec_xy)[H.rec0 + tid] : reinterpret_cast<const double2*>(A.chunks));
+  [[maybe_unused]] int32_t my_slot = 0;
+  if constexpr (kLocal) my_slot = *(tid < ncam ? &A.chunk_cams[H.cam0 + tid] : reinterpret_cast<const int32_t*>(A.chunks));
+  // the solve is over (the iteration queued ahead of the news): leave before the first global store
+  if constexpr (!kLocal) {
+    if (A.ctl != nullptr && lm_over_chain(term)) return;
+  }
 
-  // ---- P0 ------------------------------------------------------------------------------------------------------------
+  // ---- P0 (the records are in flight) ----------------------------------------------------------------------------------------------------
   // first launch of an iteration: the candidate the last decision accepted is what this sweep linearises at; its copy into the
   // state (this chunk's landmarks; the cameras and the zeroing of the reduced buffer dealt over all workgroups) runs beside P1
   bool adopt = false;
   if constexpr (!kLocal) {
     if (A.adopt_on) {
-      adopt = lm_accepted(A.ctl);
+      adopt = A.ctl != nullptr && __builtin_amdgcn_readfirstlane(accepted) != 0;
       const int64_t g0 = (int64_t)(cix - A.chunk0) * kThreads + tid, gstep = (int64_t)A.nchunks * kThreads;
       for (int64_t e = g0; e < A.nred; e += gstep) A.red[e] = 0.0;
       if (adopt) {
@@ -281,32 +304,35 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
   for (int i = tid; i < kAccU; i += kThreads) S.U[i] = 0.0;
   for (int i = tid; i < kAccG; i += kThreads) { S.gc[i] = 0.0; S.wv[i] = 0.0; }
   for (int i = tid; i < npt * (kDenseCams / 4); i += kThreads) reinterpret_cast<uint32_t*>(S.rec)[i] = 0xffffffffu;
-  if (tid < ncam) S.slot[tid] = A.chunk_cams[H.cam0 + tid];
+  if constexpr (kLocal) { if (tid < ncam) S.slot[tid] = my_slot; }
   MPSFM_STAMP(1);
   __syncthreads();
   MPSFM_STAMP(2);
+  // (nothing derived from the records is to be computed, and so waited for, in front of the barrier: the P0 work runs under their trip)
+  asm volatile("" : "+v"(my_meta), "+v"(cam));
+  if (!has_rec) my_meta = 0;  // (threads beyond the records carry meta 0 through the scans below)
 
   // ---- P1 ------------------------------------------------------------------------------------------------------------
   double my_cost = 0.0;
   int my_bad = 0;
-  uint32_t my_meta = 0;
+  uint16_t my_kv = 0xffff;       // pt_kv of the record's landmark and
+  double my_ps[3] = {0, 0, 0};   // its scale: requested here with the landmark, used again by P2
   double my_w[18];
 #pragma unroll
   for (int i = 0; i < 18; ++i) my_w[i] = 0.0;
   double Vg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // this record's share of V_p (packed upper triangle) and g_p
   if (tid < nrec) {
-    const int rix = H.rec0 + tid;
-    const uint32_t meta = A.rec_meta[rix];
-    my_meta = meta;
-    const int cam = A.rec_cam[rix];
+    // batch 2, indexed by the record's contents: landmark, scales, pt_kv, the depth triple; the camera row follows in linearize_record
+    const uint32_t meta = my_meta;
     const int lcam = meta & 0xff;
     const int lpt = (meta >> 8) & 0xff;
-    const double2 xy = reinterpret_cast<const double2*>(A.rec_xy)[rix];
-    double d = 1.0, m = 0.0, a = 1.0;
-    if (meta & kRecHasDepth) { d = A.rec_d[rix]; m = A.rec_m[rix]; a = A.rec_a[rix]; }
     const int pix = H.pt0 + lpt;
     const double X[3] = {pts_at[3 * pix], pts_at[3 * pix + 1], pts_at[3 * pix + 2]};
     const double psc[3] = {A.ps[3 * pix], A.ps[3 * pix + 1], A.ps[3 * pix + 2]};
+    my_kv = A.pt_kv[pix];
+    double d = 1.0, m = 0.0, a = 1.0;
+    if (meta & kRecHasDepth) { const int rix = H.rec0 + tid; d = A.rec_d[rix]; m = A.rec_m[rix]; a = A.rec_a[rix]; }
+    my_ps[0] = psc[0]; my_ps[1] = psc[1]; my_ps[2] = psc[2];
     RecLin L;
     if (trace) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); trace[10] = (long long)clock64(); }  // the record / landmark loads have landed (the camera row follows)
     linearize_record(camera_row<kLocal>(camtab_at, l_tab, S.slot, cam, lcam), X, psc, meta, xy.x, xy.y, d, m, a, A.loss, L);
@@ -370,8 +396,7 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
   if (tid < nrec) {
     const int lcam = my_meta & 0xff;
     const int lpt = (my_meta >> 8) & 0xff;
-    const uint16_t kv = A.pt_kv[H.pt0 + lpt];
-    if (kv != 0xffff) {  // variable landmark
+    if (my_kv != 0xffff) {  // variable landmark
       double V[6], F[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) V[k] = S.V[lpt * 6 + k];
@@ -388,7 +413,7 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
       // (a landmark whose records straddle two waves reports twice: the maximum and the invalid flag do not mind)
       if (first) {
         if (!okf) my_bad = 1;
-        const double p0 = A.ps[3 * (H.pt0 + lpt)], p1 = A.ps[3 * (H.pt0 + lpt) + 1], p2 = A.ps[3 * (H.pt0 + lpt) + 2];
+        const double p0 = my_ps[0], p1 = my_ps[1], p2 = my_ps[2];
         my_gmax = fmax(fabs(g0 / p0), fmax(fabs(g1 / p1), fabs(g2 / p2)));
         if (A.pt_fac) {  // the update sweep of this iteration starts from F and g_p (F[0] == 0: not factored)
           double* o = A.pt_fac + (size_t)9 * (H.pt0 + lpt);

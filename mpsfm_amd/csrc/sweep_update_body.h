@@ -26,42 +26,62 @@ struct UpdLdsT {
 //      model cost change and the candidate cost follow in the same registers
 // kHandoff: the dense track sweep of the same iteration — same state, same radius — has left the factor F and g_p of every
 // variable landmark in A.pt_fac.  Step 1 then only sums W^T y_c (three values through the scan and the LDS adds, no V), and step 2
-// starts from the nine doubles of the record's landmark, requested behind the linearisation and in front of the scan and the first
-// barrier (beside the record loads they are 12 more registers at the pressure peak: 119 against 107, and 0.6 us); F[0] > 0 marks a
-// valid factor.
+// starts from the nine doubles of the record's landmark, requested behind the linearisation and in front of the scan and the second
+// barrier (beside the record loads they are 12 more registers at the pressure peak, and 0.6 us); F[0] > 0 marks a valid factor.
+// Entry: the chunk header and, in the launch chain, `term` of the control block are requested together; the camera list and the
+// records follow from the header alone and are in flight while `term` is tested (in front of the first store), workgroup 0 runs the
+// fused camera update and LDS is cleared.  Behind the first barrier the candidate lanes (fused camera update) and the records
+// request their operands side by side.  117 / 119 registers (hand-off / recompute), four workgroups per CU.
 template <bool kLocal, bool kHandoff>
 __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, double lm_radius, const double* l_tab, const double* l_tab2,
                                                    const double* yc, UpdLdsT<kHandoff>& S, const CamUpdArgs& U, bool fuse) {
   constexpr int NV = kHandoff ? 3 : 9;  // sums per record: [V_p (6),] g (3)
   const int tid = thread_index<kLocal>();
+  // ---- entry: two batches of loads instead of a chain of dependent trips ---------------------------------------------------------------
+  // batch 0: the chunk header, and behind it (vector loads return in order: the header must not wait for a block that comes all the
+  // way from memory) the control block (launch chain only, see lm_term_chain)
   const ChunkHdr H = A.chunks[cix];
+  [[maybe_unused]] int32_t term = kLmRunning;
+  if constexpr (!kLocal) {
+    term = lm_term_chain(A.ctl, A.chunks);
+    if constexpr (!kHandoff) lm_radius = lm_radius_chain(A.ctl, A.chunks, lm_radius);  // (the hand-off brings the damped factors)
+  }
   const int nrec = H.nrec, npt = H.npt, ncam = H.ncam;
+  // batch 1, from the header alone: the camera list and the chunk's records.  Fused camera update: the candidate rows are formed by
+  // the LAST lanes of the workgroup (they hold a record only in a chunk of more than kThreads - kDenseCams records), which ask for
+  // their camera's slot here as well
+  constexpr int kCandTid0 = kThreads - kDenseCams;
+  const bool cand_lane = !kLocal && fuse && tid >= kCandTid0 && tid - kCandTid0 < ncam;
+  // A lane without a record (camera) keeps its guard but takes no branch: it reads the head of the chunk table, which is always
+  // readable, and drops the value.  With a branch around the requests the compiler counts the loads in flight for the path that
+  // skips them, and the wait for `term` below becomes a wait for the records.
+  const bool has_rec = tid < nrec;
+  const int32_t my_slot = *(tid < ncam ? &A.chunk_cams[H.cam0 + tid] : reinterpret_cast<const int32_t*>(A.chunks));
+  [[maybe_unused]] int32_t cand_slot = 0;
+  if constexpr (!kLocal) cand_slot = *(cand_lane ? &A.chunk_cams[H.cam0 + tid - kCandTid0] : reinterpret_cast<const int32_t*>(A.chunks));
+  uint32_t meta = *(has_rec ? &A.rec_meta[H.rec0 + tid] : reinterpret_cast<const uint32_t*>(A.chunks));
+  int cam = *(has_rec ? &A.rec_cam[H.rec0 + tid] : reinterpret_cast<const int32_t*>(A.chunks));
+  int lpt = 0;
+  double2 xy = *(has_rec ? &reinterpret_cast<const double2*>(A.rec_xy)[H.rec0 + tid] : reinterpret_cast<const double2*>(A.chunks));
+  // the solve is over (the iteration queued ahead of the news): leave before the first global store
+  if constexpr (!kLocal) {
+    if (A.ctl != nullptr && lm_over_chain(term)) return;
+    if (fuse && cix == 0) cam_update_all(U, yc, S.red);  // workgroup 0 does what k_cam_update does for all cameras
+  }
   if constexpr (!kHandoff) for (int i = tid; i < npt * 6; i += kThreads) S.V[i] = 0.0;
   for (int i = tid; i < npt * 3; i += kThreads) S.g[i] = 0.0;
-  if (tid < ncam) {
-    const int slot = A.chunk_cams[H.cam0 + tid];
-    S.slot[tid] = slot;
-    if constexpr (!kLocal) {
-      if (fuse && tid < kDenseCams) {  // the candidate row of local camera `tid`: the arithmetic of cam_update_all, so that the cost below is
-        const int i = U.cam_of_slot[slot];  // evaluated at exactly the pose workgroup 0 writes out
-        const double qq[4] = {U.q[4 * i], U.q[4 * i + 1], U.q[4 * i + 2], U.q[4 * i + 3]};
-        const double tt[3] = {U.t[3 * i], U.t[3 * i + 1], U.t[3 * i + 2]};
-        double qn[4], tn[3], s0 = 0.0, s1 = 0.0, s2 = 0.0;
-        camera_candidate(qq, tt, U.cs + 6 * i, yc + (size_t)slot * 6, nullptr, qn, tn, s0, s1, s2);
-        double* o = &S.cand[tid * 16];
-        quat_to_R(qn, o);
-        o[9] = tn[0]; o[10] = tn[1]; o[11] = tn[2];
-        const double* K = U.intr + 4 * U.intr_idx[i];
-        o[12] = K[0]; o[13] = K[1]; o[14] = K[2]; o[15] = K[3];
-      }
-    }
-  }
+  if (tid < ncam) S.slot[tid] = my_slot;
+  [[maybe_unused]] int cand_cam = 0;  // (lands under the barrier)
+  if constexpr (!kLocal) cand_cam = *(cand_lane ? &U.cam_of_slot[cand_slot] : reinterpret_cast<const int32_t*>(A.chunks));
   __syncthreads();
+  // (nothing derived from the records is to be computed, and so waited for, in front of the barrier: the clears run under their trip)
+  asm volatile("" : "+v"(meta), "+v"(cam));
+  if (!has_rec) meta = 0;
+  // (the candidate camera's index is waited for here by every lane: a load left pending on the lanes that skip the requests below
+  // would make the compiler wait for ALL loads in flight at the first reuse of its register)
+  if constexpr (!kLocal) asm volatile("" : "+v"(cand_cam));
 
   RecUpd L;
-  uint32_t meta = 0;
-  int cam = 0, lpt = 0;
-  double2 xy = {0, 0};
   double d = 1.0, m = 0.0, a = 1.0;
   double X[3] = {0, 0, 0}, psc[3] = {0, 0, 0};
   bool ok = true, variable = false;
@@ -69,18 +89,46 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
 #pragma unroll
   for (int k = 0; k < NV; ++k) Vg[k] = 0.0;
   double fac[kHandoff ? 9 : 1] = {};  // the landmark's F and g_p
+  // batch 2.  The candidate lanes first ask for what their camera's candidate row is made of (pose, scales, step, intrinsics), then
+  // every record for what its contents index: landmark, scales, pt_kv and the depth triple.  The two trips run side by side; the
+  // candidate rows, which are read behind the second barrier only (record_cost), are formed when both have landed.  The intrinsics
+  // come from the camera's row of the table at the linearisation point: k_build_camtab and cam_update_all copy them there from
+  // intr[4 intr_idx[i]] and nothing else writes them, so they are the same bits and the intr_idx -> intr trip is saved.
+  [[maybe_unused]] double cq[4], ct[3], ccs[6], cy[6], ck[4];
+  if constexpr (!kLocal) {
+    if (cand_lane) {
+      const int i = cand_cam;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { cq[k] = U.q[4 * i + k]; ck[k] = A.camtab[(size_t)i * kCamRec + 12 + k]; }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ct[k] = U.t[3 * i + k];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) { ccs[k] = U.cs[6 * i + k]; cy[k] = yc[(size_t)cand_slot * 6 + k]; }
+    }
+  }
   if (tid < nrec) {
     const int rix = H.rec0 + tid;
-    meta = A.rec_meta[rix];
-    cam = A.rec_cam[rix];
-    const int lcam = meta & 0xff;
     lpt = (meta >> 8) & 0xff;
-    xy = reinterpret_cast<const double2*>(A.rec_xy)[rix];
     if (meta & kRecHasDepth) { d = A.rec_d[rix]; m = A.rec_m[rix]; a = A.rec_a[rix]; }
     const int pix = H.pt0 + lpt;
     variable = A.pt_kv[pix] != 0xffff;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { X[k] = A.pts[3 * pix + k]; psc[k] = A.ps[3 * pix + k]; }
+  }
+  if constexpr (!kLocal) {
+    // the candidate row of local camera tid - kCandTid0: the arithmetic of cam_update_all, so that the cost below is evaluated at
+    // exactly the pose workgroup 0 writes out
+    if (cand_lane) {
+      double qn[4], tn[3], s0 = 0.0, s1 = 0.0, s2 = 0.0;
+      camera_candidate(cq, ct, ccs, cy, nullptr, qn, tn, s0, s1, s2);
+      double* o = &S.cand[(tid - kCandTid0) * 16];
+      quat_to_R(qn, o);
+      o[9] = tn[0]; o[10] = tn[1]; o[11] = tn[2];
+      o[12] = ck[0]; o[13] = ck[1]; o[14] = ck[2]; o[15] = ck[3];
+    }
+  }
+  if (tid < nrec) {
+    const int lcam = meta & 0xff;
     linearize_update(camera_row<kLocal>(A.camtab, l_tab, S.slot, cam, lcam), X, psc, meta, xy.x, xy.y, d, m, a, A.loss,
                      lcam != (int)kLcamConst ? yc + (size_t)S.slot[lcam] * 6 : nullptr, L);
     ok = L.ok;
