@@ -3,7 +3,7 @@
  *
  * These entry points are OUTSIDE the stable ABI of mpsfm_hip.h: the tests and the scripts under scripts/ call them, nothing
  * else should.  They may change or disappear without a change of MPSFM_ABI_VERSION.  The files that define them
- * (csrc/ba_debug.hip, csrc/dense_chol.hip, csrc/chol_plan.hip) include this header, so every definition is checked
+ * (csrc/ba_debug.hip, csrc/dense_chol.hip, csrc/chol_plan.hip, csrc/dev_resources.hip) include this header, so every definition is checked
  * against its declaration; mpsfm_amd/abi.py declares the same signatures for ctypes (tests/test_abi_cpu.py compares).
  */
 #ifndef MPSFM_HIP_DEBUG_H
@@ -52,6 +52,8 @@ int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* o
 int mpsfm_debug_local_clocks(mpsfm_ba_handle* h, int64_t out[12]);
 /* in every single-launch solve from now on workgroup `chunk` waits `ticks` (at most 200000) at each phase point of `phase_mask` (bits 0-4); (0, 0, 0): off */
 int mpsfm_debug_local_skew(int32_t chunk, int32_t phase_mask, int64_t ticks);
+/* what the process holds of `device`'s caches: live device blocks, their bytes, and the pooled streams, events and pinned blocks handed out and not yet given back */
+int mpsfm_debug_resources(int32_t device, int64_t out[5]);
 
 #ifdef __cplusplus
 }

@@ -442,6 +442,7 @@ DEBUG_SIGNATURES = {
     "mpsfm_debug_host_build": (I64, [P, I32, P, I64]),
     "mpsfm_debug_local_clocks": (C.c_int, [P, P]),
     "mpsfm_debug_local_skew": (C.c_int, [I32, I32, I64]),
+    "mpsfm_debug_resources": (C.c_int, [I32, P]),
 }
 
 

@@ -225,6 +225,13 @@ def debug_panel_factor(dx: np.ndarray, waves: int = 4):
     return out, bool(ok.value)
 
 
+def debug_resources(device: int = 0) -> tuple:
+    """(live device blocks, their bytes, outstanding pooled streams, events, pinned blocks) of this process on `device`."""
+    out = np.zeros(5, np.int64)
+    _check(lib().mpsfm_debug_resources(int(device), out.ctypes.data))
+    return tuple(int(v) for v in out)
+
+
 def triangulate_tracks(tr: Tracks, device: int = 0) -> np.ndarray:
     xyz = np.zeros((tr.n_tracks, 3))
     ct = tr.c_tracks()

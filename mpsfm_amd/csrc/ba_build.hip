@@ -17,28 +17,8 @@ void free_handle(mpsfm_ba_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   // Error returns of the solve (a failing all-reduce hook, a HIP error) and reset_state + destroy leave copies and
-  // kernels in flight: both streams must be idle before the blocks go back to the process-wide cache, where a
-  // handle on another stream or host thread may receive them at once.
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->ov.s2) (void)hipStreamSynchronize(h->ov.s2);
-  void* ptrs[] = {h->d_q, h->d_t, h->d_q2, h->d_t2, h->d_q0, h->d_t0, h->d_pts, h->d_pts2, h->d_pts0, h->d_pt_fac, h->d_intr, h->d_cmask,
-                  h->d_cs, h->d_camtab, h->d_camtab2, h->d_intr_idx, h->d_cam_slot, h->d_ps, h->d_diagV, h->d_chunks,
-                  h->d_chunk_cams, h->d_blk_ent_start, h->d_blk_desc, h->d_ents, h->d_red, h->d_part, h->d_part2, h->d_scal, h->d_costpart, h->d_A, h->d_yc, h->d_dwork, h->d_fail, h->d_lhdr, h->d_wl, h->d_slab, h->d_red_dests, h->d_red_srcs,
-                  h->d_sky_first, h->d_sky_start, h->d_sky_index,
-                  h->d_local_acc, h->d_local_sync, h->d_local_log, h->d_perm, h->d_user_pts, h->d_cam_of_slot,
-                  h->d_lp_items, h->d_lp_heads, h->d_lp_srcs, h->d_lp_rows, h->d_lp_struct_start, h->d_lp_struct_rows, h->d_lp_back_cols, h->d_lp_asm, h->d_lp_live, h->d_lp_col_slot};
-  for (void* p : ptrs) cached_free(p);
-  h->rt.release();
+  // kernels in flight: h->own waits for both streams before anything goes back to the process-wide caches.
   comm_destroy(h->comm);
-  release_pinned(h->h_scal);
-  release_pinned(h->h_ctl);
-  cached_free(h->d_ctl);
-  for (auto& e : h->ev2) release_event(e, true);
-  for (auto& e : h->ev) release_event(e, true);
-  for (auto& e : h->ov.evF) release_event(e, false);
-  for (auto& e : h->ov.evB) release_event(e, false);
-  release_stream(h->ov.s2);
-  if (h->own_stream) release_stream(h->stream);
   delete h;
 }
 
@@ -74,19 +54,20 @@ void level_plan_flags(const CholPlan& PL, LevelPlanDev& D) { D.valid = PL.nt >= 
 // the block pattern of S and the tables of the level-scheduled factorisation (h->spat, h->plan) to the device
 static int upload_pattern(mpsfm_ba_handle* h, bool use_graph) {
   const CholPlan& PL = h->plan;
-  if (int rc = use_graph ? dev_upload(&h->d_sky_index, h->spat.sky_index) : dev_upload(&h->d_sky_first, h->spat.sky_first, &h->d_sky_start, h->spat.sky_start))
+  DeviceBlocks& own = h->own;
+  h->sky.ns = h->ncv;
+  if (int rc = use_graph ? own.upload(&h->sky.index, h->spat.sky_index) : own.upload(&h->sky.first, h->spat.sky_first, &h->sky.start, h->spat.sky_start))
     return rc;
   std::vector<uint8_t> live((size_t)(PL.nt + 1) * (size_t)(PL.nt + 2) / 2, 0);
   for (int32_t id : PL.asm_tiles) live[(size_t)id] = 1;
-  if (int rc = dev_upload(&h->d_lp_items, PL.items, &h->d_lp_heads, PL.heads, &h->d_lp_srcs, PL.srcs, &h->d_lp_rows, PL.rows, &h->d_lp_struct_start, PL.struct_start,
-                          &h->d_lp_struct_rows, PL.struct_rows, &h->d_lp_back_cols, PL.back_cols, &h->d_lp_asm, PL.asm_tiles,
-                          &h->d_lp_col_slot, PL.slot_of_col, &h->d_lp_live, live))
-    return rc;
   LevelPlanDev& D = h->lp;
+  if (int rc = own.upload(&D.d_items, PL.items, &D.d_heads, PL.heads, &D.d_srcs, PL.srcs, &D.d_rows, PL.rows, &D.d_struct_start, PL.struct_start,
+                          &D.d_struct_rows, PL.struct_rows, &D.d_back_cols, PL.back_cols, &D.d_asm_tiles, PL.asm_tiles,
+                          &D.d_col_slot, PL.slot_of_col, &D.d_tile_live, live))
+    return rc;
+  if (PL.slot_of_col.empty()) D.d_col_slot = nullptr;  // no indirection (the block stays with the handle)
   level_plan_flags(PL, D);
-  D.d_items = h->d_lp_items; D.d_heads = h->d_lp_heads; D.d_srcs = h->d_lp_srcs; D.d_rows = h->d_lp_rows;
-  D.d_struct_start = h->d_lp_struct_start; D.d_struct_rows = h->d_lp_struct_rows; D.d_back_cols = h->d_lp_back_cols;
-  D.d_asm_tiles = h->d_lp_asm; D.d_tile_live = h->d_lp_live; D.d_col_slot = PL.slot_of_col.empty() ? nullptr : h->d_lp_col_slot; D.n_asm = (int32_t)PL.asm_tiles.size(); D.nlevels = PL.nlevels;
+  D.n_asm = (int32_t)PL.asm_tiles.size(); D.nlevels = PL.nlevels;
   D.h_launch_start = PL.launch_start.data(); D.h_back_start = PL.back_start.data();
   return 0;
 }
@@ -154,13 +135,6 @@ static void print_chunk_stats(const std::vector<ChunkHdr>& chunks) {
   std::fprintf(stderr, "\n");
 }
 
-// the record and fixed-record tables of the host build to the device
-static int upload_record_tables(HostTables& T, RecTablesDev& rt) {
-  return dev_upload(&rt.rec_cam, T.rec_cam, &rt.rec_pt, T.rec_pt, &rt.rec_meta, T.rec_meta, &rt.rec_xy, T.rec_xy, &rt.rec_d, T.rec_d, &rt.rec_m, T.rec_m,
-                    &rt.rec_a, T.rec_a, &rt.pt_rec_start, T.pt_rec_start, &rt.pt_kv, T.pt_kv, &rt.fx_cam, T.fx_cam, &rt.fx_pt, T.fx_pt,
-                    &rt.fx_meta, T.fx_meta, &rt.fx_xy, T.fx_xy, &rt.fx_d, T.fx_d, &rt.fx_m, T.fx_m, &rt.fx_a, T.fx_a);
-}
-
 // Everything the solve reads to the device.  `DB`: the device build's output (T is its host part) or, after a host build, empty;
 // `devb` forms the slab reduction tables on the device when `R` came without them (R.dests empty, R.diag_block set).
 static int upload_tables(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const CameraLayout& cams, DevBuildOut& DB, SlabTables& R, DevBuilder* devb,
@@ -168,39 +142,44 @@ static int upload_tables(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const Ca
   HostTables& T = DB.t;
   const int nc = P->n_cams;
   int rc = 0;
+  DeviceBlocks& own = h->own;
   std::vector<double> intr(P->cam_intr, P->cam_intr + (size_t)P->n_intr * 4);
   std::vector<int32_t> intr_idx(P->cam_intr_idx, P->cam_intr_idx + nc);
-  if ((rc = dev_upload(&h->d_intr, intr, &h->d_intr_idx, intr_idx, &h->d_cmask, cams.cmask, &h->d_cam_slot, h->cam_slot_h,
+  if ((rc = own.upload(&h->d_intr, intr, &h->d_intr_idx, intr_idx, &h->d_cmask, cams.cmask, &h->d_cam_slot, h->cam_slot_h,
                        &h->d_cam_of_slot, cam_of_slot_table(cams), &h->d_chunks, T.chunks, &h->d_chunk_cams, T.chunk_cams)))
     return rc;
   if (h->np > 0 && h->np == (int64_t)h->np_user) {
-    if ((rc = dev_upload(&h->d_perm, h->perm))) return rc;
-    if ((rc = dev_alloc(&h->d_user_pts, (size_t)h->np * 3))) return rc;
+    if ((rc = own.upload(&h->d_perm, h->perm))) return rc;
+    if ((rc = own.alloc(&h->d_user_pts, (size_t)h->np * 3))) return rc;
   }
   if (h->built_on_device) {  // the device build's tables are where they belong
     h->rt = DB.rt;
-    DB.rt = RecTablesDev{};
-    DB.release();  // the device copies of chunks / camera lists: the host copies (slab offsets added) are uploaded above
-  } else if ((rc = upload_record_tables(T, h->rt))) return rc;
-  if ((rc = dev_upload(&h->d_lhdr, T.lhdr))) return rc;
-  if ((rc = dev_alloc(&h->d_wl, (size_t)std::max<int64_t>(T.wl_rows, 1) * 18))) return rc;
+    own.adopt(std::move(DB.own));
+    own.drop(DB.d_chunks); own.drop(DB.d_chunk_cams);  // the host copies (slab offsets added) are uploaded above; the stream is idle
+  } else {  // the host build's record and fixed-record tables
+    RecTablesDev& rt = h->rt;
+    if ((rc = own.upload(&rt.rec_cam, T.rec_cam, &rt.rec_pt, T.rec_pt, &rt.rec_meta, T.rec_meta, &rt.rec_xy, T.rec_xy, &rt.rec_d, T.rec_d, &rt.rec_m, T.rec_m,
+                         &rt.rec_a, T.rec_a, &rt.pt_rec_start, T.pt_rec_start, &rt.pt_kv, T.pt_kv, &rt.fx_cam, T.fx_cam, &rt.fx_pt, T.fx_pt,
+                         &rt.fx_meta, T.fx_meta, &rt.fx_xy, T.fx_xy, &rt.fx_d, T.fx_d, &rt.fx_m, T.fx_m, &rt.fx_a, T.fx_a)))
+      return rc;
+  }
+  if ((rc = own.upload(&h->d_lhdr, T.lhdr))) return rc;
+  if ((rc = own.alloc(&h->d_wl, (size_t)std::max<int64_t>(T.wl_rows, 1) * 18))) return rc;
   h->n_blk_desc = (int64_t)T.blk_desc.size(); h->n_blk_ent_start = (int64_t)T.blk_ent_start.size(); h->n_ents = (int64_t)T.ents.size();
-  if ((rc = dev_upload(&h->d_blk_desc, T.blk_desc, &h->d_blk_ent_start, T.blk_ent_start, &h->d_ents, T.ents))) return rc;
+  if ((rc = own.upload(&h->d_blk_desc, T.blk_desc, &h->d_blk_ent_start, T.blk_ent_start, &h->d_ents, T.ents))) return rc;
   int32_t* d_diag_block = nullptr;
   if (!slab_tables_on_device) {
-    if ((rc = dev_upload(&h->d_red_dests, R.dests, &h->d_red_srcs, R.srcs))) return rc;
-  } else if ((rc = dev_upload(&d_diag_block, R.diag_block))) return rc;
-  if ((rc = dev_alloc(&h->d_slab, (size_t)std::max<int64_t>(R.slab_units, 1) * 18))) return rc;
+    if ((rc = own.upload(&h->d_red_dests, R.dests, &h->d_red_srcs, R.srcs))) return rc;
+  } else if ((rc = own.upload(&d_diag_block, R.diag_block))) return rc;
+  if ((rc = own.alloc(&h->d_slab, (size_t)std::max<int64_t>(R.slab_units, 1) * 18))) return rc;
 
-  if ((rc = staged_drain())) { cached_free(d_diag_block); return rc; }
+  if ((rc = staged_drain())) return rc;
   if (slab_tables_on_device) {
-    const BlockSky sky{h->d_sky_first, h->d_sky_start, h->d_sky_index, h->ncv};
-    int32_t nd = 0; int64_t ns = 0;
-    rc = devb->slab_tables(h->d_chunks, h->n_dense, h->d_chunk_cams, sky, h->spat.nblk, h->ncv, d_diag_block, &h->d_red_dests, &nd, &h->d_red_srcs, &ns);
+    if ((rc = devb->slab_tables(h->d_chunks, h->n_dense, h->d_chunk_cams, h->sky, h->spat.nblk, h->ncv, d_diag_block, own, &h->d_red_dests, &h->n_red_dests,
+                                &h->d_red_srcs, &h->n_red_srcs)))
+      return rc;
     MPSFM_TRY(hipStreamSynchronize(h->stream));  // d_diag_block goes back to the process-wide cache
-    cached_free(d_diag_block);
-    if (rc) return rc;
-    h->n_red_dests = nd; h->n_red_srcs = ns;
+    own.drop(d_diag_block);
   }
   return 0;
 }
@@ -208,51 +187,52 @@ static int upload_tables(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const Ca
 // state, reduced system, dense workspace, scalars, events; the single-launch solver's buffers where it applies
 static int alloc_work_buffers(mpsfm_ba_handle* h, const BuildOptions& opt) {
   int rc = 0;
+  DeviceBlocks& own = h->own;
   const size_t ncs = (size_t)std::max(h->nc, 1), nps = (size_t)std::max<int64_t>(h->np, 1);
-  for (double** p : {&h->d_q, &h->d_q2, &h->d_q0}) if ((rc = dev_alloc(p, ncs * 4))) return rc;
-  for (double** p : {&h->d_t, &h->d_t2, &h->d_t0}) if ((rc = dev_alloc(p, ncs * 3))) return rc;
-  for (double** p : {&h->d_pts, &h->d_pts2, &h->d_pts0, &h->d_ps, &h->d_diagV}) if ((rc = dev_alloc(p, nps * 3))) return rc;
+  for (double** p : {&h->d_q, &h->d_q2, &h->d_q0}) if ((rc = own.alloc(p, ncs * 4))) return rc;
+  for (double** p : {&h->d_t, &h->d_t2, &h->d_t0}) if ((rc = own.alloc(p, ncs * 3))) return rc;
+  for (double** p : {&h->d_pts, &h->d_pts2, &h->d_pts0, &h->d_ps, &h->d_diagV}) if ((rc = own.alloc(p, nps * 3))) return rc;
   // every chunk dense, no long track (fused_prologue's condition in solve_impl): the track sweep hands the landmark factors on
-  if (h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks) if ((rc = dev_alloc(&h->d_pt_fac, nps * 9))) return rc;
-  if ((rc = dev_alloc(&h->d_cs, ncs * 6))) return rc;
-  if ((rc = dev_alloc(&h->d_camtab, ncs * kCamRec))) return rc;
-  if ((rc = dev_alloc(&h->d_camtab2, ncs * kCamRec))) return rc;
+  if (h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks) if ((rc = own.alloc(&h->d_pt_fac, nps * 9))) return rc;
+  if ((rc = own.alloc(&h->d_cs, ncs * 6))) return rc;
+  if ((rc = own.alloc(&h->d_camtab, ncs * kCamRec))) return rc;
+  if ((rc = own.alloc(&h->d_camtab2, ncs * kCamRec))) return rc;
   h->sblk_count = h->spat.nblk * 36;
   h->red_count = h->sblk_count + 3 * (int64_t)h->n_user + SC_COUNT;
-  if ((rc = dev_alloc(&h->d_red, (size_t)h->red_count))) return rc;
+  if ((rc = own.alloc(&h->d_red, (size_t)h->red_count))) return rc;
   h->d_Sblk = h->d_red; h->d_gc = h->d_red + h->sblk_count; h->d_wv = h->d_gc + h->n_user; h->d_diagU = h->d_wv + h->n_user;
   h->d_redsc = h->d_diagU + h->n_user;
-  if ((rc = dev_alloc(&h->d_part, (size_t)std::max(h->nchunks + h->nlong, 1) * 4 * 2))) return rc;  // (second half: the single launch's odd iterations)
-  if ((rc = dev_alloc(&h->d_part2, (size_t)std::max(h->nchunks + h->nlong, 1) * 8))) return rc;
-  if ((rc = dev_alloc(&h->d_scal, (size_t)U_COUNT))) return rc;
-  if ((rc = dev_alloc(&h->d_costpart, (size_t)1024 * 4))) return rc;
+  if ((rc = own.alloc(&h->d_part, (size_t)std::max(h->nchunks + h->nlong, 1) * 4 * 2))) return rc;  // (second half: the single launch's odd iterations)
+  if ((rc = own.alloc(&h->d_part2, (size_t)std::max(h->nchunks + h->nlong, 1) * 8))) return rc;
+  if ((rc = own.alloc(&h->d_scal, (size_t)U_COUNT))) return rc;
+  if ((rc = own.alloc(&h->d_costpart, (size_t)1024 * 4))) return rc;
   static_assert(sizeof(double) * U_COUNT * 2 <= kPinnedBytes, "pinned scalar block too small");
-  MPSFM_TRY(pooled_pinned((void**)&h->h_scal));
+  MPSFM_TRY(own.pinned((void**)&h->h_scal));
   static_assert(sizeof(LmCtl) * 2 <= kPinnedBytes, "pinned block too small for two control-block copies");
-  MPSFM_TRY(pooled_pinned((void**)&h->h_ctl));
-  if ((rc = dev_alloc(&h->d_ctl, 1))) return rc;
-  for (auto& e : h->ev2) MPSFM_TRY(pooled_event(&e, true));
+  MPSFM_TRY(own.pinned((void**)&h->h_ctl));
+  if ((rc = own.alloc(&h->d_ctl, 1))) return rc;
+  for (auto& e : h->ev2) MPSFM_TRY(own.event(&e, true));
   const size_t ntiles = (size_t)(h->nt + 1) * (h->nt + 2) / 2;
-  if ((rc = dev_alloc(&h->d_A, ntiles * 1024))) return rc;
-  if ((rc = dev_alloc(&h->d_dwork, dense_work_doubles(h->nt)))) return rc;
-  if ((rc = dev_alloc(&h->d_yc, (size_t)std::max(h->n_user, 1)))) return rc;
-  if ((rc = dev_alloc(&h->d_fail, 1))) return rc;
+  if ((rc = own.alloc(&h->d_A, ntiles * 1024))) return rc;
+  if ((rc = own.alloc(&h->d_dwork, dense_work_doubles(h->nt)))) return rc;
+  if ((rc = own.alloc(&h->d_yc, (size_t)std::max(h->n_user, 1)))) return rc;
+  if ((rc = own.alloc(&h->d_fail, 1))) return rc;
   MPSFM_TRY(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));
-  for (auto& e : h->ev) MPSFM_TRY(pooled_event(&e, true));
+  for (auto& e : h->ev) MPSFM_TRY(own.event(&e, true));
   opt.apply_dense(h->nt, h->plan, h->ov);
   if (h->nt > 64 || h->ov.nb > 0) {
-    MPSFM_TRY(pooled_stream(&h->ov.s2));
-    for (auto& e : h->ov.evF) MPSFM_TRY(pooled_event(&e, false));
-    for (auto& e : h->ov.evB) MPSFM_TRY(pooled_event(&e, false));
+    MPSFM_TRY(own.stream(&h->ov.s2));
+    for (auto& e : h->ov.evF) MPSFM_TRY(own.event(&e, false));
+    for (auto& e : h->ov.evB) MPSFM_TRY(own.event(&e, false));
   }
   // Small problems (local bundle adjustment): the whole trust-region loop in one cooperative launch, one workgroup per chunk
   h->local_ok = false;
   if (opt.local_lm && !sharded(h) && h->nlong == 0 && h->nchunks > 0 && h->n_dense == h->nchunks && h->ncv >= 1 && h->ncv <= kLocalCams &&
       h->n_user == 6 * h->ncv && h->nchunks <= local_lm_max_chunks(h->device)) {
     h->local_log_cap = std::max(h->opt.max_num_iterations, 0) + 2;
-    if ((rc = dev_alloc(&h->d_local_acc, (size_t)2 * kLocalAccDoubles))) return rc;
-    if ((rc = dev_alloc(&h->d_local_sync, (size_t)16))) return rc;
-    if ((rc = dev_alloc(&h->d_local_log, (size_t)h->local_log_cap))) return rc;
+    if ((rc = own.alloc(&h->d_local_acc, (size_t)2 * kLocalAccDoubles))) return rc;
+    if ((rc = own.alloc(&h->d_local_sync, (size_t)16))) return rc;
+    if ((rc = own.alloc(&h->d_local_log, (size_t)h->local_log_cap))) return rc;
     h->local_ok = true;
   }
   MPSFM_TRY(hipMemsetAsync(h->d_ps, 0, nps * 3 * sizeof(double), h->stream));
@@ -312,7 +292,6 @@ int build_tables(const mpsfm_ba_problem* P, BuildOptions& opt, const SumExchange
     if (rc2 < 0) return rc2;
     if (rc2 == MPSFM_DEVBUILD_FALLBACK) {
       // long tracks: the host phases run after all — the grouping first, which was skipped (depths were validated by stage 1)
-      out.tables.release();
       dev = false;
       if (int rc = group_blocks_by_landmark(P, false, groups)) return rc;
       lap("device build not applicable: host phases");
@@ -460,11 +439,8 @@ int create_impl(const mpsfm_ba_problem* P, const mpsfm_ba_state* st, const mpsfm
   MPSFM_TRY(hipSetDevice(o->device));
   mpsfm_ba_handle* h = new mpsfm_ba_handle();
   h->device = o->device; h->opt = *o;
-  if (o->stream) { h->stream = (hipStream_t)o->stream; h->own_stream = false; }
-  else {
-    if (pooled_stream(&h->stream) != hipSuccess) { delete h; return fail(MPSFM_EHIP, "hipStreamCreate failed"); }
-    h->own_stream = true;
-  }
+  if (o->stream) { h->stream = (hipStream_t)o->stream; h->own.idle_first(h->stream); }
+  else if (h->own.stream(&h->stream) != hipSuccess) { delete h; return fail(MPSFM_EHIP, "hipStreamCreate failed"); }
   if (o->use_rccl && o->world_size >= 1) {
     if (int rc = comm_init_rank(h)) { free_handle(h); return rc; }
     since("ncclCommInitRank");

@@ -66,14 +66,14 @@ void comm_destroy(void* comm) {
 int allreduce_host(mpsfm_ba_handle* h, double* buf, int64_t count) {
   if (count <= 0) return 0;
   if (h->comm) {  // host values travel through a device scratch block
-    double* d = (double*)cached_malloc(sizeof(double) * (size_t)count);
+    DeviceBlocks scratch;  // waits for the stream on every return: `buf` is complete and the block is free to go back
+    scratch.idle_first(h->stream);
+    double* d = scratch.alloc<double>((size_t)count);
     if (!d) return fail(MPSFM_ENOMEM, "hipMalloc failed");
     int rc = 0;
     if (hipMemcpyAsync(d, buf, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = fail(MPSFM_EHIP, "hipMemcpyAsync failed");
     if (!rc) rc = rccl_allreduce(h, d, count);
     if (!rc && hipMemcpyAsync(buf, d, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = fail(MPSFM_EHIP, "hipMemcpyAsync failed");
-    (void)hipStreamSynchronize(h->stream);
-    cached_free(d);
     return rc;
   }
   if (!h->opt.allreduce) return 0;

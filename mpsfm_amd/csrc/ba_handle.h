@@ -13,24 +13,19 @@
 
 struct mpsfm_ba_handle {
   int device = 0;
-  hipStream_t stream = nullptr;
+  // every device block, event, pinned block and pooled stream below; waits for both streams before they go back.  The
+  // pointers of this struct are views into it.
+  mpsfm::DeviceBlocks own;
+  hipStream_t stream = nullptr;  // from `own`, or the caller's (mpsfm_ba_options::stream): waited for, never released
   void* comm = nullptr;  // ncclComm_t of a landmark-sharded run with use_rccl
   mpsfm::DenseOverlap ov;  // second stream for the dense factorisation in outer panels (MPSFM_CHOL_NB)
   mpsfm::SPattern spat;                    // which blocks of S exist: block skyline or index form (up to kIndexMaxSlots slots), host copies
-  int32_t* d_sky_first = nullptr;
-  int64_t* d_sky_start = nullptr;
-  int32_t* d_sky_index = nullptr;
+  mpsfm::BlockSky sky{nullptr, nullptr, nullptr, 0};  // the device copy
   mpsfm::CholPlan plan;                    // camera order, tile elimination tree and launch tables of the dense factorisation (chol_plan.h)
-  mpsfm::LevelPlanDev lp;
-  mpsfm::CholItem* d_lp_items = nullptr;
-  mpsfm::LevelHead* d_lp_heads = nullptr;
-  uint8_t* d_lp_live = nullptr;
-  int32_t* d_lp_col_slot = nullptr;
-  int32_t *d_lp_srcs = nullptr, *d_lp_rows = nullptr, *d_lp_struct_start = nullptr, *d_lp_struct_rows = nullptr, *d_lp_back_cols = nullptr, *d_lp_asm = nullptr;
+  mpsfm::LevelPlanDev lp;                  // the device copies of the plan's tables
   std::vector<int32_t> nat_slot;    // variable camera in the caller's order -> slot (the accessors of S and y speak the caller's order)
   int n_user = 0;                   // 6 x variable cameras: the reduced dimension the caller sees and the length of the slot-indexed vectors (n counts the
                                     // system's columns incl. the alignment padding)
-  bool own_stream = false;
   mpsfm_ba_options opt{};
   mpsfm::LossParams loss{};
   // sizes

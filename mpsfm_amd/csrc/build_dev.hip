@@ -601,11 +601,10 @@ struct DevBuilder::Impl {
   hipStream_t s = nullptr;
   int nc = 0, np = 0;
   int64_t n_obs = 0, n_dobs = 0, nblk = 0;
-  std::vector<void*> blocks;  // everything to give back
-  template <class T> T* alloc(size_t n) { T* p = (T*)cached_malloc(std::max<size_t>(n, 1) * sizeof(T)); if (p) blocks.push_back(p); return p; }
-  // rocPRIM calls with their temporary storage.  The block stays with the builder until its destructor has synchronised the
-  // stream: the caching allocator is process-wide, a block given back while the call is still queued could be handed to another
-  // host thread's handle at once and written from ITS stream (the hazard of DESIGN.md section 4b).
+  DeviceBlocks own;  // every temporary of the stages; it waits for the stream before they go back
+  template <class T> T* alloc(size_t n) { return own.alloc<T>(n); }
+  // rocPRIM calls with their temporary storage.  The block stays with the builder to its end: a block given back while the call
+  // is still queued could be handed to another host thread's handle at once (the hazard of DESIGN.md section 4b).
   template <class F>
   int with_temp(F&& f) {
     size_t bytes = 0;
@@ -626,16 +625,12 @@ struct DevBuilder::Impl {
 };
 
 DevBuilder::DevBuilder() : m(new Impl()) {}
-DevBuilder::~DevBuilder() {
-  if (m->s) (void)hipStreamSynchronize(m->s);  // the blocks go back to a process-wide cache
-  for (void* p : m->blocks) cached_free(p);
-  delete m;
-}
+DevBuilder::~DevBuilder() { delete m; }
 
 int DevBuilder::stage1(const mpsfm_ba_problem* P, hipStream_t stream, const std::vector<int32_t>& nat_slot, int ncv_real, std::vector<double>& cam_counts,
                        std::vector<uint64_t>& graph_bits, int graph_words, int64_t* max_blocks_per_landmark) {
   Impl& M = *m;
-  M.s = stream; M.nc = P->n_cams; M.np = P->n_pts; M.n_obs = P->n_obs; M.n_dobs = P->n_dobs; M.nblk = P->n_obs + P->n_dobs;
+  M.s = stream; M.own.idle_first(stream); M.nc = P->n_cams; M.np = P->n_pts; M.n_obs = P->n_obs; M.n_dobs = P->n_dobs; M.nblk = P->n_obs + P->n_dobs;
   if (M.nblk > (int64_t)INT_MAX / 2) return fail(MPSFM_EUNSUPPORTED, "device build: more than 2^30 residual blocks");
   const size_t no = (size_t)M.n_obs, nd = (size_t)M.n_dobs, np = (size_t)M.np, nc = (size_t)M.nc;
   M.obs_cam = M.alloc<int32_t>(no); M.obs_pt = M.alloc<int32_t>(no); M.obs_xy = M.alloc<double>(2 * no);
@@ -646,7 +641,7 @@ int DevBuilder::stage1(const mpsfm_ba_problem* P, hipStream_t stream, const std:
   M.err = M.alloc<int32_t>(4);
   M.bits = M.alloc<unsigned long long>((size_t)std::max(ncv_real, 1) * (size_t)std::max(graph_words, 1));
   if (P->shift_logscale) M.shift = M.alloc<double>(2 * nc);
-  for (void* p : M.blocks) if (!p) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  if (!M.own.ok()) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   int rc = 0;
   if (no) {
     if ((rc = staged_upload(M.obs_cam, P->obs_cam, 4 * no))) return rc;
@@ -833,10 +828,11 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   lap("chunk cut");
   const int nchunks = hb[0][nseg];
   int ncams = hb[1][nseg];
-  // ---- final tables (owned by the caller from here on)
-  auto own = [&](size_t bytes) { return cached_malloc(std::max<size_t>(bytes, 8)); };
+  // ---- final tables: they belong to `out`, which waits for this stream before it gives them back
+  DeviceBlocks& own = out.own;
+  own.idle_first(M.s);
   const size_t nr = (size_t)std::max(nrec_total, 1), nf = (size_t)std::max(n_fixed, 1), no = (size_t)std::max(n_order, 1);
-  out.d_chunks = (ChunkHdr*)own(sizeof(ChunkHdr) * (size_t)std::max(nchunks, 1));
+  out.d_chunks = own.alloc<ChunkHdr>((size_t)std::max(nchunks, 1));
   if (!out.d_chunks) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   unsigned long long* csets = nullptr;
   int32_t* cam0 = nullptr;
@@ -845,7 +841,7 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
     csets = M.alloc<unsigned long long>((size_t)nchunks * Wp);
     int32_t* cncam = M.alloc<int32_t>((size_t)nchunks + 1);
     cam0 = M.alloc<int32_t>((size_t)nchunks + 1);
-    if (!csets || !cncam || !cam0) { (void)hipStreamSynchronize(M.s); out.release(); return fail(MPSFM_ENOMEM, "hipMalloc failed"); }
+    if (!csets || !cncam || !cam0) return fail(MPSFM_ENOMEM, "hipMalloc failed");
     const unsigned gc = (unsigned)((nchunks + kT - 1) / kT);
     switch (Wp) {
       case 1: hipLaunchKernelGGL(k_chunk_sets<1>, dim3(gc), dim3(kT), 0, M.s, nchunks, np_chunked, nseg, cbase, starts, lmask, rec_off, hvk, out.d_chunks, cncam, csets); break;
@@ -855,20 +851,19 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
       default: hipLaunchKernelGGL(k_chunk_sets<16>, dim3(gc), dim3(kT), 0, M.s, nchunks, np_chunked, nseg, cbase, starts, lmask, rec_off, hvk, out.d_chunks, cncam, csets); break;
     }
     MPSFM_TRY(hipMemsetAsync(cncam + nchunks, 0, 4, M.s));
-    if ((rc = M.with_temp([&](void* t, size_t& sz) { return rocprim::exclusive_scan(t, sz, cncam, cam0, 0, (size_t)nchunks + 1, rocprim::plus<int32_t>(), M.s); }))) { (void)hipStreamSynchronize(M.s); out.release(); return rc; }
+    if ((rc = M.with_temp([&](void* t, size_t& sz) { return rocprim::exclusive_scan(t, sz, cncam, cam0, 0, (size_t)nchunks + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
     MPSFM_TRY(hipMemcpyAsync(&ncams, cam0 + nchunks, 4, hipMemcpyDeviceToHost, M.s));
     MPSFM_TRY(hipStreamSynchronize(M.s));
   }
-  out.d_chunk_cams = (int32_t*)own(4 * (size_t)std::max(ncams, 1));
-  out.rt.rec_cam = (int32_t*)own(4 * nr); out.rt.rec_pt = (int32_t*)own(4 * nr); out.rt.rec_meta = (uint32_t*)own(4 * nr);
-  out.rt.rec_xy = (double*)own(16 * nr); out.rt.rec_d = (double*)own(8 * nr); out.rt.rec_m = (double*)own(8 * nr); out.rt.rec_a = (double*)own(8 * nr);
-  out.rt.pt_rec_start = (int32_t*)own(4 * (no + 1)); out.rt.pt_kv = (uint16_t*)own(2 * (no + 1));
-  out.rt.fx_cam = (int32_t*)own(4 * nf); out.rt.fx_pt = (int32_t*)own(4 * nf); out.rt.fx_meta = (uint32_t*)own(4 * nf);
-  out.rt.fx_xy = (double*)own(16 * nf); out.rt.fx_d = (double*)own(8 * nf); out.rt.fx_m = (double*)own(8 * nf); out.rt.fx_a = (double*)own(8 * nf);
+  RecTablesDev& rt = out.rt;
+  out.d_chunk_cams = own.alloc<int32_t>((size_t)std::max(ncams, 1));
+  rt.rec_cam = own.alloc<int32_t>(nr); rt.rec_pt = own.alloc<int32_t>(nr); rt.rec_meta = own.alloc<uint32_t>(nr);
+  rt.rec_xy = own.alloc<double>(2 * nr); rt.rec_d = own.alloc<double>(nr); rt.rec_m = own.alloc<double>(nr); rt.rec_a = own.alloc<double>(nr);
+  rt.pt_rec_start = own.alloc<int32_t>(no + 1); rt.pt_kv = own.alloc<uint16_t>(no + 1);
+  rt.fx_cam = own.alloc<int32_t>(nf); rt.fx_pt = own.alloc<int32_t>(nf); rt.fx_meta = own.alloc<uint32_t>(nf);
+  rt.fx_xy = own.alloc<double>(2 * nf); rt.fx_d = own.alloc<double>(nf); rt.fx_m = own.alloc<double>(nf); rt.fx_a = own.alloc<double>(nf);
   unsigned long long* counters = M.alloc<unsigned long long>(2);
-  void* all[] = {out.d_chunks, out.d_chunk_cams, out.rt.rec_cam, out.rt.rec_pt, out.rt.rec_meta, out.rt.rec_xy, out.rt.rec_d, out.rt.rec_m, out.rt.rec_a, out.rt.pt_rec_start,
-                 out.rt.pt_kv, out.rt.fx_cam, out.rt.fx_pt, out.rt.fx_meta, out.rt.fx_xy, out.rt.fx_d, out.rt.fx_m, out.rt.fx_a, counters};
-  for (void* p : all) if (!p) { (void)hipStreamSynchronize(M.s); out.release(); return fail(MPSFM_ENOMEM, "hipMalloc failed"); }
+  if (!own.ok() || !counters) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   MPSFM_TRY(hipMemsetAsync(counters, 0, 16, M.s));
   if (nchunks > 0 && jump) {
     const unsigned gc = (unsigned)((nchunks + kT - 1) / kT);
@@ -903,14 +898,14 @@ int DevBuilder::stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, i
   MPSFM_TRY(hipMemcpyAsync(er, M.err, 16, hipMemcpyDeviceToHost, M.s));
   MPSFM_TRY(hipStreamSynchronize(M.s));
   lap("downloads");
-  if (er[0] & 2) { out.release(); return fail(MPSFM_EINVAL, "shifted/scaled depth prior must be positive"); }
+  if (er[0] & 2) return fail(MPSFM_EINVAL, "shifted/scaled depth prior must be positive");
   out.t.nblk_reduced = (int64_t)hc[0]; out.t.nvarpts = (double)hc[1];
   return 0;
 }
 
 // Reduction tables of the dense chunks' slabs from the device copies of the chunk headers (slab offsets set) and camera lists.
 int DevBuilder::slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t* d_chunk_cams, const BlockSky& sky, int64_t nsb, int ncv,
-                            const int32_t* d_diag_block, RedDest** d_dests, int32_t* n_dests, int32_t** d_srcs, int64_t* n_srcs) {
+                            const int32_t* d_diag_block, DeviceBlocks& own, RedDest** d_dests, int32_t* n_dests, int32_t** d_srcs, int64_t* n_srcs) {
   Impl& M = *m;
   *d_dests = nullptr; *d_srcs = nullptr; *n_dests = 0; *n_srcs = 0;
   if (n_dense <= 0) return 0;
@@ -936,34 +931,27 @@ int DevBuilder::slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t
   uint32_t* key = M.alloc<uint32_t>((size_t)n_ent);
   uint32_t* key_s = M.alloc<uint32_t>((size_t)n_ent);
   int32_t* val = M.alloc<int32_t>((size_t)n_ent);
-  int32_t* val_s = (int32_t*)cached_malloc(4 * (size_t)n_ent);  // becomes the source list: owned by the caller
-  if (!key || !key_s || !val || !val_s) { cached_free(val_s); return fail(MPSFM_ENOMEM, "hipMalloc failed"); }
-  auto bail = [&](int code) { (void)hipStreamSynchronize(M.s); cached_free(val_s); return code; };
+  int32_t* val_s = own.alloc<int32_t>((size_t)n_ent);  // becomes the source list
+  if (!key || !key_s || !val || !val_s) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   hipLaunchKernelGGL(k_slab_entries, dim3((unsigned)n_dense), dim3(64), 0, M.s, n_dense, d_chunks, d_chunk_cams, sky, nsb, ndst, ent0, key, val, cnt, M.err);
   hipLaunchKernelGGL(k_slab_mark_diag, dim3((unsigned)((ncv + kT - 1) / kT)), dim3(kT), 0, M.s, ncv, d_diag_block, nsb, is_diag);
   unsigned bits = 1;
   while ((1u << bits) <= (unsigned)ndst) ++bits;  // keys 0 .. ndst (ndst: no destination)
-  if ((rc = M.with_temp([&](void* t, size_t& sz) { return rocprim::radix_sort_pairs(t, sz, key, key_s, val, val_s, (size_t)n_ent, 0, bits, M.s); }))) return bail(rc);
-  if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, cnt, start, 0, (size_t)ndst + 1, rocprim::plus<int32_t>(), M.s); }))) return bail(rc);
+  if ((rc = M.with_temp([&](void* t, size_t& sz) { return rocprim::radix_sort_pairs(t, sz, key, key_s, val, val_s, (size_t)n_ent, 0, bits, M.s); }))) return rc;
+  if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, cnt, start, 0, (size_t)ndst + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
   hipLaunchKernelGGL(k_slab_part_counts, dim3((unsigned)((ndst + 1 + kT - 1) / kT)), dim3(kT), 0, M.s, ndst, cnt, nparts);
-  if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, nparts, pstart, 0, (size_t)ndst + 1, rocprim::plus<int32_t>(), M.s); }))) return bail(rc);
+  if ((rc = M.with_temp([&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, nparts, pstart, 0, (size_t)ndst + 1, rocprim::plus<int32_t>(), M.s); }))) return rc;
   int32_t tot[2] = {0, 0}, er[4] = {0, 0, 0, 0};
   if (hipMemcpyAsync(&tot[0], start + ndst, 4, hipMemcpyDeviceToHost, M.s) != hipSuccess || hipMemcpyAsync(&tot[1], pstart + ndst, 4, hipMemcpyDeviceToHost, M.s) != hipSuccess ||
       hipMemcpyAsync(er, M.err, 16, hipMemcpyDeviceToHost, M.s) != hipSuccess || hipStreamSynchronize(M.s) != hipSuccess)
-    return bail(fail(MPSFM_EHIP, "device build: copying the slab table sizes failed"));
-  if (er[1]) return bail(fail(MPSFM_EUNSUPPORTED, "internal: block index beyond S"));
-  RedDest* dests = (RedDest*)cached_malloc(sizeof(RedDest) * (size_t)std::max(tot[1], 1));
-  if (!dests) return bail(fail(MPSFM_ENOMEM, "hipMalloc failed"));
+    return fail(MPSFM_EHIP, "device build: copying the slab table sizes failed");
+  if (er[1]) return fail(MPSFM_EUNSUPPORTED, "internal: block index beyond S");
+  RedDest* dests = own.alloc<RedDest>((size_t)std::max(tot[1], 1));
+  if (!dests) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   hipLaunchKernelGGL(k_slab_parts, dim3((unsigned)((ndst + kT - 1) / kT)), dim3(kT), 0, M.s, ndst, nsb, cnt, start, pstart, is_diag, dests);
-  if (hipGetLastError() != hipSuccess) { cached_free(dests); return bail(fail(MPSFM_EHIP, "device build: slab table kernels failed")); }
+  if (hipGetLastError() != hipSuccess) return fail(MPSFM_EHIP, "device build: slab table kernels failed");
   *d_dests = dests; *n_dests = tot[1]; *d_srcs = val_s; *n_srcs = tot[0];
   return 0;
-}
-
-void DevBuildOut::release() {
-  cached_free(d_chunks); cached_free(d_chunk_cams);
-  d_chunks = nullptr; d_chunk_cams = nullptr;
-  rt.release();
 }
 
 }  // namespace mpsfm

@@ -5,7 +5,6 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
-#include <vector>
 
 #include "common.h"
 #include "dev_resources.h"
@@ -41,19 +40,17 @@ struct CallScope {
   CallScope() = default;
   CallScope(const CallScope&) = delete;
   CallScope& operator=(const CallScope&) = delete;
-  // the stream must be idle before the blocks go back to the caching allocator (an early return on a failed call would
-  // otherwise free memory that is still in use) and before the stream goes back to the pool
+  // the owner waits for the stream, then gives the blocks and the stream back (an early return on a failed call would
+  // otherwise free memory that is still in use)
   ~CallScope() {
-    if (st) (void)hipStreamSynchronize(st);
+    own.reset();
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
-    for (void* p : blocks) cached_free(p);
-    release_stream(st);
   }
 
   // takes the stream, and the event pair of a call that reports its device time
   int open(bool timed = false) {
-    MPSFM_TRY(pooled_stream(&st));
+    MPSFM_TRY(own.stream(&st));
     if (timed) {
       MPSFM_TRY(hipEventCreate(&ev[0]));
       MPSFM_TRY(hipEventCreate(&ev[1]));
@@ -61,14 +58,12 @@ struct CallScope {
     return 0;
   }
 
-  // a cached block that lives as long as the scope; nullptr: out of memory
-  void* get(size_t bytes) {
-    void* p = cached_malloc(bytes ? bytes : 1);
-    if (p) blocks.push_back(p);
-    return p;
-  }
+  // a cached block / pinned host memory that lives as long as the scope; nullptr: out of memory
+  void* get(size_t bytes) { return own.get(bytes); }
   template <typename T>
-  T* alloc(size_t count) { return (T*)get(sizeof(T) * count); }
+  T* alloc(size_t count) { return own.alloc<T>(count); }
+  template <typename T>
+  T* host(size_t count) { return own.host<T>(count); }
   // block + queued staged upload (complete after staged_drain())
   template <typename T>
   int up(const T** dst, const T* src, size_t count) {
@@ -105,7 +100,7 @@ struct CallScope {
   }
 
  private:
-  std::vector<void*> blocks;
+  DeviceBlocks own;
   hipEvent_t ev[2] = {nullptr, nullptr};
 };
 

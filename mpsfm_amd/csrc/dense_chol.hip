@@ -694,9 +694,10 @@ __global__ __launch_bounds__(kStepThreads) void k_panel_probe(const double* dx, 
 extern "C" int mpsfm_debug_panel_factor(const double* dx, int waves, double* out, int* ok) {
   if (!dx || !out || !ok || (waves != 1 && waves != kWgWaves)) return MPSFM_EINVAL;
   const size_t bytes = (size_t)2 * kTileElems * sizeof(double);
-  double* d_in = (double*)cached_malloc(bytes);
-  double* d_out = (double*)cached_malloc(bytes);
-  int* d_fail = (int*)cached_malloc(sizeof(int));
+  DeviceBlocks own;  // the copies below are synchronous: nothing to wait for
+  double* d_in = own.alloc<double>((size_t)2 * kTileElems);
+  double* d_out = own.alloc<double>((size_t)2 * kTileElems);
+  int* d_fail = own.alloc<int>(1);
   hipError_t e = (d_in && d_out && d_fail) ? hipSuccess : hipErrorOutOfMemory;
   int h_fail = 0;
   if (e == hipSuccess) e = hipMemcpy(d_in, dx, bytes, hipMemcpyHostToDevice);
@@ -708,9 +709,6 @@ extern "C" int mpsfm_debug_panel_factor(const double* dx, int waves, double* out
   }
   if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(&h_fail, d_fail, sizeof(int), hipMemcpyDeviceToHost);
-  if (d_in) cached_free(d_in);
-  if (d_out) cached_free(d_out);
-  if (d_fail) cached_free(d_fail);
   if (e != hipSuccess) return e == hipErrorOutOfMemory ? MPSFM_ENOMEM : MPSFM_EHIP;
   *ok = h_fail ? 0 : 1;
   return MPSFM_OK;

@@ -4,6 +4,8 @@
 #pragma once
 #include <cstddef>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -22,17 +24,9 @@ inline int fail(int code, const std::string& m) { g_err = m; return code; }
 // Caching device allocator: hipMalloc / hipFree cost 10-300 us each and a handle makes ~60 of them; freed blocks are kept
 // per device (up to a cap) and handed out again — with whatever an earlier owner left in them: every consumer initialises
 // what it reads (MPSFM_POISON=1 fills each block with 0xFF to prove it).
-void* cached_malloc(size_t bytes);
-void cached_free(void* p);
 // Streams, events and the small pinned scalar blocks of a handle are recycled the same way: creating and destroying them
-// costs more than a whole solve of a small problem.  Per device; never destroyed.  A released stream must be idle.
-hipError_t pooled_stream(hipStream_t* s);  // non-blocking
-void release_stream(hipStream_t s);
-hipError_t pooled_event(hipEvent_t* e, bool timing);
-void release_event(hipEvent_t e, bool timing);
+// costs more than a whole solve of a small problem.  Per device; never destroyed.  Both are reached through DeviceBlocks only.
 constexpr size_t kPinnedBytes = 4096;
-hipError_t pooled_pinned(void** p);  // a block of kPinnedBytes
-void release_pinned(void* p);
 
 // Uploads of caller / table memory go through a pinned staging buffer per device (two halves, the host copy into one overlaps
 // the DMA out of the other).  Handing pageable memory to hipMemcpy directly makes the runtime pin and later unpin every source
@@ -41,25 +35,55 @@ int staged_upload(void* dst, const void* src, size_t bytes);  // queued: complet
 int staged_drain();                                            // waits for everything queued
 int staged_h2d(void* dst, const void* src, size_t bytes);     // queued and drained: complete on return
 
-template <typename T>
-int dev_alloc(T** p, size_t count) {
-  if (count == 0) count = 1;
-  *p = (T*)cached_malloc(count * sizeof(T));
-  if (!*p) return fail(MPSFM_ENOMEM, "hipMalloc failed");
-  return 0;
-}
-// block + queued staged upload of anything with data() and size() (complete after staged_drain())
-template <typename T, typename C>
-int dev_upload(T** p, const C& v) {
-  static_assert(sizeof(*v.data()) == sizeof(T), "element type of the table and of its device pointer differ");
-  if (int rc = dev_alloc(p, v.size())) return rc;
-  return staged_upload(*p, v.data(), v.size() * sizeof(T));
-}
-// several (pointer, table) pairs in a row; stops at the first failure
-template <typename T, typename C, typename... More>
-int dev_upload(T** p, const C& v, More&&... more) {
-  if (int rc = dev_upload(p, v)) return rc;
-  return dev_upload(more...);
-}
+// The owner of everything a call, a builder or a handle takes from the caches above, and the one place that gives it back
+// (DESIGN.md section 4b): the destructor first waits for every stream that may still touch the resources — a block back in
+// the process-wide cache is handed to another host thread's handle at once, a released stream must be idle — then releases
+// them all, on the current device (a handle makes its device current first).  Move-only.
+class DeviceBlocks {
+ public:
+  DeviceBlocks() = default;
+  DeviceBlocks(DeviceBlocks&& o) noexcept { adopt(std::move(o)); }
+  DeviceBlocks(const DeviceBlocks&) = delete;
+  DeviceBlocks& operator=(const DeviceBlocks&) = delete;
+  ~DeviceBlocks() { reset(); }
+
+  // a cached device block of at least one element; nullptr: out of memory (ok() stays false from then on)
+  void* get(size_t bytes);
+  template <typename T>
+  T* alloc(size_t count) { return (T*)get((count ? count : 1) * sizeof(T)); }
+  template <typename T>
+  int alloc(T** p, size_t count) { return (*p = alloc<T>(count)) ? 0 : fail(MPSFM_ENOMEM, "hipMalloc failed"); }
+  bool ok() const { return ok_; }
+  // block + queued staged upload of anything with data() and size() (complete after staged_drain()); several (pointer, table)
+  // pairs in a row stop at the first failure
+  template <typename T, typename C, typename... More>
+  int upload(T** p, const C& v, More&&... more) {
+    static_assert(sizeof(*v.data()) == sizeof(T), "element type of the table and of its device pointer differ");
+    if (int rc = alloc(p, v.size())) return rc;
+    if (int rc = staged_upload((void*)*p, v.data(), v.size() * sizeof(T))) return rc;  // (T may be const: a view's field)
+    if constexpr (sizeof...(More) > 0) return upload(more...);
+    return 0;
+  }
+  // pinned host memory of any size (read-backs that are plain DMA, not staged copies); nullptr: out of memory
+  void* get_host(size_t bytes);
+  template <typename T>
+  T* host(size_t count) { return (T*)get_host((count ? count : 1) * sizeof(T)); }
+  // recycled objects: a pinned block of kPinnedBytes, an event, a non-blocking stream (waited for like an idle_first stream)
+  hipError_t pinned(void** p);
+  hipError_t event(hipEvent_t* e, bool timing);
+  hipError_t stream(hipStream_t* s);
+  // a stream somebody else owns that works on these resources: waited for before anything goes back, never released
+  void idle_first(hipStream_t s) { if (s) idle_.push_back(s); }
+
+  void adopt(DeviceBlocks&& o);  // everything `o` owns and waits for
+  void drop(void* p);            // one device block back early: the caller knows that no stream uses it any more
+  void reset();                  // what the destructor does
+
+ private:
+  bool ok_ = true;
+  std::vector<void*> blocks_, hosts_, pinned_;
+  std::vector<hipEvent_t> events_[2];  // [timing]
+  std::vector<hipStream_t> streams_, idle_;
+};
 
 }  // namespace mpsfm

@@ -11,6 +11,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/mpsfm_hip_debug.h"
 #include "host_parts.h"
 
 namespace mpsfm {
@@ -90,46 +91,89 @@ DevCache& dev_cache() {
   return *c;
 }
 }  // namespace
-void* cached_malloc(size_t bytes) { return dev_cache().alloc(bytes); }
-void cached_free(void* p) { dev_cache().release(p); }
 
 // ---- streams, events, pinned blocks --------------------------------------------------------------------
 namespace {
 struct HandleResources {
   std::mutex mu;
   std::vector<hipStream_t> streams[16];
-  std::vector<hipEvent_t> timing_events[16], plain_events[16];
+  std::vector<hipEvent_t> events[2][16];  // [timing]
   std::vector<void*> pinned[16];  // blocks of kPinnedBytes
+  int64_t out_streams[16] = {}, out_events[16] = {}, out_pinned[16] = {};  // handed out and not yet given back (mpsfm_debug_resources)
 };
 HandleResources& pool() { static HandleResources* r = new HandleResources(); return *r; }
-// a recycled object of the current device, if there is one / an object back to its list
-template <typename T>
-bool pool_take(std::vector<T> (&lists)[16], T* out) {
-  HandleResources& R = pool();
-  std::lock_guard<std::mutex> lk(R.mu);
-  std::vector<T>& v = lists[device_slot()];
-  if (v.empty()) return false;
-  *out = v.back();
-  v.pop_back();
-  return true;
+// a recycled object of the current device or a fresh one from `make` / an object back to its list
+template <typename T, typename F>
+hipError_t pool_take(std::vector<T> (&lists)[16], int64_t (&out)[16], T* x, F&& make) {
+  std::lock_guard<std::mutex> lk(pool().mu);
+  const int dev = device_slot();
+  std::vector<T>& v = lists[dev];
+  if (!v.empty()) { *x = v.back(); v.pop_back(); }
+  else if (hipError_t e = make(x)) return e;
+  ++out[dev];
+  return hipSuccess;
 }
 template <typename T>
-void pool_give(std::vector<T> (&lists)[16], T x) {
+void pool_give(std::vector<T> (&lists)[16], int64_t (&out)[16], T x) {
   if (!x) return;
-  HandleResources& R = pool();
-  std::lock_guard<std::mutex> lk(R.mu);
-  lists[device_slot()].push_back(x);
+  std::lock_guard<std::mutex> lk(pool().mu);
+  const int dev = device_slot();
+  lists[dev].push_back(x);
+  --out[dev];
 }
 }  // namespace
-hipError_t pooled_stream(hipStream_t* s) { return pool_take(pool().streams, s) ? hipSuccess : hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
-void release_stream(hipStream_t s) { pool_give(pool().streams, s); }
-hipError_t pooled_event(hipEvent_t* e, bool timing) {
-  if (pool_take(timing ? pool().timing_events : pool().plain_events, e)) return hipSuccess;
-  return timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming);
+
+// ---- the owner (dev_resources.h): the only caller of the allocator and the pools ----------------------------
+void* DeviceBlocks::get(size_t bytes) {
+  void* p = dev_cache().alloc(bytes);
+  if (p) blocks_.push_back(p);
+  else ok_ = false;
+  return p;
 }
-void release_event(hipEvent_t e, bool timing) { pool_give(timing ? pool().timing_events : pool().plain_events, e); }
-hipError_t pooled_pinned(void** p) { return pool_take(pool().pinned, p) ? hipSuccess : hipHostMalloc(p, kPinnedBytes, hipHostMallocDefault); }
-void release_pinned(void* p) { pool_give(pool().pinned, p); }
+void* DeviceBlocks::get_host(size_t bytes) {
+  void* p = nullptr;
+  if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) return nullptr;
+  hosts_.push_back(p);
+  return p;
+}
+hipError_t DeviceBlocks::pinned(void** p) {
+  hipError_t e = pool_take(pool().pinned, pool().out_pinned, p, [](void** q) { return hipHostMalloc(q, kPinnedBytes, hipHostMallocDefault); });
+  if (e == hipSuccess) pinned_.push_back(*p);
+  return e;
+}
+hipError_t DeviceBlocks::event(hipEvent_t* ev, bool timing) {
+  hipError_t e = pool_take(pool().events[timing], pool().out_events, ev,
+                           [timing](hipEvent_t* q) { return timing ? hipEventCreate(q) : hipEventCreateWithFlags(q, hipEventDisableTiming); });
+  if (e == hipSuccess) events_[timing].push_back(*ev);
+  return e;
+}
+hipError_t DeviceBlocks::stream(hipStream_t* s) {
+  hipError_t e = pool_take(pool().streams, pool().out_streams, s, [](hipStream_t* q) { return hipStreamCreateWithFlags(q, hipStreamNonBlocking); });
+  if (e == hipSuccess) { streams_.push_back(*s); idle_.push_back(*s); }
+  return e;
+}
+void DeviceBlocks::adopt(DeviceBlocks&& o) {
+  auto take = [](auto& dst, auto& src) { dst.insert(dst.end(), src.begin(), src.end()); src.clear(); };
+  take(blocks_, o.blocks_); take(hosts_, o.hosts_); take(pinned_, o.pinned_); take(events_[0], o.events_[0]); take(events_[1], o.events_[1]);
+  take(streams_, o.streams_); take(idle_, o.idle_);
+  ok_ = ok_ && o.ok_;
+}
+void DeviceBlocks::drop(void* p) {
+  auto it = std::find(blocks_.begin(), blocks_.end(), p);
+  if (it == blocks_.end()) return;
+  blocks_.erase(it);
+  dev_cache().release(p);
+}
+void DeviceBlocks::reset() {
+  for (hipStream_t s : idle_) (void)hipStreamSynchronize(s);
+  for (void* p : blocks_) dev_cache().release(p);
+  for (void* p : hosts_) (void)hipHostFree(p);
+  for (void* p : pinned_) pool_give(pool().pinned, pool().out_pinned, p);
+  for (int timing = 0; timing < 2; ++timing)
+    for (hipEvent_t e : events_[timing]) pool_give(pool().events[timing], pool().out_events, e);
+  for (auto it = streams_.rbegin(); it != streams_.rend(); ++it) pool_give(pool().streams, pool().out_streams, *it);
+  blocks_.clear(); hosts_.clear(); pinned_.clear(); events_[0].clear(); events_[1].clear(); streams_.clear(); idle_.clear();
+}
 
 // ---- pinned staging uploader ---------------------------------------------------------------------------
 namespace {
@@ -216,3 +260,21 @@ int staged_h2d(void* dst, const void* src, size_t bytes) {
 }
 
 }  // namespace mpsfm
+
+// Diagnostics / tests: what the current process holds of `device`'s caches — live device blocks and their bytes, and the
+// pooled streams, events and pinned blocks handed out and not yet given back.  Equal before and after a balanced call.
+extern "C" int mpsfm_debug_resources(int32_t device, int64_t out[5]) {
+  using namespace mpsfm;
+  if (!out || device < 0 || device > 15) return fail(MPSFM_EINVAL, "mpsfm_debug_resources: out is NULL or the device ordinal is out of range");
+  out[0] = out[1] = 0;
+  {
+    DevCache& C = dev_cache();
+    std::lock_guard<std::mutex> lk(C.mu);
+    for (const auto& kv : C.live)
+      if (kv.second.second == device) { ++out[0]; out[1] += (int64_t)kv.second.first; }
+  }
+  HandleResources& R = pool();
+  std::lock_guard<std::mutex> lk(R.mu);
+  out[2] = R.out_streams[device]; out[3] = R.out_events[device]; out[4] = R.out_pinned[device];
+  return 0;
+}

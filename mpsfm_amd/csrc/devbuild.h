@@ -5,12 +5,14 @@
 
 #include "build_host.h"
 #include "common.h"
+#include "dev_resources.h"
 
 namespace mpsfm {
 
 constexpr int MPSFM_DEVBUILD_FALLBACK = 1;  // stage2: the problem needs the host build (long tracks); nothing was produced
 
-// The record and fixed-record tables on the device (cached_malloc blocks): built there by the device build, uploaded by the host build.
+// The record and fixed-record tables on the device: built there by the device build, uploaded by the host build.  A view: the blocks
+// belong to a DeviceBlocks (the build's output, then the handle).
 struct RecTablesDev {
   int32_t *rec_cam = nullptr, *rec_pt = nullptr;
   uint32_t* rec_meta = nullptr;
@@ -21,22 +23,15 @@ struct RecTablesDev {
   int32_t *fx_cam = nullptr, *fx_pt = nullptr;
   uint32_t* fx_meta = nullptr;
   double *fx_xy = nullptr, *fx_d = nullptr, *fx_m = nullptr, *fx_a = nullptr;
-  void release() {
-    for (void* p : {(void*)rec_cam, (void*)rec_pt, (void*)rec_meta, (void*)rec_xy, (void*)rec_d, (void*)rec_m, (void*)rec_a, (void*)pt_rec_start, (void*)pt_kv,
-                    (void*)fx_cam, (void*)fx_pt, (void*)fx_meta, (void*)fx_xy, (void*)fx_d, (void*)fx_m, (void*)fx_a})
-      cached_free(p);
-    *this = RecTablesDev{};
-  }
 };
 
 struct DevBuildOut {
-  // device tables, owned by the receiver (cached_malloc blocks)
+  DeviceBlocks own;  // the device tables below; it waits for the builder's stream
   ChunkHdr* d_chunks = nullptr;
   int32_t* d_chunk_cams = nullptr;
   RecTablesDev rt;
   // host copies of the small tables the rest of build_tables() works on: chunks, chunk_cams, order and the counts
   HostTables t;
-  void release();
 };
 
 class DevBuilder {
@@ -53,10 +48,10 @@ class DevBuilder {
   // rec_cap: records a DENSE chunk may hold (kObsMax, or less for small problems); pts_by_cams: dense_pts_cap by the camera set (BuildOptions)
   int stage2(const std::vector<int32_t>& slot_of_cam, bool dense_on, int rec_cap, int pts_by_cams, DevBuildOut& out);
   // the reduction tables of the dense chunks' slabs (k_reduce_slabs) from device copies of the chunk headers (slab offsets set) and
-  // camera lists; d_diag_block[slot]: the block of S on that slot's diagonal or -1.  The two tables are the receiver's
-  // (cached_malloc blocks); stage1 must have run (the builder's stream).
+  // camera lists; d_diag_block[slot]: the block of S on that slot's diagonal or -1.  The two tables are allocated from `own`;
+  // stage1 must have run (the builder's stream).
   int slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t* d_chunk_cams, const BlockSky& sky, int64_t nsb, int ncv, const int32_t* d_diag_block,
-                  RedDest** d_dests, int32_t* n_dests, int32_t** d_srcs, int64_t* n_srcs);
+                  DeviceBlocks& own, RedDest** d_dests, int32_t* n_dests, int32_t** d_srcs, int64_t* n_srcs);
 
  private:
   struct Impl;

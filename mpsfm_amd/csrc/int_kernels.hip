@@ -426,29 +426,6 @@ __global__ __launch_bounds__(kIT) void k_int_exp(size_t n, const double* z, doub
   if (p < n) out[p] = exp(z[p]);
 }
 
-struct IntPool {
-  std::vector<void*> v, vh;
-  ~IntPool() {
-    for (void* p : v) cached_free(p);
-    for (void* p : vh) if (p) (void)hipHostFree(p);
-  }
-  // pinned host memory: the per-iteration read-backs (done flags, energy partials) are plain DMA, not staged copies
-  template <typename T>
-  T* get_host(size_t n) {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault) != hipSuccess) return nullptr;
-    vh.push_back(p);
-    return (T*)p;
-  }
-  template <typename T>
-  T* get(size_t n) {
-    void* p = cached_malloc(std::max<size_t>(n, 1) * sizeof(T));
-    if (!p) return nullptr;
-    v.push_back(p);
-    return (T*)p;
-  }
-};
-
 // b = 1, x0 = 0: the system of IntegrationUncertainty (column sums of the inverse)
 __global__ __launch_bounds__(kIT) void k_int_unit_rhs(IntDev Dall) {
   if (!Dall.act[blockIdx.y]) return;
@@ -458,9 +435,8 @@ __global__ __launch_bounds__(kIT) void k_int_unit_rhs(IntDev Dall) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-// A batch of images of one size and one configuration, resident on the device.
+// A batch of images of one size and one configuration, resident on the device: blocks of the call's scope.
 struct IntBatch {
-  IntPool pool;
   IntDev D{};
   int B = 0, G = 0;
   size_t N = 0;
@@ -497,7 +473,8 @@ static bool int_same_config(const mpsfm_int_problem& a, const mpsfm_int_problem&
 }
 
 // process_sparse_depth (+ the scale filter of _integrate when asked), device buffers, uploads
-static int int_setup(const mpsfm_int_problem* Ps, int B, bool use_sparse, bool scale_filter, hipStream_t st, IntBatch& U) {
+static int int_setup(const mpsfm_int_problem* Ps, int B, bool use_sparse, bool scale_filter, CallScope& A, IntBatch& U) {
+  hipStream_t st = A.st;
   const mpsfm_int_problem& P0 = Ps[0];
   const int H = P0.H, W = P0.W;
   const size_t N = (size_t)H * W;
@@ -525,24 +502,23 @@ static int int_setup(const mpsfm_int_problem* Ps, int B, bool use_sparse, bool s
     for (int k = 0; k < 4; ++k) Kh[(size_t)b * 4 + k] = P->K[k];
   }
   const auto& ids = U.ids;
-  IntPool& pool = U.pool;
   IntDev& D = U.D;
   const int G = U.G = (int)((N + kIT - 1) / kIT);
   D.H = H; D.W = W; D.N = (int)N; D.B = B; D.G = G;
   const size_t BN = (size_t)B * N;
-  double* big = pool.get<double>(BN * 28);
-  double* d_in = U.d_in = pool.get<double>(BN * 9);
-  U.d_valid = pool.get<uint8_t>(BN);
-  D.part = pool.get<double>((size_t)B * G * 8);
-  D.state = pool.get<double>((size_t)B * 8);
-  U.d_ids = pool.get<int32_t>(ids.size());
-  U.d_off = pool.get<int32_t>((size_t)B + 1);
-  U.d_act = pool.get<int32_t>((size_t)B);
-  U.d_keep = pool.get<int32_t>((size_t)B);
-  U.d_sp = pool.get<double>(ids.size() * 2 + 1);
-  U.d_out = pool.get<double>(BN);
-  U.d_K = pool.get<double>((size_t)B * 4);
-  U.d_esp = pool.get<double>((size_t)B);
+  double* big = A.alloc<double>(BN * 28);
+  double* d_in = U.d_in = A.alloc<double>(BN * 9);
+  U.d_valid = A.alloc<uint8_t>(BN);
+  D.part = A.alloc<double>((size_t)B * G * 8);
+  D.state = A.alloc<double>((size_t)B * 8);
+  U.d_ids = A.alloc<int32_t>(ids.size());
+  U.d_off = A.alloc<int32_t>((size_t)B + 1);
+  U.d_act = A.alloc<int32_t>((size_t)B);
+  U.d_keep = A.alloc<int32_t>((size_t)B);
+  U.d_sp = A.alloc<double>(ids.size() * 2 + 1);
+  U.d_out = A.alloc<double>(BN);
+  U.d_K = A.alloc<double>((size_t)B * 4);
+  U.d_esp = A.alloc<double>((size_t)B);
   if (!big || !d_in || !U.d_valid || !D.part || !D.state || !U.d_ids || !U.d_off || !U.d_act || !U.d_keep || !U.d_sp || !U.d_out || !U.d_K || !U.d_esp)
     return fail(MPSFM_ENOMEM, "hipMalloc failed");
   D.act = U.d_act;
@@ -554,32 +530,32 @@ static int int_setup(const mpsfm_int_problem* Ps, int B, bool use_sparse, bool s
     D.spd = take(1); D.spb = take(1); D.r = take(1); D.zz = take(1); D.p0 = take(1); D.p1 = take(1); D.q = take(1);
   }
   // inputs: [prior | unc | init] each [B][N], then normals [B][N][3], nvar [B][N][3]
-  auto up = [&](void* dst, const void* src, size_t bytes) { return staged_upload(dst, src, bytes); };
   for (int b = 0; b < B; ++b) {
     const mpsfm_int_problem* P = &Ps[b];
-    if (int rc = up(d_in + (size_t)b * N, P->depth_prior, sizeof(double) * N)) return rc;
-    if (int rc = up(d_in + BN + (size_t)b * N, P->depth_uncertainty, sizeof(double) * N)) return rc;
-    if (int rc = up(d_in + 2 * BN + (size_t)b * N, P->depth_init, sizeof(double) * N)) return rc;
-    if (int rc = up(d_in + 3 * BN + (size_t)b * 3 * N, P->normals, sizeof(double) * 3 * N)) return rc;
-    if (int rc = up(d_in + 6 * BN + (size_t)b * 3 * N, P->normals_var, sizeof(double) * 3 * N)) return rc;
-    if (int rc = up(U.d_valid + (size_t)b * N, P->valid, N)) return rc;
+    if (int rc = staged_upload(d_in + (size_t)b * N, P->depth_prior, sizeof(double) * N)) return rc;
+    if (int rc = staged_upload(d_in + BN + (size_t)b * N, P->depth_uncertainty, sizeof(double) * N)) return rc;
+    if (int rc = staged_upload(d_in + 2 * BN + (size_t)b * N, P->depth_init, sizeof(double) * N)) return rc;
+    if (int rc = staged_upload(d_in + 3 * BN + (size_t)b * 3 * N, P->normals, sizeof(double) * 3 * N)) return rc;
+    if (int rc = staged_upload(d_in + 6 * BN + (size_t)b * 3 * N, P->normals_var, sizeof(double) * 3 * N)) return rc;
+    if (int rc = staged_upload(U.d_valid + (size_t)b * N, P->valid, N)) return rc;
   }
-  if (int rc = up(D.spd, spd.data(), sizeof(double) * BN)) return rc;
-  if (int rc = up(D.spb, spb.data(), sizeof(double) * BN)) return rc;
-  if (int rc = up(U.d_K, Kh.data(), sizeof(double) * 4 * B)) return rc;
-  if (int rc = up(U.d_off, U.sp_off.data(), sizeof(int32_t) * ((size_t)B + 1))) return rc;
+  if (int rc = staged_upload(D.spd, spd.data(), sizeof(double) * BN)) return rc;
+  if (int rc = staged_upload(D.spb, spb.data(), sizeof(double) * BN)) return rc;
+  if (int rc = staged_upload(U.d_K, Kh.data(), sizeof(double) * 4 * B)) return rc;
+  if (int rc = staged_upload(U.d_off, U.sp_off.data(), sizeof(int32_t) * ((size_t)B + 1))) return rc;
   MPSFM_TRY(hipMemsetAsync(D.p0, 0, sizeof(double) * 2 * BN, st));
   if (!ids.empty()) {
-    if (int rc = up(U.d_ids, ids.data(), sizeof(int32_t) * ids.size())) return rc;
-    if (int rc = up(U.d_sp, U.sprec.data(), sizeof(double) * ids.size())) return rc;
-    if (int rc = up(U.d_sp + ids.size(), U.sdep.data(), sizeof(double) * ids.size())) return rc;
+    if (int rc = staged_upload(U.d_ids, ids.data(), sizeof(int32_t) * ids.size())) return rc;
+    if (int rc = staged_upload(U.d_sp, U.sprec.data(), sizeof(double) * ids.size())) return rc;
+    if (int rc = staged_upload(U.d_sp + ids.size(), U.sdep.data(), sizeof(double) * ids.size())) return rc;
   }
   U.act.assign((size_t)B, 1);
-  if (int rc = up(U.d_act, U.act.data(), sizeof(int32_t) * B)) return rc;
+  if (int rc = staged_upload(U.d_act, U.act.data(), sizeof(int32_t) * B)) return rc;
   // everything staged must be on the device before the first kernel on st (and spd / spb / Kh die with this frame)
   if (int rc = staged_drain()) return rc;
   MPSFM_TRY(hipStreamSynchronize(st));
-  double* hblk = pool.get_host<double>((size_t)B * G * 8 + (size_t)B * 9);
+  // pinned: the per-iteration read-backs (done flags, energy partials) are plain DMA, not staged copies
+  double* hblk = A.host<double>((size_t)B * G * 8 + (size_t)B * 9);
   if (!hblk) return fail(MPSFM_ENOMEM, "hipHostMalloc failed");
   U.hpart = hblk; U.hstate = hblk + (size_t)B * G * 8; U.hesp = U.hstate + (size_t)B * 8;
   return 0;
@@ -656,14 +632,12 @@ extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_pro
   MPSFM_TRY(hipSetDevice(device));
   std::memset(Ss, 0, sizeof(*Ss) * (size_t)B);
   // a stream of its own: concurrent calls from different host threads overlap on the GPU
-  // U before the guard: destructors run in reverse order, so every early `return rc` first waits for the stream
-  // (the guard) and only then hands U's device blocks back to the caching allocator
-  IntBatch U;
   CallScope sg;
-  if (int rc = sg.open()) return rc;
+  if (int rc = sg.open(true)) return rc;
   hipStream_t st = sg.st;
+  IntBatch U;
   const size_t N = (size_t)P->H * P->W;
-  if (int rc = int_setup(Ps, B, true, P->scale_filter != 0, st, U)) return rc;
+  if (int rc = int_setup(Ps, B, true, P->scale_filter != 0, sg, U)) return rc;
   IntDev& D = U.D;
   const dim3 grid(U.G, B);
   std::vector<int32_t> keep((size_t)B, 0);
@@ -676,9 +650,7 @@ extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_pro
   }
   MPSFM_TRY(hipMemcpyAsync(U.d_keep, keep.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st));
   MPSFM_TRY(hipStreamSynchronize(st));
-  hipEvent_t e0, e1;
-  MPSFM_TRY(hipEventCreate(&e0)); MPSFM_TRY(hipEventCreate(&e1));
-  MPSFM_TRY(hipEventRecord(e0, st));
+  if (int rc = sg.begin()) return rc;
   int_launch_prepare(P, U, st);
 
   // energies of the active images -> en[b]
@@ -701,10 +673,8 @@ extern "C" int mpsfm_integrate_depth_batch(int32_t n_images, const mpsfm_int_pro
     return 0;
   };
   auto finish = [&](int rc) {
-    float ms = 0.f;
-    (void)hipEventRecord(e1, st); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
-    for (int b = 0; b < B; ++b) Ss[b].ms = ms;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    (void)sg.end();
+    for (int b = 0; b < B; ++b) Ss[b].ms = (float)sg.ms;
     return rc;
   };
   auto save_weights = [&]() -> int {
@@ -799,20 +769,18 @@ extern "C" int mpsfm_integration_variances(const mpsfm_int_problem* P, int32_t d
     if (qx[i] < 0 || qx[i] >= P->W || qy[i] < 0 || qy[i] >= P->H) return fail(MPSFM_EINVAL, "query pixel outside the map");
   MPSFM_TRY(hipSetDevice(device));
   std::memset(S, 0, sizeof(*S));
-  IntBatch U;  // before the guard, see mpsfm_integrate_depth_batch
   CallScope sg;
-  if (int rc = sg.open()) return rc;
+  if (int rc = sg.open(true)) return rc;
   hipStream_t st = sg.st;
+  IntBatch U;
   const int N = P->H * P->W;
-  if (int rc = int_setup(P, 1, use_sparse != 0, false, st, U)) return rc;  // calculate_hessian applies no scale filter (:542)
+  if (int rc = int_setup(P, 1, use_sparse != 0, false, sg, U)) return rc;  // calculate_hessian applies no scale filter (:542)
   IntDev& D = U.D;
   const dim3 grid(U.G, 1);
   int32_t zero = 0;
   MPSFM_TRY(hipMemcpyAsync(U.d_keep, &zero, sizeof(int32_t), hipMemcpyHostToDevice, st));
   MPSFM_TRY(hipStreamSynchronize(st));
-  hipEvent_t e0, e1;
-  MPSFM_TRY(hipEventCreate(&e0)); MPSFM_TRY(hipEventCreate(&e1));
-  MPSFM_TRY(hipEventRecord(e0, st));
+  if (int rc = sg.begin()) return rc;
   int_launch_prepare(P, U, st);
   hipLaunchKernelGGL(k_int_weights, grid, dim3(kIT), 0, st, D, P->k, P->lambda1, (const int32_t*)U.d_keep);  // init=False: weights from the checkpoint
   hipLaunchKernelGGL(k_int_system, grid, dim3(kIT), 0, st, D, P->lambda1);
@@ -820,11 +788,9 @@ extern "C" int mpsfm_integration_variances(const mpsfm_int_problem* P, int32_t d
   int its = 0;
   bool conv = false;
   int rc = int_run_cg(U, st, rtol, max_iter, &its, &conv);
-  float ms = 0.f;
-  (void)hipEventRecord(e1, st); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  (void)sg.end();
   if (rc) return rc;
-  S->ms = ms;
+  S->ms = (float)sg.ms;
   S->irls_iterations = 1;
   S->cg_iters[0] = its;
   S->cg_iterations_total = its;
