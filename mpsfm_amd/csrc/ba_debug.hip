@@ -129,7 +129,9 @@ int mpsfm_debug_read_trace(mpsfm_ba_handle* h, long long* out, int64_t count) {
 // 6 rec_d, 7 rec_m, 8 rec_a, 9 pt_rec_start, 10 pt_kv, 11 fx_cam, 12 fx_pt, 13 fx_meta, 14 fx_xy, 15 fx_d, 16 fx_m, 17 fx_a,
 // 18 landmark order (host), 19 reduction destinations, 20 reduction sources, 21 camera slots (host), 22: 1 byte, built on the device?,
 // 23 blk_desc, 24 blk_ent_start, 25 ents (pair tables of the general chunks), 27 long-track headers, 28 sky_index, 29 sky_first,
-// 30 sky_start (host), 31 cmask, 32 cam_of_slot, 33 the ten numbers of mpsfm_ba_dense_plan
+// 30 sky_start (host), 31 cmask, 32 cam_of_slot, 33 the ten numbers of mpsfm_ba_dense_plan, 34 the launches the last solve on this
+// handle enqueued (host, int64 each): track sweeps, k_reduce_slabs, k_assemble, k_chol_level, the rest of the dense solve, update
+// sweeps, decisions, scales and camera table, everything else (LaunchFamily of ba_launch.h)
 int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t cap) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   const void* src = nullptr;
@@ -171,6 +173,7 @@ int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t 
     case 31: src = h->d_cmask; bytes = 48 * (int64_t)h->nc; break;
     case 32: src = h->d_cam_of_slot; bytes = 4 * (int64_t)std::max(h->ncv, 1); break;
     case 33: { static thread_local int64_t info[10]; if (int rc = mpsfm_ba_dense_plan(h, info)) return rc; src = info; bytes = 80; host = true; break; }
+    case 34: src = h->last_launches; bytes = (int64_t)sizeof(h->last_launches); host = true; break;
     default: return fail(MPSFM_EINVAL, "unknown table");
   }
   if (!out || cap < bytes) return bytes;

@@ -74,6 +74,8 @@ struct mpsfm_ba_handle {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   double last_radius = 1e4;
   bool scales_ready = false;
+  int64_t last_launches[mpsfm::kLfCount] = {};  // what the last solve enqueued, per kernel family (code 34 of mpsfm_debug_table)
+  double split_front_s = 0.0;  // ev0 -> ev1 of the last iteration read (solve_impl: is the front long enough to enqueue the back half behind it?)
   // single-launch solver of small problems (local_lm.hip): two accumulators | barrier words + clocks | per-iteration heads
   bool local_ok = false;
   double* d_local_acc = nullptr;

@@ -739,8 +739,8 @@ __global__ void k_gmax_from_slots(const double* redsc, double* scal) {
     scal[U_X_COST] = redsc[SC_COST]; scal[U_X_BAD] = redsc[SC_BAD]; scal[U_GMAX_PTS] = m;
   }
 }
-void launch_gmax_to_slot(double* redsc, int rank, hipStream_t s) { hipLaunchKernelGGL(k_gmax_to_slot, dim3(1), dim3(64), 0, s, redsc, rank); }
-void launch_gmax_from_slots(const double* redsc, double* scal, hipStream_t s) { hipLaunchKernelGGL(k_gmax_from_slots, dim3(1), dim3(64), 0, s, redsc, scal); }
+void launch_gmax_to_slot(double* redsc, int rank, hipStream_t s) { count_launch(kLfOther); hipLaunchKernelGGL(k_gmax_to_slot, dim3(1), dim3(64), 0, s, redsc, rank); }
+void launch_gmax_from_slots(const double* redsc, double* scal, hipStream_t s) { count_launch(kLfOther); hipLaunchKernelGGL(k_gmax_from_slots, dim3(1), dim3(64), 0, s, redsc, scal); }
 
 
 // ---- Levenberg-Marquardt control on the device ------------------------------------------------------------------
@@ -900,11 +900,12 @@ __global__ void k_lm_init(LmCtl* C, const double* scal, const double* sums) {
     C->fixed_cost = f0 + f1;
   }
 }
-void launch_lm_pack(const double* scal, double* sums, hipStream_t s) { hipLaunchKernelGGL(k_lm_pack, dim3(1), dim3(64), 0, s, scal, sums); }
-void launch_lm_init(LmCtl* ctl, const double* scal, const double* sums, hipStream_t s) { hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, s, ctl, scal, sums); }
+void launch_lm_pack(const double* scal, double* sums, hipStream_t s) { count_launch(kLfOther); hipLaunchKernelGGL(k_lm_pack, dim3(1), dim3(64), 0, s, scal, sums); }
+void launch_lm_init(LmCtl* ctl, const double* scal, const double* sums, hipStream_t s) { count_launch(kLfOther); hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, s, ctl, scal, sums); }
 
 // ---- launch wrappers ------------------------------------------------------------------------------
 void launch_track_sweep(const SweepArgs& a, int nchunks, bool diag_only, hipStream_t s) {
+  count_launch(kLfTrackSweep, (nchunks > 0 ? 1 : 0) + (a.nlong > 0 ? 1 : 0));
   if (nchunks > 0) {
     if (diag_only) hipLaunchKernelGGL(k_track_sweep<MODE_DIAG>, dim3(nchunks), dim3(kThreads), 0, s, a);
     else hipLaunchKernelGGL(k_track_sweep<MODE_FULL>, dim3(nchunks), dim3(kThreads), 0, s, a);
@@ -917,6 +918,7 @@ void launch_track_sweep(const SweepArgs& a, int nchunks, bool diag_only, hipStre
 void launch_update_sweep(const SweepArgs& a, int nchunks, hipStream_t s, const CamUpdArgs* cu) {
   CamUpdArgs u{};
   if (cu) u = *cu;
+  count_launch(kLfUpdateSweep, (nchunks > 0 ? 1 : 0) + (a.nlong > 0 ? 1 : 0));
   if (nchunks > 0) {
     if (a.pt_fac) hipLaunchKernelGGL(k_update_sweep<true>, dim3(nchunks), dim3(kThreads), 0, s, a, u);
     else hipLaunchKernelGGL(k_update_sweep<false>, dim3(nchunks), dim3(kThreads), 0, s, a, u);
@@ -924,34 +926,41 @@ void launch_update_sweep(const SweepArgs& a, int nchunks, hipStream_t s, const C
   if (a.nlong > 0) hipLaunchKernelGGL(k_long_update_sweep, dim3(a.nlong), dim3(kThreads), 0, s, a);
 }
 void launch_cost_records(const CostArgs& a, int nblocks, hipStream_t s) {
+  count_launch(kLfOther);
   hipLaunchKernelGGL(k_cost_records, dim3(nblocks), dim3(kThreads), 0, s, a);
 }
 void launch_reduce_cols(const double* part, int64_t rows, int stride, int ncols, uint32_t max_mask, double* out,
                         hipStream_t s, double* out2, int gmax_slot) {
+  count_launch(kLfOther);
   hipLaunchKernelGGL(k_reduce_cols, dim3(1), dim3(kReduceThreads), 0, s, part, rows, stride, ncols, max_mask, out, out2, gmax_slot);
 }
 void launch_build_camtab(int nc, const double* q, const double* t, const double* intr, const int32_t* intr_idx,
                          const double* cs, double* camtab, hipStream_t s) {
   if (nc <= 0) return;
+  count_launch(kLfScales);
   hipLaunchKernelGGL(k_build_camtab, dim3((nc + 127) / 128), dim3(128), 0, s, nc, q, t, intr, intr_idx, cs, camtab);
 }
 void launch_cam_scales(int nc, const int32_t* cam_slot, const double* cmask, const double* diagU, int jacobi,
                        double* cs, hipStream_t s) {
   if (nc <= 0) return;
+  count_launch(kLfScales);
   hipLaunchKernelGGL(k_cam_scales, dim3((nc * 6 + 127) / 128), dim3(128), 0, s, nc, cam_slot, cmask, diagU, jacobi, cs);
 }
 void launch_pt_scales(int64_t np, const uint16_t* pt_kv, const double* diagV, int jacobi, double* ps, hipStream_t s) {
   if (np <= 0) return;
   const int64_t n3 = np * 3;
+  count_launch(kLfScales);
   hipLaunchKernelGGL(k_pt_scales, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, s, n3, pt_kv, diagV, jacobi, ps);
 }
 void launch_cam_update(int nc, const int32_t* cam_slot, const double* q, const double* t, const double* cs,
                        const double* yc, const double* gc, double* q2, double* t2, double* scal, hipStream_t s,
                        const double* intr, const int32_t* intr_idx, double* camtab2, int* chol_fail, const LmCtl* ctl) {
+  count_launch(kLfOther);
   hipLaunchKernelGGL(k_cam_update, dim3(1), dim3(kThreads), 0, s, nc, cam_slot, q, t, cs, yc, gc, q2, t2, scal, intr, intr_idx,
                      camtab2, chol_fail, ctl);
 }
 void launch_lm_decide(LmCtl* ctl, double* scal, const LmOpts& o, LmCtl* host_copy, hipStream_t s, const double* redsc) {
+  count_launch(kLfDecide);
   hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(64), 0, s, ctl, scal, o, host_copy, redsc);
 }
 __global__ __launch_bounds__(256) void k_zero(double* p, int64_t n, const LmCtl* ctl) {
@@ -960,24 +969,29 @@ __global__ __launch_bounds__(256) void k_zero(double* p, int64_t n, const LmCtl*
 }
 void launch_zero(double* p, int64_t n, const LmCtl* ctl, hipStream_t s) {
   if (n <= 0) return;
+  count_launch(kLfOther);
   hipLaunchKernelGGL(k_zero, dim3((unsigned)std::min<int64_t>(2048, (n + 255) / 256)), dim3(256), 0, s, p, n, ctl);
 }
 void launch_lm_reduce_decide(const double* part, const double* part2, int64_t rows, LmCtl* ctl, double* scal, const LmOpts& o, LmCtl* host_copy, hipStream_t s) {
+  count_launch(kLfDecide);
   hipLaunchKernelGGL(k_lm_reduce_decide, dim3(1), dim3(kReduceThreads), 0, s, part, part2, rows, ctl, scal, o, host_copy);
 }
 void launch_lm_prologue(const LmCtl* ctl, double* red, int64_t nred, int nc, int64_t np, double* q, double* t, double* camtab, double* pts, const double* q2,
                         const double* t2, const double* camtab2, const double* pts2, hipStream_t s) {
   const int64_t total = std::max<int64_t>(nred, 3 * np + (int64_t)nc * (4 + 3 + kCamRec));
   const int grid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (total + 255) / 256));
+  count_launch(kLfOther);
   hipLaunchKernelGGL(k_lm_prologue, dim3(grid), dim3(256), 0, s, ctl, red, nred, nc, np, q, t, camtab, pts, q2, t2, camtab2, pts2);
 }
 void launch_lm_accept(const LmCtl* ctl, int nc, int64_t np, double* q, double* t, double* camtab, double* pts, const double* q2, const double* t2,
                       const double* camtab2, const double* pts2, hipStream_t s) {
   const int64_t total = 3 * np + (int64_t)nc * (4 + 3 + kCamRec);
   const int grid = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (total + 255) / 256));
+  count_launch(kLfOther);
   hipLaunchKernelGGL(k_lm_accept, dim3(grid), dim3(256), 0, s, ctl, nc, np, q, t, camtab, pts, q2, t2, camtab2, pts2);
 }
 void launch_pts_sqnorm(int64_t np, const uint16_t* pt_kv, const double* pts, double* part, int nblocks, hipStream_t s) {
+  count_launch(kLfOther);
   hipLaunchKernelGGL(k_pts_sqnorm, dim3(nblocks), dim3(kThreads), 0, s, np, pt_kv, pts, part);
 }
 

@@ -6,6 +6,23 @@
 #include "local_lm.h"
 
 namespace mpsfm {
+// ---- launches enqueued by the calling thread, per kernel family: counted on the host in the wrappers below; a solve starts them
+// from zero and leaves its counts with the handle (code 34 of mpsfm_debug_table) ------------------------------------------------
+enum LaunchFamily {
+  kLfTrackSweep,   // k_track_sweep_dense, k_track_sweep, k_long_track_sweep
+  kLfReduceSlabs,  // k_reduce_slabs
+  kLfAssemble,     // k_assemble
+  kLfCholLevel,    // k_chol_level
+  kLfDenseRest,    // behind the level launches: k_inv_y, k_back_level (the outer-panel path is not counted)
+  kLfUpdateSweep,  // k_update_sweep, k_long_update_sweep
+  kLfDecide,       // k_lm_reduce_decide, k_lm_decide
+  kLfScales,       // k_cam_scales, k_pt_scales, k_build_camtab
+  kLfOther,        // the rest of this header
+  kLfCount
+};
+extern thread_local int64_t g_launches[kLfCount];  // dense_chol.hip
+inline void count_launch(LaunchFamily f, int n = 1) { g_launches[f] += n; }
+
 // ---- ba_kernels.hip / sweep_dense.hip ----------------------------------------------------------------------------------------
 void launch_track_sweep(const SweepArgs&, int nchunks, bool diag_only, hipStream_t);
 void launch_update_sweep(const SweepArgs&, int nchunks, hipStream_t, const CamUpdArgs* cu = nullptr);

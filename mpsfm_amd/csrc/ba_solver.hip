@@ -170,6 +170,10 @@ static int summary_from_ctl(mpsfm_ba_handle* h, const LmCtl& last, mpsfm_ba_summ
 // host synchronisation before the end — the loop is ONE cooperative launch (local_lm.hip).  Returns kLocalRefused when the launch
 // is not accepted (nothing has changed the state then: the launch chain takes over).
 constexpr int kLocalRefused = 1;
+// Shortest front half of an iteration (ev0 -> ev1, seconds) behind which the back half is enqueued only once the iteration before
+// has been decided (solve_impl).  Twice the shortest front measured on MI355X, 19 us, where the forced split still did not lose
+// (DESIGN.md, round 9): the host's wake-up from the event wait varies from call to call.
+constexpr double kSplitMinFront = 40e-6;
 // MPSFM_PT_HANDOFF=0: the update sweep recomputes the landmark factors everywhere (the comparison path); read per solve
 // MPSFM_CHOL_ENTRY=list: the level launches walk item -> source list -> operands instead of reading launch records (the comparison
 // path of dense_chol.hip); read per solve like the switch above
@@ -237,7 +241,9 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   const auto t_begin = clk::now();
   sum->num_residual_blocks = (int64_t)h->nblocks_global;
   sum->reduced_dim = h->n_user;
+  std::fill(g_launches, g_launches + kLfCount, (int64_t)0);
   auto finish = [&](int rc) {
+    std::copy(g_launches, g_launches + kLfCount, h->last_launches);
     sum->time_total_s = std::chrono::duration<double>(clk::now() - t_begin).count();
     return rc;
   };
@@ -279,9 +285,13 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
 
   // ---- Levenberg-Marquardt loop.  The decisions are taken on the device (k_lm_decide, LmCtl in common.h): the host
   // enqueues iteration i+1 BEFORE it looks at the outcome of iteration i, so the stream never runs dry, and only reads a
-  // pinned copy of the control block one iteration late.  When that copy says the solve is over, the one iteration queued
+  // pinned copy of the control block one iteration late.  When that copy says the solve is over, what is queued
   // ahead returns at once in every kernel.  Every rank of a sharded run sees the same decisions at the same iteration, so
   // all of them enqueue the same sequence of collectives.
+  //   Queued ahead is the whole iteration, or only its front half (sweeps and slab reduction) with the back half (dense solve ...
+  // decision) following once the outcome of iteration i is known to be "go on": the solve then ends with two dead launches instead
+  // of some twenty.  The host has the front's run time to wake up, read the control block and enqueue the first back launch, so
+  // the split is taken where the front measured long enough for that (kSplitMinFront), on one rank and with all chunks dense.
   h->h_ctl[0] = initial_ctl(o);  // x_norm and fixed_cost: from the device scalars
   MPSFM_TRY(hipMemcpyAsync(h->d_ctl, &h->h_ctl[0], sizeof(LmCtl), hipMemcpyHostToDevice, s));
   double* sums = nullptr;
@@ -298,17 +308,21 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   const bool fuse_cam = [] { const char* e = std::getenv("MPSFM_FUSE_CAM"); return !(e && std::atoi(e) == 0); }();
   const bool pt_handoff = pt_handoff_enabled() && h->d_pt_fac != nullptr;  // (allocated where all chunks are dense and no track is long)
   h->ov.entry_list = chol_entry_list();
-  auto enqueue_iteration = [&](int it) -> int {
+  // all chunks dense: the dense sweep adopts an accepted candidate and zeroes the reduced buffer itself (sharded runs too: the
+  // exchange of the reduced buffer comes behind the slab reduction, the camera scalars are the same on every rank)
+  const bool fused_prologue = fuse_prologue && h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks;
+  auto enqueue_front = [&](int it) -> int {
     hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
     MPSFM_TRY(hipEventRecord(ev[0], s));
-    // all chunks dense: the dense sweep adopts an accepted candidate and zeroes the reduced buffer itself (sharded runs too: the
-    // exchange of the reduced buffer comes behind the slab reduction, the camera scalars are the same on every rank)
-    const bool fused_prologue = fuse_prologue && h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks;
     if (!fused_prologue)
       launch_lm_prologue(h->d_ctl, h->d_red, h->red_count, h->nc, h->np, h->d_q, h->d_t, h->d_camtab, h->d_pts, h->d_q2, h->d_t2, h->d_camtab2, h->d_pts2, s);
     if (int rc = run_track_sweep(h, no_radius, ctl, true, fused_prologue, pt_handoff)) return rc;
     if (int rc = allreduce_dev(h, h->d_red, h->red_count)) return rc;
     MPSFM_TRY(hipEventRecord(ev[1], s));
+    return 0;
+  };
+  auto enqueue_back = [&](int it) -> int {
+    hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
     if (int rc = run_dense(h, no_radius, ctl)) return rc;
     MPSFM_TRY(hipEventRecord(ev[2], s));
     // all chunks dense and one rank: the update sweep forms the candidate cameras itself (CamUpdArgs)
@@ -334,27 +348,38 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
     MPSFM_TRY(hipEventRecord(ev[3], s));
     return 0;
   };
+  auto enqueue_iteration = [&](int it) -> int {
+    if (int rc = enqueue_front(it)) return rc;
+    return enqueue_back(it);
+  };
   LmCtl last = h->h_ctl[0];
   if (last.term == kLmRunning) {
     if (int rc = enqueue_iteration(1)) return rc;
     const bool speculate = [] { const char* e = std::getenv("MPSFM_LM_SPECULATE"); return !(e && std::atoi(e) == 0); }();  // per solve: tests switch it
+    // MPSFM_LM_SPLIT=0/1 forces the choice between the whole iteration and its front half ahead (where the split is possible at all)
+    const int force_split = [] { const char* e = std::getenv("MPSFM_LM_SPLIT"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }();
+    const bool can_split = speculate && !sharded(h) && fused_prologue;
     for (int it = 1;; ++it) {
-      if (speculate) { if (int rc = enqueue_iteration(it + 1)) return rc; }  // ahead of the news about iteration `it`
+      // ahead of the news about iteration `it`; the front's length: ev0 -> ev1 of the last iteration read (this handle's previous solve at first)
+      const bool split = can_split && (force_split >= 0 ? force_split == 1 : h->split_front_s >= kSplitMinFront);
+      if (speculate) { if (int rc = split ? enqueue_front(it + 1) : enqueue_iteration(it + 1)) return rc; }
       hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
       MPSFM_TRY(hipEventSynchronize(ev[3]));
       MPSFM_TRY(hipGetLastError());
       float ms;
       MPSFM_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); sum->time_linearize_s += 1e-3 * ms;
+      h->split_front_s = 1e-3 * ms;
       MPSFM_TRY(hipEventElapsedTime(&ms, ev[1], ev[2])); sum->time_dense_s += 1e-3 * ms;
       MPSFM_TRY(hipEventElapsedTime(&ms, ev[2], ev[3])); sum->time_update_s += 1e-3 * ms;
       last = h->h_ctl[it & 1];
       if (o.verbose > 0) print_iteration(it, last, last.fixed_cost);
       if (last.term != kLmRunning) break;
       if (!speculate) { if (int rc = enqueue_iteration(it + 1)) return rc; }
+      else if (split) { if (int rc = enqueue_back(it + 1)) return rc; }
     }
     // the iteration that ended the solve may have been accepted (iteration or radius limit); the copy is idempotent
     launch_lm_accept(h->d_ctl, h->nc, h->np, h->d_q, h->d_t, h->d_camtab, h->d_pts, h->d_q2, h->d_t2, h->d_camtab2, h->d_pts2, s);
-    MPSFM_TRY(hipStreamSynchronize(s));  // the iteration queued ahead has drained (every kernel of it returned at once)
+    MPSFM_TRY(hipStreamSynchronize(s));  // what was queued ahead has drained (every kernel of it returned at once)
   }
   return finish(summary_from_ctl(h, last, sum));
 }

@@ -215,6 +215,7 @@ __global__ __launch_bounds__(256) void k_big_update(double* A, int nt, int j, in
 }
 
 int g_dbg_flags = 0;
+thread_local int64_t g_launches[kLfCount] = {};
 extern "C" void mpsfm_debug_set(int f) { g_dbg_flags = f; }
 // Phase timeline of the factorisation (diagnostics, scripts/dbg_chol_trace.py): when a buffer is registered, the
 // workgroup that owns the diagonal tile of every step stores wall_clock64() (100 MHz) at its phase boundaries:
@@ -920,6 +921,7 @@ __global__ __launch_bounds__(256) void k_inv_y(const double* A, const double* Li
 // ---- host wrappers -----------------------------------------------------------------------------------
 void launch_assemble(const AssembleArgs& a, hipStream_t s) {
   const int64_t ntiles = a.tile_list ? (int64_t)a.n_list : (int64_t)(a.nt + 1) * (a.nt + 2) / 2;
+  count_launch(kLfAssemble);
   hipLaunchKernelGGL(k_assemble, dim3((unsigned)ntiles), dim3(256), 0, s, a);
 }
 
@@ -969,16 +971,19 @@ void launch_dense_solve(double* A, double* work, int nt, int n, double* y, int* 
       if (grid <= 0) continue;
       G.items = lp->d_items + lp->h_launch_start[l];
       G.heads = lp->d_heads + lp->h_launch_start[l];
+      count_launch(kLfCholLevel);
       if (list) hipLaunchKernelGGL(k_chol_level<true>, dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
       else hipLaunchKernelGGL(k_chol_level<false>, dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
     }
     if (Pinv) {
+      count_launch(kLfDenseRest);
       hipLaunchKernelGGL(k_inv_y, dim3(nt, kInvSplit), dim3(256), 0, s, A, LinvT, Pinv, nt, n, y, lp->d_col_slot, ctl);
       return;
     }
     for (int l = 0; l < lp->nlevels; ++l) {
       const int grid = lp->h_back_start[l + 1] - lp->h_back_start[l];
       if (grid <= 0) continue;
+      count_launch(kLfDenseRest);
       hipLaunchKernelGGL(k_back_level, dim3((unsigned)grid), dim3(256), 0, s, A, LinvT, lp->d_back_cols + lp->h_back_start[l], lp->d_struct_start,
                          lp->d_struct_rows, nt, n, zbuf, y, lp->d_col_slot, ctl);
     }

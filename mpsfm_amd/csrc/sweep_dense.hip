@@ -80,11 +80,11 @@ __global__ __launch_bounds__(256) void k_reduce_slabs(const RedDest* __restrict_
 }
 
 void launch_track_sweep_dense(const SweepArgs& a, int nchunks, hipStream_t s) {
-  if (nchunks > 0) hipLaunchKernelGGL(k_track_sweep_dense, dim3(nchunks), dim3(kThreads), 0, s, a);
+  if (nchunks > 0) { count_launch(kLfTrackSweep); hipLaunchKernelGGL(k_track_sweep_dense, dim3(nchunks), dim3(kThreads), 0, s, a); }
 }
 void launch_reduce_slabs(const RedDest* dests, int ndest, const int32_t* srcs, const double* slab, double* Sblk, double* gc, double* wv, double* diagU,
                          const LmCtl* ctl, hipStream_t s) {
-  if (ndest > 0) hipLaunchKernelGGL(k_reduce_slabs, dim3((ndest + 3) / 4), dim3(256), 0, s, dests, ndest, srcs, slab, Sblk, gc, wv, diagU, ctl);
+  if (ndest > 0) { count_launch(kLfReduceSlabs); hipLaunchKernelGGL(k_reduce_slabs, dim3((ndest + 3) / 4), dim3(256), 0, s, dests, ndest, srcs, slab, Sblk, gc, wv, diagU, ctl); }
 }
 
 }  // namespace mpsfm
