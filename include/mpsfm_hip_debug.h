@@ -40,6 +40,10 @@ int mpsfm_debug_graph_union(const uint8_t* adj, int32_t world, int32_t n, uint8_
 
 /* 1: the handle's track sweep hands the landmark factors to its update sweep, 0: the update sweep recomputes them */
 int mpsfm_debug_pt_handoff(mpsfm_ba_handle* h);
+/* 1: a solve on this handle, under the switches set now, adds the slab sums straight into the tiles of the dense solve (no k_assemble), 0: it launches k_assemble */
+int mpsfm_debug_direct_front(mpsfm_ba_handle* h);
+/* one track sweep and slab reduction at `radius` in both forms: the tiles behind k_assemble and the tiles of the direct form ((nt+1)(nt+2)/2 x 1024 doubles each), damp [32 nt] (what the first level launch adds to the diagonal, -1: padding column), live [(nt+1)(nt+2)/2], info: nt, n, live tiles, accumulator and y words not left zero */
+int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_parent, double* A_direct, double* damp, uint8_t* live, int64_t info[4]);
 /* mpsfm_ba_dense_solve_once on the given system (S n x n and rhs in the caller's camera order, zero outside the handle's block pattern) instead of the last sweep's; *failed: a pivot was not positive */
 int mpsfm_debug_dense_solve_given(mpsfm_ba_handle* h, const double* S, const double* rhs, int32_t n, int32_t* failed);
 /* the first `count` 8-byte words of the landmark-diagonal buffer, where the dense sweep leaves its phase stamps under debug flag 128 */

@@ -159,6 +159,23 @@ class BAHandle:
         """True when the handle's track sweep hands the landmark factors to its update sweep, False when that sweep recomputes them."""
         return bool(lib().mpsfm_debug_pt_handoff(self._h))
 
+    def direct_front(self) -> bool:
+        """True when a solve on this handle, under the switches set now, adds the slab sums straight into the tiles of the dense
+        solve; False when it launches k_assemble."""
+        return bool(lib().mpsfm_debug_direct_front(self._h))
+
+    def direct_assemble(self, radius: float = 1e4) -> dict:
+        """One track sweep and slab reduction at `radius` in both forms.  parent / direct: the tiles [tile][32][32] behind k_assemble and
+        of the direct form (undamped, padding diagonals zero); damp [32 nt]: what the first level launch adds to the diagonal, -1 for a padding
+        column (set to 1); live [tile]; nt, n; unzeroed: words of the inverse accumulators and y the direct form did not leave zero."""
+        nt = self.dense_plan()["tile_columns"]
+        ntiles = (nt + 1) * (nt + 2) // 2
+        ap, ad = np.zeros((ntiles, 32, 32)), np.zeros((ntiles, 32, 32))
+        damp, live, info = np.zeros(32 * nt), np.zeros(ntiles, np.uint8), np.zeros(4, np.int64)
+        _check(lib().mpsfm_debug_direct_assemble(self._h, float(radius), ap.ctypes.data, ad.ctypes.data, damp.ctypes.data, live.ctypes.data, info.ctypes.data))
+        assert int(info[0]) == nt
+        return dict(parent=ap, direct=ad, damp=damp, live=live.astype(bool), nt=nt, n=int(info[1]), n_live=int(info[2]), unzeroed=int(info[3]))
+
     def sweep_once(self, radius: float = 1e4) -> float:
         ms = C.c_float(0)
         _check(lib().mpsfm_ba_sweep_once(self._h, radius, C.byref(ms)))

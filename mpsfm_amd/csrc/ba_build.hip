@@ -61,10 +61,35 @@ static int upload_pattern(mpsfm_ba_handle* h, bool use_graph) {
   std::vector<uint8_t> live((size_t)(PL.nt + 1) * (size_t)(PL.nt + 2) / 2, 0);
   for (int32_t id : PL.asm_tiles) live[(size_t)id] = 1;
   LevelPlanDev& D = h->lp;
+  // for the direct form of the front (DirectAsm): the inverse accumulators the roles write, and the columns of the first launch
+  std::vector<int32_t> pinv_tiles;
+  std::vector<uint8_t> level0((size_t)std::max(PL.nt, 1), 0);
+  bool first_is_plain = false;
+  {
+    std::vector<uint8_t> seen(live.size(), 0);
+    for (const CholItem& it : PL.items)
+      if (it.type == kItemRole)
+        for (uint32_t q = 0; q < it.nsrc; ++q) {
+          const int64_t id = lt_tile(PL.rows[(size_t)it.aux + q], it.tk);
+          if (!seen[(size_t)id]) { seen[(size_t)id] = 1; pinv_tiles.push_back((int32_t)id); }
+        }
+    std::sort(pinv_tiles.begin(), pinv_tiles.end());
+    for (int l = 0; l + 1 < (int)PL.launch_start.size(); ++l) {
+      if (PL.launch_start[(size_t)l + 1] <= PL.launch_start[(size_t)l]) continue;
+      first_is_plain = true;  // the first launch that is not empty: panel items without sources only?
+      for (int32_t i = PL.launch_start[(size_t)l]; i < PL.launch_start[(size_t)l + 1]; ++i) {
+        const CholItem& it = PL.items[(size_t)i];
+        if (it.type != kItemPanel || it.nsrc != 0) first_is_plain = false;
+        else if (it.ti == it.tk) level0[it.tk] = 1;
+      }
+      break;
+    }
+  }
   if (int rc = own.upload(&D.d_items, PL.items, &D.d_heads, PL.heads, &D.d_srcs, PL.srcs, &D.d_rows, PL.rows, &D.d_struct_start, PL.struct_start,
                           &D.d_struct_rows, PL.struct_rows, &D.d_back_cols, PL.back_cols, &D.d_asm_tiles, PL.asm_tiles,
-                          &D.d_col_slot, PL.slot_of_col, &D.d_tile_live, live))
+                          &D.d_col_slot, PL.slot_of_col, &D.d_tile_live, live, &D.d_pinv_tiles, pinv_tiles, &D.d_level0, level0))
     return rc;
+  D.n_pinv_tiles = (int32_t)pinv_tiles.size(); D.damp_in_launch0 = first_is_plain;
   if (PL.slot_of_col.empty()) D.d_col_slot = nullptr;  // no indirection (the block stays with the handle)
   level_plan_flags(PL, D);
   D.n_asm = (int32_t)PL.asm_tiles.size(); D.nlevels = PL.nlevels;
@@ -218,6 +243,9 @@ static int alloc_work_buffers(mpsfm_ba_handle* h, const BuildOptions& opt) {
   if ((rc = own.alloc(&h->d_yc, (size_t)std::max(h->n_user, 1)))) return rc;
   if ((rc = own.alloc(&h->d_fail, 1))) return rc;
   MPSFM_TRY(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));
+  // the inverse accumulators no role writes are zero from here on (LevelPlanDev::d_pinv_tiles)
+  if (double* pinv = dense_pinv(h->d_dwork, h->nt, nullptr, nullptr))
+    MPSFM_TRY(hipMemsetAsync(pinv, 0, sizeof(double) * (size_t)h->nt * (size_t)(h->nt + 1) / 2 * 1024, h->stream));
   for (auto& e : h->ev) MPSFM_TRY(own.event(&e, true));
   opt.apply_dense(h->nt, h->plan, h->ov);
   if (h->nt > 64 || h->ov.nb > 0) {
@@ -238,6 +266,48 @@ static int alloc_work_buffers(mpsfm_ba_handle* h, const BuildOptions& opt) {
   MPSFM_TRY(hipMemsetAsync(h->d_ps, 0, nps * 3 * sizeof(double), h->stream));
   MPSFM_TRY(hipMemsetAsync(h->d_yc, 0, (size_t)std::max(h->n_user, 1) * sizeof(double), h->stream));
   MPSFM_TRY(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ---- where the destinations of the slab reduction land in the tiles of the dense solve (DirectAsm in common.h) ---------------------
+// One pass over the block index gives every block of S the first system columns of its two slots; a small kernel then reads them per
+// destination part, whichever builder made the destination table (it may exist on the device only).
+__global__ __launch_bounds__(256) void k_dest_cols(const RedDest* __restrict__ dests, int ndest, const RedCols* __restrict__ blk_cols,
+                                                   const int32_t* __restrict__ col_of_slot, RedDestCols* __restrict__ out) {
+  const int w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= ndest) return;
+  const RedDest D = dests[w];
+  out[w] = RedDestCols{D, D.kind == 2 ? RedCols{col_of_slot[D.dst], 0} : blk_cols[D.dst], {0, 0}};
+}
+// every chunk dense, no long track, one rank, a level plan (the solve adds the conditions that can change from solve to solve)
+static int build_direct_tables(mpsfm_ba_handle* h) {
+  if (sharded(h) || h->nlong != 0 || h->n_dense <= 0 || h->n_dense != h->nchunks || !h->lp.valid || !h->lp.damp_in_launch0 || h->n <= 0 || h->n_red_dests <= 0)
+    return 0;
+  const CholPlan& PL = h->plan;
+  std::vector<int32_t> col((size_t)std::max(h->ncv, 1), 0);
+  for (int i = 0; i < h->ncv; ++i) col[(size_t)i] = PL.col_of_slot.empty() ? 6 * i : PL.col_of_slot[(size_t)i];
+  const BlockSky sky{h->spat.sky_first.data(), h->spat.sky_start.data(), h->spat.sky_index.empty() ? nullptr : h->spat.sky_index.data(), h->ncv};
+  std::vector<RedCols> blk_cols((size_t)std::max<int64_t>(h->spat.nblk, 1), RedCols{0, 0});
+  for (int j = 0; j < h->ncv; ++j)
+    for (int i = sky.index ? 0 : sky.first[j]; i <= j; ++i) {
+      if (!sky_has(sky, i, j)) continue;
+      const int64_t b = sky_block(sky, i, j);
+      if (b < 0 || b >= h->spat.nblk || col[(size_t)i] + 6 > h->n || col[(size_t)j] + 6 > h->n) return fail(MPSFM_EUNSUPPORTED, "internal: block index and plan disagree");
+      blk_cols[(size_t)b] = RedCols{col[(size_t)i], col[(size_t)j]};
+    }
+  RedCols* d_blk_cols = nullptr;
+  int32_t* d_col = nullptr;
+  DeviceBlocks& own = h->own;
+  if (int rc = own.upload(&d_blk_cols, blk_cols, &d_col, col)) return rc;
+  if (int rc = staged_drain()) return rc;
+  RedDestCols* out = nullptr;
+  if (int rc = own.alloc(&out, (size_t)h->n_red_dests)) return rc;
+  if (int rc = own.alloc(&h->d_diag_col, (size_t)h->nt * 32)) return rc;
+  hipLaunchKernelGGL(k_dest_cols, dim3((h->n_red_dests + 255) / 256), dim3(256), 0, h->stream, h->d_red_dests, h->n_red_dests, d_blk_cols, d_col, out);
+  MPSFM_TRY(hipGetLastError());
+  MPSFM_TRY(hipStreamSynchronize(h->stream));
+  own.drop(d_blk_cols); own.drop(d_col);
+  h->d_red_cols = out;
   return 0;
 }
 
@@ -364,6 +434,8 @@ static int build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P) {
   lap("upload tables");
   if (int rc = alloc_work_buffers(h, opt)) return rc;
   lap("allocate work buffers");
+  if (int rc = build_direct_tables(h)) return rc;
+  lap("direct assembly tables");
   return 0;
 }
 

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "../../include/mpsfm_hip_debug.h"
@@ -88,6 +89,74 @@ int mpsfm_ba_dense_plan(mpsfm_ba_handle* h, int64_t info[10]) {
 // 1: the handle's track sweep hands the landmark factors to its update sweep (every chunk dense, no long track; MPSFM_PT_HANDOFF=0
 // still selects the recompute form per solve), 0: its update sweep recomputes them
 int mpsfm_debug_pt_handoff(mpsfm_ba_handle* h) { return h && h->d_pt_fac != nullptr ? 1 : 0; }
+
+// 1: a solve on this handle, under the switches set now, takes the direct form of the front (the slab reduction adds into the tiles of
+// the dense solve, no k_assemble), 0: it launches k_assemble
+int mpsfm_debug_direct_front(mpsfm_ba_handle* h) {
+  return h && direct_front(h) ? 1 : 0;
+}
+
+// Test hook (tests/test_gpu_direct_assemble.py): one track sweep and slab reduction at the current state and `radius` in both forms.
+// A_parent: the tiles k_assemble leaves behind Sblk; A_direct: the tiles the direct slab reduction leaves, after the sweep's own zero
+// fill — both (nt + 1)(nt + 2) / 2 x 1024 doubles; the tiles start as zeros (dead) and NaNs (live), the inverse accumulators the roles
+// write, y and diag U by column as NaNs.  damp [32 nt]: what the first level launch adds to the diagonal of column g, -1: a padding
+// column, set to 1.
+// live [(nt + 1)(nt + 2) / 2]: 1 for the tiles the factorisation reads.  info: nt, n, live tiles, words of the inverse accumulators and
+// of y that the direct form did not leave exactly zero.
+int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_parent, double* A_direct, double* damp, uint8_t* live, int64_t info[4]) {
+  if (!h || !A_parent || !A_direct || !damp || !live || !info) return fail(MPSFM_EINVAL, "handle or output is NULL");
+  if (!mpsfm_debug_direct_front(h)) return fail(MPSFM_EUNSUPPORTED, "the handle does not take the direct form of the front");
+  MPSFM_TRY(hipSetDevice(h->device));
+  if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
+  hipStream_t s = h->stream;
+  const int nt = h->nt;
+  const size_t ntiles = (size_t)(nt + 1) * (size_t)(nt + 2) / 2;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> img(ntiles * 1024, 0.0);
+  std::fill(live, live + ntiles, (uint8_t)0);
+  for (int32_t id : h->plan.asm_tiles) { live[(size_t)id] = 1; std::fill(img.begin() + (size_t)id * 1024, img.begin() + ((size_t)id + 1) * 1024, nan); }
+  // the parent's form: zeroed reduced buffer, sweep, reduction into Sblk, k_assemble
+  MPSFM_TRY(hipMemcpyAsync(h->d_A, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice, s));
+  if (int rc = run_track_sweep(h, radius)) return rc;
+  run_assemble(h, radius);
+  MPSFM_TRY(hipMemcpyAsync(A_parent, h->d_A, sizeof(double) * img.size(), hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipStreamSynchronize(s));
+  // the direct form: the sweep zeroes, the reduction adds into the tiles
+  SweepArgs a = sweep_args(h, radius);
+  a.adopt_on = 1; a.adopt_nc = h->nc;  // (no control block: nothing is adopted, the zero fill runs)
+  direct_zero_args(h, a);
+  MPSFM_TRY(hipMemcpyAsync(h->d_A, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice, s));
+  for (int k = 0; k < 2; ++k) MPSFM_TRY(hipMemsetAsync(a.zero_p[k], 0xff, sizeof(double) * (size_t)a.zero_n[k], s));
+  // the inverse accumulators: the ones the roles write as NaNs, the others are zero since the handle's creation and stay so
+  const size_t npinv = (size_t)nt * (size_t)(nt + 1) / 2 * 1024;
+  std::vector<double> pimg(npinv, 0.0);
+  for (const CholItem& it : h->plan.items)
+    if (it.type == kItemRole)
+      for (uint32_t q = 0; q < it.nsrc; ++q) {
+        const size_t id = (size_t)lt_tile(h->plan.rows[(size_t)it.aux + q], it.tk);
+        std::fill(pimg.begin() + id * 1024, pimg.begin() + (id + 1) * 1024, nan);
+      }
+  MPSFM_TRY(hipMemcpyAsync(a.zero_P, pimg.data(), sizeof(double) * npinv, hipMemcpyHostToDevice, s));
+  launch_track_sweep_dense(a, h->n_dense, s);
+  const DirectAsm da = direct_asm(h);
+  launch_reduce_slabs(h->d_red_dests, h->n_red_dests, h->d_red_srcs, h->d_slab, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, nullptr, s, &da);
+  std::vector<double> pinv(npinv), y((size_t)std::max(h->n_user, 1)), dcol((size_t)nt * 32);
+  MPSFM_TRY(hipMemcpyAsync(A_direct, h->d_A, sizeof(double) * img.size(), hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipMemcpyAsync(pinv.data(), a.zero_P, sizeof(double) * pinv.size(), hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipMemcpyAsync(y.data(), h->d_yc, sizeof(double) * (size_t)h->n_user, hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipMemcpyAsync(dcol.data(), h->d_diag_col, sizeof(double) * dcol.size(), hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipStreamSynchronize(s));
+  MPSFM_TRY(hipGetLastError());
+  h->last_radius = radius;
+  const int32_t* slot_of_col = h->plan.slot_of_col.empty() ? nullptr : h->plan.slot_of_col.data();
+  for (int g = 0; g < nt * 32; ++g)
+    damp[g] = vec_index(slot_of_col, g, h->n) < 0 ? -1.0 : std::min(std::max(dcol[(size_t)g], h->opt.min_lm_diagonal), h->opt.max_lm_diagonal) / radius;
+  int64_t bad = 0;
+  for (double v : pinv) bad += v == 0.0 ? 0 : 1;
+  for (int i = 0; i < h->n_user; ++i) bad += y[(size_t)i] == 0.0 ? 0 : 1;
+  info[0] = nt; info[1] = h->n; info[2] = (int64_t)h->plan.asm_tiles.size(); info[3] = bad;
+  return 0;
+}
 
 int mpsfm_ba_sweep_once(mpsfm_ba_handle* h, double radius, float* elapsed_ms) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");

@@ -38,6 +38,9 @@ struct mpsfm_ba_handle {
   double* d_slab = nullptr;         // slabs of the dense chunks
   mpsfm::RedDest* d_red_dests = nullptr;   // slab reduction: destination parts and their sources
   int32_t* d_red_srcs = nullptr;
+  mpsfm::RedDestCols* d_red_cols = nullptr;  // direct form of the slab reduction (DirectAsm): where every destination part lands; NULL: the
+                                           // handle has a general chunk, a long track, several ranks or no level plan and keeps k_assemble
+  double* d_diag_col = nullptr;            // [32 nt] diag U by system column, for the damping in the first level launch
   int n_red_dests = 0;
   int64_t n_red_srcs = 0, n_chunk_cams = 0, n_blk_desc = 0, n_blk_ent_start = 0, n_ents = 0;  // table sizes (diagnostics: mpsfm_debug_table)
   bool built_on_device = false;
@@ -130,9 +133,18 @@ SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullp
 int prepare_scales(mpsfm_ba_handle* h);
 // one track sweep at the current state: fills the reduced buffer and its scalar tail (inside the solve loop the prologue kernel
 // has zeroed the buffer; single-rank runs reduce the partials with the decision)
-int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool in_loop = false, bool adopt = false, bool handoff = false);
+int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool in_loop = false, bool adopt = false, bool handoff = false,
+                    bool direct = false);
 void run_assemble(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);  // the first launch of run_dense (h->n > 0)
-int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);
+// direct: the track sweep ran with direct_front() — A holds the undamped system, no k_assemble, the first level launch damps
+int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool direct = false);
+// May this solve take the direct form of the front (DirectAsm in common.h)?  The handle's tables allow it, the solve is level-scheduled
+// with inverse accumulators, and MPSFM_ASSEMBLE=launch (read per solve) does not force k_assemble.
+bool direct_front(mpsfm_ba_handle* h);
+DirectAsm direct_asm(const mpsfm_ba_handle* h);
+// the zero fill of the direct form, dealt over the dense sweep's workgroups (SweepArgs::zero_*): camera vectors, y, diag U by column,
+// the inverse accumulators the roles write and the live tiles of A
+void direct_zero_args(mpsfm_ba_handle* h, SweepArgs& a);
 bool chol_entry_list();  // MPSFM_CHOL_ENTRY=list, read per solve into DenseOverlap::entry_list
 
 // the single-launch solver's skew hook (mpsfm_debug_local_skew): process-wide like g_dbg_flags, read when a solve is launched

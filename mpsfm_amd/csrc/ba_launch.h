@@ -27,8 +27,9 @@ inline void count_launch(LaunchFamily f, int n = 1) { g_launches[f] += n; }
 void launch_track_sweep(const SweepArgs&, int nchunks, bool diag_only, hipStream_t);
 void launch_update_sweep(const SweepArgs&, int nchunks, hipStream_t, const CamUpdArgs* cu = nullptr);
 void launch_track_sweep_dense(const SweepArgs&, int nchunks, hipStream_t);
+// direct (may be NULL): the sums go straight into the tiles of the dense solve (DirectAsm in common.h), Sblk is not written
 void launch_reduce_slabs(const RedDest* dests, int ndest, const int32_t* srcs, const double* slab, double* Sblk, double* gc, double* wv, double* diagU,
-                         const LmCtl* ctl, hipStream_t);
+                         const LmCtl* ctl, hipStream_t, const DirectAsm* direct = nullptr);
 void launch_cost_records(const CostArgs&, int nblocks, hipStream_t);
 void launch_reduce_cols(const double* part, int64_t rows, int stride, int ncols, uint32_t max_mask, double* out, hipStream_t,
                         double* out2 = nullptr, int gmax_slot = -1);
@@ -56,8 +57,10 @@ void launch_gmax_from_slots(const double* redsc, double* scal, hipStream_t);
 // ---- dense_chol.hip ----------------------------------------------------------------------------------------------------------
 extern int g_dbg_flags;  // bits 0-7 dense-solve ablations, bits 8-15 track-sweep ablations (mpsfm_debug_set)
 void launch_assemble(const AssembleArgs&, hipStream_t);
+// damp (may be NULL; level-scheduled path only): A comes undamped from the direct slab reduction, the first level launch adds the damping
+// (DampArgs; the caller has seen LevelPlanDev::damp_in_launch0)
 void launch_dense_solve(double* A, double* work, int nt, int n, double* y, int* fail, hipStream_t, DenseOverlap* ov, const LevelPlanDev* lp,
-                        const LmCtl* ctl = nullptr);
+                        const LmCtl* ctl = nullptr, const DampArgs* damp = nullptr);
 bool dense_level(const DenseOverlap* ov, const LevelPlanDev* lp);
 int dense_plain_max_tiles();
 int dense_inv_rows();

@@ -80,14 +80,31 @@ int prepare_scales(mpsfm_ba_handle* h) {
 
 // the full track sweep: dense chunks through their slabs (k_track_sweep_dense + k_reduce_slabs), the others and the long
 // tracks through the general kernels (global atomics); all of them add into the zeroed reduced buffer
-static void launch_sweeps(mpsfm_ba_handle* h, SweepArgs a, hipStream_t s) {
+static void launch_sweeps(mpsfm_ba_handle* h, SweepArgs a, hipStream_t s, bool direct) {
   launch_track_sweep_dense(a, h->n_dense, s);
-  launch_reduce_slabs(h->d_red_dests, h->n_red_dests, h->d_red_srcs, h->d_slab, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, a.ctl, s);
+  const DirectAsm da = direct ? direct_asm(h) : DirectAsm{};
+  launch_reduce_slabs(h->d_red_dests, h->n_red_dests, h->d_red_srcs, h->d_slab, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, a.ctl, s, direct ? &da : nullptr);
   a.chunk0 = h->n_dense;
   launch_track_sweep(a, h->nchunks - h->n_dense, false, s);
 }
 
-int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in_loop, bool adopt, bool handoff) {
+bool direct_front(mpsfm_ba_handle* h) {
+  const char* e = std::getenv("MPSFM_ASSEMBLE");
+  if (e && std::strcmp(e, "launch") == 0) return false;
+  const char* f = std::getenv("MPSFM_FUSE_PROLOGUE");  // the zero fill rides on the sweep's fused prologue (solve_impl)
+  if (f && std::atoi(f) == 0) return false;
+  return h->d_red_cols != nullptr && !sharded(h) && h->n > 0 && dense_level(&h->ov, &h->lp) && dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp) != nullptr;
+}
+DirectAsm direct_asm(const mpsfm_ba_handle* h) { return DirectAsm{h->d_red_cols, h->d_A, h->d_diag_col, h->nt}; }
+void direct_zero_args(mpsfm_ba_handle* h, SweepArgs& a) {
+  a.red = h->d_gc; a.nred = h->red_count - h->sblk_count;  // Sblk is neither written nor read
+  a.zero_p[0] = h->d_yc; a.zero_n[0] = h->n_user;
+  a.zero_p[1] = h->d_diag_col; a.zero_n[1] = (int64_t)h->nt * 32;
+  a.zero_A = h->d_A; a.zero_tiles = h->lp.d_asm_tiles; a.zero_ntiles = h->lp.n_asm;
+  a.zero_P = dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp); a.zero_ptiles = h->lp.d_pinv_tiles; a.zero_nptiles = h->lp.n_pinv_tiles;
+}
+
+int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in_loop, bool adopt, bool handoff, bool direct) {
   hipStream_t s = h->stream;
   if (!in_loop) launch_zero(h->d_red, h->red_count, ctl, s);
   SweepArgs a = sweep_args(h, radius, ctl);
@@ -95,9 +112,10 @@ int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in
     a.adopt_on = 1; a.adopt_nc = h->nc;
     a.pts_rw = h->d_pts; a.q_rw = h->d_q; a.t_rw = h->d_t; a.camtab_rw = h->d_camtab; a.q2 = h->d_q2; a.t2 = h->d_t2;
     a.red = h->d_red; a.nred = h->red_count;
+    if (direct) direct_zero_args(h, a);
   }
   if (handoff) a.pt_fac = h->d_pt_fac;
-  launch_sweeps(h, a, s);
+  launch_sweeps(h, a, s, direct && adopt);
   if (h->nchunks + h->nlong > 0 && !(in_loop && !sharded(h)))
     launch_reduce_cols(h->d_part, h->nchunks + h->nlong, 4, 3, 1u << 2, h->d_redsc, s, sharded(h) ? nullptr : h->d_scal + U_X_COST,
                        sharded(h) ? (h->opt.rank > 0 ? h->opt.rank : 0) % kMaxRankSlots : -1);
@@ -117,11 +135,12 @@ void run_assemble(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
   launch_assemble(as, h->stream);
 }
 
-int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
+int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool direct) {
   // d_fail is zero here: cleared at creation and re-armed by k_cam_update after every read
   if (h->n > 0) {
-    run_assemble(h, radius, ctl);
-    launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, h->stream, &h->ov, &h->lp, ctl);
+    if (!direct) run_assemble(h, radius, ctl);
+    const DampArgs damp{h->d_diag_col, h->lp.d_col_slot, h->lp.d_level0, h->n, h->opt.min_lm_diagonal, h->opt.max_lm_diagonal, radius};
+    launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, h->stream, &h->ov, &h->lp, ctl, direct ? &damp : nullptr);
   }
   return 0;
 }
@@ -311,19 +330,21 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   // all chunks dense: the dense sweep adopts an accepted candidate and zeroes the reduced buffer itself (sharded runs too: the
   // exchange of the reduced buffer comes behind the slab reduction, the camera scalars are the same on every rank)
   const bool fused_prologue = fuse_prologue && h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks;
+  // ... and one rank, level-scheduled: the slab reduction adds straight into the tiles of the dense solve, no k_assemble (DirectAsm)
+  const bool direct = fused_prologue && direct_front(h);  // (d_red_cols exists only where every chunk is dense and no track is long)
   auto enqueue_front = [&](int it) -> int {
     hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
     MPSFM_TRY(hipEventRecord(ev[0], s));
     if (!fused_prologue)
       launch_lm_prologue(h->d_ctl, h->d_red, h->red_count, h->nc, h->np, h->d_q, h->d_t, h->d_camtab, h->d_pts, h->d_q2, h->d_t2, h->d_camtab2, h->d_pts2, s);
-    if (int rc = run_track_sweep(h, no_radius, ctl, true, fused_prologue, pt_handoff)) return rc;
+    if (int rc = run_track_sweep(h, no_radius, ctl, true, fused_prologue, pt_handoff, direct)) return rc;
     if (int rc = allreduce_dev(h, h->d_red, h->red_count)) return rc;
     MPSFM_TRY(hipEventRecord(ev[1], s));
     return 0;
   };
   auto enqueue_back = [&](int it) -> int {
     hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
-    if (int rc = run_dense(h, no_radius, ctl)) return rc;
+    if (int rc = run_dense(h, no_radius, ctl, direct)) return rc;
     MPSFM_TRY(hipEventRecord(ev[2], s));
     // all chunks dense and one rank: the update sweep forms the candidate cameras itself (CamUpdArgs)
     const bool fused_cam = fuse_cam && fused_prologue;

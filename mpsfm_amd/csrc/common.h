@@ -73,6 +73,11 @@ __host__ __device__ inline int64_t slab_doubles(int ncam) { return (int64_t)(nca
 // One destination of the slab reduction: a 6x6 block of S (kind 0: all 36 entries, 1: a diagonal block, upper triangle) or a camera's
 // vectors (kind 2).  Destinations with many sources are split into parts (every part adds atomically into the zeroed buffer).
 struct RedDest { int32_t kind; int32_t dst; int32_t s0, s1; };
+// Where a destination lands in the tile-major system of the dense solve (the direct form of the slab reduction): the first system
+// column of its two slots, lower slot first (a camera's vectors: its one slot's, then 0) — from the plan's col_of_slot, per handle.
+struct RedCols { int32_t c0, c1; };
+// ... and the table the direct form reads instead of RedDest: the destination with its columns, one 32-byte load
+struct alignas(32) RedDestCols { RedDest d; RedCols c; int32_t pad_[2]; };
 
 // A landmark whose track does not fit a chunk (more than kObsMax records or kLocalCamsMax cameras)
 // is swept by a workgroup of its own that strides over the records (k_long_track_sweep).
@@ -377,6 +382,11 @@ struct SweepArgs {
   double* pts_rw; double* q_rw; double* t_rw; double* camtab_rw;
   const double* q2; const double* t2;
   double* red; int64_t nred;
+  // direct form (DirectAsm): instead of the whole reduced buffer the workgroups zero what k_assemble would zero or overwrite — the
+  // camera vectors (red / nred then cover gc | wv | diagU | scalars only), these blocks, and the listed tiles of the system
+  double* zero_p[2]; int64_t zero_n[2];  // y | column-indexed diag U
+  double* zero_A; const int32_t* zero_tiles; int32_t zero_ntiles;     // tiles of A (LevelPlanDev::d_asm_tiles)
+  double* zero_P; const int32_t* zero_ptiles; int32_t zero_nptiles;   // inverse accumulators (LevelPlanDev::d_pinv_tiles)
   // hand-off of the landmark factors from the dense track sweep to the update sweep of the same iteration (all chunks dense, no
   // long tracks; NULL: the update sweep forms V_p, its factor and g_p again): 9 doubles per landmark, F = chol(V + D)^-1 as
   // spd3_inv_factor packs it, then g_p.  F[0] == 0 marks a failed factorisation; the slot of a constant landmark is never written
@@ -433,9 +443,33 @@ struct LevelPlanDev {
   const int32_t* d_col_slot = nullptr;   // AssembleArgs::col_slot
   const int32_t* d_asm_tiles = nullptr;
   const uint8_t* d_tile_live = nullptr;  // [(nt+1)(nt+2)/2] 1 for the tiles in d_asm_tiles
+  const int32_t* d_pinv_tiles = nullptr; // packed ids of the inverse accumulators the roles write: the others stay zero from the handle's
+  int32_t n_pinv_tiles = 0;              // creation on (k_assemble zeroes all of them, the direct form these)
+  const uint8_t* d_level0 = nullptr;     // [nt] 1: the tile column is factored in the first launch
+  bool damp_in_launch0 = false;          // the first launch holds panel items without sources only (DampArgs)
   int32_t n_asm = 0, nlevels = 0;
   const int32_t* h_launch_start = nullptr;  // host: [nlevels + 1]
   const int32_t* h_back_start = nullptr;    // host: [nlevels + 1]
+};
+
+// The direct form of the front of the dense solve (every chunk dense, one rank, inverse propagation): k_reduce_slabs adds the sums
+// of the slabs straight into the tiles of A — the element (R, C), R >= C, of the system at lt_tile(R >> 5, C >> 5) * 1024 +
+// (R & 31) * 32 + (C & 31), mirrored inside a diagonal tile — and wv - gc into row 0 of tile row nt; no Sblk, no k_assemble.  A stays
+// undamped: the first level launch adds the damping (DampArgs), from diag U by COLUMN — its panel items to the diagonal tile they
+// factor, in registers, and a few workgroups more to the diagonal tiles of all later columns in memory (nothing else touches those in
+// that launch: the first level has no trailing items), so that the later launches run the code they always ran.
+struct DirectAsm {
+  const RedDestCols* dests;  // per destination part: RedDest and where it lands
+  double* A;
+  double* diag_col;      // [32 nt] diag U by system column (padding columns stay zero)
+  int32_t nt;
+};
+struct DampArgs {
+  const double* diag_col;   // NULL: A is damped already (k_assemble)
+  const int32_t* col_slot;  // LevelPlanDev::d_col_slot (NULL: no padding columns inside the system)
+  const uint8_t* level0;    // [nt] 1: the tile column is factored in the first launch (LevelPlanDev::d_level0)
+  int32_t n;
+  double min_diag, max_diag, radius;  // radius: without a control block
 };
 
 struct AssembleArgs {

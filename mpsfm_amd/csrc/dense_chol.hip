@@ -438,7 +438,45 @@ struct LevelArgs {
   const LmCtl* ctl;
   long long* trace;     // phase timeline (mpsfm_debug_set_chol_trace), NULL: off
   int32_t panel_waves;  // waves that factor a panel: kWgWaves or 1 (MPSFM_CHOL_PANEL_WAVES)
+  DampArgs damp;        // direct form of the front (DirectAsm), first launch only (k_chol_level<., true>)
+  int32_t nitems;       // ... whose workgroups beyond the items damp the diagonal tiles of the later columns
 };
+
+// The damping of the direct form (DampArgs; the first level launch, k_chol_level<., true>): A comes undamped from the slab reduction.
+//   A panel item of that launch adds clamp(diag U, min, max) / radius to the diagonal of the tile it factors in front of the tile's way
+// to LDS (a padding column: 1.0, its row of A is zero).  A quadrant on the diagonal (mi == ni) keeps element (q, q) in the lane with
+// (lane & 15) == (lane >> 4) + 4 r, register r.  Three independent loads per lane — diag U by column, the column's slot, the radius —
+// without a branch in front of them, so they travel with the tile requests.
+//   The workgroups behind the items do the same in memory for the columns of all later launches, one thread per column (damp_columns):
+// nothing else reads or writes those diagonal tiles in the first launch, which has no trailing items.
+struct DampReq { double du, radius; int32_t cs; };
+__device__ __forceinline__ void damp_request(const DampArgs& P, const LmCtl* ctl, int g, DampReq& q) {
+  q.du = P.diag_col[g];
+  const int32_t cs = *(P.col_slot ? P.col_slot + min(g, P.n - 1) : reinterpret_cast<const int32_t*>(P.diag_col));
+  q.radius = lm_radius_chain(ctl, P.diag_col, P.radius);
+  q.cs = g >= P.n ? -1 : (P.col_slot ? cs : 0);
+}
+__device__ __forceinline__ double damp_value(const DampArgs& P, const DampReq& q, double d) {
+  return q.cs < 0 ? 1.0 : d + fmin(fmax(q.du, P.min_diag), P.max_diag) / q.radius;
+}
+__device__ __forceinline__ void damp_apply(const DampArgs& P, const DampReq& q, int mi, int ni, int lane, v4d& dacc) {
+  if (mi != ni || ((lane & 15) & 3) != (lane >> 4)) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (r == ((lane & 15) >> 2)) dacc[r] = damp_value(P, q, dacc[r]);
+}
+__device__ __forceinline__ void damp_columns(const DampArgs& P, const LmCtl* ctl, double* A, int nt, int g) {
+  const int32_t term = lm_term_chain(ctl, P.diag_col);
+  const bool mine = g < nt * kTile;
+  const int gc = mine ? g : 0, tk = gc >> 5, c = gc & 31;
+  const uint8_t in_panel = P.level0[tk];
+  double* d = A + lt_tile(tk, tk) * kTileElems + c * kTile + c;
+  const double v = *d;
+  DampReq q;
+  damp_request(P, ctl, gc, q);
+  if (ctl != nullptr && lm_over_chain(term)) return;
+  if (mine && !in_panel) *d = damp_value(P, q, v);
+}
 
 // The entry of a level launch.  Every workgroup is a chain of latencies before its first tile is on its way, and the launch ends
 // with its slowest workgroup.  Behind the kernel arguments the entry makes one trip for the item's launch record (64 bytes, one
@@ -506,7 +544,7 @@ __device__ __forceinline__ void quad_operand_lds(const double* S, int lane, int 
   for (int s = 0; s < 4; ++s) { const double2 x = p[s]; o[2 * s] = x.x; o[2 * s + 1] = x.y; }
 }
 
-template <bool kList>
+template <bool kList, bool kDamp>
 __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
   __shared__ double s_T[kTile][kTile + 1];
   __shared__ double s_X[kTile][kTile + 1];
@@ -515,6 +553,12 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int mi = wave & 1, ni = wave >> 1;  // this wave's quadrant
   double* A = G.A;
+  if constexpr (kDamp) {
+    if ((int)blockIdx.x >= G.nitems) {  // (workgroup-uniform)
+      damp_columns(G.damp, G.ctl, A, G.nt, ((int)blockIdx.x - G.nitems) * kStepThreads + (int)threadIdx.x);
+      return;
+    }
+  }
   int type, ti, tk, nsrc;
   int32_t term = kLmRunning;
   const bool has_ctl = !kList && G.ctl != nullptr;  // `term` holds the control block's word
@@ -595,6 +639,8 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
   {
     v4d dacc, xacc;
     const double* D = A + lt_tile(tk, tk) * kTileElems;
+    [[maybe_unused]] DampReq dq;
+    if constexpr (kDamp) damp_request(G.damp, G.ctl, tk * kTile + 16 * ni + (lane & 15), dq);
     if constexpr (kList) {
       quad_load(D, kTile, lane, mi, ni, dacc);
       if (!diag) quad_load(C, kTile, lane, mi, ni, xacc);
@@ -663,6 +709,7 @@ __global__ __launch_bounds__(kStepThreads) void k_chol_level(LevelArgs G) {
         }
       }
     }
+    if constexpr (kDamp) damp_apply(G.damp, dq, mi, ni, lane, dacc);
     quad_store(&s_T[0][0], kTile + 1, lane, mi, ni, dacc);
     if (diag) {  // identity: x L^-T = row of L^-T
 #pragma unroll
@@ -957,23 +1004,32 @@ double* dense_pinv(double* work, int nt, const DenseOverlap* ov, const LevelPlan
 // columns of the NEXT panel are updated on the main stream (the factorisation needs them next), the columns
 // beyond run on the second stream under the next panel's factorisation steps.
 void launch_dense_solve(double* A, double* work, int nt, int n, double* y, int* fail, hipStream_t s, DenseOverlap* ov, const LevelPlanDev* lp,
-                        const LmCtl* ctl) {
+                        const LmCtl* ctl, const DampArgs* damp) {
   if (nt <= 0) return;
   double* LinvT = work;
   double* zbuf = work + (size_t)nt * kTileElems;
   const int panel_waves = (ov ? ov->panel_waves : kPanelWavesDefault) == 1 ? 1 : kWgWaves;
   if (dense_level(ov, lp)) {
     double* Pinv = dense_pinv(work, nt, ov, lp);
-    LevelArgs G{A, LinvT, Pinv, nullptr, lp->d_srcs, lp->d_rows, nullptr, fail, nt, g_dbg_flags, ctl, g_chol_trace, panel_waves};
+    LevelArgs G{A, LinvT, Pinv, nullptr, lp->d_srcs, lp->d_rows, nullptr, fail, nt, g_dbg_flags, ctl, g_chol_trace, panel_waves, damp ? *damp : DampArgs{}, 0};
     const bool list = ov && ov->entry_list;
+    bool damped = damp == nullptr;  // the first launch damps (the caller has seen LevelPlanDev::damp_in_launch0)
     for (int l = 0; l < lp->nlevels; ++l) {
       const int grid = lp->h_launch_start[l + 1] - lp->h_launch_start[l];
       if (grid <= 0) continue;
       G.items = lp->d_items + lp->h_launch_start[l];
       G.heads = lp->d_heads + lp->h_launch_start[l];
       count_launch(kLfCholLevel);
-      if (list) hipLaunchKernelGGL(k_chol_level<true>, dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
-      else hipLaunchKernelGGL(k_chol_level<false>, dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
+      if (!damped) {
+        G.nitems = grid;
+        const unsigned g2 = (unsigned)(grid + (nt * kTile + kStepThreads - 1) / kStepThreads);
+        if (list) hipLaunchKernelGGL((k_chol_level<true, true>), dim3(g2), dim3(kStepThreads), 0, s, G);
+        else hipLaunchKernelGGL((k_chol_level<false, true>), dim3(g2), dim3(kStepThreads), 0, s, G);
+        damped = true;
+        continue;
+      }
+      if (list) hipLaunchKernelGGL((k_chol_level<true, false>), dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
+      else hipLaunchKernelGGL((k_chol_level<false, false>), dim3((unsigned)grid), dim3(kStepThreads), 0, s, G);
     }
     if (Pinv) {
       count_launch(kLfDenseRest);

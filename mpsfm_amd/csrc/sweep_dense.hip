@@ -43,17 +43,43 @@ __global__ __launch_bounds__(kThreads, 3) void k_track_sweep_dense(SweepArgs A) 
 }
 
 // One wave per destination part: sums the part's slab sources in table order and adds the sum into the (zeroed) reduced buffer.
-__global__ __launch_bounds__(256) void k_reduce_slabs(const RedDest* __restrict__ dests, int ndest, const int32_t* __restrict__ srcs,
+// kDirect (DirectAsm in common.h): the blocks of S go to the tiles of A instead of Sblk — where an element lands is arithmetic on
+// the first columns of the destination's two slots, requested beside the destination and worked out under the sums —, the camera
+// vectors also as wv - gc to the right-hand-side row and diag U by column for the panels' damping.
+// (256, 8): eight waves per SIMD in either form — the parts of C3 fill the device once at that occupancy, and at seven a second round
+// of workgroups repeats the whole chain of dependent loads.
+template <bool kDirect>
+__global__ __launch_bounds__(256, kDirect ? 8 : 1) void k_reduce_slabs(const RedDest* __restrict__ dests, int ndest, const int32_t* __restrict__ srcs,
                                                       const double* __restrict__ slab, double* Sblk, double* gc, double* wv, double* diagU,
-                                                      const LmCtl* ctl) {
+                                                      const LmCtl* ctl, DirectAsm T) {
   if (lm_over(ctl)) return;
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (w >= ndest) return;
-  const RedDest D = dests[w];
+  RedDest D;
+  [[maybe_unused]] RedCols cc{0, 0};
+  if constexpr (kDirect) { const RedDestCols X = T.dests[w]; D = X.d; cc = X.c; }
+  else D = dests[w];
   bool active;
   if (D.kind == 2) active = lane < 18;
   else if (D.kind == 1) { const int ra = lane / 6, cb = lane - 6 * ra; active = lane < 36 && cb >= ra; }
   else active = lane < 36;
+  // the element's place in A and, inside a diagonal tile, its mirror image's (32-bit: the direct form is taken up to 64 tile columns);
+  // camera vectors: the system column.  Every destination lies in a tile the factorisation reads (the plan's tile pattern holds every
+  // pair of cameras that share a landmark), so no look at the table of live tiles.
+  [[maybe_unused]] int32_t o0 = 0, o1 = -1, col = 0;
+  if constexpr (kDirect) {
+    if (D.kind == 2) {
+      col = cc.c0 + lane % 6;
+      o0 = (int32_t)lt_tile(T.nt, col >> 5) * 1024 + (col & 31);  // row 0 of the right-hand-side tile
+    } else {
+      const int a = lane / 6, b = lane - 6 * a;
+      const int r = cc.c0 + a, c = cc.c1 + b;  // the stored block is (lower slot, higher slot); a diagonal block holds its upper triangle
+      const int R = r > c ? r : c, C = r > c ? c : r;
+      const int32_t id = active ? (int32_t)lt_tile(R >> 5, C >> 5) : 0;
+      o0 = id * 1024 + (R & 31) * 32 + (C & 31);
+      if ((R >> 5) == (C >> 5) && R != C) o1 = id * 1024 + (C & 31) * 32 + (R & 31);
+    }
+  }
   double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int s = D.s0;
   for (; s + 8 <= D.s1; s += 8) {
@@ -72,10 +98,15 @@ __global__ __launch_bounds__(256) void k_reduce_slabs(const RedDest* __restrict_
   if (D.kind == 2) {
     double* base = lane < 6 ? gc : (lane < 12 ? wv : diagU);
     atomicAdd(&base[(size_t)D.dst * 6 + (lane % 6)], v);
-  } else {
-    atomicAdd(&Sblk[(size_t)D.dst * 36 + lane], v);
-    if (D.kind == 1) {  // nothing: diag U travels in the camera vectors
+    if constexpr (kDirect) {
+      if (lane >= 12) atomicAdd(&T.diag_col[col], v);
+      else atomicAdd(&T.A[o0], lane < 6 ? -v : v);  // rhs = wv - gc
     }
+  } else if constexpr (kDirect) {
+    atomicAdd(&T.A[o0], v);
+    if (o1 >= 0) atomicAdd(&T.A[o1], v);
+  } else {
+    atomicAdd(&Sblk[(size_t)D.dst * 36 + lane], v);  // (a diagonal block: diag U travels in the camera vectors)
   }
 }
 
@@ -83,8 +114,11 @@ void launch_track_sweep_dense(const SweepArgs& a, int nchunks, hipStream_t s) {
   if (nchunks > 0) { count_launch(kLfTrackSweep); hipLaunchKernelGGL(k_track_sweep_dense, dim3(nchunks), dim3(kThreads), 0, s, a); }
 }
 void launch_reduce_slabs(const RedDest* dests, int ndest, const int32_t* srcs, const double* slab, double* Sblk, double* gc, double* wv, double* diagU,
-                         const LmCtl* ctl, hipStream_t s) {
-  if (ndest > 0) { count_launch(kLfReduceSlabs); hipLaunchKernelGGL(k_reduce_slabs, dim3((ndest + 3) / 4), dim3(256), 0, s, dests, ndest, srcs, slab, Sblk, gc, wv, diagU, ctl); }
+                         const LmCtl* ctl, hipStream_t s, const DirectAsm* direct) {
+  if (ndest <= 0) return;
+  count_launch(kLfReduceSlabs);
+  if (direct) hipLaunchKernelGGL(k_reduce_slabs<true>, dim3((ndest + 3) / 4), dim3(256), 0, s, dests, ndest, srcs, slab, Sblk, gc, wv, diagU, ctl, *direct);
+  else hipLaunchKernelGGL(k_reduce_slabs<false>, dim3((ndest + 3) / 4), dim3(256), 0, s, dests, ndest, srcs, slab, Sblk, gc, wv, diagU, ctl, DirectAsm{});
 }
 
 }  // namespace mpsfm

@@ -286,6 +286,13 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
       adopt = A.ctl != nullptr && __builtin_amdgcn_readfirstlane(accepted) != 0;
       const int64_t g0 = (int64_t)(cix - A.chunk0) * kThreads + tid, gstep = (int64_t)A.nchunks * kThreads;
       for (int64_t e = g0; e < A.nred; e += gstep) A.red[e] = 0.0;
+      // direct form: what the dense solve accumulates into, and the live tiles of A (the slab reduction adds into them)
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        for (int64_t e = g0; e < A.zero_n[k]; e += gstep) A.zero_p[k][e] = 0.0;
+      for (int64_t e = g0; e < (int64_t)A.zero_nptiles * 1024; e += gstep) A.zero_P[(int64_t)A.zero_ptiles[e >> 10] * 1024 + (e & 1023)] = 0.0;
+      // (dealt from the last workgroup down: the first ones have the accumulators)
+      for (int64_t e = gstep - 1 - g0; e < (int64_t)A.zero_ntiles * 1024; e += gstep) A.zero_A[(int64_t)A.zero_tiles[e >> 10] * 1024 + (e & 1023)] = 0.0;
       if (adopt) {
         for (int i = tid; i < 3 * npt; i += kThreads) A.pts_rw[(size_t)3 * H.pt0 + i] = A.pts2[(size_t)3 * H.pt0 + i];
         const int64_t n_q = 4 * (int64_t)A.adopt_nc, n_t = 3 * (int64_t)A.adopt_nc, n_tab = (int64_t)kCamRec * A.adopt_nc;
