@@ -995,6 +995,74 @@ int mpsfm_match_descriptors_batch(int32_t num_images, const int64_t* image_start
                                   int32_t* matches0, double* scores0 /* [match_start[num_pairs]] */,
                                   int64_t* pair_num_matches /* [num_pairs], may be NULL */, mpsfm_match_batch_report* report /* may be NULL */);
 
+/* ---- global descriptors to image pairs: the top num_select db images of every query image without the nq x nd similarity
+ *    matrix (reference: mpsfm/extraction/pairs/hloc/pairs_from_retrieval.py, einsum + masked_fill + torch.topk; the contract,
+ *    the tie rule, the kernels and the margins: DESIGN.md section 4r).
+ *
+ *    Similarities are fp64 dot products of the fp32 descriptor values, accumulated with k ascending on the matrix pipe; every
+ *    element goes through the same operation sequence wherever it sits, so identical descriptors give bitwise identical
+ *    similarities (the contract of mpsfm_match_descriptors).  CANDIDATES of query row i: every db column j but those a test
+ *    removes, which are never offered and never occupy a slot:
+ *      identity  query_id[i] == db_id[j], when both id arrays are given (the reference's `self` mask; ids stand for names, so a
+ *                query may share its id with several db columns or with none);
+ *      score     sim < min_score, when use_min_score != 0 (a similarity EQUAL to min_score stays, as with the reference's
+ *                `scores < min_score`).
+ *    RESULT of row i: the first num_select candidates under the order (similarity descending, index ascending), in that order:
+ *    indices[i][0 .. counts[i]) and scores[i][0 .. counts[i]), counts[i] <= num_select, the rest of the row -1 / 0.  The result
+ *    is a function of the SET of candidates only: it depends on neither column_ranges nor scheduling, and equal similarities
+ *    go to the lowest index (the reference leaves ties to the torch build).
+ *
+ *    column_ranges 0: every strip's column tiles (64 columns each) are shared out over ceil(8 CUs / strips of 64 rows)
+ *    workgroups, at most one per column tile and at most 4096; an explicit value asks for that many per strip, clamped the same
+ *    way.  Results do not depend on it.
+ *
+ *    query == db is allowed and is the common case: the set is scanned and uploaded once.  inputs_on_device / stream: as for
+ *    mpsfm_match_options (query and db are device pointers, checked; an event is recorded on `stream` and the call's own stream
+ *    waits for it).  Ids, options and all outputs are host memory, complete on return; the host waits ONCE per call
+ *    (info->num_syncs == 1); nothing is retained.
+ *
+ *    MPSFM_EINVAL before any device is touched: NULL pointers (opts NULL: defaults; info may be NULL), negative counts or
+ *    column_ranges, dim outside 1 .. 65536, more than 2^24 rows on a side, num_select outside 1 .. 128 or greater than nd when
+ *    nd > 0, one id array without the other, a non-finite min_score, a non-finite host value (device inputs are scanned by a
+ *    kernel: MPSFM_EINVAL after it).  nq == 0 returns 0; nd == 0 gives all counts 0 (indices -1, scores 0); both without a
+ *    device.  MPSFM_ENODEVICE without a device, but only when one is needed.  The lists of all column ranges
+ *    (12 B x nq x column_ranges x num_select) live on the device during the call: MPSFM_ENOMEM when they do not fit. ---- */
+typedef struct mpsfm_retrieval_options {
+  int32_t num_select;        /* entries per query row, 1 .. 128 */
+  int32_t use_min_score;     /* != 0: similarities below min_score are no candidates */
+  double min_score;
+  int32_t column_ranges;     /* 0: default rule */
+  int32_t inputs_on_device;
+  void* stream;              /* hipStream_t of the caller, read only with inputs_on_device */
+} mpsfm_retrieval_options;
+
+typedef struct mpsfm_retrieval_info {
+  int64_t num_pairs;      /* listed pairs: the sum of counts */
+  int64_t num_launches;   /* kernel launches of the call */
+  int64_t num_syncs;      /* stream synchronisations of the call */
+  float ms;               /* device time, first kernel to last (HIP events), transfers excluded */
+  int32_t column_ranges;  /* workgroups that shared the columns of one strip of rows (results do not depend on it) */
+} mpsfm_retrieval_info;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_retrieval_options) == 32 && offsetof(mpsfm_retrieval_options, use_min_score) == 4 &&
+                  offsetof(mpsfm_retrieval_options, min_score) == 8 && offsetof(mpsfm_retrieval_options, column_ranges) == 16 &&
+                  offsetof(mpsfm_retrieval_options, inputs_on_device) == 20 && offsetof(mpsfm_retrieval_options, stream) == 24,
+              "ABI of mpsfm_retrieval_options");
+static_assert(sizeof(mpsfm_retrieval_info) == 32 && offsetof(mpsfm_retrieval_info, num_launches) == 8 &&
+                  offsetof(mpsfm_retrieval_info, num_syncs) == 16 && offsetof(mpsfm_retrieval_info, ms) == 24 &&
+                  offsetof(mpsfm_retrieval_info, column_ranges) == 28,
+              "ABI of mpsfm_retrieval_info");
+#endif
+
+/* the reference's defaults: num_select 20, score test on at 0, host inputs */
+void mpsfm_retrieval_default_options(mpsfm_retrieval_options* opts);
+
+int mpsfm_retrieve_topk(int64_t nq, int64_t nd, int32_t dim, const float* query /* [nq][dim] */, const float* db /* [nd][dim] */,
+                        const int32_t* query_id /* [nq] or NULL */, const int32_t* db_id /* [nd] or NULL: both or neither */,
+                        const mpsfm_retrieval_options* opts /* NULL: defaults */, int32_t device,
+                        int32_t* indices /* [nq][num_select] */, double* scores /* [nq][num_select] */, int32_t* counts /* [nq] */,
+                        mpsfm_retrieval_info* info /* may be NULL */);
+
 /* ---- dense reciprocal matches from descriptor maps: the dense leg of the reference's MASt3R matcher
  *    (mpsfm/extraction/pairwise/models/mast3r.py:119-170 merge_corres, extract_correspondences, with MASt3R's
  *    fast_reciprocal_NNs; the contract, the kernels and the measurements: DESIGN.md section 4p).

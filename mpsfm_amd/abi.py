@@ -275,6 +275,18 @@ class CMatchBatchReport(C.Structure):
                 ("num_workgroups", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
 
 
+class CRetrievalOptions(C.Structure):
+    _c_name_ = "mpsfm_retrieval_options"
+    _fields_ = [("num_select", C.c_int32), ("use_min_score", C.c_int32), ("min_score", C.c_double), ("column_ranges", C.c_int32),
+                ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
+
+
+class CRetrievalInfo(C.Structure):
+    _c_name_ = "mpsfm_retrieval_info"
+    _fields_ = [("num_pairs", C.c_int64), ("num_launches", C.c_int64), ("num_syncs", C.c_int64), ("ms", C.c_float),
+                ("column_ranges", C.c_int32)]
+
+
 class CRecipOptions(C.Structure):
     _c_name_ = "mpsfm_recip_options"
     _fields_ = [("subsample", C.c_int32), ("max_iter", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
@@ -412,6 +424,8 @@ SIGNATURES = {
     "mpsfm_match_descriptors": (C.c_int, [I64, I64, I32, P, P, P, I32, P, P, P]),
     "mpsfm_match_descriptors_batch": (C.c_int, [I32, P, I32, P, I64, P, P, P, P, I32, I32, I32, P, P, P, P]),
     "mpsfm_match_map_descriptors": (C.c_int, [P, P, I32, I32, P, P, I32, I32, I32, I64, P, I64, P, P, I32, P, P, P]),
+    "mpsfm_retrieval_default_options": (None, [P]),
+    "mpsfm_retrieve_topk": (C.c_int, [I64, I64, I32, P, P, P, P, P, I32, P, P, P, P]),
     "mpsfm_recip_default_options": (None, [P]),
     "mpsfm_recip_seed_count": (I64, [I32, I32, I32]),
     "mpsfm_reciprocal_nns": (C.c_int, [P, I32, I32, P, I32, I32, I32, P, I32, I64, P, P, P, P]),

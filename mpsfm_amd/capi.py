@@ -14,7 +14,7 @@ from .abi import (  # noqa: F401 - declared in abi.py; these names stay importab
     ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CDcImage, CDcSummary, CDepthGather, CDepthPriorConf,
     CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
-    CRecipOptions, CRegImage, CRelPoseOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
+    CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
     CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
 )
 from .problem import BAProblem, Tracks
@@ -937,6 +937,56 @@ def match_descriptors_batch(descs, pairs, ratio_threshold=None, distance_thresho
     info = dict(num_matches=int(R.num_matches), num_groups=int(R.num_groups), num_launches=int(R.num_launches), num_syncs=int(R.num_syncs),
                 num_workgroups=int(R.num_workgroups), ms=float(R.ms), pair_num_matches=cnt[:len(pr)])
     return ms, ss, info
+
+
+MAX_NUM_SELECT = 128  # entries of a row's list in k_sim_topk (csrc/sim_topk.h: kMaxSelect)
+
+
+def retrieve_topk(query, db, num_select, min_score=0.0, query_ids=None, db_ids=None, device=None, column_ranges=0, return_info=False):
+    """mpsfm_retrieve_topk: query [nq, D], db [nd, D], float16 / float32 NumPy arrays, host tensors or device tensors (device tensors
+    go in as device pointers with the caller's current stream); `query is db` is uploaded once.  Candidates of a query row: every db
+    column but those with `query_ids[i] == db_ids[j]` (both id arrays or neither) and those with a similarity below `min_score`
+    (None: no score test).  Returns indices int64 [nq, num_select] (-1 beyond the row's count), scores float64 [nq, num_select] (0
+    beyond it), counts int64 [nq][, info dict(num_pairs, num_launches, num_syncs, ms, column_ranges)]: the first num_select
+    candidates of every row under (similarity descending, index ascending).  `column_ranges` 0: the library's default rule; results
+    do not depend on it."""
+    o = CRetrievalOptions()
+    lib().mpsfm_retrieval_default_options(C.addressof(o))
+    o.num_select = int(num_select)
+    o.use_min_score = 0 if min_score is None else 1
+    o.min_score = 0.0 if min_score is None else float(min_score)
+    o.column_ranges = int(column_ranges)
+    one = query is db
+    if _on_device(query, db):
+        tensors, device = _device_inputs(o, [query] if one else [query, db], device)
+        a, b = tensors[0], tensors[-1]
+        pa, pb = a.data_ptr(), b.data_ptr()
+    else:
+        a = _host_f32(query, "query")
+        b = a if one else _host_f32(db, "db")
+        pa, pb = a.ctypes.data, b.ctypes.data
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("descriptors must be [nq, dim] and [nd, dim]")
+    nq, nd, dim = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+    if (query_ids is None) != (db_ids is None):
+        raise ValueError("query_ids and db_ids: both or neither")
+    qi = di = None
+    if query_ids is not None:
+        qi, di = np.ascontiguousarray(query_ids, np.int32).reshape(-1), np.ascontiguousarray(db_ids, np.int32).reshape(-1)
+        if len(qi) != nq or len(di) != nd:
+            raise ValueError("one id per descriptor")
+        if nq == 0 or nd == 0:  # nothing to compare: an empty array has no address
+            qi = di = None
+    k = max(int(num_select), 1)
+    idx, val, cnt, I = np.full((max(nq, 1), k), -1, np.int32), np.zeros((max(nq, 1), k)), np.zeros(max(nq, 1), np.int32), CRetrievalInfo()
+    _check(lib().mpsfm_retrieve_topk(nq, nd, dim, pa or None, pb or None, None if qi is None else qi.ctypes.data,
+                                     None if di is None else di.ctypes.data, C.addressof(o), int(device or 0), idx.ctypes.data, val.ctypes.data,
+                                     cnt.ctypes.data, C.addressof(I)))
+    out = idx[:nq].astype(np.int64), val[:nq], cnt[:nq].astype(np.int64)
+    if not return_info:
+        return out
+    return (*out, dict(num_pairs=int(I.num_pairs), num_launches=int(I.num_launches), num_syncs=int(I.num_syncs), ms=float(I.ms),
+                       column_ranges=int(I.column_ranges)))
 
 
 def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=None, ratio_threshold=None, distance_threshold=None,
