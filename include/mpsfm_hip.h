@@ -1321,6 +1321,62 @@ int mpsfm_normal_priors(int32_t n_images, const mpsfm_normal_prior_problem* prob
                         const mpsfm_normal_prior_conf* conf, int32_t device, const mpsfm_normal_prior_output* outputs /* [n_images] */,
                         mpsfm_prior_summary* summary /* may be NULL */);
 
+/* ---- the correspondence graph from the inlier matches of all image pairs, in one call (COLMAP 3.11 CorrespondenceGraph::
+ *    AddCorrespondences + Finalize, restated as a set rule so that no result depends on arrival order; what consumes it:
+ *    mpsfm_tri_graph; the design and the measurements: DESIGN.md section 4s).
+ *
+ *    Images i = 0 .. n_images - 1 with nkp(i) = kp_start[i + 1] - kp_start[i] keypoints; the global index of keypoint idx of
+ *    image i is kp_start[i] + idx, n_kp = kp_start[n_images].  Match lists l = 0 .. n_lists - 1: the rows
+ *    matches[list_start[l] .. list_start[l + 1])[2] are (point2D index in list_image0[l], point2D index in list_image1[l]);
+ *    n_matches = list_start[n_lists].  The same image pair may occur in several lists and in either orientation.
+ *
+ *    match_status[m] of every match, tested in this order (COLMAP refuses a whole list of self matches before it looks at
+ *    an index):
+ *      2 self pair   list_image0 == list_image1
+ *      1 invalid     an index outside [0, nkp(image))
+ *      3 duplicate   an equal UNDIRECTED pair of global keypoints occurs among the matches of status 0 or 3 at a lower position
+ *                    in `matches`, whatever the orientation of either list
+ *      0 added       everything else.  A keypoint may keep several partners in one other image, as in COLMAP.
+ *
+ *    corr_start [n_kp + 1] / corr_kp [n_corr]: the layout of mpsfm_tri_graph.  Row k holds the global indices of the partners
+ *    of keypoint k, ascending; *n_corr = 2 x the number of added matches.
+ *    image_num_correspondences[i]: the entries of the rows of image i; image_num_observations[i]: its non-empty rows.
+ *    kp_two_view[k] = 1 where row k has exactly one entry and that entry's row has exactly one (IsTwoViewObservation).
+ *    The pair view: the *n_pairs distinct image pairs with an added match, pair_image0 < pair_image1, ascending by
+ *    (image0, image1); the added matches of pair p are pair_matches[pair_start[p] .. pair_start[p + 1])[2], local indices
+ *    (in image0, in image1), ascending by (idx0, idx1).
+ *
+ *    Capacities, all caller-allocated host memory: match_status [n_matches], corr_kp [2 n_matches], pair_image0 / pair_image1
+ *    [n_lists], pair_start [n_lists + 1], pair_matches [n_matches][2]; what lies behind n_corr / n_pairs is set to 0.  Every
+ *    output is a function of the input alone: bitwise the same from run to run.  Nothing is retained; the host waits ONCE per
+ *    call (info->num_syncs == 1).
+ *
+ *    MPSFM_EINVAL before any device is touched: NULL pointers (info may be NULL; arrays of length 0 may be NULL), negative
+ *    counts, kp_start[0] or list_start[0] != 0, a decreasing kp_start or list_start, a list image outside [0, n_images).
+ *    MPSFM_EUNSUPPORTED: n_kp >= 2^31 or 2 n_matches >= 2^31.  No matches or no keypoints: the empty graph (every match a
+ *    self pair or invalid) without a device.  MPSFM_ENODEVICE without a device, but only when one is needed. ---- */
+typedef struct mpsfm_corr_graph_info {
+  int64_t num_added, num_invalid, num_self_pairs, num_duplicates; /* matches per status */
+  int64_t num_launches; /* kernel launches of the call, the library sorts and scans excluded */
+  int64_t num_syncs;    /* stream synchronisations of the call */
+  float ms;             /* device time from the first kernel to the last (HIP events), transfers excluded */
+  int32_t reserved;
+} mpsfm_corr_graph_info;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_corr_graph_info) == 56 && offsetof(mpsfm_corr_graph_info, num_launches) == 32 &&
+                  offsetof(mpsfm_corr_graph_info, ms) == 48,
+              "ABI of mpsfm_corr_graph_info");
+#endif
+
+int mpsfm_corr_graph_build(int32_t n_images, const int64_t* kp_start /* [n_images + 1] */, int32_t n_lists,
+                           const int32_t* list_image0, const int32_t* list_image1 /* [n_lists] image indices */,
+                           const int64_t* list_start /* [n_lists + 1] */, const int32_t* matches /* [n_matches][2] */, int32_t device,
+                           uint8_t* match_status /* [n_matches] */, int64_t* corr_start /* [n_kp + 1] */,
+                           int64_t* corr_kp /* [2 n_matches] */, int64_t* n_corr, int32_t* image_num_correspondences /* [n_images] */,
+                           int32_t* image_num_observations /* [n_images] */, uint8_t* kp_two_view /* [n_kp] */, int64_t* n_pairs,
+                           int32_t* pair_image0, int32_t* pair_image1 /* [n_lists] */, int64_t* pair_start /* [n_lists + 1] */,
+                           int32_t* pair_matches /* [n_matches][2] */, mpsfm_corr_graph_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -287,6 +287,12 @@ class CRetrievalInfo(C.Structure):
                 ("column_ranges", C.c_int32)]
 
 
+class CCorrGraphInfo(C.Structure):
+    _c_name_ = "mpsfm_corr_graph_info"
+    _fields_ = [("num_added", C.c_int64), ("num_invalid", C.c_int64), ("num_self_pairs", C.c_int64), ("num_duplicates", C.c_int64),
+                ("num_launches", C.c_int64), ("num_syncs", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+
 class CRecipOptions(C.Structure):
     _c_name_ = "mpsfm_recip_options"
     _fields_ = [("subsample", C.c_int32), ("max_iter", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
@@ -436,6 +442,7 @@ SIGNATURES = {
     "mpsfm_warp_matches": (C.c_int, [I32, I32, P, P, I32, I32, I32, I32, I32, P, I64, P, I64, P, I32, P, P, P, P, P, P, P, P]),
     "mpsfm_depth_priors": (C.c_int, [I32, P, P, I32, P, P]),
     "mpsfm_normal_priors": (C.c_int, [I32, P, P, I32, P, P]),
+    "mpsfm_corr_graph_build": (C.c_int, [I32, P, I32, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
 }
 
 # include/mpsfm_hip_debug.h: test and diagnostic hooks, outside the stable ABI

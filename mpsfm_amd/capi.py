@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
-    ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CDcImage, CDcSummary, CDepthGather, CDepthPriorConf,
+    ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CCorrGraphInfo, CDcImage, CDcSummary, CDepthGather, CDepthPriorConf,
     CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
     CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
@@ -987,6 +987,43 @@ def retrieve_topk(query, db, num_select, min_score=0.0, query_ids=None, db_ids=N
         return out
     return (*out, dict(num_pairs=int(I.num_pairs), num_launches=int(I.num_launches), num_syncs=int(I.num_syncs), ms=float(I.ms),
                        column_ranges=int(I.column_ranges)))
+
+
+CORR_STATUS = ("added", "invalid", "self_pair", "duplicate")  # match_status 0 .. 3 of mpsfm_corr_graph_build
+
+
+def corr_graph_build(kp_start, list_image0, list_image1, list_start, matches, device=0):
+    """mpsfm_corr_graph_build: `kp_start` int64 [n_images + 1], lists l of matches[list_start[l] : list_start[l + 1]] int32 [n, 2] between the
+    image INDICES list_image0[l], list_image1[l].  Returns a dict of match_status uint8 [n], corr_start int64 [n_kp + 1], corr_kp int64
+    [n_corr], image_num_correspondences / image_num_observations int32 [n_images], kp_two_view uint8 [n_kp], pair_image0 / pair_image1
+    int32 [n_pairs], pair_start int64 [n_pairs + 1], pair_matches int32 [n_added, 2] and info (matches per status, num_launches,
+    num_syncs, ms).  The arrays own their memory."""
+    kp_start = np.ascontiguousarray(kp_start, np.int64).reshape(-1)
+    li0, li1 = np.ascontiguousarray(list_image0, np.int32).reshape(-1), np.ascontiguousarray(list_image1, np.int32).reshape(-1)
+    lstart = np.ascontiguousarray(list_start, np.int64).reshape(-1)
+    matches = np.ascontiguousarray(matches, np.int32).reshape(-1, 2)
+    n_images, n_lists = len(kp_start) - 1, len(li0)
+    if n_images < 0 or len(li1) != n_lists or len(lstart) != n_lists + 1:
+        raise ValueError("kp_start is [n_images + 1], list_image0 / list_image1 [n_lists], list_start [n_lists + 1]")
+    if int(lstart[-1]) != len(matches):
+        raise ValueError("list_start[n_lists] must be the number of matches")
+    n_kp, n = max(int(kp_start[-1]), 0), len(matches)
+    status, corr_start, corr_kp = np.zeros(max(n, 1), np.uint8), np.zeros(n_kp + 1, np.int64), np.zeros(max(2 * n, 1), np.int64)
+    im_corr, im_obs, two_view = np.zeros(max(n_images, 1), np.int32), np.zeros(max(n_images, 1), np.int32), np.zeros(max(n_kp, 1), np.uint8)
+    p0, p1, pstart = np.zeros(max(n_lists, 1), np.int32), np.zeros(max(n_lists, 1), np.int32), np.zeros(n_lists + 1, np.int64)
+    pm = np.zeros((max(n, 1), 2), np.int32)
+    n_corr, n_pairs, I = C.c_int64(0), C.c_int64(0), CCorrGraphInfo()
+    _check(lib().mpsfm_corr_graph_build(n_images, kp_start.ctypes.data, n_lists, li0.ctypes.data if n_lists else None,
+                                        li1.ctypes.data if n_lists else None, lstart.ctypes.data, matches.ctypes.data if n else None, int(device),
+                                        status.ctypes.data, corr_start.ctypes.data, corr_kp.ctypes.data, C.addressof(n_corr), im_corr.ctypes.data,
+                                        im_obs.ctypes.data, two_view.ctypes.data, C.addressof(n_pairs), p0.ctypes.data, p1.ctypes.data,
+                                        pstart.ctypes.data, pm.ctypes.data, C.addressof(I)))
+    nc, npairs = int(n_corr.value), int(n_pairs.value)
+    info = dict(num_added=int(I.num_added), num_invalid=int(I.num_invalid), num_self_pairs=int(I.num_self_pairs),
+                num_duplicates=int(I.num_duplicates), num_launches=int(I.num_launches), num_syncs=int(I.num_syncs), ms=float(I.ms))
+    return dict(match_status=status[:n], corr_start=corr_start, corr_kp=corr_kp[:nc].copy(), image_num_correspondences=im_corr[:n_images],
+                image_num_observations=im_obs[:n_images], kp_two_view=two_view[:n_kp], pair_image0=p0[:npairs].copy(), pair_image1=p1[:npairs].copy(),
+                pair_start=pstart[:npairs + 1].copy(), pair_matches=pm[:nc // 2].copy(), info=info)
 
 
 def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=None, ratio_threshold=None, distance_threshold=None,

@@ -14,6 +14,7 @@ ObservationManager keeps doing the bookkeeping.
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 
 import numpy as np
 
@@ -48,13 +49,27 @@ def _image_pairs(cg):
 
 
 def graph_arrays(correspondence_graph, mpsfm_rec):
-    """Keypoints and correspondence graph of a scene as the flat arrays of `mpsfm_tri_graph` (include/mpsfm_hip.h)."""
+    """Keypoints and correspondence graph of a scene as the flat arrays of `mpsfm_tri_graph` (include/mpsfm_hip.h).
+
+    A graph that offers `csr()` (HipCorrespondenceGraph) hands over its arrays as they are, provided it was given exactly the scene's
+    images with the scene's keypoint counts.  If it was not (an image left out, a count that differs), the arrays would index other
+    keypoints than the scene's, so they are rebuilt pair by pair on the host, as for every other graph object, and a warning says so."""
     image_ids = sorted(mpsfm_rec.images.keys())
     im_index = {imid: i for i, imid in enumerate(image_ids)}
     nkp = [len(mpsfm_rec.images[i].points2D) for i in image_ids]
     kp_start = np.concatenate([[0], np.cumsum(nkp)]).astype(np.int64)
     kp_xy = np.concatenate([np.asarray(mpsfm_rec.keypoints(i), np.float64).reshape(-1, 2) for i in image_ids]) if sum(nkp) else np.zeros((0, 2))
     intr = np.array([pinhole_params(mpsfm_rec.rec.cameras[mpsfm_rec.images[i].camera_id]) for i in image_ids], np.float64).reshape(-1, 4)
+    n_kp = int(kp_start[-1])
+    kp_image = np.repeat(np.arange(len(image_ids)), nkp)
+    fixed = dict(image_ids=image_ids, im_index=im_index, kp_start=kp_start, kp_xy=np.ascontiguousarray(kp_xy), intr=np.ascontiguousarray(intr),
+                 kp_image=kp_image)
+    if hasattr(correspondence_graph, "csr"):  # a graph that was built as these arrays (HipCorrespondenceGraph): no walk over the pairs
+        g = correspondence_graph.csr()
+        if list(g["image_ids"]) == image_ids and np.array_equal(g["kp_start"], kp_start):
+            return dict(fixed, corr_start=np.ascontiguousarray(g["corr_start"], np.int64), corr_kp=np.ascontiguousarray(g["corr_kp"], np.int64))
+        warnings.warn("the correspondence graph's images or keypoint counts differ from the scene's: its CSR is not used, the graph is "
+                      "walked pair by pair on the host", RuntimeWarning, stacklevel=2)
     src, dst = [], []
     for id1, id2 in _image_pairs(correspondence_graph):
         if id1 not in im_index or id2 not in im_index:
@@ -63,16 +78,13 @@ def graph_arrays(correspondence_graph, mpsfm_rec):
         a, b = kp_start[im_index[id1]] + m[:, 0], kp_start[im_index[id2]] + m[:, 1]
         src += [a, b]
         dst += [b, a]
-    n_kp = int(kp_start[-1])
     if src:
         src, dst = np.concatenate(src), np.concatenate(dst)
         order = np.lexsort((dst, src))
         src, dst = src[order], dst[order]
     else:
         src = dst = np.zeros(0, np.int64)
-    return dict(image_ids=image_ids, im_index=im_index, kp_start=kp_start, kp_xy=np.ascontiguousarray(kp_xy), intr=np.ascontiguousarray(intr),
-                corr_start=np.searchsorted(src, np.arange(n_kp + 1)).astype(np.int64), corr_kp=np.ascontiguousarray(dst, np.int64),
-                kp_image=np.repeat(np.arange(len(image_ids)), nkp))
+    return dict(fixed, corr_start=np.searchsorted(src, np.arange(n_kp + 1)).astype(np.int64), corr_kp=np.ascontiguousarray(dst, np.int64))
 
 
 def state_arrays(mpsfm_rec, image_ids, kp_start):
