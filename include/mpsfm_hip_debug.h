@@ -56,6 +56,24 @@ int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* o
 int mpsfm_debug_local_clocks(mpsfm_ba_handle* h, int64_t out[12]);
 /* in every single-launch solve from now on workgroup `chunk` waits `ticks` (at most 200000) at each phase point of `phase_mask` (bits 0-4); (0, 0, 0): off */
 int mpsfm_debug_local_skew(int32_t chunk, int32_t phase_mask, int64_t ticks);
+/* the Levenberg-Marquardt control block of the device (LmCtl of csrc/common.h, field for field) and the options its decisions read (LmOpts) */
+typedef struct mpsfm_debug_lm_ctl {
+  double radius, decrease_factor, x_norm, cur_cost, fixed_cost, initial_cost;
+  double last_x_cost, last_cand, last_rel, last_step_norm, last_mcc;
+  int32_t term, iter, invalid_run, check_gradient, accepted, n_success, n_unsuccess, n_cost_evals, n_jac_evals, last_chol_fail, trace_len, pad_;
+  double trace_cost[MPSFM_MAX_TRACE], trace_radius[MPSFM_MAX_TRACE];
+  uint8_t trace_accepted[MPSFM_MAX_TRACE];
+} mpsfm_debug_lm_ctl;
+typedef struct mpsfm_debug_lm_opts {
+  double function_tolerance, gradient_tolerance, parameter_tolerance, min_relative_decrease, max_radius, min_radius;
+  int32_t max_iterations, max_invalid_steps;
+} mpsfm_debug_lm_opts;
+/* ONE launch of a decision kernel on the given block, through the solver's own launch wrappers, with a pinned host copy as its destination.
+   form 0: k_lm_decide on scal [16]; 1: k_lm_decide with redsc (scal [16] and the all-reduced tail redsc [info[2]]); 2: k_lm_reduce_decide on scal [16] and the partial
+   tables part [rows][4], part2 [rows][8].  The pinned copy starts as `fill` in every byte.  Out: ctl_out the device block, host_out the pinned copy, scal as the kernel
+   left it.  info (may be NULL, filled also when every other argument is NULL): sizeof(LmHead), sizeof(LmCtl), the slots of redsc, the threads of k_lm_reduce_decide */
+int mpsfm_debug_lm_decide(int32_t form, const mpsfm_debug_lm_ctl* ctl_in, const mpsfm_debug_lm_opts* opts, double* scal, const double* redsc, const double* part,
+                          const double* part2, int64_t rows, int32_t fill, mpsfm_debug_lm_ctl* ctl_out, mpsfm_debug_lm_ctl* host_out, int64_t info[4]);
 /* what the process holds of `device`'s caches: live device blocks, their bytes, and the pooled streams, events and pinned blocks handed out and not yet given back */
 int mpsfm_debug_resources(int32_t device, int64_t out[5]);
 

@@ -365,6 +365,26 @@ class CPriorSummary(C.Structure):
     _fields_ = [("ms", C.c_float), ("n_images", C.c_int32), ("n_pixels", C.c_int64)]
 
 
+# include/mpsfm_hip_debug.h: the Levenberg-Marquardt control block and its options as the decision kernels see them
+LM_HEAD_DOUBLES = ("radius", "decrease_factor", "x_norm", "cur_cost", "fixed_cost", "initial_cost", "last_x_cost", "last_cand", "last_rel",
+                   "last_step_norm", "last_mcc")
+LM_HEAD_INTS = ("term", "iter", "invalid_run", "check_gradient", "accepted", "n_success", "n_unsuccess", "n_cost_evals", "n_jac_evals",
+                "last_chol_fail", "trace_len", "pad_")
+
+
+class CDebugLmCtl(C.Structure):
+    _c_name_ = "mpsfm_debug_lm_ctl"
+    _fields_ = ([(f, C.c_double) for f in LM_HEAD_DOUBLES] + [(f, C.c_int32) for f in LM_HEAD_INTS]
+                + [("trace_cost", C.c_double * MAX_TRACE), ("trace_radius", C.c_double * MAX_TRACE), ("trace_accepted", C.c_uint8 * MAX_TRACE)])
+
+
+class CDebugLmOpts(C.Structure):
+    _c_name_ = "mpsfm_debug_lm_opts"
+    _fields_ = [("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("min_relative_decrease", C.c_double), ("max_radius", C.c_double), ("min_radius", C.c_double), ("max_iterations", C.c_int32),
+                ("max_invalid_steps", C.c_int32)]
+
+
 # ---- functions -----------------------------------------------------------------------------------------------------------------
 # name -> (restype, argtypes).  Pointers are c_void_p (it takes byref(), addressof(), an array's .ctypes.data and None alike); the few
 # POINTER(...) entries are out-parameters that every caller passes with byref().  `int` returns are the MPSFM_* status codes.
@@ -465,6 +485,7 @@ DEBUG_SIGNATURES = {
     "mpsfm_debug_host_build": (I64, [P, I32, P, I64]),
     "mpsfm_debug_local_clocks": (C.c_int, [P, P]),
     "mpsfm_debug_local_skew": (C.c_int, [I32, I32, I64]),
+    "mpsfm_debug_lm_decide": (C.c_int, [I32, P, P, P, P, P, P, I64, I32, P, P, P]),
     "mpsfm_debug_resources": (C.c_int, [I32, P]),
 }
 

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
-    ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CCorrGraphInfo, CDcImage, CDcSummary, CDepthGather, CDepthPriorConf,
+    ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CCorrGraphInfo, CDcImage, CDebugLmCtl, CDebugLmOpts, CDcSummary, CDepthGather, CDepthPriorConf,
     CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
     CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
@@ -240,6 +240,38 @@ def debug_panel_factor(dx: np.ndarray, waves: int = 4):
     out, ok = np.zeros((64, 32)), C.c_int(0)
     _check(lib().mpsfm_debug_panel_factor(dx.ctypes.data, int(waves), out.ctypes.data, C.byref(ok)))
     return out, bool(ok.value)
+
+
+def debug_lm_constants() -> dict:
+    """Sizes the decision kernels are built with: bytes of the control block's head and of the whole block, slots of the all-reduced
+    scalar tail, threads of k_lm_reduce_decide.  No device involved."""
+    info = np.zeros(4, np.int64)
+    _check(lib().mpsfm_debug_lm_decide(0, None, None, None, None, None, None, 0, 0, None, None, info.ctypes.data))
+    return dict(head_bytes=int(info[0]), ctl_bytes=int(info[1]), redsc_slots=int(info[2]), reduce_threads=int(info[3]))
+
+
+LM_DECIDE_FORMS = {"scalars": 0, "redsc": 1, "reduce": 2}
+
+
+def debug_lm_decide(ctl: CDebugLmCtl, opts: CDebugLmOpts, scal, form: str = "scalars", redsc=None, part=None, part2=None, fill: int = 0xA5):
+    """One launch of a decision kernel of the trust-region loop on the block `ctl`: k_lm_decide on the 16 scalars ("scalars"), k_lm_decide
+    with the all-reduced tail `redsc` ("redsc"), or k_lm_reduce_decide on the partial tables part [rows][4], part2 [rows][8] ("reduce").
+    The pinned host copy starts as the byte `fill`.  Returns (device block, host copy, the scalars as the kernel left them)."""
+    scal = np.array(scal, np.float64)
+    assert scal.shape == (16,)
+    rows = 0
+    if form == "redsc":
+        redsc = np.ascontiguousarray(redsc, np.float64)
+        assert redsc.shape == (debug_lm_constants()["redsc_slots"],)
+    if form == "reduce":
+        part, part2 = np.ascontiguousarray(part, np.float64), np.ascontiguousarray(part2, np.float64)
+        rows = part.shape[0]
+        assert part.shape == (rows, 4) and part2.shape == (rows, 8)
+    dev, host = CDebugLmCtl(), CDebugLmCtl()
+    _check(lib().mpsfm_debug_lm_decide(LM_DECIDE_FORMS[form], C.addressof(ctl), C.addressof(opts), scal.ctypes.data,
+                                       redsc.ctypes.data if form == "redsc" else None, part.ctypes.data if rows else None,
+                                       part2.ctypes.data if rows else None, rows, int(fill), C.addressof(dev), C.addressof(host), None))
+    return dev, host, scal
 
 
 def debug_resources(device: int = 0) -> tuple:

@@ -78,6 +78,67 @@ extern "C" int mpsfm_debug_graph_union(const uint8_t* adj, int32_t world, int32_
   return mpsfm::graph_digits(world);
 }
 
+// Test hook (tests/test_gpu_lm_control.py): one launch of a decision kernel of the trust-region loop on a given control block, through
+// the wrappers solve_impl calls and with a pinned block as the host copy's destination, as there.  The mirror structs of the header
+// are LmCtl and LmOpts field for field:
+#define MPSFM_SAME_FIELD(T, U, f) static_assert(offsetof(T, f) == offsetof(U, f) && sizeof(T::f) == sizeof(U::f), "mirror field " #f)
+static_assert(sizeof(mpsfm_debug_lm_ctl) == sizeof(LmCtl) && sizeof(mpsfm_debug_lm_opts) == sizeof(LmOpts), "mirror sizes");
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, radius); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, decrease_factor); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, x_norm);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, cur_cost); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, fixed_cost); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, initial_cost);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, last_x_cost); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, last_cand); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, last_rel);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, last_step_norm); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, last_mcc); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, term);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, iter); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, invalid_run); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, check_gradient);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, accepted); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, n_success); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, n_unsuccess);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, n_cost_evals); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, n_jac_evals); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, last_chol_fail);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, trace_len); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, pad_); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, trace_cost);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, trace_radius); MPSFM_SAME_FIELD(mpsfm_debug_lm_ctl, LmCtl, trace_accepted);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, function_tolerance); MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, gradient_tolerance);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, parameter_tolerance); MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, min_relative_decrease);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, max_radius); MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, min_radius);
+MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, max_iterations); MPSFM_SAME_FIELD(mpsfm_debug_lm_opts, LmOpts, max_invalid_steps);
+#undef MPSFM_SAME_FIELD
+static_assert(sizeof(LmCtl) <= kPinnedBytes, "the pinned block holds a control block");
+
+extern "C" int mpsfm_debug_lm_decide(int32_t form, const mpsfm_debug_lm_ctl* ctl_in, const mpsfm_debug_lm_opts* opts, double* scal, const double* redsc,
+                                     const double* part, const double* part2, int64_t rows, int32_t fill, mpsfm_debug_lm_ctl* ctl_out,
+                                     mpsfm_debug_lm_ctl* host_out, int64_t info[4]) {
+  if (info) { info[0] = (int64_t)sizeof(LmHead); info[1] = (int64_t)sizeof(LmCtl); info[2] = SC_COUNT; info[3] = kReduceThreads; }
+  if (!ctl_in && !opts && !scal && !ctl_out && !host_out && info) return 0;  // the constants alone
+  if (!ctl_in || !opts || !scal || !ctl_out || !host_out || form < 0 || form > 2) return fail(MPSFM_EINVAL, "block, options, scalars or output is NULL, or unknown form");
+  if ((form == 1 && !redsc) || (form == 2 && (rows < 0 || (rows > 0 && (!part || !part2))))) return fail(MPSFM_EINVAL, "the form's tables are missing");
+  if (ctl_in->trace_len < 0 || ctl_in->trace_len > MPSFM_MAX_TRACE) return fail(MPSFM_EINVAL, "trace_len outside the trace arrays");
+  DeviceBlocks own;  // waits for the stream before the blocks go back
+  hipStream_t s = nullptr;
+  MPSFM_TRY(own.stream(&s));
+  void* pinned = nullptr;
+  MPSFM_TRY(own.pinned(&pinned));
+  const size_t nrows = form == 2 ? (size_t)rows : 0;
+  LmCtl* d_ctl = own.alloc<LmCtl>(1);
+  double* d_scal = own.alloc<double>(U_COUNT);
+  double* d_redsc = own.alloc<double>(SC_COUNT);
+  double* d_part = own.alloc<double>(nrows * 4);
+  double* d_part2 = own.alloc<double>(nrows * 8);
+  if (!own.ok()) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  std::memset(pinned, fill & 0xff, sizeof(LmCtl));
+  MPSFM_TRY(hipMemcpyAsync(d_ctl, ctl_in, sizeof(LmCtl), hipMemcpyHostToDevice, s));
+  MPSFM_TRY(hipMemcpyAsync(d_scal, scal, sizeof(double) * U_COUNT, hipMemcpyHostToDevice, s));
+  if (form == 1) MPSFM_TRY(hipMemcpyAsync(d_redsc, redsc, sizeof(double) * SC_COUNT, hipMemcpyHostToDevice, s));
+  if (nrows > 0) {
+    MPSFM_TRY(hipMemcpyAsync(d_part, part, sizeof(double) * nrows * 4, hipMemcpyHostToDevice, s));
+    MPSFM_TRY(hipMemcpyAsync(d_part2, part2, sizeof(double) * nrows * 8, hipMemcpyHostToDevice, s));
+  }
+  LmOpts o;
+  std::memcpy(&o, opts, sizeof(o));
+  if (form == 2) launch_lm_reduce_decide(d_part, d_part2, rows, d_ctl, d_scal, o, static_cast<LmCtl*>(pinned), s);
+  else launch_lm_decide(d_ctl, d_scal, o, static_cast<LmCtl*>(pinned), s, form == 1 ? d_redsc : nullptr);
+  MPSFM_TRY(hipGetLastError());
+  MPSFM_TRY(hipMemcpyAsync(ctl_out, d_ctl, sizeof(LmCtl), hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipMemcpyAsync(scal, d_scal, sizeof(double) * U_COUNT, hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipStreamSynchronize(s));
+  std::memcpy(host_out, pinned, sizeof(LmCtl));
+  return 0;
+}
+
 extern "C" {
 
 int mpsfm_ba_dense_plan(mpsfm_ba_handle* h, int64_t info[10]) {

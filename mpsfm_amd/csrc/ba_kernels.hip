@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_track_sweep(SweepArgs A) {
     const double psc[3] = {A.ps[3 * pix], A.ps[3 * pix + 1], A.ps[3 * pix + 2]};
     RecLin L;
     linearize_record(A.camtab + (size_t)cam * kCamRec, X, psc, meta, xy.x, xy.y, d, m, a, A.loss, L);
-    my_cost = L.cost;
+    my_cost = L.ok ? L.cost : __builtin_nan("");  // a residual that cannot be evaluated: the cost is not a number (lm_decide.h)
     my_bad = L.ok ? 0 : 1;
     if (L.ok) {
       // landmark block
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(kThreads) void k_long_track_sweep(SweepArgs A) {
     if (meta & kRecHasDepth) { d = A.rec_d[rix]; m = A.rec_m[rix]; a = A.rec_a[rix]; }
     RecLin L;
     linearize_record(A.camtab + (size_t)cam * kCamRec, X, psc, meta, xy.x, xy.y, d, m, a, A.loss, L);
-    my_cost += L.cost;
+    my_cost += L.ok ? L.cost : __builtin_nan("");  // (as in k_track_sweep)
     if (!L.ok) { my_bad += 1.0; continue; }
     if (psc[0] != 0.0) {
 #pragma unroll
@@ -626,7 +626,6 @@ __global__ __launch_bounds__(kThreads) void k_cost_records(CostArgs A) {
 }
 
 // deterministic column sums (or max for columns flagged in max_mask) of a [rows][stride] array
-constexpr int kReduceThreads = 1024;
 // fixed summation order (thread-strided rows, wave tree, then the 16 wave results in order): deterministic run to run.
 // out2 (optional) receives a second copy.  s: 8 * kReduceThreads / 64 doubles of LDS, free again on return.
 __device__ __forceinline__ void reduce_cols_block(const double* part, int64_t rows, int stride, int ncols, uint32_t max_mask, double* out, double* out2,

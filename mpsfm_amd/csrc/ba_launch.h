@@ -40,6 +40,7 @@ void launch_pt_scales(int64_t np, const uint16_t* pt_kv, const double* diagV, in
 void launch_cam_update(int nc, const int32_t* cam_slot, const double* q, const double* t, const double* cs, const double* yc,
                        const double* gc, double* q2, double* t2, double* scal, hipStream_t, const double* intr = nullptr,
                        const int32_t* intr_idx = nullptr, double* camtab2 = nullptr, int* chol_fail = nullptr, const LmCtl* ctl = nullptr);
+constexpr int kReduceThreads = 1024;  // the workgroup of k_reduce_cols and k_lm_reduce_decide
 void launch_lm_decide(LmCtl* ctl, double* scal, const LmOpts& o, LmCtl* host_copy, hipStream_t, const double* redsc = nullptr);
 void launch_zero(double* p, int64_t n, const LmCtl* ctl, hipStream_t);
 void launch_lm_reduce_decide(const double* part, const double* part2, int64_t rows, LmCtl* ctl, double* scal, const LmOpts& o, LmCtl* host_copy, hipStream_t);

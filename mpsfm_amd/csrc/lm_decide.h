@@ -29,7 +29,9 @@ __device__ __forceinline__ void lm_decide_logic(LmHead& L, LmCtl* C, const doubl
   const bool x_bad = sc[U_X_BAD] > 0.0;  // residual not evaluable or a landmark block not positive definite
   L.last_x_cost = x_cost;
   if (L.iter == 1) {
-    if (!isfinite(x_cost) || x_bad) { L.term = kLmNumericError; return; }
+    // The initial point cannot be evaluated: the track sweeps make the cost of such a residual a NaN.  A landmark block that is not
+    // positive definite (x_bad with a finite cost: the damping overflowed, say) is a failed linear solve, an invalid step below.
+    if (!isfinite(x_cost)) { L.term = kLmNumericError; return; }
     L.initial_cost = x_cost + L.fixed_cost;
     L.cur_cost = x_cost;
     trace(x_cost + L.fixed_cost, L.radius, 1);

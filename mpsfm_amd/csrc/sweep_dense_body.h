@@ -343,7 +343,7 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
     RecLin L;
     if (trace) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); trace[10] = (long long)clock64(); }  // the record / landmark loads have landed (the camera row follows)
     linearize_record(camera_row<kLocal>(camtab_at, l_tab, S.slot, cam, lcam), X, psc, meta, xy.x, xy.y, d, m, a, A.loss, L);
-    my_cost = L.cost;
+    my_cost = L.ok ? L.cost : __builtin_nan("");  // a residual that cannot be evaluated: the cost is not a number (lm_decide.h)
     if (trace) { asm volatile("" : "+v"(L.Jc[0]), "+v"(L.Jp[8]), "+v"(L.cost)); trace[11] = (long long)clock64(); }
     my_bad = L.ok ? 0 : 1;
     if (L.ok) {
