@@ -1377,6 +1377,72 @@ int mpsfm_corr_graph_build(int32_t n_images, const int64_t* kp_start /* [n_image
                            int32_t* pair_image0, int32_t* pair_image1 /* [n_lists] */, int64_t* pair_start /* [n_lists + 1] */,
                            int32_t* pair_matches /* [n_matches][2] */, mpsfm_corr_graph_info* info /* may be NULL */);
 
+/* ---- scene queries of the incremental loop: which image to register next, and the local bundle of an image (the design and the
+ *    measurements: DESIGN.md section 4t).  Both read the arrays of mpsfm_tri_graph / mpsfm_tri_state; images, keypoints and
+ *    points are addressed as there (global keypoint index kp_start[image] + point2D_idx).  Stateless; inputs and outputs are
+ *    caller-allocated host memory; the host waits ONCE per call (info->num_syncs == 1).  The fork's COLMAP source is not in
+ *    the reference tree: both rules are restated from upstream COLMAP 3.11, parity unpinned.
+ *
+ *    mpsfm_visibility_scores: COLMAP's per-image statistics num_visible_points3D and point3D_visibility_score
+ *    (VisibilityPyramid::SetPoint applied to the set that ObservationManager maintains incrementally), stated on sets:
+ *      keypoint k is VISIBLE when some entry p of its row corr_kp[corr_start[k] .. corr_start[k + 1]) has kp_point[p] >= 0
+ *      (its own point does not count).  With D = 1 << num_levels, cx = clamp((int64) trunc((double) D * x / width), 0, D - 1),
+ *      a negative or NaN operand giving 0, and cy likewise from height: level l = 1 .. num_levels has 2^l x 2^l cells, the
+ *      visible keypoint occupies cell (cy >> (num_levels - l), cx >> (num_levels - l)) of it;
+ *      score[i] = sum over l of occupied_cells(l) * 4^l, num_visible[i] = the number of visible keypoints of image i,
+ *      kp_visible[k] = 1 / 0 (may be NULL).  num_levels: 6 is COLMAP's kNumPoint3DVisibilityPyramidLevels; 1 .. 8 are accepted.
+ *      image_size [n_images][2]: width, height.  Every output is an integer: bitwise the same from run to run.
+ *    MPSFM_EINVAL before any device is touched: NULL pointers (info and kp_visible may be NULL; arrays of length 0 may be NULL),
+ *    a negative count, num_levels outside 1 .. 8, kp_start[0] or corr_start[0] != 0, a decreasing kp_start or corr_start, a
+ *    corr_kp outside [0, n_kp), a width or height <= 0.  MPSFM_EUNSUPPORTED: n_kp >= 2^31.  No keypoints: zeros without a device.
+ *
+ *    mpsfm_local_bundles: IncrementalMapper::FindLocalBundle for n_refs reference images in one call (the same image may occur
+ *    twice).  Keypoints of images that are not registered are ignored.  With m_r(p) the number of keypoints of reference r whose
+ *    point is p:
+ *      shared[r][j]   = sum over the keypoints k' of image j != r with a point p' of m_r(p'): track elements count with
+ *                       multiplicity, as in COLMAP's map.  shared[r][r] = 0.
+ *      overlapping images: shared > 0, ordered by shared descending, equal counts by ascending image index (COLMAP leaves
+ *                       those to an unordered map).
+ *      angle list of (r, j): ONE entry per keypoint k' of j with m_r(p') > 0, the triangulation angle of X_p' between the
+ *                       projection centres C = -R^T t of r and j (CalculateTriangulationAngle, radians).
+ *      angle75[r][j]  = the element of rank floor(0.75 (n - 1) + 0.5) of that list in ascending order (COLMAP's Percentile,
+ *                       which rounds), -1 where shared == 0.  Exact: it does not depend on the order of the list.
+ *      selection: N = num_images - 1, E = min(N, #overlapping).  If #overlapping == E all are taken in order.  Otherwise, with
+ *                       T the number of keypoints of r with a point, the eight thresholds (min_tri_angle_rad / {1, 1.5, 2, 2.5,
+ *                       3, 4, 5, 6}, {0.6, 0.6, 0.5, 0.4, 0.3, 0.2, 0.1, 0.1} * T) are walked in turn, each over the overlapping
+ *                       images in order: the walk of a threshold stops at the first image whose shared is below the second
+ *                       number, images already taken are skipped, an image is taken when angle75 >= the first number;
+ *                       everything stops at E images, and what is missing is filled with untaken images in order.
+ *      bundle [n_refs][num_images - 1]: image indices, padded with -1; bundle_len [n_refs]; shared and angle75 [n_refs][n_images].
+ *    MPSFM_EINVAL before any device is touched: NULL pointers, negative counts, kp_start as above, num_images < 1, a
+ *    min_tri_angle_deg that is negative or not finite, a reference outside [0, n_images) or not registered, a kp_point
+ *    outside [-1, n_points), a pose of a registered image or a point that is not finite.  Many references are worked off in
+ *    groups that share one workspace (info->num_groups), still with one wait. ---- */
+typedef struct mpsfm_scene_query_info {
+  int64_t num_launches; /* kernel launches of the call */
+  int64_t num_syncs;    /* stream synchronisations of the call */
+  int64_t num_groups;   /* groups of reference images (mpsfm_local_bundles; 1 for mpsfm_visibility_scores) */
+  float ms;             /* device time from the first kernel to the last (HIP events), transfers excluded */
+  int32_t reserved;
+} mpsfm_scene_query_info;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_scene_query_info) == 32 && offsetof(mpsfm_scene_query_info, num_groups) == 16 &&
+                  offsetof(mpsfm_scene_query_info, ms) == 24,
+              "ABI of mpsfm_scene_query_info");
+#endif
+
+int mpsfm_visibility_scores(int32_t n_images, const int64_t* kp_start /* [n_images + 1] */, const double* kp_xy /* [n_kp][2] */,
+                            const int64_t* corr_start /* [n_kp + 1] */, const int64_t* corr_kp /* [n_corr] */,
+                            const int64_t* kp_point /* [n_kp] */, const int32_t* image_size /* [n_images][2] */, int32_t num_levels,
+                            int32_t device, int32_t* num_visible /* [n_images] */, int64_t* score /* [n_images] */,
+                            uint8_t* kp_visible /* [n_kp], may be NULL */, mpsfm_scene_query_info* info /* may be NULL */);
+
+int mpsfm_local_bundles(int32_t n_images, const int64_t* kp_start /* [n_images + 1] */, const mpsfm_tri_state* state, int32_t n_refs,
+                        const int32_t* ref_image /* [n_refs] */, int32_t num_images, double min_tri_angle_deg, int32_t device,
+                        int32_t* bundle /* [n_refs][num_images - 1] */, int32_t* bundle_len /* [n_refs] */,
+                        int32_t* shared /* [n_refs][n_images] */, double* angle75 /* [n_refs][n_images] */,
+                        mpsfm_scene_query_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,6 +293,11 @@ class CCorrGraphInfo(C.Structure):
                 ("num_launches", C.c_int64), ("num_syncs", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
 
 
+class CSceneQueryInfo(C.Structure):
+    _c_name_ = "mpsfm_scene_query_info"
+    _fields_ = [("num_launches", C.c_int64), ("num_syncs", C.c_int64), ("num_groups", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+
 class CRecipOptions(C.Structure):
     _c_name_ = "mpsfm_recip_options"
     _fields_ = [("subsample", C.c_int32), ("max_iter", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
@@ -463,6 +468,8 @@ SIGNATURES = {
     "mpsfm_depth_priors": (C.c_int, [I32, P, P, I32, P, P]),
     "mpsfm_normal_priors": (C.c_int, [I32, P, P, I32, P, P]),
     "mpsfm_corr_graph_build": (C.c_int, [I32, P, I32, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "mpsfm_visibility_scores": (C.c_int, [I32, P, P, P, P, P, P, I32, I32, P, P, P, P]),
+    "mpsfm_local_bundles": (C.c_int, [I32, P, P, I32, P, I32, F64, I32, P, P, P, P, P]),
 }
 
 # include/mpsfm_hip_debug.h: test and diagnostic hooks, outside the stable ABI

@@ -14,7 +14,7 @@ from .abi import (  # noqa: F401 - declared in abi.py; these names stay importab
     ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CCorrGraphInfo, CDcImage, CDebugLmCtl, CDebugLmOpts, CDcSummary, CDepthGather, CDepthPriorConf,
     CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
-    CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
+    CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CSceneQueryInfo, CTriState, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
     CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
 )
 from .problem import BAProblem, Tracks
@@ -1056,6 +1056,69 @@ def corr_graph_build(kp_start, list_image0, list_image1, list_start, matches, de
     return dict(match_status=status[:n], corr_start=corr_start, corr_kp=corr_kp[:nc].copy(), image_num_correspondences=im_corr[:n_images],
                 image_num_observations=im_obs[:n_images], kp_two_view=two_view[:n_kp], pair_image0=p0[:npairs].copy(), pair_image1=p1[:npairs].copy(),
                 pair_start=pstart[:npairs + 1].copy(), pair_matches=pm[:nc // 2].copy(), info=info)
+
+
+def _ptr(a):
+    """The address of an array, NULL for None."""
+    return None if a is None else a.ctypes.data
+
+
+def _scene_query_info(I):
+    return dict(num_launches=int(I.num_launches), num_syncs=int(I.num_syncs), num_groups=int(I.num_groups), ms=float(I.ms))
+
+
+def visibility_scores(kp_start, kp_xy, corr_start, corr_kp, kp_point, image_size, num_levels=6, device=0, return_kp_visible=True):
+    """mpsfm_visibility_scores on the arrays of graph_arrays() / state_arrays() (sfm/mapper/track_engine.py): `image_size` int32
+    [n_images, 2] (width, height).  Returns a dict of num_visible int32 [n_images], score int64 [n_images], kp_visible uint8 [n_kp]
+    (None when not asked for) and info.  The library checks the values (MPSFM_EINVAL); None stands for a NULL pointer."""
+    def arr(a, dt):
+        return None if a is None else np.ascontiguousarray(a, dt)
+
+    kp_start, kp_xy, corr_start = arr(kp_start, np.int64), arr(kp_xy, np.float64), arr(corr_start, np.int64)
+    corr_kp, kp_point, image_size = arr(corr_kp, np.int64), arr(kp_point, np.int64), arr(image_size, np.int32)
+    n_images = -1 if kp_start is None else len(kp_start) - 1
+    n_kp = 0 if kp_start is None or n_images < 0 else max(int(kp_start[-1]), 0)
+    for a, n, what in ((kp_xy, 2 * n_kp, "kp_xy [n_kp, 2]"), (corr_start, n_kp + 1, "corr_start [n_kp + 1]"), (kp_point, n_kp, "kp_point [n_kp]"),
+                       (image_size, 2 * max(n_images, 0), "image_size [n_images, 2]")):
+        if a is not None and a.size < n:
+            raise ValueError(f"{what} is too short")
+    if corr_kp is not None and corr_start is not None and len(corr_start) and corr_kp.size < int(corr_start.reshape(-1)[n_kp]):
+        raise ValueError("corr_kp is shorter than corr_start[n_kp]")
+    nvis, score = np.zeros(max(n_images, 1), np.int32), np.zeros(max(n_images, 1), np.int64)
+    vis = np.zeros(max(n_kp, 1), np.uint8) if return_kp_visible else None
+    I = CSceneQueryInfo()
+    _check(lib().mpsfm_visibility_scores(n_images, _ptr(kp_start), _ptr(kp_xy), _ptr(corr_start), _ptr(corr_kp), _ptr(kp_point), _ptr(image_size),
+                                         int(num_levels), int(device), nvis.ctypes.data, score.ctypes.data, _ptr(vis), C.addressof(I)))
+    n = max(n_images, 0)
+    return dict(num_visible=nvis[:n], score=score[:n], kp_visible=None if vis is None else vis[:n_kp], info=_scene_query_info(I))
+
+
+def local_bundles(kp_start, registered, cam_quat_xyzw, cam_t, kp_point, xyz, ref_image, num_images, min_tri_angle_deg, device=0):
+    """mpsfm_local_bundles on the arrays of state_arrays(): `ref_image` image INDICES.  Returns a dict of bundle int32
+    [n_refs, num_images - 1] (padded with -1), bundle_len int32 [n_refs], shared int32 [n_refs, n_images], angle75 float64
+    [n_refs, n_images] (radians, -1 where shared == 0) and info.  The library checks the values (MPSFM_EINVAL)."""
+    kp_start = np.ascontiguousarray(kp_start, np.int64).reshape(-1)
+    n_images = len(kp_start) - 1
+    n_kp = max(int(kp_start[-1]), 0) if n_images >= 0 else 0
+    reg = np.ascontiguousarray(registered, np.uint8).reshape(-1)
+    quat, trans = np.ascontiguousarray(cam_quat_xyzw, np.float64).reshape(-1, 4), np.ascontiguousarray(cam_t, np.float64).reshape(-1, 3)
+    kp_point, xyz = np.ascontiguousarray(kp_point, np.int64).reshape(-1), np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    refs = np.ascontiguousarray(ref_image, np.int32).reshape(-1)
+    if len(reg) != max(n_images, 0) or len(quat) != len(reg) or len(trans) != len(reg) or len(kp_point) < n_kp:
+        raise ValueError("registered / cam_quat_xyzw / cam_t are [n_images], kp_point is [n_kp]")
+    n_refs, width = len(refs), max(int(num_images) - 1, 0)
+    bundle, blen = np.full((max(n_refs, 1), max(width, 1)), -1, np.int32), np.zeros(max(n_refs, 1), np.int32)
+    shared = np.zeros((max(n_refs, 1), max(n_images, 1)), np.int32)
+    angle75 = np.full((max(n_refs, 1), max(n_images, 1)), -1.0)
+    st = CTriState(reg.ctypes.data if len(reg) else None, quat.ctypes.data if len(reg) else None, trans.ctypes.data if len(reg) else None,
+                   kp_point.ctypes.data if n_kp else None, len(xyz), xyz.ctypes.data if len(xyz) else None)
+    I = CSceneQueryInfo()
+    _check(lib().mpsfm_local_bundles(n_images, kp_start.ctypes.data, C.addressof(st), n_refs, refs.ctypes.data if n_refs else None, int(num_images),
+                                     float(min_tri_angle_deg), int(device), bundle.ctypes.data, blen.ctypes.data, shared.ctypes.data,
+                                     angle75.ctypes.data, C.addressof(I)))
+    n = max(n_images, 0)
+    return dict(bundle=bundle[:n_refs, :width], bundle_len=blen[:n_refs], shared=shared[:n_refs, :n], angle75=angle75[:n_refs, :n],
+                info=_scene_query_info(I))
 
 
 def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=None, ratio_threshold=None, distance_threshold=None,

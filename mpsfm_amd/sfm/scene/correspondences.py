@@ -8,7 +8,7 @@ By default each pair is one stateless call of ``mpsfm_two_view_geometry`` in a p
 pool, with the same result for every pair.
 ``Correspondences`` reads keypoints and matches from a ``CorrespondenceStore`` in memory where the reference reads the extractor's
 HDF5 files, verifies all pairs in one batched call and fills a ``HipCorrespondenceGraph``, which one GPU call builds
-(DESIGN.md section 4s).  HDF5 I/O and ``ImageSelection`` stay with the reference.
+(DESIGN.md section 4s).  HDF5 I/O stays with the reference; ``ImageSelection`` is sfm/mapper/image_selection.py.
 """
 
 from __future__ import annotations
