@@ -269,6 +269,48 @@ int mpsfm_filter_tracks(const mpsfm_tracks* tracks, const double* xyz /* [n_trac
                         int32_t device, double* max_tri_angle /* [n_tracks] */,
                         double* el_sq_err /* [n_el] */, uint8_t* el_front /* [n_el] */);
 
+/* -- depth lifting of low-parallax points (mpsfm/sfm/mapper/triangulator.py:49-83, 125-161) for a batch of tracks in
+ *    one call.  Per track t, with the elements in the order given:
+ *      risky[t]      = max_tri_angle[t] < min_angle_rad, the angle bit for bit that of mpsfm_filter_tracks for the same
+ *                      inputs (tracks of 0 or 1 elements have angle 0: risky whenever min_angle_rad > 0).
+ *      lift_el[t]    of a risky track: the position in the track of the first element e whose camera is activated and
+ *                      whose bilinear sample of valid_map at the keypoint is exactly 1 (PriorUtils.valid_at_kps);
+ *                      -1 where no element lifts (the caller deletes such a point without a replacement).
+ *      lift_depth[t] = d, the bilinear sample of depth_map at the same coordinate.
+ *      lift_xyz[t]   = R^T (((x - cx) / fx, (y - cy) / fy, 1) d - t) with the pose and intrinsics of that element's
+ *                      camera, every operation rounded on its own.
+ *      el_keep[e']   = (row 2 of R' times lift_xyz + t'_2 >= 2^-52) for EVERY element e' of a lifted track, the lifting
+ *                      element included (a sampled depth <= 0 drops it).
+ *    A track that is not risky, and a risky one that does not lift, get lift_el = -1 and zeros in lift_depth, lift_xyz
+ *    and el_keep.  Two phases with one host wait each: the angles (the kernel of mpsfm_filter_tracks), then, for the
+ *    risky tracks only, the maps of the activated cameras that occur in them in one staged upload and the lift launch
+ *    (one wavefront per risky track).  Without a risky track the call ends after the first phase.
+ *    MPSFM_EINVAL: what mpsfm_filter_tracks refuses; NULL maps, NULL arrays of maps, NULL outputs; an activated
+ *    camera of a risky track with a NULL map, map_h < 2, map_w < 2 or more than 2^30 pixels; min_angle_rad NaN or
+ *    negative.  n_tracks == 0 returns 0 before any device work. -------------------------------------------------- */
+typedef struct mpsfm_lift_maps {   /* per camera of mpsfm_tracks, in the same order */
+  const uint8_t* activated;        /* [n_cams] image.depth.activated */
+  const int32_t* map_h;            /* [n_cams], read where activated */
+  const int32_t* map_w;            /* [n_cams], read where activated */
+  const double* const* depth_map;  /* [n_cams] -> H*W depth.data; an entry may be NULL where not activated */
+  const uint8_t* const* valid_map; /* [n_cams] -> H*W depth.valid; likewise */
+  const double* sx;                /* [n_cams] camera.sx */
+  const double* sy;                /* [n_cams] camera.sy */
+} mpsfm_lift_maps;
+
+typedef struct mpsfm_lift_info {
+  int64_t n_risky, n_lifted, n_no_lift; /* risky tracks; those with and without a lifting element */
+  int32_t n_maps_uploaded;              /* cameras whose two maps went to the device */
+  int64_t bytes_uploaded;               /* bytes of those maps */
+  double ms;                            /* device time of the angle launch plus the lift launch (HIP events) */
+} mpsfm_lift_info;
+
+int mpsfm_lift_tracks(const mpsfm_tracks* tracks, const double* xyz /* [n_tracks][3] current points */,
+                      const mpsfm_lift_maps* maps, double min_angle_rad, int32_t device,
+                      uint8_t* risky /* [n_tracks] */, int32_t* lift_el /* [n_tracks] position in the track, -1: none */,
+                      double* lift_depth /* [n_tracks] */, double* lift_xyz /* [n_tracks][3] */,
+                      uint8_t* el_keep /* [n_el] */, mpsfm_lift_info* info /* may be NULL */);
+
 /* -- row f2: track-graph logic of pycolmap.IncrementalTriangulator as MpsfmTriangulator drives it
  *    (mpsfm/sfm/mapper/triangulator.py:32-48, 88-100, 123, 165-175): Find / Create / Continue, Complete, Merge,
  *    Retriangulate with the fork's ignore_image_ids.  COLMAP 3.11 semantics (the fork's source is not in the reference

@@ -106,6 +106,18 @@ class CTracks(C.Structure):
     ]
 
 
+class CLiftMaps(C.Structure):
+    _c_name_ = "mpsfm_lift_maps"
+    _fields_ = [("activated", C.c_void_p), ("map_h", C.c_void_p), ("map_w", C.c_void_p), ("depth_map", C.c_void_p),
+                ("valid_map", C.c_void_p), ("sx", C.c_void_p), ("sy", C.c_void_p)]
+
+
+class CLiftInfo(C.Structure):
+    _c_name_ = "mpsfm_lift_info"
+    _fields_ = [("n_risky", C.c_int64), ("n_lifted", C.c_int64), ("n_no_lift", C.c_int64), ("n_maps_uploaded", C.c_int32),
+                ("bytes_uploaded", C.c_int64), ("ms", C.c_double)]
+
+
 class CIntProblem(C.Structure):
     _c_name_ = "mpsfm_int_problem"
     _fields_ = [
@@ -420,6 +432,7 @@ SIGNATURES = {
     "mpsfm_point_covs": (C.c_int, [P, P, I32, P]),
     "mpsfm_triangulate_tracks": (C.c_int, [P, I32, P]),
     "mpsfm_filter_tracks": (C.c_int, [P, P, I32, P, P, P]),
+    "mpsfm_lift_tracks": (C.c_int, [P, P, P, F64, I32, P, P, P, P, P, P]),
     "mpsfm_tri_default_options": (None, [P]),
     "mpsfm_triangulator_create": (C.c_int, [P, I32, _pp]),
     "mpsfm_triangulator_destroy": (None, [P]),

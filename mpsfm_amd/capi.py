@@ -12,7 +12,7 @@ import numpy as np
 
 from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
     ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CCorrGraphInfo, CDcImage, CDebugLmCtl, CDebugLmOpts, CDcSummary, CDepthGather, CDepthPriorConf,
-    CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
+    CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CLiftInfo, CLiftMaps, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
     CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CSceneQueryInfo, CTriState, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
     CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
@@ -294,6 +294,44 @@ def filter_tracks(tr: Tracks, xyz: np.ndarray, device: int = 0):
     ct = tr.c_tracks()
     _check(lib().mpsfm_filter_tracks(C.byref(ct), xyz.ctypes.data, device, ang.ctypes.data, err.ctypes.data, front.ctypes.data))
     return ang, err, front.astype(bool)
+
+
+def lift_tracks(tr: Tracks, xyz, activated, depth_maps, valid_maps, sx, sy, min_angle_deg, device=0) -> dict:
+    """mpsfm_lift_tracks: the depth lifting of the low-parallax points among `tr` in one call.  `activated`, `depth_maps`,
+    `valid_maps`, `sx`, `sy`: one entry per camera of `tr`; the maps of a camera that is not activated may be None.
+    Returns dict(risky bool [n_tracks], lift_el int32 [n_tracks] (-1: no lift), lift_depth [n_tracks], lift_xyz [n_tracks,3],
+    el_keep bool [n_el], info dict)."""
+    n_cams = tr.cam_quat.shape[0]
+    if not (len(activated) == len(depth_maps) == len(valid_maps) == len(sx) == len(sy) == n_cams):
+        raise ValueError("lift_tracks: one entry per camera of the tracks")
+    xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    if len(xyz) != tr.n_tracks:
+        raise ValueError("lift_tracks: one point per track")
+    act = np.ascontiguousarray(activated, np.uint8)
+    dm = [None if m is None else np.ascontiguousarray(m, np.float64) for m in depth_maps]
+    vm = [None if m is None else np.ascontiguousarray(m.view(np.uint8) if getattr(m, "dtype", None) == np.bool_ else m, np.uint8) for m in valid_maps]
+    for d, v in zip(dm, vm):
+        if d is not None and v is not None and (d.ndim != 2 or d.shape != v.shape):
+            raise ValueError("lift_tracks: depth and valid maps must be [H,W] arrays of one shape")
+    hh = np.array([0 if m is None else m.shape[0] for m in dm], np.int32)
+    ww = np.array([0 if m is None else m.shape[1] for m in dm], np.int32)
+    sx, sy = np.ascontiguousarray(sx, np.float64), np.ascontiguousarray(sy, np.float64)
+    dptr = (C.c_void_p * max(n_cams, 1))(*[None if m is None else m.ctypes.data for m in dm])
+    vptr = (C.c_void_p * max(n_cams, 1))(*[None if m is None else m.ctypes.data for m in vm])
+    M = CLiftMaps()
+    M.activated, M.map_h, M.map_w = act.ctypes.data, hh.ctypes.data, ww.ctypes.data
+    M.depth_map, M.valid_map = C.addressof(dptr), C.addressof(vptr)
+    M.sx, M.sy = sx.ctypes.data, sy.ctypes.data
+    nt, ne = tr.n_tracks, tr.n_el
+    risky, keep = np.zeros(nt, np.uint8), np.zeros(ne, np.uint8)
+    lift_el, lift_depth, lift_xyz = np.full(nt, -1, np.int32), np.zeros(nt), np.zeros((nt, 3))
+    I = CLiftInfo()
+    ct = tr.c_tracks()
+    _check(lib().mpsfm_lift_tracks(C.byref(ct), xyz.ctypes.data, C.byref(M), float(np.deg2rad(float(min_angle_deg))), int(device),
+                                   risky.ctypes.data, lift_el.ctypes.data, lift_depth.ctypes.data, lift_xyz.ctypes.data, keep.ctypes.data,
+                                   C.byref(I)))
+    info = {k: getattr(I, k) for k, _ in CLiftInfo._fields_}
+    return dict(risky=risky.astype(bool), lift_el=lift_el, lift_depth=lift_depth, lift_xyz=lift_xyz, el_keep=keep.astype(bool), info=info)
 
 
 def depth_blocks(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts, scale_filter_factor=1.5,

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "tri_math.h"
 #include "call_scope.h"
+#include "tri_launch.h"
 
 namespace mpsfm {
 
@@ -59,13 +60,7 @@ __global__ void k_pcov_invert(int np, const double* H, const uint8_t* n_seen, do
   o[6] = Vi[2]; o[7] = Vi[4]; o[8] = Vi[5];
 }
 
-// ---- triangulation -------------------------------------------------------------------------------
-struct TrackArgs {
-  int32_t n_tracks;
-  const double* q; const double* t; const double* intr; const int32_t* intr_idx;
-  const int64_t* start; const int32_t* el_cam; const double* el_xy;
-};
-
+// ---- triangulation (TrackArgs: tri_launch.h) -----------------------------------------------------
 __global__ void k_triangulate(TrackArgs T, double* xyz) {
   const int tr = blockIdx.x * blockDim.x + threadIdx.x;
   if (tr >= T.n_tracks) return;
@@ -159,7 +154,7 @@ __global__ void k_filter(TrackArgs T, const double* xyz, double* max_angle, doub
   if (max_angle) max_angle[tr] = best;
 }
 
-static int check_tracks(const mpsfm_tracks* T) {
+int check_tracks(const mpsfm_tracks* T) {
   if (!T || T->n_tracks < 0 || T->n_cams < 0) return fail(MPSFM_EINVAL, "tracks is NULL or has negative sizes");
   if (T->n_tracks > 0 && !T->track_start) return fail(MPSFM_EINVAL, "track_start is NULL");
   if (T->n_tracks == 0) return 0;
@@ -177,7 +172,7 @@ static int check_tracks(const mpsfm_tracks* T) {
   return 0;
 }
 
-static int upload_tracks(const mpsfm_tracks* T, CallScope& B, TrackArgs& a) {
+int upload_tracks(const mpsfm_tracks* T, CallScope& B, TrackArgs& a) {
   const int64_t ne = T->n_tracks > 0 ? T->track_start[T->n_tracks] : 0;
   a.n_tracks = T->n_tracks;
   a.q = B.put(T->cam_quat_xyzw, (size_t)T->n_cams * 4);
@@ -189,6 +184,10 @@ static int upload_tracks(const mpsfm_tracks* T, CallScope& B, TrackArgs& a) {
   a.el_xy = B.put(T->el_xy, (size_t)ne * 2);
   if (!a.q || !a.t || !a.intr || !a.intr_idx || !a.start || !a.el_cam || !a.el_xy) return fail(MPSFM_ENOMEM, "hipMalloc failed");
   return 0;
+}
+
+void launch_filter_tracks(const TrackArgs& a, const double* xyz, double* max_angle, double* sq_err, uint8_t* front, hipStream_t st) {
+  hipLaunchKernelGGL(k_filter, dim3((a.n_tracks + 127) / 128), dim3(128), 0, st, a, xyz, max_angle, sq_err, front);
 }
 
 }  // namespace mpsfm
@@ -270,7 +269,7 @@ int mpsfm_filter_tracks(const mpsfm_tracks* T, const double* xyz, int32_t device
   double* derr = el_sq_err ? B.alloc<double>((size_t)ne) : nullptr;
   uint8_t* dfr = el_front ? B.alloc<uint8_t>((size_t)ne) : nullptr;
   if (!dxyz || (max_tri_angle && !dang) || (el_sq_err && !derr) || (el_front && !dfr)) return fail(MPSFM_ENOMEM, "hipMalloc failed");
-  hipLaunchKernelGGL(k_filter, dim3((T->n_tracks + 127) / 128), dim3(128), 0, B.st, a, dxyz, dang, derr, dfr);
+  launch_filter_tracks(a, dxyz, dang, derr, dfr, B.st);
   MPSFM_TRY(hipGetLastError());
   if (dang) MPSFM_TRY(B.down(max_tri_angle, dang, sizeof(double) * (size_t)T->n_tracks));
   if (derr) MPSFM_TRY(B.down(el_sq_err, derr, sizeof(double) * (size_t)ne));

@@ -100,6 +100,12 @@ class MpsfmTriangulator(BaseClass, ColmapTriangulatorWrapper):
         # one of this repository (built on first use: the scene's keypoints must all be there by then)
         self._triangulator = engine
         self.device = int(kwargs.get("device", 0))
+        # "loop": the reference's per-point Python loop (_lift_points); "batch": one mpsfm_lift_tracks call per lift_low_parallax
+        self.lift = kwargs.get("lift", "loop")
+        if self.lift not in ("loop", "batch"):
+            raise ValueError(f"lift must be 'loop' or 'batch', not {self.lift!r}")
+        # a callable with capi.lift_tracks's signature and return value, used instead of the library (tests without a GPU)
+        self.lift_backend = kwargs.get("lift_backend")
         opts = self.conf.colmap_options
         if isinstance(opts, dict):
             self.options = dict(opts)
@@ -153,8 +159,50 @@ class MpsfmTriangulator(BaseClass, ColmapTriangulatorWrapper):
         ids = np.array([int(p) for p in point3D_ids if int(p) in self.mpsfm_rec.points3D], dtype=np.int64)
         if len(ids) == 0:
             return []
+        if self.lift == "batch":
+            return self._lift_points_batch(ids, min_angle)
         ang, _, _ = track_quality(self.mpsfm_rec, ids, self.device)
         return self._lift_points(ids[ang < np.deg2rad(float(min_angle))])
+
+    def _lift_points_batch(self, ids, min_angle):
+        """lift_low_parallax in one mpsfm_lift_tracks call: the angles, the choice of the lifting element, the lifted point
+        and the cheirality of every track element come back per track; the scene is then changed in the order of `ids`,
+        point by point as the loop does it, so new ids are allocated in the same sequence."""
+        rec = self.mpsfm_rec
+        # (the elements of the few risky tracks are read from the points below, in the order tracks_from_scene walked them:
+        # keep_elements=True would build a tuple per element of every track, a fifth of this method's time at 150 k elements)
+        tr, imids = tracks_from_scene(rec, ids)
+        activated, depth_maps, valid_maps, sx, sy = [], [], [], [], []
+        for imid in imids:
+            image = rec.images[imid]
+            cam = rec.rec.cameras[image.camera_id]
+            on = bool(image.depth.activated)
+            activated.append(on)
+            depth_maps.append(image.depth.data if on else None)
+            valid_maps.append(image.depth.valid if on else None)
+            sx.append(cam.sx)
+            sy.append(cam.sy)
+        lift = self.lift_backend
+        if lift is None:
+            from ... import capi
+
+            lift = capi.lift_tracks
+        out = lift(tr, rec.point3D_coordinates(ids), activated, depth_maps, valid_maps, sx, sy, float(min_angle), self.device)
+        self.last_lift_info = out["info"]
+        start, new_ids = tr.track_start, []
+        for k in np.flatnonzero(out["risky"]):
+            pid = int(ids[k])
+            old = rec.points3D[pid].track
+            elements = [(el.image_id, el.point2D_idx) for el in old.elements]
+            rec.obs.delete_point3D(pid)
+            if out["lift_el"][k] < 0:
+                continue
+            track = type(old)()
+            for el, keep in zip(elements, out["el_keep"][int(start[k]):int(start[k + 1])]):
+                if keep:
+                    track.add_element(*el)
+            new_ids.append(rec.obs.add_point3D(np.array(out["lift_xyz"][k]), track))
+        return new_ids
 
     def triangulate_image(self, imid, **kwargs) -> bool:
         self._require_engine()
@@ -164,16 +212,24 @@ class MpsfmTriangulator(BaseClass, ColmapTriangulatorWrapper):
             self.lift_low_parallax(set(self.mpsfm_rec.points3D.keys()) - in3D, self.conf.hard_angle)
         return True
 
+    def _num_safe_points(self, imid) -> int:
+        """Points observed by the image whose track has more than two elements (reference :134-136): one bulk read of
+        the track lengths where the scene offers it, else point by point."""
+        rec = self.mpsfm_rec
+        image = rec.images[imid]
+        p3d = image.point3D_ids(image.get_observation_point2D_idxs())
+        if hasattr(rec, "point3D_track_lengths"):
+            ids = np.unique(np.asarray(p3d, dtype=np.uint64))
+            return int((np.asarray(rec.point3D_track_lengths(ids)) > 2).sum())
+        return sum(1 for p in set(p3d) if len(rec.points3D[p].track.elements) > 2)
+
     def retriangulate(self):
         self._require_engine()
         rec = self.mpsfm_rec
         risky_imids = []
         if self.conf.new_retry_nbatch is not None:
             for imid in list(rec.registered_images):
-                image = rec.images[imid]
-                p3d = set(image.point3D_ids(image.get_observation_point2D_idxs()))
-                nsafe = sum(1 for p in p3d if len(rec.points3D[p].track.elements) > 2)
-                if nsafe < self.conf.nsafe_threshold:
+                if self._num_safe_points(imid) < self.conf.nsafe_threshold:
                     risky_imids.append(imid)
             expanded = sum((rec.find_local_bundle_ids(i, self.conf.new_retry_nbatch) for i in risky_imids), [])
             risky_imids = risky_imids + expanded
