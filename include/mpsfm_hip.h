@@ -1485,6 +1485,73 @@ int mpsfm_local_bundles(int32_t n_images, const int64_t* kp_start /* [n_images +
                         int32_t* shared /* [n_refs][n_images] */, double* angle75 /* [n_refs][n_images] */,
                         mpsfm_scene_query_info* info /* may be NULL */);
 
+/* ---- the filter behind a bundle adjustment, over the scene's arrays (reference mpsfm/sfm/mapper/base.py:686-797: filter_bundle /
+ *    filter_all; the design and the measurements: DESIGN.md section 4v).  ONE stateless call does what the mapper does through
+ *    ObservationManager one filter at a time: filter_observations_with_negative_depth, the "risky" set of find_invalid_depth_points,
+ *    filter_points3D on that set and filter_points3D on the bundle's points.  It reads kp_start, kp_xy and cam_intr of
+ *    mpsfm_tri_graph (corr_* may be NULL) and the whole mpsfm_tri_state; it changes nothing: the caller applies the answer.  One
+ *    host wait per call (info->num_syncs == 1); every output is the same bit for bit from run to run.
+ *
+ *    The rules (COLMAP 3.11 ObservationManager as sfm/scene/observations.py freezes it), per point p with the elements
+ *    E = {k : kp_point[k] == p}, in ascending k.  A point index without an element is untouched and never counted.
+ *      per element     with R, t of the image that owns k (R from the quaternion, C = -R^T t) and its fx fy cx cy:
+ *                      (xc, yc, zc) = R X + t, front = zc >= 2^-52, sq_err = (fx xc / zc + cx - x)^2 + (fy yc / zc + cy - y)^2.
+ *                      Every product and sum rounds on its own (no fused multiply-add), left to right.
+ *      step 0          only with negative_depth.  n = |E|, m = the elements that are not in front.  m == 0: nothing.  n - m >= 2:
+ *                      those m observations are removed, num_negative += m.  Otherwise the point dies, num_negative +=
+ *                      max(n - 1, 1): the delete_observation calls up to and including the one that meets a track of length <= 2.
+ *      risky set A     on what step 0 left: p is in A iff in_bundle and kp_invalid_depth are given, at least one image is in the
+ *                      bundle, and every bundle image owns at least one surviving element of p with kp_invalid_depth == 1 (two
+ *                      such keypoints of one image count once): set.intersection(*find_invalid_depth_points(optim_ids)).
+ *      a pass (max_err, thr) on the current elements, L of them: bad = not in front, or sq_err > max_err^2 (strict; a NaN error is
+ *                      not bad by itself).  L < 2 or |bad| >= L - 1: the point dies, changed += L.  Otherwise the bad observations
+ *                      are removed, changed += |bad|, and the largest pairwise angle of the remaining elements is taken (b2 =
+ *                      |C1 - C2|^2, r1 = |X - C1|^2, r2 = |X - C2|^2, den = 2 sqrt(r1 r2), 0 where den == 0, else a =
+ *                      |acos(clamp((r1 + r2 - b2) / den))|, min(a, pi - a)); if !(angle >= thr) the point dies, changed += 1.
+ *      order           pass A = pass(max_reproj_error, risky_min_tri_angle_rad) on the points of A (num_changed_a), then pass B =
+ *                      pass(max_reproj_error, min_tri_angle_rad) on the points of point_sel that still exist (num_changed_b); a
+ *                      point in both sets gets both.  point_sel == NULL selects every point: with no bundle that is filter_all.
+ *                      Points in neither set do step 0 only.
+ *    Outputs: kp_deleted [n_kp] 0, or 1 / 2 / 3 for an observation removed on its own in step 0 / pass A / pass B from a point that
+ *    lives on (the observations that go with a whole point are not marked, whenever they left it).  point_fate [n_points] 0 untouched,
+ *    1 kept with observations removed, 2 died in step 0, 3 / 4 died in pass A by reprojection / by angle, 5 / 6 the same in pass B.
+ *    point_risky [n_points] 1 for the points of A.  point_max_angle [n_points] (may be NULL) the angle of the angle test run on the
+ *    point, 0 where none ran.  kp_sq_err [n_kp] (may be NULL) sq_err of every keypoint with a point, 0 for the others.
+ *    MPSFM_EINVAL before any device is touched: NULL pointers (in_bundle, kp_invalid_depth, point_sel, point_max_angle, kp_sq_err and
+ *    info may be NULL; arrays of length 0 may be NULL), a negative count, kp_start[0] != 0 or decreasing, a kp_point outside
+ *    [-1, n_points), a keypoint with a point in an image that is not registered, a pose of a registered image, a point or an
+ *    intrinsic that is not finite, a max_reproj_error or an angle that is negative or not finite, a negative_depth other than 0 / 1.
+ *    MPSFM_EUNSUPPORTED: 2^31 keypoints or points.  n_points == 0 or n_kp == 0: zeroed outputs, no device. ---- */
+typedef struct mpsfm_scene_filter_options {
+  double max_reproj_error;         /* pixels: filter_max_reproj_error x median(kp_std) */
+  double min_tri_angle_rad;        /* pass B */
+  double risky_min_tri_angle_rad;  /* pass A: the mapper's 1.5 degrees */
+  int32_t negative_depth;          /* 1: step 0 runs */
+  int32_t reserved;
+} mpsfm_scene_filter_options;
+typedef struct mpsfm_scene_filter_info {
+  int64_t num_negative;           /* what filter_observations_with_negative_depth returns */
+  int64_t num_changed_a;          /* what filter_points3D returns on the risky set */
+  int64_t num_changed_b;          /* ... and on the selected points */
+  int64_t n_points_deleted;       /* points with point_fate >= 2 */
+  int64_t n_observations_deleted; /* keypoints with kp_deleted != 0 */
+  int64_t num_syncs;              /* stream synchronisations of the call */
+  float ms;                       /* device time from the first kernel to the last (HIP events), transfers excluded */
+  float ms_tracks;                /* ... of which the track lists: image records, keys, sort, segment starts */
+} mpsfm_scene_filter_info;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_scene_filter_options) == 32 && sizeof(mpsfm_scene_filter_info) == 56 &&
+                  offsetof(mpsfm_scene_filter_info, ms) == 48,
+              "ABI of mpsfm_filter_scene");
+#endif
+
+int mpsfm_filter_scene(const mpsfm_tri_graph* graph, const mpsfm_tri_state* state, const uint8_t* in_bundle /* [n_images] or NULL */,
+                       const uint8_t* kp_invalid_depth /* [n_kp] or NULL */, const uint8_t* point_sel /* [n_points] or NULL */,
+                       const mpsfm_scene_filter_options* options, int32_t device, uint8_t* kp_deleted /* [n_kp] */,
+                       uint8_t* point_fate /* [n_points] */, uint8_t* point_risky /* [n_points] */,
+                       double* point_max_angle /* [n_points], may be NULL */, double* kp_sq_err /* [n_kp], may be NULL */,
+                       mpsfm_scene_filter_info* info /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

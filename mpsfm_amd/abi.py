@@ -310,6 +310,19 @@ class CSceneQueryInfo(C.Structure):
     _fields_ = [("num_launches", C.c_int64), ("num_syncs", C.c_int64), ("num_groups", C.c_int64), ("ms", C.c_float), ("reserved", C.c_int32)]
 
 
+class CSceneFilterOptions(C.Structure):
+    _c_name_ = "mpsfm_scene_filter_options"
+    _fields_ = [("max_reproj_error", C.c_double), ("min_tri_angle_rad", C.c_double), ("risky_min_tri_angle_rad", C.c_double),
+                ("negative_depth", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CSceneFilterInfo(C.Structure):
+    _c_name_ = "mpsfm_scene_filter_info"
+    _fields_ = [("num_negative", C.c_int64), ("num_changed_a", C.c_int64), ("num_changed_b", C.c_int64), ("n_points_deleted", C.c_int64),
+                ("n_observations_deleted", C.c_int64), ("num_syncs", C.c_int64), ("ms", C.c_float),
+                ("ms_tracks", C.c_float)]
+
+
 class CRecipOptions(C.Structure):
     _c_name_ = "mpsfm_recip_options"
     _fields_ = [("subsample", C.c_int32), ("max_iter", C.c_int32), ("inputs_on_device", C.c_int32), ("stream", C.c_void_p)]
@@ -483,6 +496,7 @@ SIGNATURES = {
     "mpsfm_corr_graph_build": (C.c_int, [I32, P, I32, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "mpsfm_visibility_scores": (C.c_int, [I32, P, P, P, P, P, P, I32, I32, P, P, P, P]),
     "mpsfm_local_bundles": (C.c_int, [I32, P, P, I32, P, I32, F64, I32, P, P, P, P, P]),
+    "mpsfm_filter_scene": (C.c_int, [P, P, P, P, P, P, I32, P, P, P, P, P, P]),
 }
 
 # include/mpsfm_hip_debug.h: test and diagnostic hooks, outside the stable ABI

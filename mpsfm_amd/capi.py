@@ -14,7 +14,7 @@ from .abi import (  # noqa: F401 - declared in abi.py; these names stay importab
     ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CCorrGraphInfo, CDcImage, CDebugLmCtl, CDebugLmOpts, CDcSummary, CDepthGather, CDepthPriorConf,
     CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CLiftInfo, CLiftMaps, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
-    CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CSceneQueryInfo, CTriState, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
+    CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CSceneFilterInfo, CSceneFilterOptions, CSceneQueryInfo, CTriGraph, CTriState, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
     CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
 )
 from .problem import BAProblem, Tracks
@@ -1157,6 +1157,58 @@ def local_bundles(kp_start, registered, cam_quat_xyzw, cam_t, kp_point, xyz, ref
     n = max(n_images, 0)
     return dict(bundle=bundle[:n_refs, :width], bundle_len=blen[:n_refs], shared=shared[:n_refs, :n], angle75=angle75[:n_refs, :n],
                 info=_scene_query_info(I))
+
+
+def filter_scene(kp_start, kp_xy, intr, registered, cam_quat_xyzw, cam_t, kp_point, xyz, max_reproj_error, min_tri_angle_deg,
+                 risky_min_tri_angle_deg=1.5, in_bundle=None, kp_invalid_depth=None, point_sel=None, negative_depth=True, device=0,
+                 return_values=True) -> dict:
+    """mpsfm_filter_scene on the arrays of graph_arrays() / state_arrays() (sfm/mapper/track_engine.py): the whole filter behind a
+    bundle adjustment in one call.  `in_bundle` uint8 [n_images] and `kp_invalid_depth` uint8 [n_kp] describe the risky set (None: no
+    such set), `point_sel` uint8 [n_points] the points of the second pass (None: every point).  Angles in degrees, converted with
+    np.deg2rad: the thresholds are bit for bit those of sfm/scene/observations.py.  Returns a dict of kp_deleted uint8 [n_kp],
+    point_fate uint8 [n_points] (0 .. 6 as in include/mpsfm_hip.h), point_risky uint8 [n_points], point_max_angle float64 [n_points] and kp_sq_err
+    float64 [n_kp] (both None unless `return_values`) and info.  The library checks the values (MPSFM_EINVAL)."""
+    kp_start = np.ascontiguousarray(kp_start, np.int64).reshape(-1)
+    n_images = len(kp_start) - 1
+    if n_images < 0:
+        raise ValueError("filter_scene: kp_start is [n_images + 1]")
+    n_kp = max(int(kp_start[-1]), 0)
+    kp_xy, intr = np.ascontiguousarray(kp_xy, np.float64).reshape(-1, 2), np.ascontiguousarray(intr, np.float64).reshape(-1, 4)
+    reg = np.ascontiguousarray(registered, np.uint8).reshape(-1)
+    quat, trans = np.ascontiguousarray(cam_quat_xyzw, np.float64).reshape(-1, 4), np.ascontiguousarray(cam_t, np.float64).reshape(-1, 3)
+    kp_point, xyz = np.ascontiguousarray(kp_point, np.int64).reshape(-1), np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    n_points = len(xyz)
+    if not (len(intr) == len(reg) == len(quat) == len(trans) == n_images):
+        raise ValueError("filter_scene: intr / registered / cam_quat_xyzw / cam_t are [n_images]")
+    if len(kp_xy) < n_kp or len(kp_point) < n_kp:
+        raise ValueError("filter_scene: kp_xy / kp_point are [n_kp]")
+
+    def flags(a, n, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(a) != 0, np.uint8).reshape(-1)
+        if len(a) != n:
+            raise ValueError(f"filter_scene: {what}")
+        return a
+
+    in_bundle = flags(in_bundle, n_images, "in_bundle is [n_images]")
+    kp_invalid_depth = flags(kp_invalid_depth, n_kp, "kp_invalid_depth is [n_kp]")
+    point_sel = flags(point_sel, n_points, "point_sel is [n_points]")
+    o = CSceneFilterOptions(float(max_reproj_error), float(np.deg2rad(float(min_tri_angle_deg))), float(np.deg2rad(float(risky_min_tri_angle_deg))),
+                            1 if negative_depth else 0, 0)
+    g = CTriGraph(n_images, kp_start.ctypes.data, kp_xy.ctypes.data if n_kp else None, intr.ctypes.data if n_images else None, None, None)
+    st = CTriState(reg.ctypes.data if n_images else None, quat.ctypes.data if n_images else None, trans.ctypes.data if n_images else None,
+                   kp_point.ctypes.data if n_kp else None, n_points, xyz.ctypes.data if n_points else None)
+    deleted, fate, risky = np.zeros(max(n_kp, 1), np.uint8), np.zeros(max(n_points, 1), np.uint8), np.zeros(max(n_points, 1), np.uint8)
+    angle = np.zeros(max(n_points, 1)) if return_values else None
+    sq_err = np.zeros(max(n_kp, 1)) if return_values else None
+    I = CSceneFilterInfo()
+    _check(lib().mpsfm_filter_scene(C.addressof(g), C.addressof(st), _ptr(in_bundle) if n_images else None, _ptr(kp_invalid_depth) if n_kp else None,
+                                    _ptr(point_sel) if n_points else None, C.addressof(o), int(device), deleted.ctypes.data, fate.ctypes.data,
+                                    risky.ctypes.data, _ptr(angle), _ptr(sq_err), C.addressof(I)))
+    info = {k: (float if k.startswith("ms") else int)(getattr(I, k)) for k, _ in CSceneFilterInfo._fields_}
+    return dict(kp_deleted=deleted[:n_kp], point_fate=fate[:n_points], point_risky=risky[:n_points],
+                point_max_angle=None if angle is None else angle[:n_points], kp_sq_err=None if sq_err is None else sq_err[:n_kp], info=info)
 
 
 def match_map_descriptors(map0, conf0, map1, conf1, kps0, kps1, score_threshold=None, ratio_threshold=None, distance_threshold=None,
