@@ -76,6 +76,9 @@ int mpsfm_debug_lm_decide(int32_t form, const mpsfm_debug_lm_ctl* ctl_in, const 
                           const double* part2, int64_t rows, int32_t fill, mpsfm_debug_lm_ctl* ctl_out, mpsfm_debug_lm_ctl* host_out, int64_t info[4]);
 /* what the process holds of `device`'s caches: live device blocks, their bytes, and the pooled streams, events and pinned blocks handed out and not yet given back */
 int mpsfm_debug_resources(int32_t device, int64_t out[5]);
+/* the device paths of csrc/common.h's lean math over n items (at most 2^24).  kind 0: out[i] = lean_log(x[i]); 1: out[2i], out[2i + 1] = sin(t) / t and
+   cos(t) for t^2 = x[i]; 2: out[4i ..] = quat_plus(q = x[7i .. 7i + 3], d = x[7i + 4 .. 7i + 6]) */
+int mpsfm_debug_math_probe(int32_t kind, const double* x, int64_t n, double* out);
 
 #ifdef __cplusplus
 }

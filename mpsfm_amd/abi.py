@@ -521,6 +521,7 @@ DEBUG_SIGNATURES = {
     "mpsfm_debug_local_skew": (C.c_int, [I32, I32, I64]),
     "mpsfm_debug_lm_decide": (C.c_int, [I32, P, P, P, P, P, P, I64, I32, P, P, P]),
     "mpsfm_debug_resources": (C.c_int, [I32, P]),
+    "mpsfm_debug_math_probe": (C.c_int, [I32, P, I64, P]),
 }
 
 

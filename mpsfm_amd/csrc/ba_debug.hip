@@ -139,6 +139,44 @@ extern "C" int mpsfm_debug_lm_decide(int32_t form, const mpsfm_debug_lm_ctl* ctl
   return 0;
 }
 
+// Test hook (tests/test_gpu_lean_math.py): the device paths of the lean math of common.h over an array of n items.
+// kind 0: out[i] = lean_log(x[i]);  kind 1: out[2i], out[2i + 1] = sin(n) / n and cos(n) for n^2 = x[i] (quat_sinc_cos, both sides
+// of its branch);  kind 2: out[4i .. 4i + 3] = quat_plus(q = x[7i .. 7i + 3], d = x[7i + 4 .. 7i + 6]).
+__global__ __launch_bounds__(256) void k_math_probe(int kind, const double* __restrict__ x, int64_t n, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (kind == 0) {
+    out[i] = lean_log(x[i]);
+  } else if (kind == 1) {
+    double s, c;
+    quat_sinc_cos(x[i], s, c);
+    out[2 * i] = s; out[2 * i + 1] = c;
+  } else {
+    double q[4], d[3], o[4];
+    for (int k = 0; k < 4; ++k) q[k] = x[7 * i + k];
+    for (int k = 0; k < 3; ++k) d[k] = x[7 * i + 4 + k];
+    quat_plus(q, d, o);
+    for (int k = 0; k < 4; ++k) out[4 * i + k] = o[k];
+  }
+}
+extern "C" int mpsfm_debug_math_probe(int32_t kind, const double* x, int64_t n, double* out) {
+  if (kind < 0 || kind > 2 || n < 0 || n > (int64_t)1 << 24 || (n > 0 && (!x || !out))) return fail(MPSFM_EINVAL, "math probe: unknown kind, n outside [0, 2^24] or a NULL array");
+  if (n == 0) return 0;
+  const size_t nin = (size_t)n * (kind == 2 ? 7 : 1), nout = (size_t)n * (kind == 0 ? 1 : (kind == 1 ? 2 : 4));
+  DeviceBlocks own;  // waits for the stream before the blocks go back
+  hipStream_t s = nullptr;
+  MPSFM_TRY(own.stream(&s));
+  double* d_x = own.alloc<double>(nin);
+  double* d_out = own.alloc<double>(nout);
+  if (!own.ok()) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  MPSFM_TRY(hipMemcpyAsync(d_x, x, sizeof(double) * nin, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (int)kind, d_x, n, d_out);
+  MPSFM_TRY(hipGetLastError());
+  MPSFM_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
 extern "C" {
 
 int mpsfm_ba_dense_plan(mpsfm_ba_handle* h, int64_t info[10]) {

@@ -175,9 +175,7 @@ __global__ __launch_bounds__(kThreads) void k_track_sweep(SweepArgs A) {
       double V[6], Vi[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) V[k] = s_V[tid * 6 + k];
-      V[0] += fmin(fmax(V[0], A.min_diag), A.max_diag) / lm_radius;
-      V[3] += fmin(fmax(V[3], A.min_diag), A.max_diag) / lm_radius;
-      V[5] += fmin(fmax(V[5], A.min_diag), A.max_diag) / lm_radius;
+      damp_landmark(V, A.min_diag, A.max_diag, lm_radius, sweep_rcp(lm_radius));
       // Vi <- F = L^-1 of V + D = L L^T: the Schur products become Z Z'^T with Z = W F^T (see spd3_inv_factor)
       if (!spd3_inv_factor(V, Vi)) {
         my_bad = 1;
@@ -188,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void k_track_sweep(SweepArgs A) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) s_V[tid * 6 + k] = Vi[k];
       s_g[tid * 3] = Vi[0] * g0; s_g[tid * 3 + 1] = Vi[1] * g0 + Vi[2] * g1; s_g[tid * 3 + 2] = Vi[3] * g0 + Vi[4] * g1 + Vi[5] * g2;  // F g
-      my_gmax = fmax(fabs(g0 / my_ps[0]), fmax(fabs(g1 / my_ps[1]), fabs(g2 / my_ps[2])));
+      my_gmax = fmax(fabs(sweep_div(g0, my_ps[0])), fmax(fabs(sweep_div(g1, my_ps[1])), fabs(sweep_div(g2, my_ps[2]))));
     }
   }
   if (MODE == MODE_FULL) {
@@ -330,7 +328,7 @@ __global__ __launch_bounds__(kThreads) void k_track_sweep(SweepArgs A) {
 // Update sweep: y_p = -(V+D)^-1 (g_p + W^T y_c), model cost change, candidate landmarks, candidate
 // cost.  Recomputes the linearisation (cheaper than storing 240 B per record in HBM).
 #ifndef MPSFM_UPD_OCC
-#define MPSFM_UPD_OCC 4  // 117 / 119 registers without spills; LDS (6.4 / 12 KB) does not limit.  5 means 96 registers: 34 spilled, 49.7 instead of 38 us
+#define MPSFM_UPD_OCC 4  // 118 registers without spills; LDS (6.4 / 12 KB) does not limit.  5 means 96 registers: 34 spilled, 49.7 instead of 38 us
 #endif
 // kHandoff: F and g_p of every landmark come from the track sweep of the same iteration (SweepArgs::pt_fac)
 template <bool kHandoff>
@@ -434,12 +432,10 @@ __global__ __launch_bounds__(kThreads) void k_long_track_sweep(SweepArgs A) {
     double Vi[6] = {0, 0, 0, 0, 0, 0}, vg[3] = {0, 0, 0};
     if (pvar) {
       double V[6] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5]};
-      V[0] += fmin(fmax(V[0], A.min_diag), A.max_diag) / lm_radius;
-      V[3] += fmin(fmax(V[3], A.min_diag), A.max_diag) / lm_radius;
-      V[5] += fmin(fmax(V[5], A.min_diag), A.max_diag) / lm_radius;
+      damp_landmark(V, A.min_diag, A.max_diag, lm_radius, sweep_rcp(lm_radius));
       if (!spd3_inverse(V, Vi)) { my_bad += 1.0; for (int k = 0; k < 6; ++k) Vi[k] = 0.0; }
       sym3_mul(Vi, acc[6], acc[7], acc[8], vg);
-      my_gmax = fmax(fabs(acc[6] / psc[0]), fmax(fabs(acc[7] / psc[1]), fabs(acc[8] / psc[2])));
+      my_gmax = fmax(fabs(sweep_div(acc[6], psc[0])), fmax(fabs(sweep_div(acc[7], psc[1])), fabs(sweep_div(acc[8], psc[2]))));
     }
     for (int k = 0; k < 6; ++k) s_vi[k] = Vi[k];
     for (int k = 0; k < 3; ++k) s_vi[6 + k] = vg[k];
@@ -550,9 +546,7 @@ __global__ __launch_bounds__(kThreads) void k_long_update_sweep(SweepArgs A) {
     double yp[3] = {0, 0, 0}, X2[3] = {X[0], X[1], X[2]};
     if (pvar) {
       double V[6] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5]}, Vi[6];
-      V[0] += fmin(fmax(V[0], A.min_diag), A.max_diag) / lm_radius;
-      V[3] += fmin(fmax(V[3], A.min_diag), A.max_diag) / lm_radius;
-      V[5] += fmin(fmax(V[5], A.min_diag), A.max_diag) / lm_radius;
+      damp_landmark(V, A.min_diag, A.max_diag, lm_radius, sweep_rcp(lm_radius));
       if (!spd3_inverse(V, Vi)) {
         bad += 1.0;
       } else {

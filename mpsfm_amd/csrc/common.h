@@ -170,6 +170,13 @@ __device__ __forceinline__ double lm_radius_chain(const LmCtl* c, const void* re
 }
 
 // ---- small device math -------------------------------------------------------------------
+// Comparison builds (MPSFM_EXTRA_FLAGS): -DMPSFM_LIBM_MATH puts libm's log(), sqrt(), sin(), cos() and the IEEE quotients back where
+// lean_log, quat_plus' polynomials and sweep_rcp stand; -DMPSFM_LIBM_LOG, -DMPSFM_LIBM_QUAT and -DMPSFM_LIBM_DIV do so one by one.
+#ifdef MPSFM_LIBM_MATH
+#define MPSFM_LIBM_LOG 1
+#define MPSFM_LIBM_QUAT 1
+#define MPSFM_LIBM_DIV 1
+#endif
 // Reciprocal, square root and reciprocal square root in a handful of instructions: the hardware estimate (v_rcp_f64 / v_rsq_f64,
 // ~2^-22 relative) refined by two Newton steps (error ~ e^4: below one ulp; the last bit may differ from the IEEE-rounded quotient
 // the compiler's ~30-instruction expansion of `/` and sqrt() delivers).  The sweeps take five quotients and three roots per record.
@@ -199,6 +206,90 @@ __host__ __device__ inline void fast_sqrt_rsqrt(double x, double& s, double& r) 
 }
 __host__ __device__ inline double fast_sqrt(double x) { double s, r; fast_sqrt_rsqrt(x, s, r); return s; }
 
+// A polynomial coefficient that lives where it is used and no longer.  As plain constants the compiler lifts all of them out of the
+// enclosing loop — the camera loop of cam_update_all, beside the constants of libm's sine and cosine, and the iteration loop of
+// k_local_lm — runs out of scalar registers, moves them to vector registers and spills: two scalar moves per use instead.
+__host__ __device__ inline double local_const(double c) {
+#ifdef __HIP_DEVICE_COMPILE__
+  asm volatile("" : "+s"(c));
+#endif
+  return c;
+}
+
+// Natural logarithm of a finite x > 0 (subnormals included; +inf gives +inf), within one ulp: fdlibm's e_log.c without its special
+// cases.  x = 2^k m with m in [sqrt(1/2), sqrt(2)), f = m - 1, s = f / (2 + f), log(m) = f - f^2/2 + s (f^2/2 + R(s^2)).  The
+// mantissa and the exponent come from the hardware's frexp (which normalises subnormals), the quotient from the reciprocal estimate,
+// two Newton steps and one residual correction: about 45 vector instructions where ocml's log() takes about 95.  Arguments <= 0 and
+// NaN are the callers' business (they test Zc > 0, and Cauchy's argument is >= 1).
+__host__ __device__ inline double lean_log(double x) {
+#ifdef MPSFM_LIBM_LOG
+  return log(x);
+#else
+  constexpr double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+  constexpr double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+                   Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+                   Lg7 = 1.479819860511658591e-01;
+#ifdef __HIP_DEVICE_COMPILE__
+  double m = __builtin_amdgcn_frexp_mant(x);  // [1/2, 1)
+  const int e = __builtin_amdgcn_frexp_exp(x);
+#else
+  if (x == HUGE_VAL) return x;
+  int e;
+  double m = frexp(x, &e);
+#endif
+  const bool low = m < 0.70710678118654752440;
+  m = low ? 2.0 * m : m;
+  const double k = (double)(low ? e - 1 : e);
+  const double f = m - 1.0, den = 2.0 + f;
+#ifdef __HIP_DEVICE_COMPILE__
+  const double y = fast_rcp(den);
+  double s = f * y;
+  s = fma(fma(-s, den, f), y, s);
+#else
+  const double s = f / den;
+#endif
+  const double z = s * s, w = z * z;
+  const double t1 = w * fma(w, fma(w, local_const(Lg6), local_const(Lg4)), local_const(Lg2));
+  const double t2 = z * fma(w, fma(w, fma(w, local_const(Lg7), local_const(Lg5)), local_const(Lg3)), local_const(Lg1));
+  const double R = t2 + t1, hfsq = 0.5 * f * f;
+  const double r = k * ln2_hi - ((hfsq - (s * (hfsq + R) + k * ln2_lo)) - f);
+#ifdef __HIP_DEVICE_COMPILE__
+  return x == HUGE_VAL ? x : r;
+#else
+  return r;
+#endif
+#endif
+}
+
+// The quotients of the sweeps — clamp(V) / lm_radius for the damping of a landmark block, g / p and g_c / s for the gradient maxima —
+// as products with a fast_rcp reciprocal (k_assemble and damp_columns keep the IEEE quotient for the camera side)
+__host__ __device__ inline double sweep_rcp(double x) {
+#ifdef MPSFM_LIBM_DIV
+  return 1.0 / x;
+#else
+  return fast_rcp(x);
+#endif
+}
+__host__ __device__ inline double sweep_div(double a, double b) {
+#ifdef MPSFM_LIBM_DIV
+  return a / b;
+#else
+  return a * fast_rcp(b);
+#endif
+}
+// V packed upper [00 01 02 11 12 22] += clamp(diag V) * inv_radius, inv_radius = sweep_rcp(lm_radius)
+__host__ __device__ inline void damp_landmark(double* V, double min_diag, double max_diag, double lm_radius, double inv_radius) {
+#ifdef MPSFM_LIBM_DIV
+  V[0] += fmin(fmax(V[0], min_diag), max_diag) / lm_radius;
+  V[3] += fmin(fmax(V[3], min_diag), max_diag) / lm_radius;
+  V[5] += fmin(fmax(V[5], min_diag), max_diag) / lm_radius;
+#else
+  V[0] = fma(fmin(fmax(V[0], min_diag), max_diag), inv_radius, V[0]);
+  V[3] = fma(fmin(fmax(V[3], min_diag), max_diag), inv_radius, V[3]);
+  V[5] = fma(fmin(fmax(V[5], min_diag), max_diag), inv_radius, V[5]);
+#endif
+}
+
 __host__ __device__ inline void loss_eval(int type, double a, double s, double& rho0, double& rho1) {
   if (type == MPSFM_LOSS_SOFT_L1) {
     const double b = a * a, c = fast_rcp(b);
@@ -210,7 +301,7 @@ __host__ __device__ inline void loss_eval(int type, double a, double s, double& 
   } else if (type == MPSFM_LOSS_CAUCHY) {
     const double b = a * a, c = fast_rcp(b);
     const double sum = 1.0 + s * c;
-    rho0 = b * log(sum);
+    rho0 = b * lean_log(sum);
     rho1 = fmax(DBL_MIN, fast_rcp(sum));
   } else {
     rho0 = s;
@@ -229,17 +320,63 @@ __host__ __device__ inline void quat_to_R(const double* q, double* R) {
   R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
 }
 
-// EigenQuaternionManifold::Plus, q' = exp(d) * q
-__host__ __device__ inline void quat_plus(const double* q, const double* d, double* out) {
-  const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-  if (n == 0.0) { out[0] = q[0]; out[1] = q[1]; out[2] = q[2]; out[3] = q[3]; return; }
-  const double sbd = sin(n) / n;
-  const double px = sbd * d[0], py = sbd * d[1], pz = sbd * d[2], pw = cos(n);
+// sin(n) / n and cos(n) are even in n: for z = n^2 <= (pi/4)^2 they are fdlibm's __kernel_sin and __kernel_cos as polynomials in z —
+// no square root, no division, and z == 0 gives (1, 1) exactly, so that the plus below returns q itself.
+constexpr double kQuatPolyMaxZ = 0.61685027506808491368;  // (pi/4)^2
+__host__ __device__ inline double quat_sinc_poly(double z) {
+  constexpr double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+                   S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+  double p = z * local_const(S6) + local_const(S5);
+  p = fma(z, p, local_const(S4)); p = fma(z, p, local_const(S3)); p = fma(z, p, local_const(S2)); p = fma(z, p, local_const(S1));
+  return fma(z, p, 1.0);
+}
+__host__ __device__ inline double quat_cos_poly(double z) {
+  constexpr double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+                   C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+  double p = z * local_const(C6) + local_const(C5);
+  p = fma(z, p, local_const(C4)); p = fma(z, p, local_const(C3)); p = fma(z, p, local_const(C2)); p = fma(z, p, local_const(C1));
+  const double r = z * p;
+  return 1.0 - (0.5 * z - z * r);
+}
+// ... and beyond the polynomials' range: libm's sine and cosine of n, with n and 1 / n from one reciprocal square root
+__host__ __device__ inline void quat_sinc_cos_far(double z, double& sbd, double& pw) {
+  double n, in, sn;
+  fast_sqrt_rsqrt(z, n, in);
+#ifdef __HIP_DEVICE_COMPILE__
+  sincos(n, &sn, &pw);
+#else
+  sn = sin(n); pw = cos(n);
+#endif
+  sbd = sn * in;
+}
+// sbd = sin(n) / n, pw = cos(n) for z = n^2 >= 0 (the second branch is lane-divergent; no ordinary step takes it)
+__host__ __device__ inline void quat_sinc_cos(double z, double& sbd, double& pw) {
+  if (z <= kQuatPolyMaxZ) { sbd = quat_sinc_poly(z); pw = quat_cos_poly(z); }
+  else quat_sinc_cos_far(z, sbd, pw);
+}
+
+// q' = exp(d) * q from sbd = sin|d| / |d| and pw = cos|d|
+__host__ __device__ inline void quat_apply(const double* q, const double* d, double sbd, double pw, double* out) {
+  const double px = sbd * d[0], py = sbd * d[1], pz = sbd * d[2];
   const double qx = q[0], qy = q[1], qz = q[2], qw = q[3];
   out[0] = pw * qx + px * qw + py * qz - pz * qy;
   out[1] = pw * qy - px * qz + py * qw + pz * qx;
   out[2] = pw * qz + px * qy - py * qx + pz * qw;
   out[3] = pw * qw - px * qx - py * qy - pz * qz;
+}
+// EigenQuaternionManifold::Plus, q' = exp(d) * q (the branch of quat_sinc_cos, with the product on either side of it)
+__host__ __device__ inline void quat_plus(const double* q, const double* d, double* out) {
+#ifdef MPSFM_LIBM_QUAT
+  const double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  if (n == 0.0) { out[0] = q[0]; out[1] = q[1]; out[2] = q[2]; out[3] = q[3]; return; }
+  const double sbd = sin(n) / n, pw = cos(n);
+#else
+  const double z = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+  if (z <= kQuatPolyMaxZ) { quat_apply(q, d, quat_sinc_poly(z), quat_cos_poly(z), out); return; }
+  double sbd, pw;
+  quat_sinc_cos_far(z, sbd, pw);
+#endif
+  quat_apply(q, d, sbd, pw, out);
 }
 
 // 3x3 SPD inverse via LL^T; V packed upper [00 01 02 11 12 22]

@@ -68,7 +68,7 @@ __device__ __forceinline__ void linearize_record(const double* __restrict__ cam,
     if (!(Zc > 0.0)) {
       o.ok = false;
     } else {
-      const double rd = log(Zc) - d;  // d: log of the prior depth (the table build)
+      const double rd = lean_log(Zc) - d;  // d: log of the prior depth (the table build)
       double rho0, rho1;
       loss_eval(L.depth_type, a, rd * rd, rho0, rho1);
       o.cost += 0.5 * m * rho0;
@@ -138,7 +138,7 @@ __device__ __forceinline__ void linearize_update(const double* __restrict__ cam,
     if (!(Zc > 0.0)) {
       o.ok = false;
     } else {
-      const double rd = log(Zc) - d;  // d: log of the prior depth (the table build)
+      const double rd = lean_log(Zc) - d;  // d: log of the prior depth (the table build)
       // the robust weight alone (loss_eval's rho1): the loss value is not needed here
       double rho1 = 1.0;
       if (L.depth_type == MPSFM_LOSS_SOFT_L1) { double t, it; fast_sqrt_rsqrt(1.0 + rd * rd * fast_rcp(a * a), t, it); rho1 = fmax(DBL_MIN, it); }
@@ -175,7 +175,7 @@ __device__ __forceinline__ double record_cost(const double* __restrict__ cam, co
     if (!(Zc > 0.0)) {
       ok = false;
     } else {
-      const double rd = log(Zc) - d;  // d: log of the prior depth (the table build)
+      const double rd = lean_log(Zc) - d;  // d: log of the prior depth (the table build)
       double rho0, rho1;
       loss_eval(L.depth_type, a, rd * rd, rho0, rho1);
       cost += 0.5 * m * rho0;
@@ -248,7 +248,7 @@ __device__ __forceinline__ void camera_candidate(const double* qq, const double*
   for (int k = 0; k < 6; ++k) {
     const double s = cs6[k];
     dl[k] = s * y6[k];
-    g[k] = (gc6 && s > 0.0) ? -gc6[k] / s : 0.0;
+    g[k] = (gc6 && s > 0.0) ? sweep_div(-gc6[k], s) : 0.0;
   }
   quat_plus(qq, dl, qn);
 #pragma unroll

@@ -407,9 +407,7 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
       double V[6], F[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) V[k] = S.V[lpt * 6 + k];
-      V[0] += fmin(fmax(V[0], A.min_diag), A.max_diag) / lm_radius;
-      V[3] += fmin(fmax(V[3], A.min_diag), A.max_diag) / lm_radius;
-      V[5] += fmin(fmax(V[5], A.min_diag), A.max_diag) / lm_radius;
+      damp_landmark(V, A.min_diag, A.max_diag, lm_radius, sweep_rcp(lm_radius));
       const bool okf = spd3_inv_factor(V, F);
       if (!okf) {
 #pragma unroll
@@ -421,7 +419,7 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
       if (first) {
         if (!okf) my_bad = 1;
         const double p0 = my_ps[0], p1 = my_ps[1], p2 = my_ps[2];
-        my_gmax = fmax(fabs(g0 / p0), fmax(fabs(g1 / p1), fabs(g2 / p2)));
+        my_gmax = fmax(fabs(sweep_div(g0, p0)), fmax(fabs(sweep_div(g1, p1)), fabs(sweep_div(g2, p2))));
         if (A.pt_fac) {  // the update sweep of this iteration starts from F and g_p (F[0] == 0: not factored)
           double* o = A.pt_fac + (size_t)9 * (H.pt0 + lpt);
 #pragma unroll

@@ -29,9 +29,9 @@ struct UpdLdsT {
 // starts from the nine doubles of the record's landmark, requested behind the linearisation and in front of the scan and the second
 // barrier (beside the record loads they are 12 more registers at the pressure peak, and 0.6 us); F[0] > 0 marks a valid factor.
 // Entry: the chunk header and, in the launch chain, `term` of the control block are requested together; the camera list and the
-// records follow from the header alone and are in flight while `term` is tested (in front of the first store), workgroup 0 runs the
-// fused camera update and LDS is cleared.  Behind the first barrier the candidate lanes (fused camera update) and the records
-// request their operands side by side.  117 / 119 registers (hand-off / recompute), four workgroups per CU.
+// records follow from the header alone and are in flight while `term` is tested (in front of the first store) and LDS is cleared.
+// Behind the first barrier the candidate lanes (fused camera update) and the records request their operands side by side; workgroup
+// 0 runs the fused camera update for all cameras at the very end.  118 registers (hand-off and recompute), four workgroups per CU.
 template <bool kLocal, bool kHandoff>
 __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, double lm_radius, const double* l_tab, const double* l_tab2,
                                                    const double* yc, UpdLdsT<kHandoff>& S, const CamUpdArgs& U, bool fuse) {
@@ -66,7 +66,6 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
   // the solve is over (the iteration queued ahead of the news): leave before the first global store
   if constexpr (!kLocal) {
     if (A.ctl != nullptr && lm_over_chain(term)) return;
-    if (fuse && cix == 0) cam_update_all(U, yc, S.red);  // workgroup 0 does what k_cam_update does for all cameras
   }
   if constexpr (!kHandoff) for (int i = tid; i < npt * 6; i += kThreads) S.V[i] = 0.0;
   for (int i = tid; i < npt * 3; i += kThreads) S.g[i] = 0.0;
@@ -181,9 +180,7 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
         double V[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) V[k] = S.V[lpt * 6 + k];
-        V[0] += fmin(fmax(V[0], A.min_diag), A.max_diag) / lm_radius;
-        V[3] += fmin(fmax(V[3], A.min_diag), A.max_diag) / lm_radius;
-        V[5] += fmin(fmax(V[5], A.min_diag), A.max_diag) / lm_radius;
+        damp_landmark(V, A.min_diag, A.max_diag, lm_radius, sweep_rcp(lm_radius));
         okf = spd3_inv_factor(V, F);  // F = chol(V + D)^-1, the factor the track sweep forms for the same block
       }
       if (!okf) {
@@ -226,6 +223,15 @@ __device__ __forceinline__ void update_sweep_chunk(const SweepArgs& A, int cix, 
   if (tid < 5) {
     const double* s = &S.red[4 * tid];
     A.part2[(size_t)cix * 8 + tid] = (s[0] + s[1]) + (s[2] + s[3]);
+  }
+  // Workgroup 0 does what k_cam_update does for all cameras, behind its own chunk: nothing of the chunk is alive here, and the camera
+  // loop keeps the constants of libm's sine and cosine in registers (in front of the chunk, where the record loads are in flight, that
+  // was the register peak of the whole kernel).  No other workgroup of this launch reads what it writes.
+  if constexpr (!kLocal) {
+    if (fuse && cix == 0) {
+      __syncthreads();  // S.red is read above
+      cam_update_all(U, yc, S.red);
+    }
   }
 }
 
