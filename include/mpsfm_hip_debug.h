@@ -24,7 +24,8 @@ int mpsfm_debug_set_chol_trace(long long* dev_buf);
 /* one workgroup factors the stacked host matrix dx [64][32] = [D; X] with `waves` (1 or 4) waves; out: L, X L^-T; *ok: every pivot positive */
 int mpsfm_debug_panel_factor(const double* dx, int waves, double* out, int* ok);
 
-/* the Cholesky plan of a camera graph, no device involved; adj: n x n bytes; depth -2: choose, >= -1: that order; NULL on bad arguments */
+/* the Cholesky plan of a camera graph, no device involved; adj: n x n bytes; depth -2: choose among the level-structure dissections, -3: what a handle
+   does (the window-separator orders compete too), >= -1: that order; NULL on bad arguments */
 mpsfm_plan_handle* mpsfm_debug_plan_create(const uint8_t* adj, int32_t n, int32_t depth, int32_t pinv_max_tiles, int32_t inv_rows);
 /* frees a plan of mpsfm_debug_plan_create; NULL is allowed */
 void mpsfm_debug_plan_destroy(mpsfm_plan_handle* h);

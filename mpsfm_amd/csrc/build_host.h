@@ -17,7 +17,8 @@ namespace mpsfm {
 struct BuildOptions {
   // false only when the variable is set and equal to 0
   bool dev_build = true, chol_graph = true, sweep_dense = true, chol_inverse = true, chol_envelope = true, local_lm = true;
-  int chol_nd = -2;            // MPSFM_CHOL_ND: -1 caller's order, >= 0 dissection depth; -2: not set
+  bool chol_cuts = true;       // MPSFM_CHOL_CUTS=0: the automatic camera order without the window-separator candidates (chol_plan.h)
+  int chol_nd = -2;           // MPSFM_CHOL_ND: -1 caller's order, >= 0 dissection depth; -2: not set
   int slab_tables_host = -1;   // MPSFM_SLAB_TABLES_HOST: 1 host loop, 0 device kernels; -1: not set (by size)
   int chunk_records = 0;       // MPSFM_CHUNK_RECORDS clamped to [16, kObsMax]; 0: not set
   int chunk_pts_by_cams = -1;  // MPSFM_CHUNK_PTS_BY_CAMS as 0 / 1; -1: not set

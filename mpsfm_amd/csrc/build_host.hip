@@ -132,7 +132,7 @@ BuildOptions BuildOptions::from_environment() {
   auto read = [](const char* name, int& v) { const char* e = std::getenv(name); if (e) v = std::atoi(e); return e != nullptr; };
   o.dev_build = !off("MPSFM_DEV_BUILD"); o.chol_graph = !off("MPSFM_CHOL_GRAPH"); o.sweep_dense = !off("MPSFM_SWEEP_DENSE");
   o.chol_inverse = !off("MPSFM_CHOL_INVERSE"); o.chol_envelope = !off("MPSFM_CHOL_ENVELOPE"); o.local_lm = !off("MPSFM_LOCAL_LM");
-  read("MPSFM_CHOL_ND", o.chol_nd);
+  read("MPSFM_CHOL_ND", o.chol_nd); o.chol_cuts = !off("MPSFM_CHOL_CUTS");
   read("MPSFM_SLAB_TABLES_HOST", o.slab_tables_host);
   if (read("MPSFM_CHUNK_RECORDS", o.chunk_records)) o.chunk_records = std::min(std::max(o.chunk_records, 16), (int)kObsMax);
   if (read("MPSFM_CHUNK_PTS_BY_CAMS", o.chunk_pts_by_cams)) o.chunk_pts_by_cams = o.chunk_pts_by_cams != 0;
@@ -319,7 +319,7 @@ int union_graph_over_ranks(CamGraph& graph, const SumExchange& exchange) {
 // (chol_plan.h) — and which 6x6 blocks of S exist.
 void plan_camera_order(const CamGraph& graph, const BuildOptions& opt, CholPlan& plan, CameraLayout& cams) {
   const int forced_depth = opt.chol_nd;
-  plan_auto(graph, forced_depth, forced_depth >= -1, !opt.chol_inverse ? 0 : dense_plain_max_tiles(), dense_inv_rows(), plan,
+  plan_auto(graph, forced_depth, forced_depth >= -1, opt.chol_cuts, !opt.chol_inverse ? 0 : dense_plain_max_tiles(), dense_inv_rows(), plan,
             [](int n, void (*fn)(void*, int), void* ctx) { run_parts(n, [&](int t, int) { fn(ctx, t); }); });
   cams.nat_slot = plan.slot_of_nat;
   cams.ncv = plan.nslots;                 // a permutation of the variable cameras

@@ -81,7 +81,11 @@ void tile_pattern(const CamGraph& g, const std::vector<int32_t>& slot_of_nat, co
                   std::vector<uint8_t>& pat, int& nt);
 // tries the caller's order and dissection depths 0 .. max, keeps the cheapest by the launch-cost model (forced_depth >= -1: that one)
 // pfor(n, fn, ctx): runs fn(ctx, i) for i in [0, n), possibly on several threads (the caller's worker pool); NULL: one after the other
+// cuts (only without a forced depth): orders from a dissection by minimal window separators of a linear arrangement compete too
+// (graphs of 64 cameras and more whose chosen chain has 8 levels or more).  One of them replaces the choice above only with at
+// least two levels less, the inverse accumulators kept (nt <= pinv_max_tiles) where that choice has them, and no panel / trailing
+// item beyond the 2 / 4 sources of k_chol_level's unrolled forms — otherwise the plan is what cuts = false gives, table for table
 typedef void (*PlanParallelFor)(int n, void (*fn)(void* ctx, int i), void* ctx);
-void plan_auto(const CamGraph& g, int forced_depth, bool forced, int pinv_max_tiles, int inv_rows, CholPlan& P, PlanParallelFor pfor = nullptr);
+void plan_auto(const CamGraph& g, int forced_depth, bool forced, bool cuts, int pinv_max_tiles, int inv_rows, CholPlan& P, PlanParallelFor pfor = nullptr);
 
 }  // namespace mpsfm

@@ -16,6 +16,11 @@ namespace {
 constexpr int kTileCols = 32;    // every segment but the last ends on a tile boundary (padding columns)
 constexpr int kMinLeaf = 32;     // no dissection below this many cameras
 constexpr int kMinBfsLevels = 5;
+constexpr int kMinCutCams = 64;   // ... and on graphs of at least this many cameras (twelve tile columns)
+constexpr int kMinCutLevels = 8;  // the window-separator orders are tried on chains of at least this many levels
+constexpr int kMinCutGain = 2;    // ... and taken for at least this many levels less: one level (~8 us per iteration) is within what
+                                  // their padding columns and extra products may cost, two are not
+constexpr int kFastPanelSrc = 2, kFastTrailSrc = 4;  // sources the unrolled forms of k_chol_level take (dense_chol.hip: kPanelBatch, kTrailBatch)
 constexpr double kMaxPlanProducts = 3.0e6;  // tile products beyond which no item table is built (tens of MB of tables, seconds to build)
 
 using Mask = std::vector<uint64_t>;
@@ -178,6 +183,144 @@ void flatten(const std::vector<Seg>& tree, int node, bool is_root, int move_up, 
   if (!is_root) out.push_back(kSegEnd);
 }
 
+// slots and first columns of the ncams cameras of a segment tree
+void slots_from_tree(const std::vector<Seg>& tree, int ncams, int move_up, std::vector<int32_t>& slot_of_nat, std::vector<int32_t>& col_of_slot, int& n_cols) {
+  slot_of_nat.assign((size_t)ncams, -1);
+  col_of_slot.assign((size_t)ncams, 0);
+  std::vector<int> out, up;
+  flatten(tree, 0, true, move_up, out, up);
+  while (!out.empty() && out.back() == kSegEnd) out.pop_back();  // nothing follows the last segment
+  int slot = 0, col = 0;
+  for (int v : out) {
+    if (v == kSegEnd) { col = (col + kTileCols - 1) / kTileCols * kTileCols; continue; }
+    slot_of_nat[(size_t)v] = slot;
+    col_of_slot[(size_t)slot] = col;
+    ++slot; col += 6;
+  }
+  n_cols = col;
+}
+
+// ---- dissection by minimal window separators ------------------------------------------------------------------------------------
+// dissect() cuts at whole breadth-first levels, balances in cameras and leaves parts below kMinLeaf alone.  Here a part is laid
+// out as a linear arrangement (the breadth-first order from a pseudo-peripheral camera, forwards and backwards, and the caller's
+// order) and cut by a WINDOW of it: with far[i] the last position adjacent to position i, the narrowest separator that starts
+// at c is [c, max far[0 .. c) + 1) — no link passes over it.  Cuts are chosen and kept by the length of the chain in TILES.
+inline int seg_tiles(int cams) { return (6 * cams + kTileCols - 1) / kTileCols; }
+
+// Tile columns on the longest root-to-leaf path of a segment tree, the hand-over of flatten() included (up: cameras handed on).
+// An upper bound of the levels of the real symbolic factorisation: a segment's tile columns need not be one chain.
+int chain_tiles(const std::vector<Seg>& tree, int node, bool is_root, int move_up, int& up) {
+  int k = 0, below = 0;
+  for (int c : tree[(size_t)node].child) {
+    int moved = 0;
+    below = std::max(below, chain_tiles(tree, c, false, move_up, moved));
+    k += moved;
+  }
+  up = 0;
+  const int own = (int)tree[(size_t)node].cams.size();
+  if (!is_root && own == 0) { up = k; return below; }
+  k += own;
+  if (k == 0) return below;
+  if (!is_root) {
+    const int whole = (6 * k) / kTileCols * kTileCols / 6, over = k - whole;
+    if (over > 0 && over <= move_up && whole > 0 && (6 * k) % kTileCols != 0) { up = over; k = whole; }
+  }
+  return below + seg_tiles(k);
+}
+
+int tree_depth(const std::vector<Seg>& tree, int node) {  // separators above the deepest leaf
+  int d = 0;
+  for (int c : tree[(size_t)node].child) d = std::max(d, 1 + tree_depth(tree, c));
+  return d;
+}
+
+struct WindowCut { int lo = 0, hi = 0; long cost = 1L << 60; int sep = 0, skew = 0; };  // separator [lo, hi) of the arrangement, trimmed sizes
+
+// the best window of one arrangement of a connected part; pos / far are scratch of g.n entries
+void best_window(const CamGraph& g, const Mask& in, const std::vector<int>& arr, std::vector<int>& pos, std::vector<int>& far, WindowCut& best, int& best_arr, int arr_id) {
+  const int m = (int)arr.size();
+  for (int q = 0; q < m; ++q) pos[(size_t)arr[(size_t)q]] = q;
+  for (int q = 0; q < m; ++q) {
+    int f = q;
+    const uint64_t* r = g.row(arr[(size_t)q]);
+    for (int w = 0; w < g.words; ++w) {
+      uint64_t b = r[w] & in[(size_t)w];
+      while (b) { f = std::max(f, pos[(size_t)(w * 64 + __builtin_ctzll(b))]); b &= b - 1; }
+    }
+    far[(size_t)q] = f;
+  }
+  int reach = -1;  // max far[0 .. c)
+  for (int c = 1; c < m; ++c) {
+    reach = std::max(reach, far[(size_t)c - 1]);
+    const int e = std::max(c, reach + 1);
+    if (e >= m) break;  // reach only grows: no later window leaves a right part
+    if (e == c) continue;  // (a connected part has no empty separator)
+    int back = 0;  // window cameras that see nothing beyond the window go to the left part
+    for (int q = c; q < e; ++q) back += far[(size_t)q] < e;
+    const int nl = c + back, ns = e - c - back, nr = m - e;
+    if (ns <= 0) continue;
+    const long cost = std::max(seg_tiles(nl), seg_tiles(nr)) + seg_tiles(ns);
+    const int skew = std::abs(nl - nr);
+    if (cost < best.cost || (cost == best.cost && (ns < best.sep || (ns == best.sep && skew < best.skew)))) {
+      best.lo = c; best.hi = e; best.cost = cost; best.sep = ns; best.skew = skew; best_arr = arr_id;
+    }
+  }
+}
+
+using Tree = std::vector<Seg>;  // node 0 is the root
+int graft(Tree& t, Tree&& sub) {  // appends a tree, returns where its root went
+  const int off = (int)t.size();
+  for (Seg& s : sub) {
+    for (int& c : s.child) c += off;
+    t.push_back(std::move(s));
+  }
+  return off;
+}
+
+Tree cut_dissect(Sub& S, const std::vector<int>& nodes, int move_up) {
+  Tree t(1);
+  std::vector<std::vector<int>> comps;
+  components(S, nodes, comps);
+  if (comps.size() > 1) {
+    for (const auto& c : comps) { const int ch = graft(t, cut_dissect(S, c, move_up)); t[0].child.push_back(ch); }
+    return t;
+  }
+  const int m = (int)nodes.size();
+  if (seg_tiles(m) >= 2 && m >= 3) {
+    constexpr int kArr = 3;
+    std::vector<int> arr[kArr], ls;
+    pseudo_peripheral(S, nodes, arr[0], ls);  // (leaves S.in = nodes)
+    arr[1].assign(arr[0].rbegin(), arr[0].rend());
+    arr[2] = nodes;  // ascending: the caller's order
+    std::vector<int> pos((size_t)S.g.n, 0), far((size_t)m, 0);
+    WindowCut cut;
+    int which = -1;
+    for (int a = 0; a < kArr; ++a) best_window(S.g, S.in, arr[a], pos, far, cut, which, a);
+    if (which >= 0 && cut.cost <= seg_tiles(m)) {
+      const std::vector<int>& ar = arr[which];
+      std::vector<int> A(ar.begin(), ar.begin() + cut.lo), sep(ar.begin() + cut.lo, ar.begin() + cut.hi), B(ar.begin() + cut.hi, ar.end()), keep;
+      S.set_nodes(B);
+      for (int v : sep) { if (S.degree(v) > 0) keep.push_back(v); else A.push_back(v); }
+      sep.swap(keep); keep.clear();
+      S.set_nodes(A);  // and those that see nothing on the left side go to the right one
+      for (int v : sep) { if (S.degree(v) > 0) keep.push_back(v); else B.push_back(v); }
+      if (!keep.empty() && (int)keep.size() < m) {
+        sep.swap(keep);
+        std::sort(A.begin(), A.end()); std::sort(B.begin(), B.end()); std::sort(sep.begin(), sep.end());
+        Tree cand(1);
+        const int ca = graft(cand, cut_dissect(S, A, move_up));
+        const int cb = graft(cand, cut_dissect(S, B, move_up));
+        cand[0].child = {ca, cb};
+        rcm(S, sep, cand[0].cams);
+        int up = 0;
+        if (chain_tiles(cand, 0, false, move_up, up) < seg_tiles(m)) return cand;  // kept only if it shortens the part's chain
+      }
+    }
+  }
+  rcm(S, nodes, t[0].cams);
+  return t;
+}
+
 }  // namespace
 
 void order_cameras(const CamGraph& g, int depth, int move_up, std::vector<int32_t>& slot_of_nat, std::vector<int32_t>& col_of_slot, int& n_cols) {
@@ -193,17 +336,7 @@ void order_cameras(const CamGraph& g, int depth, int move_up, std::vector<int32_
   std::vector<int> all((size_t)g.n);
   for (int i = 0; i < g.n; ++i) all[(size_t)i] = i;
   dissect(S, tree, all, depth);
-  std::vector<int> out, up;
-  flatten(tree, 0, true, move_up, out, up);
-  while (!out.empty() && out.back() == kSegEnd) out.pop_back();  // nothing follows the last segment
-  int slot = 0, col = 0;
-  for (int v : out) {
-    if (v == kSegEnd) { col = (col + kTileCols - 1) / kTileCols * kTileCols; continue; }
-    slot_of_nat[(size_t)v] = slot;
-    col_of_slot[(size_t)slot] = col;
-    ++slot; col += 6;
-  }
-  n_cols = col;
+  slots_from_tree(tree, g.n, move_up, slot_of_nat, col_of_slot, n_cols);
 }
 
 void tile_pattern(const CamGraph& g, const std::vector<int32_t>& slot_of_nat, const std::vector<int32_t>& col_of_slot, int n_cols,
@@ -384,13 +517,15 @@ void plan_from_pattern(const std::vector<uint8_t>& pat, int nt, bool use_pinv, i
   P.est_us = 9.5 * P.nlevels + 0.02 * (double)P.products + 0.004 * (double)P.roles + (use_pinv ? 10.0 : 6.5 * P.nlevels);
 }
 
-void plan_auto(const CamGraph& g, int forced_depth, bool forced, int pinv_max_tiles, int inv_rows, CholPlan& best, PlanParallelFor pfor) {
+void plan_auto(const CamGraph& g, int forced_depth, bool forced, bool cuts, int pinv_max_tiles, int inv_rows, CholPlan& best, PlanParallelFor pfor) {
   int dmax = -1;
   for (int s = g.n; s >= kMinLeaf / 2; s /= 2) ++dmax;  // candidate depths down to parts of ~kMinLeaf / 2 cameras (dissect() itself
   dmax = std::min(dmax, 6);                             // stops at kMinLeaf); the cost model decides (C3: depth 3, 14 levels)
   // the candidate orders are independent: evaluated side by side on host threads when the graph is large (C4: 6 ms one after
   // the other), the cheapest by the launch-cost model wins, ties go to the first in this list (what the sequential loop chose)
-  struct Cand { int depth, move_up; CholPlan P; std::vector<uint8_t> pat; };
+  // cut: an order from the dissection by window separators (below).  Its tree is built and rated by tile arithmetic beside the
+  // legacy candidates (`chain`, O(cameras)); `rated`: it has its symbolic factorisation too
+  struct Cand { int depth, move_up; CholPlan P; std::vector<uint8_t> pat; bool cut = false, rated = false; int chain = 0; };
   std::vector<Cand> cands;
   for (int d = -1; d <= (forced ? -1 : dmax); ++d) {
     const int depth = forced ? forced_depth : d;
@@ -399,32 +534,94 @@ void plan_auto(const CamGraph& g, int forced_depth, bool forced, int pinv_max_ti
       cands.push_back(Cand{depth, move_up, CholPlan(), {}});
     }
   }
+  const size_t n_legacy = cands.size();
+  if (cuts && !forced && g.n >= kMinCutCams)
+    for (int move_up : {0, 2, 4}) { cands.push_back(Cand{0, move_up, CholPlan(), {}}); cands.back().cut = true; }
   auto evaluate = [&](Cand& c) {
     CholPlan& P = c.P;
+    if (c.cut && !c.rated) {  // first pass: the tree, its chain in tiles and the order it gives
+      Sub S(g);
+      std::vector<int> all((size_t)g.n);
+      for (int i = 0; i < g.n; ++i) all[(size_t)i] = i;
+      const Tree tree = cut_dissect(S, all, c.move_up);
+      int up = 0;
+      c.depth = tree_depth(tree, 0);
+      c.chain = chain_tiles(tree, 0, true, c.move_up, up);
+      slots_from_tree(tree, g.n, c.move_up, P.slot_of_nat, P.col_of_slot, P.n);
+      return;
+    }
     P.ncv = g.n; P.nd_depth = c.depth;
     P.nslots = g.n;
-    order_cameras(g, c.depth, c.move_up, P.slot_of_nat, P.col_of_slot, P.n);
+    if (!c.cut) order_cameras(g, c.depth, c.move_up, P.slot_of_nat, P.col_of_slot, P.n);
     int nt = 0;
     tile_pattern(g, P.slot_of_nat, P.col_of_slot, P.n, c.pat, nt);
     plan_from_pattern(c.pat, nt, nt <= pinv_max_tiles, inv_rows, P, /*tables=*/false);
   };
-  if (pfor && g.n >= 64 && cands.size() > 1) {  // the caller's persistent workers (C3: 0.5 -> 0.15 ms; C4: 6.3 -> 1.9 ms)
-    struct Ctx { decltype(evaluate)* ev; std::vector<Cand>* c; } ctx{&evaluate, &cands};
-    pfor((int)cands.size(), [](void* p, int i) { Ctx* x = static_cast<Ctx*>(p); (*x->ev)((*x->c)[(size_t)i]); }, &ctx);
-  } else if (g.n >= 256 && cands.size() > 1) {
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < cands.size(); ++i) th.emplace_back([&, i] { evaluate(cands[i]); });
-    evaluate(cands[0]);
-    for (auto& x : th) x.join();
-  } else {
-    for (Cand& c : cands) evaluate(c);
-  }
+  auto evaluate_all = [&](const std::vector<Cand*>& todo) {
+    const size_t cnt = todo.size();
+    if (pfor && g.n >= 64 && cnt > 1) {  // the caller's persistent workers (C3: 0.5 -> 0.15 ms; C4: 6.3 -> 1.9 ms)
+      struct Ctx { decltype(evaluate)* ev; Cand* const* c; } ctx{&evaluate, todo.data()};
+      pfor((int)cnt, [](void* p, int i) { Ctx* x = static_cast<Ctx*>(p); (*x->ev)(*x->c[i]); }, &ctx);
+    } else if (g.n >= 256 && cnt > 1) {
+      std::vector<std::thread> th;
+      for (size_t i = 1; i < cnt; ++i) th.emplace_back([&, i] { evaluate(*todo[i]); });
+      evaluate(*todo[0]);
+      for (auto& x : th) x.join();
+    } else {
+      for (Cand* c : todo) evaluate(*c);
+    }
+  };
+  std::vector<Cand*> todo;
+  for (Cand& c : cands) todo.push_back(&c);
+  evaluate_all(todo);
   size_t bi = 0;
-  for (size_t i = 1; i < cands.size(); ++i)
+  for (size_t i = 1; i < n_legacy; ++i)
     if (cands[i].P.est_us < cands[bi].P.est_us - 1e-9) bi = i;
+  const size_t legacy = bi;
+  // The second family: dissection by minimal window separators.  Only the best few trees by their arithmetic (an upper bound
+  // of the levels, met on every graph tried) get a symbolic factorisation, and only where the arithmetic promises a gain.
+  // Not taken on a short chain (fewer than kMinCutLevels levels: at most a launch or two to gain, against more padding
+  // columns), which also keeps small systems on the plans the kernels' tests are built around.
+  if (cands.size() > n_legacy && cands[legacy].P.nlevels >= kMinCutLevels) {
+    constexpr size_t kMaxCutCands = 2;
+    todo.clear();
+    for (size_t i = n_legacy; i < cands.size(); ++i) {
+      Cand& c = cands[i];
+      bool known = c.depth < 1 || c.chain + kMinCutGain > cands[legacy].P.nlevels;  // nothing was cut, or too little to gain
+      for (const Cand* o : todo) known = known || (o->P.slot_of_nat == c.P.slot_of_nat && o->P.col_of_slot == c.P.col_of_slot);
+      if (!known) todo.push_back(&c);
+    }
+    std::stable_sort(todo.begin(), todo.end(), [](const Cand* a, const Cand* b) { return a->chain < b->chain; });
+    if (todo.size() > kMaxCutCands) todo.resize(kMaxCutCands);
+    for (Cand* c : todo) c->rated = true;
+    if (!todo.empty()) evaluate_all(todo);
+    // A cut-search order replaces the legacy choice only with fewer levels (by kMinCutGain), and only if it keeps the inverse
+    // accumulators where the legacy plan has them; among several, the fewest levels, then the cost model.
+    const CholPlan& L = cands[legacy].P;
+    for (size_t i = n_legacy; i < cands.size(); ++i) {
+      const CholPlan& C = cands[i].P;
+      if (!cands[i].rated || C.nlevels <= 0 || C.nlevels + kMinCutGain > L.nlevels || (L.nt <= pinv_max_tiles && C.nt > pinv_max_tiles)) continue;
+      if (bi == legacy || C.nlevels < cands[bi].P.nlevels || (C.nlevels == cands[bi].P.nlevels && C.est_us < cands[bi].P.est_us - 1e-9)) bi = i;
+    }
+  }
   best = std::move(cands[bi].P);
   std::vector<uint8_t> best_pat = std::move(cands[bi].pat);
   plan_from_pattern(best_pat, best.nt, best.nt <= pinv_max_tiles, inv_rows, best, /*tables=*/true);
+  if (bi != legacy) {
+    // ... and only if its items stay in the unrolled forms of k_chol_level (a panel with up to kFastPanelSrc sources, a trailing
+    // tile with up to kFastTrailSrc): a level of the slower list loops can cost what a level less saves.  Otherwise, and on any
+    // tie or loss above, the legacy plan stands as it was, table for table.
+    int psrc = 0, tsrc = 0;
+    for (const CholItem& it : best.items) {
+      if (it.type == kItemPanel) psrc = std::max<int>(psrc, it.nsrc);
+      if (it.type == kItemTrail) tsrc = std::max<int>(tsrc, it.nsrc);
+    }
+    if (psrc > kFastPanelSrc || tsrc > kFastTrailSrc) {
+      best = std::move(cands[legacy].P);
+      best_pat = std::move(cands[legacy].pat);
+      plan_from_pattern(best_pat, best.nt, best.nt <= pinv_max_tiles, inv_rows, best, /*tables=*/true);
+    }
+  }
   best.nat_of_slot.assign((size_t)best.nslots, -1);
   for (int i = 0; i < g.n; ++i) best.nat_of_slot[(size_t)best.slot_of_nat[(size_t)i]] = i;
   best.slot_of_col.assign((size_t)best.n, -1);
@@ -440,15 +637,16 @@ extern "C" {
 
 struct mpsfm_plan_handle { mpsfm::CholPlan P; };
 
-// adj: n x n bytes (symmetric, nonzero = the cameras share a landmark).  depth -2: choose; >= -1: that order.
+// adj: n x n bytes (symmetric, nonzero = the cameras share a landmark).  depth -2: choose among the level-structure dissections;
+// -3: what a handle does by default (the window-separator orders compete too); >= -1: that order.
 mpsfm_plan_handle* mpsfm_debug_plan_create(const uint8_t* adj, int32_t n, int32_t depth, int32_t pinv_max_tiles, int32_t inv_rows) {
-  if (!adj || n < 0) return nullptr;
+  if (!adj || n < 0 || depth < -3) return nullptr;
   mpsfm::CamGraph g;
   g.init(n);
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) if (i != j && adj[(size_t)i * n + j]) g.set(i, j);
   auto* h = new mpsfm_plan_handle();
-  mpsfm::plan_auto(g, depth, depth >= -1, pinv_max_tiles, inv_rows, h->P);
+  mpsfm::plan_auto(g, depth, depth >= -1, /*cuts=*/depth == -3, pinv_max_tiles, inv_rows, h->P);
   return h;
 }
 void mpsfm_debug_plan_destroy(mpsfm_plan_handle* h) { delete h; }
