@@ -47,6 +47,12 @@ int mpsfm_debug_direct_front(mpsfm_ba_handle* h);
 int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_parent, double* A_direct, double* damp, uint8_t* live, int64_t info[4]);
 /* mpsfm_ba_dense_solve_once on the given system (S n x n and rhs in the caller's camera order, zero outside the handle's block pattern) instead of the last sweep's; *failed: a pivot was not positive */
 int mpsfm_debug_dense_solve_given(mpsfm_ba_handle* h, const double* S, const double* rhs, int32_t n, int32_t* failed);
+/* ONE update sweep at the handle's state, `radius` and the GIVEN camera step yc [n = reduced dim] (scaled coordinates, caller's camera order), behind a track sweep at `radius`;
+   form: bit 0 hand-off of the landmark factors, bit 1 fused camera update (MPSFM_EUNSUPPORTED where the handle cannot take it).  Out: pts2 [n_pts][3] (caller's order; unreferenced
+   landmarks untouched), q2 [n_cams][4], t2 [n_cams][3], part2 [rows = chunks + long tracks][8] (NaN before the launch), scal [8] = U_CAND_COST, U_BAD, U_MCC, U_STEP_SQ_PTS,
+   U_XN_SQ_PTS, U_STEP_SQ_CAMS, U_XN_SQ_CAMS, U_GMAX_CAMS; cs [n_cams][6], ps [n_pts][3] (NULL allowed): the column scales the sweeps ran with.  The handle's state (cameras, landmarks) is not changed; its scratch is: the dense solution (yc takes its place), the reduced buffer, the scalars of the last sweep and the candidates */
+int mpsfm_debug_update_once(mpsfm_ba_handle* h, double radius, const double* yc, int32_t n, int32_t form, double* pts2, double* q2, double* t2, double* part2, int64_t rows,
+                            double* scal, double* cs, double* ps);
 /* the first `count` 8-byte words of the landmark-diagonal buffer, where the dense sweep leaves its phase stamps under debug flag 128 */
 int mpsfm_debug_read_trace(mpsfm_ba_handle* h, long long* out, int64_t count);
 /* table `which` (numbering in csrc/ba_debug.hip) of the handle copied to `out` (at most `cap` bytes); returns its size in bytes or a negative error code */

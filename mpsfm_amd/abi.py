@@ -514,6 +514,7 @@ DEBUG_SIGNATURES = {
     "mpsfm_debug_direct_front": (C.c_int, [P]),
     "mpsfm_debug_direct_assemble": (C.c_int, [P, C.c_double, P, P, P, P, P]),
     "mpsfm_debug_dense_solve_given": (C.c_int, [P, P, P, I32, C.POINTER(I32)]),
+    "mpsfm_debug_update_once": (C.c_int, [P, F64, P, I32, I32, P, P, P, P, I64, P, P, P]),
     "mpsfm_debug_read_trace": (C.c_int, [P, P, I64]),
     "mpsfm_debug_table": (I64, [P, I32, P, I64]),
     "mpsfm_debug_host_build": (I64, [P, I32, P, I64]),

@@ -215,6 +215,32 @@ class BAHandle:
         _check(lib().mpsfm_ba_get_dense_solution(self._h, y.ctypes.data, n))
         return y
 
+    UPDATE_SCALARS = ("cand_cost", "bad", "mcc", "step_sq_pts", "xn_sq_pts", "step_sq_cams", "xn_sq_cams", "gmax_cams")
+
+    def update_once(self, radius: float, yc: np.ndarray, handoff: bool = False, fused_cam: bool = False) -> dict:
+        """One update sweep at the handle's state, `radius` and the given camera step `yc` (scaled coordinates, the order of
+        dense_solution()), behind a track sweep at `radius`; handoff: the landmark factors come from that track sweep, otherwise the
+        update sweep recomputes them; fused_cam: workgroup 0 of the update sweep forms the candidate cameras, otherwise k_cam_update.
+        A form the handle cannot take raises (MPSFM_EUNSUPPORTED).  Returns pts2 (caller's landmark order), q2, t2, part2 (the rows of
+        the chunks and long tracks, columns as UPDATE_SCALARS[:5]), the eight scalars by name, the state (pts, q, t) and the column scales the
+        sweeps ran with (cs, ps).  The handle's state is unchanged."""
+        n = self.reduced_dim
+        yc = np.ascontiguousarray(yc, np.float64)
+        assert yc.shape == (n,), (yc.shape, n)
+        info = (C.c_int64 * 4)()
+        _check(lib().mpsfm_ba_sweep_parts(self._h, None, info))
+        rows = int(info[0] + info[1] + info[2])
+        st = self.prob.copy()
+        self.get_state(st)  # what a landmark no block references keeps
+        pts2, q2, t2 = st.pts.copy(), np.full((self.prob.n_cams, 4), np.nan), np.full((self.prob.n_cams, 3), np.nan)
+        part2, scal = np.full((rows, 8), np.nan), np.full(8, np.nan)
+        cs, ps = np.zeros((self.prob.n_cams, 6)), np.zeros((self.prob.n_pts, 3))  # (an unreferenced landmark is no variable: scale 0)
+        _check(lib().mpsfm_debug_update_once(self._h, float(radius), yc.ctypes.data, n, int(bool(handoff)) | (int(bool(fused_cam)) << 1), pts2.ctypes.data,
+                                             q2.ctypes.data, t2.ctypes.data, part2.ctypes.data, rows, scal.ctypes.data, cs.ctypes.data, ps.ctypes.data))
+        out = dict(pts2=pts2, q2=q2, t2=t2, part2=part2[:, :5], pts=st.pts, q=st.cam_quat, t=st.cam_t, cs=cs, ps=ps)
+        out.update({k: float(v) for k, v in zip(self.UPDATE_SCALARS, scal)})
+        return out
+
 
 def ba_solve(prob: BAProblem, options: COptions | None = None) -> dict:
     """One-shot mpsfm_ba_solve: refines prob.cam_quat / cam_t / pts in place."""

@@ -2,6 +2,7 @@
 // bundle adjustment (one sweep, one dense solve, the reduced system).  Nothing here is on the path of a solve.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <limits>
 #include <vector>
@@ -279,6 +280,75 @@ int mpsfm_ba_sweep_once(mpsfm_ba_handle* h, double radius, float* elapsed_ms) {
   float ms = 0.f;
   MPSFM_TRY(hipEventElapsedTime(&ms, h->ev[0], h->ev[3]));
   if (elapsed_ms) *elapsed_ms = ms;
+  return 0;
+}
+
+// Test hook (tests/test_gpu_update_once.py): ONE update sweep at the handle's current state, `radius` and a GIVEN camera step, in the
+// form asked for.  The track sweep runs first through run_track_sweep (it leaves g_c for the gradient maximum and, with the hand-off,
+// F and g_p of every landmark); then the camera update and launch_update_sweep as solve_impl's enqueue_back orders them, without a
+// control block; then the reduction of part2 in the order of the one-rank loop (reduce_cols_block's, which k_lm_reduce_decide repeats).
+// yc [n = reduced_dim]: the camera step in scaled coordinates, caller's camera order (what mpsfm_ba_get_dense_solution returns).
+// form: bit 0 hand-off of the landmark factors (needs the handle's buffer), bit 1 fused camera update (needs every chunk dense and no
+// long track); a form the handle cannot take is refused with MPSFM_EUNSUPPORTED.  Out: pts2 [n_pts][3] in the caller's landmark order
+// (a landmark no block references keeps what the caller put there, as in mpsfm_ba_get_state), q2 [n_cams][4], t2 [n_cams][3], part2
+// [rows][8] with rows = chunks + long tracks (NaN before the launch: columns 5-7 stay so), scal [8]: U_CAND_COST .. U_GMAX_CAMS; cs
+// [n_cams][6] and ps [n_pts][3] (either may be NULL): the column scales the sweeps ran with, ps in the caller's order like pts2.  The
+// state of the handle (cameras, landmarks) is not changed.  Its scratch is not preserved: d_yc holds the caller's step afterwards (so
+// mpsfm_ba_get_dense_solution returns yc), the reduced buffer is the track sweep's at `radius`, d_scal loses what the last sweep left
+// (U_X_COST among it), and the candidates (q2, t2, camtab2, pts2), part2 and pt_fac are this call's.
+int mpsfm_debug_update_once(mpsfm_ba_handle* h, double radius, const double* yc, int32_t n, int32_t form, double* pts2, double* q2, double* t2,
+                            double* part2, int64_t rows, double* scal, double* cs, double* ps) {
+  if (!h || !pts2 || !q2 || !t2 || !scal) return fail(MPSFM_EINVAL, "handle or output is NULL");
+  if (n != h->n_user || (n > 0 && !yc)) return fail(MPSFM_EINVAL, "n does not match the reduced dimension, or yc is NULL");
+  if (!(radius > 0.0) || !std::isfinite(radius)) return fail(MPSFM_EINVAL, "radius must be positive and finite");
+  if (form < 0 || form > 3) return fail(MPSFM_EINVAL, "form: bit 0 hand-off, bit 1 fused camera update");
+  if (rows != (int64_t)h->nchunks + h->nlong || (rows > 0 && !part2)) return fail(MPSFM_EINVAL, "rows must be chunks + long tracks, part2 not NULL");
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(yc[i])) return fail(MPSFM_EINVAL, "yc is not finite");
+  if (sharded(h)) return fail(MPSFM_EUNSUPPORTED, "update_once: one rank only");
+  const bool handoff = (form & 1) != 0, fused_cam = (form & 2) != 0;
+  const bool all_dense = h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks;
+  if (handoff && !h->d_pt_fac) return fail(MPSFM_EUNSUPPORTED, "the handle has no hand-off buffer (a general chunk or a long track)");
+  if (fused_cam && !all_dense) return fail(MPSFM_EUNSUPPORTED, "the fused camera update needs every chunk dense and no long track");
+  MPSFM_TRY(hipSetDevice(h->device));
+  if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
+  hipStream_t s = h->stream;
+  if (int rc = run_track_sweep(h, radius, nullptr, false, false, handoff)) return rc;
+  std::vector<double> ys((size_t)std::max(h->n_user, 1), 0.0);
+  for (int i = 0; i < n; ++i) ys[(size_t)(6 * h->nat_slot[(size_t)(i / 6)] + i % 6)] = yc[i];
+  MPSFM_TRY(hipMemcpyAsync(h->d_yc, ys.data(), sizeof(double) * ys.size(), hipMemcpyHostToDevice, s));
+  if (h->np > 0) MPSFM_TRY(hipMemcpyAsync(h->d_pts2, h->d_pts, sizeof(double) * 3 * h->np, hipMemcpyDeviceToDevice, s));  // (as solve_impl: landmarks outside every chunk)
+  if (rows > 0) MPSFM_TRY(hipMemsetAsync(h->d_part2, 0xff, sizeof(double) * 8 * (size_t)rows, s));  // NaN: a row no workgroup writes shows
+  MPSFM_TRY(hipMemsetAsync(h->d_scal, 0xff, sizeof(double) * U_COUNT, s));
+  CamUpdArgs cu{1, h->nc, h->d_cam_slot, h->d_cam_of_slot, h->d_q, h->d_t, h->d_cs, h->d_gc, h->d_intr, h->d_intr_idx,
+                h->d_q2, h->d_t2, h->d_camtab2, h->d_scal, h->d_fail};
+  if (!fused_cam)
+    launch_cam_update(h->nc, h->d_cam_slot, h->d_q, h->d_t, h->d_cs, h->d_yc, h->d_gc, h->d_q2, h->d_t2, h->d_scal, s, h->d_intr, h->d_intr_idx,
+                      h->d_camtab2, h->d_fail, nullptr);
+  {
+    SweepArgs a = sweep_args(h, radius, nullptr);
+    if (handoff) a.pt_fac = h->d_pt_fac;
+    launch_update_sweep(a, h->nchunks, s, fused_cam ? &cu : nullptr);
+  }
+  if (rows > 0) launch_reduce_cols(h->d_part2, rows, 8, 5, 0u, h->d_scal, s);
+  std::vector<double> sorted((size_t)h->np * 3), sorted_ps((size_t)h->np * 3), sc((size_t)U_COUNT);
+  if (h->np > 0) MPSFM_TRY(hipMemcpyAsync(sorted.data(), h->d_pts2, sizeof(double) * 3 * (size_t)h->np, hipMemcpyDeviceToHost, s));
+  if (h->np > 0 && ps) MPSFM_TRY(hipMemcpyAsync(sorted_ps.data(), h->d_ps, sizeof(double) * 3 * (size_t)h->np, hipMemcpyDeviceToHost, s));
+  if (h->nc > 0 && cs) MPSFM_TRY(hipMemcpyAsync(cs, h->d_cs, sizeof(double) * 6 * (size_t)h->nc, hipMemcpyDeviceToHost, s));
+  if (h->nc > 0) {
+    MPSFM_TRY(hipMemcpyAsync(q2, h->d_q2, sizeof(double) * 4 * (size_t)h->nc, hipMemcpyDeviceToHost, s));
+    MPSFM_TRY(hipMemcpyAsync(t2, h->d_t2, sizeof(double) * 3 * (size_t)h->nc, hipMemcpyDeviceToHost, s));
+  }
+  if (rows > 0) MPSFM_TRY(hipMemcpyAsync(part2, h->d_part2, sizeof(double) * 8 * (size_t)rows, hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipMemcpyAsync(sc.data(), h->d_scal, sizeof(double) * U_COUNT, hipMemcpyDeviceToHost, s));
+  MPSFM_TRY(hipStreamSynchronize(s));
+  MPSFM_TRY(hipGetLastError());
+  for (int64_t k = 0; k < h->np; ++k)
+    for (int c = 0; c < 3; ++c) {
+      pts2[3 * (size_t)h->perm[(size_t)k] + c] = sorted[3 * (size_t)k + c];
+      if (ps) ps[3 * (size_t)h->perm[(size_t)k] + c] = sorted_ps[3 * (size_t)k + c];
+    }
+  for (int i = 0; i < 8; ++i) scal[i] = sc[(size_t)i];
   return 0;
 }
 

@@ -49,7 +49,7 @@ def scene(n_cams, tracks, seed, const_cams=(0,), every_depth=False):
         depth_loss_type=base.depth_loss_type)
 
 
-def _random_tracks(rng, n, cams, kmin, kmax):
+def random_tracks(rng, n, cams, kmin, kmax):
     """n tracks of kmin..kmax distinct cameras out of `cams`."""
     return [tuple(sorted(rng.choice(cams, size=int(rng.integers(kmin, kmax + 1)), replace=False).tolist())) for _ in range(n)]
 
@@ -66,12 +66,12 @@ def _two_view():
 
 def _pairs16():
     rng = np.random.default_rng(32)
-    return scene(17, _random_tracks(rng, 500, np.arange(1, 17), 2, 2), seed=32)
+    return scene(17, random_tracks(rng, 500, np.arange(1, 17), 2, 2), seed=32)
 
 
 def _mixed16():
     rng = np.random.default_rng(37)  # a seed whose greedy cut closes two 16-camera chunks at exactly 252 records
-    return scene(17, _random_tracks(rng, 300, np.arange(1, 17), 2, 16) + [tuple(range(1, 17))] * 15, seed=37)
+    return scene(17, random_tracks(rng, 300, np.arange(1, 17), 2, 16) + [tuple(range(1, 17))] * 15, seed=37)
 
 
 def _one_var():
@@ -88,12 +88,12 @@ def _g17_40():
 
 def _dup_aab():
     rng = np.random.default_rng(36)
-    return scene(5, [(1, 1, 2)] * 200 + _random_tracks(rng, 150, np.arange(5), 2, 4), seed=36, every_depth=True)
+    return scene(5, [(1, 1, 2)] * 200 + random_tracks(rng, 150, np.arange(5), 2, 4), seed=36, every_depth=True)
 
 
 def _dup_aa():
     rng = np.random.default_rng(37)
-    fill = [(0, 1, 4), (0, 2, 3, 4)] * 20 + _random_tracks(rng, 110, np.arange(5), 2, 4)
+    fill = [(0, 1, 4), (0, 2, 3, 4)] * 20 + random_tracks(rng, 110, np.arange(5), 2, 4)
     return scene(5, [(1, 1)] * 300 + fill, seed=37, every_depth=True)
 
 
