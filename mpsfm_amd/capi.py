@@ -176,6 +176,14 @@ class BAHandle:
         assert int(info[0]) == nt
         return dict(parent=ap, direct=ad, damp=damp, live=live.astype(bool), nt=nt, n=int(info[1]), n_live=int(info[2]), unzeroed=int(info[3]))
 
+    def debug_table(self, which: int, dtype) -> np.ndarray:
+        """Table `which` of the handle (the codes of mpsfm_debug_table) as an array of `dtype`."""
+        return _table(lambda out, cap: lib().mpsfm_debug_table(self._h, which, out, cap), dtype)
+
+    def sweep_order(self) -> np.ndarray:
+        """The chunk every workgroup of the dense track sweep takes, in launch order (heaviest first)."""
+        return self.debug_table(35, np.int32)
+
     def sweep_once(self, radius: float = 1e4) -> float:
         ms = C.c_float(0)
         _check(lib().mpsfm_ba_sweep_once(self._h, radius, C.byref(ms)))
@@ -240,6 +248,22 @@ class BAHandle:
         out = dict(pts2=pts2, q2=q2, t2=t2, part2=part2[:, :5], pts=st.pts, q=st.cam_quat, t=st.cam_t, cs=cs, ps=ps)
         out.update({k: float(v) for k, v in zip(self.UPDATE_SCALARS, scal)})
         return out
+
+
+def _table(call, dtype) -> np.ndarray:
+    n = int(call(None, 0))
+    if n < 0:
+        raise MpsfmHipError(n, (lib().mpsfm_last_error() or b"").decode())
+    buf = np.zeros(max(n, 1), np.uint8)
+    if n > 0 and int(call(buf.ctypes.data, n)) != n:
+        raise MpsfmHipError(-1, "table changed size between two reads")
+    return buf[:n].view(dtype).copy()
+
+
+def host_build_table(prob: BAProblem, which: int, dtype) -> np.ndarray:
+    """Table `which` (the codes of mpsfm_debug_table) from the host phases of the table build alone: no device involved."""
+    cp = prob.c_problem()
+    return _table(lambda out, cap: lib().mpsfm_debug_host_build(C.byref(cp), which, out, cap), dtype)
 
 
 def ba_solve(prob: BAProblem, options: COptions | None = None) -> dict:

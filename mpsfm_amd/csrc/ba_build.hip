@@ -194,7 +194,7 @@ static int upload_tables(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const Ca
   if ((rc = own.upload(&h->d_blk_desc, T.blk_desc, &h->d_blk_ent_start, T.blk_ent_start, &h->d_ents, T.ents))) return rc;
   int32_t* d_diag_block = nullptr;
   if (!slab_tables_on_device) {
-    if ((rc = own.upload(&h->d_red_dests, R.dests, &h->d_red_srcs, R.srcs))) return rc;
+    if ((rc = own.upload(&h->d_red_dests, R.dests, &h->d_red_srcs, R.srcs, &h->d_sweep_order, R.sweep_order))) return rc;
   } else if ((rc = own.upload(&d_diag_block, R.diag_block))) return rc;
   if ((rc = own.alloc(&h->d_slab, (size_t)std::max<int64_t>(R.slab_units, 1) * 18))) return rc;
 
@@ -203,6 +203,7 @@ static int upload_tables(mpsfm_ba_handle* h, const mpsfm_ba_problem* P, const Ca
     if ((rc = devb->slab_tables(h->d_chunks, h->n_dense, h->d_chunk_cams, h->sky, h->spat.nblk, h->ncv, d_diag_block, own, &h->d_red_dests, &h->n_red_dests,
                                 &h->d_red_srcs, &h->n_red_srcs)))
       return rc;
+    if ((rc = devb->sweep_order(h->d_chunks, h->n_dense, own, &h->d_sweep_order))) return rc;
     MPSFM_TRY(hipStreamSynchronize(h->stream));  // d_diag_block goes back to the process-wide cache
     own.drop(d_diag_block);
   }
@@ -397,6 +398,7 @@ int build_tables(const mpsfm_ba_problem* P, BuildOptions& opt, const SumExchange
   if (int rc = assign_slabs(T.chunks, slabs)) return rc;
   out.slab_tables_on_device = dev && slabs.n_dense > 0 && (opt.slab_tables_host == 0 || (opt.slab_tables_host < 0 && slabs.n_dense >= 512));
   if (int rc = slab_reduction_tables(T, cams, out.plan, out.spat, !out.slab_tables_on_device, slabs)) return rc;
+  if (!out.slab_tables_on_device) dense_sweep_order(T.chunks, slabs.n_dense, slabs.sweep_order);  // (otherwise DevBuilder::sweep_order, with the tables)
   lap("slab reduction tables");
   return 0;
 }
@@ -426,7 +428,7 @@ static int build(mpsfm_ba_handle* h, const mpsfm_ba_problem* P) {
   h->nblocks_total = P->n_obs + P->n_dobs; h->nblocks_reduced = T.nblk_reduced;
   h->nblocks_global = B.nblocks_global; h->nblocks_reduced_global = B.nblocks_reduced_global; h->nvarpts_global = B.nvarpts_global;
   h->n_dense = B.slabs.n_dense; h->n_red_dests = (int)B.slabs.dests.size();
-  h->n_red_srcs = (int64_t)B.slabs.srcs.size(); h->n_chunk_cams = (int64_t)T.chunk_cams.size();
+  h->n_red_srcs = (int64_t)B.slabs.srcs.size(); h->slab_units = B.slabs.slab_units; h->n_chunk_cams = (int64_t)T.chunk_cams.size();
   h->perm.swap(T.order);
 
   if (int rc = upload_pattern(h, cams.use_graph)) return rc;

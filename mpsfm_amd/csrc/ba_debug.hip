@@ -207,6 +207,7 @@ int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_par
   if (!h || !A_parent || !A_direct || !damp || !live || !info) return fail(MPSFM_EINVAL, "handle or output is NULL");
   if (!mpsfm_debug_direct_front(h)) return fail(MPSFM_EUNSUPPORTED, "the handle does not take the direct form of the front");
   MPSFM_TRY(hipSetDevice(h->device));
+  read_sweep_order_switch(h);
   if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
   hipStream_t s = h->stream;
   const int nt = h->nt;
@@ -261,6 +262,7 @@ int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_par
 int mpsfm_ba_sweep_once(mpsfm_ba_handle* h, double radius, float* elapsed_ms) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   MPSFM_TRY(hipSetDevice(h->device));
+  read_sweep_order_switch(h);
   if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
   MPSFM_TRY(hipMemsetAsync(h->d_red, 0, sizeof(double) * (size_t)h->red_count, h->stream));
   SweepArgs a = sweep_args(h, radius);
@@ -311,6 +313,7 @@ int mpsfm_debug_update_once(mpsfm_ba_handle* h, double radius, const double* yc,
   if (handoff && !h->d_pt_fac) return fail(MPSFM_EUNSUPPORTED, "the handle has no hand-off buffer (a general chunk or a long track)");
   if (fused_cam && !all_dense) return fail(MPSFM_EUNSUPPORTED, "the fused camera update needs every chunk dense and no long track");
   MPSFM_TRY(hipSetDevice(h->device));
+  read_sweep_order_switch(h);
   if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
   hipStream_t s = h->stream;
   if (int rc = run_track_sweep(h, radius, nullptr, false, false, handoff)) return rc;
@@ -369,7 +372,10 @@ int mpsfm_debug_read_trace(mpsfm_ba_handle* h, long long* out, int64_t count) {
 // 23 blk_desc, 24 blk_ent_start, 25 ents (pair tables of the general chunks), 27 long-track headers, 28 sky_index, 29 sky_first,
 // 30 sky_start (host), 31 cmask, 32 cam_of_slot, 33 the ten numbers of mpsfm_ba_dense_plan, 34 the launches the last solve on this
 // handle enqueued (host, int64 each): track sweeps, k_reduce_slabs, k_assemble, k_chol_level, the rest of the dense solve, update
-// sweeps, decisions, scales and camera table, everything else (LaunchFamily of ba_launch.h)
+// sweeps, decisions, scales and camera table, everything else (LaunchFamily of ba_launch.h), 35 the order table of the dense sweep
+// (int32 per dense chunk: the chunk the b-th workgroup takes), 36 dense_sweep_cost of every dense chunk (int32, from the headers),
+// 37 the slabs as the last dense sweep left them (doubles, ChunkHdr::slab0 in units of 18), 38 pt_fac [np][9] as the last track sweep
+// with the hand-off left it (empty: the handle has no such buffer)
 int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t cap) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   const void* src = nullptr;
@@ -412,6 +418,21 @@ int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t 
     case 32: src = h->d_cam_of_slot; bytes = 4 * (int64_t)std::max(h->ncv, 1); break;
     case 33: { static thread_local int64_t info[10]; if (int rc = mpsfm_ba_dense_plan(h, info)) return rc; src = info; bytes = 80; host = true; break; }
     case 34: src = h->last_launches; bytes = (int64_t)sizeof(h->last_launches); host = true; break;
+    case 35: src = h->d_sweep_order; bytes = 4 * (int64_t)h->n_dense; break;
+    case 36: {
+      static thread_local std::vector<int32_t> cost;
+      std::vector<ChunkHdr> hdr((size_t)h->n_dense);
+      if (h->n_dense > 0) {
+        if (hipSetDevice(h->device) != hipSuccess || hipMemcpy(hdr.data(), h->d_chunks, sizeof(ChunkHdr) * hdr.size(), hipMemcpyDeviceToHost) != hipSuccess)
+          return fail(MPSFM_EHIP, "copy failed");
+      }
+      cost.resize(hdr.size());
+      for (size_t c = 0; c < hdr.size(); ++c) cost[c] = dense_sweep_cost(hdr[c].nrec, hdr[c].npt, hdr[c].ncam);
+      src = cost.data(); bytes = 4 * (int64_t)cost.size(); host = true;
+      break;
+    }
+    case 37: src = h->d_slab; bytes = 144 * h->slab_units; break;
+    case 38: src = h->d_pt_fac; bytes = h->d_pt_fac ? 72 * h->np : 0; break;
     default: return fail(MPSFM_EINVAL, "unknown table");
   }
   if (!out || cap < bytes) return bytes;
@@ -425,7 +446,7 @@ int64_t mpsfm_debug_table(mpsfm_ba_handle* h, int32_t which, void* out, int64_t 
 
 // Diagnostics / tests (tests/test_build_tables_cpu.py; no device involved): build_tables — the function mpsfm_ba_create runs — for
 // a single rank and without the device stages on `P`, then table `which` copied out: numbering, arguments and return value of
-// mpsfm_debug_table (26 is a work buffer and does not exist here).  Rebuilds on every call.
+// mpsfm_debug_table (26, 37 and 38 are work buffers and do not exist here; 35 and 36 come from the host sort).  Rebuilds on every call.
 int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* out, int64_t cap) {
   if (int rc = check_problem(P)) return rc;
   BuildOptions opt = BuildOptions::from_environment();
@@ -440,7 +461,7 @@ int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* o
   const void* src = nullptr;
   int64_t bytes = 0;
   const int64_t nr = T.nrec, nf = T.nfixed;
-  std::vector<int32_t> cam_of_slot;
+  std::vector<int32_t> cam_of_slot, sweep_cost;
   int64_t info[10];
   const uint8_t on_device = 0;
   auto vec = [&](const auto& v) { src = v.data(); bytes = (int64_t)(sizeof(v[0]) * v.size()); };
@@ -477,6 +498,8 @@ int64_t mpsfm_debug_host_build(const mpsfm_ba_problem* P, int32_t which, void* o
     case 30: vec(S.sky_start); break;
     case 31: vec(cams.cmask); break;
     case 32: cam_of_slot = cam_of_slot_table(cams); vec(cam_of_slot); break;
+    case 35: vec(slabs.sweep_order); break;
+    case 36: for (int c = 0; c < slabs.n_dense; ++c) sweep_cost.push_back(dense_sweep_cost(T.chunks[(size_t)c].nrec, T.chunks[(size_t)c].npt, T.chunks[(size_t)c].ncam)); vec(sweep_cost); break;
     case 33: {
       DenseOverlap ov;
       LevelPlanDev lp;

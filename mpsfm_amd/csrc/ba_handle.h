@@ -38,6 +38,9 @@ struct mpsfm_ba_handle {
   double* d_slab = nullptr;         // slabs of the dense chunks
   mpsfm::RedDest* d_red_dests = nullptr;   // slab reduction: destination parts and their sources
   int32_t* d_red_srcs = nullptr;
+  int32_t* d_sweep_order = nullptr;        // [n_dense] the chunk the b-th workgroup of k_track_sweep_dense takes: heaviest first (SweepArgs::order)
+  int64_t slab_units = 0;                  // 18-double units of d_slab
+  bool sweep_order_on = true;              // MPSFM_SWEEP_ORDER, read per solve (read_sweep_order_switch): false: sweep_args leaves the table out
   mpsfm::RedDestCols* d_red_cols = nullptr;  // direct form of the slab reduction (DirectAsm): where every destination part lands; NULL: the
                                            // handle has a general chunk, a long track, several ranks or no level plan and keeps k_assemble
   double* d_diag_col = nullptr;            // [32 nt] diag U by system column, for the damping in the first level launch
@@ -145,6 +148,7 @@ DirectAsm direct_asm(const mpsfm_ba_handle* h);
 // the zero fill of the direct form, dealt over the dense sweep's workgroups (SweepArgs::zero_*): camera vectors, y, diag U by column,
 // the inverse accumulators the roles write and the live tiles of A
 void direct_zero_args(mpsfm_ba_handle* h, SweepArgs& a);
+void read_sweep_order_switch(mpsfm_ba_handle* h);  // MPSFM_SWEEP_ORDER into h->sweep_order_on
 bool chol_entry_list();  // MPSFM_CHOL_ENTRY=list, read per solve into DenseOverlap::entry_list
 
 // the single-launch solver's skew hook (mpsfm_debug_local_skew): process-wide like g_dbg_flags, read when a solve is launched

@@ -30,6 +30,7 @@ SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
   a.Sblk = h->d_Sblk; a.gc = h->d_gc; a.wv = h->d_wv; a.diagU = h->d_diagU; a.part = h->d_part; a.diagV = h->d_diagV;
   a.yc = h->d_yc; a.camtab2 = h->d_camtab2; a.pts2 = h->d_pts2; a.part2 = h->d_part2;
   a.slab = h->d_slab; a.chunk0 = 0;
+  a.order = h->sweep_order_on ? h->d_sweep_order : nullptr;
   return a;
 }
 
@@ -197,6 +198,9 @@ constexpr double kSplitMinFront = 40e-6;
 // MPSFM_CHOL_ENTRY=list: the level launches walk item -> source list -> operands instead of reading launch records (the comparison
 // path of dense_chol.hip); read per solve like the switch above
 bool chol_entry_list() { const char* e = std::getenv("MPSFM_CHOL_ENTRY"); return e && std::strcmp(e, "list") == 0; }
+// MPSFM_SWEEP_ORDER=0: every workgroup of the dense sweep takes chunk blockIdx.x + chunk0 instead of the order table's (the comparison
+// path: same chunks, same outputs, another start order); read per solve and by the probes that sweep
+void read_sweep_order_switch(mpsfm_ba_handle* h) { const char* e = std::getenv("MPSFM_SWEEP_ORDER"); h->sweep_order_on = !(e && std::atoi(e) == 0); }
 static bool pt_handoff_enabled() { const char* e = std::getenv("MPSFM_PT_HANDOFF"); return !(e && std::atoi(e) == 0); }
 
 static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
@@ -255,6 +259,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   MPSFM_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const mpsfm_ba_options& o = h->opt;
+  read_sweep_order_switch(h);
   std::memset(sum, 0, sizeof(*sum));
   MPSFM_TRY(hipStreamSynchronize(s));
   const auto t_begin = clk::now();

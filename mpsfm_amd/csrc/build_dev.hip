@@ -571,6 +571,16 @@ __global__ __launch_bounds__(64) void k_slab_entries(int n_dense, const ChunkHdr
     if (k < (uint32_t)ndst) atomicAdd(&cnt[k], 1);
   }
 }
+// ---- order table of the dense sweep (SweepArgs::order): the chunks by descending dense_sweep_cost, ties by ascending index — one
+// sort of unique 64-bit keys, whose low words are the table
+__global__ __launch_bounds__(kT) void k_sweep_order_keys(int n_dense, const ChunkHdr* chunks, unsigned long long* key) {
+  const int c = blockIdx.x * kT + threadIdx.x;
+  if (c < n_dense) key[c] = dense_sweep_order_key(chunks[c], c);
+}
+__global__ __launch_bounds__(kT) void k_sweep_order_table(int n_dense, const unsigned long long* key, int32_t* order) {
+  const int c = blockIdx.x * kT + threadIdx.x;
+  if (c < n_dense) order[c] = (int32_t)(uint32_t)key[c];
+}
 __global__ __launch_bounds__(kT) void k_slab_mark_diag(int ncv, const int32_t* diag_block, int64_t nsb, uint8_t* is_diag) {
   const int sl = blockIdx.x * kT + threadIdx.x;
   if (sl >= ncv) return;
@@ -951,6 +961,24 @@ int DevBuilder::slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t
   hipLaunchKernelGGL(k_slab_parts, dim3((unsigned)((ndst + kT - 1) / kT)), dim3(kT), 0, M.s, ndst, nsb, cnt, start, pstart, is_diag, dests);
   if (hipGetLastError() != hipSuccess) return fail(MPSFM_EHIP, "device build: slab table kernels failed");
   *d_dests = dests; *n_dests = tot[1]; *d_srcs = val_s; *n_srcs = tot[0];
+  return 0;
+}
+
+// Order table of the dense sweep from the device copy of the chunk headers: what dense_sweep_order (build_host.hip) gives on the host.
+int DevBuilder::sweep_order(const ChunkHdr* d_chunks, int n_dense, DeviceBlocks& own, int32_t** d_order) {
+  Impl& M = *m;
+  *d_order = nullptr;
+  if (n_dense <= 0) return 0;
+  unsigned long long* key = M.alloc<unsigned long long>((size_t)n_dense);
+  unsigned long long* key_s = M.alloc<unsigned long long>((size_t)n_dense);
+  int32_t* order = own.alloc<int32_t>((size_t)n_dense);
+  if (!key || !key_s || !order) return fail(MPSFM_ENOMEM, "hipMalloc failed");
+  const unsigned nb = (unsigned)((n_dense + kT - 1) / kT);
+  hipLaunchKernelGGL(k_sweep_order_keys, dim3(nb), dim3(kT), 0, M.s, n_dense, d_chunks, key);
+  if (int rc = M.with_temp([&](void* t, size_t& sz) { return rocprim::radix_sort_keys(t, sz, key, key_s, (size_t)n_dense, 0, 63, M.s); })) return rc;
+  hipLaunchKernelGGL(k_sweep_order_table, dim3(nb), dim3(kT), 0, M.s, n_dense, key_s, order);
+  if (hipGetLastError() != hipSuccess) return fail(MPSFM_EHIP, "device build: sweep order kernels failed");
+  *d_order = order;
   return 0;
 }
 

@@ -81,6 +81,7 @@ struct SlabTables {
   int64_t slab_units = 0;  // 18-double units of all slabs
   std::vector<RedDest> dests;
   std::vector<int32_t> srcs, diag_block;  // diag_block[slot]: the block of S on that slot's diagonal or -1
+  std::vector<int32_t> sweep_order;       // [n_dense] the chunk the b-th workgroup of k_track_sweep_dense takes (dense_sweep_order)
 };
 
 struct Rec { int32_t cam; int32_t slot; uint32_t flags; double u, v, d, m, a; };
@@ -123,6 +124,8 @@ int s_pattern_skyline(const CameraLayout& cams, const HostTables& T, const Build
                       CholPlan& plan);
 // -- slabs: offsets into the chunk headers, then the reduction tables (tables = false: diag_block only, the device forms the rest)
 int assign_slabs(std::vector<ChunkHdr>& chunks, SlabTables& R);
+// -- the order in which the dense sweep's workgroups take the chunks: descending dense_sweep_cost (common.h), ties by ascending index
+void dense_sweep_order(const std::vector<ChunkHdr>& chunks, int n_dense, std::vector<int32_t>& order);
 int slab_reduction_tables(const HostTables& T, const CameraLayout& cams, const CholPlan& plan, const SPattern& S, bool tables, SlabTables& R);
 
 }  // namespace mpsfm

@@ -831,6 +831,15 @@ int assign_slabs(std::vector<ChunkHdr>& chunks, SlabTables& R) {
   return 0;
 }
 
+// order table of the dense sweep (SweepArgs::order): the dense chunks by descending dense_sweep_cost, ties by ascending index
+void dense_sweep_order(const std::vector<ChunkHdr>& chunks, int n_dense, std::vector<int32_t>& order) {
+  std::vector<uint64_t> key((size_t)std::max(n_dense, 0));
+  for (int c = 0; c < n_dense; ++c) key[(size_t)c] = dense_sweep_order_key(chunks[(size_t)c], c);
+  std::sort(key.begin(), key.end());
+  order.resize(key.size());
+  for (size_t i = 0; i < key.size(); ++i) order[i] = (int32_t)(uint32_t)key[i];
+}
+
 // per destination — a block of S or a camera's vectors — the slab positions that contribute, in chunk order; destinations with
 // many sources are split into parts
 int slab_reduction_tables(const HostTables& T, const CameraLayout& cams, const CholPlan& plan, const SPattern& S, bool tables, SlabTables& R) {

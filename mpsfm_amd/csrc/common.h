@@ -70,6 +70,24 @@ __host__ __device__ inline int dense_pts_cap(int ncams, int by_cams) { return (!
 // written with plain stores by k_track_sweep_dense and summed per destination by k_reduce_slabs
 __host__ __device__ inline int64_t slab_doubles(int ncam) { return (int64_t)(ncam * (ncam + 1) / 2) * 36 + (int64_t)ncam * 18; }
 
+// Estimated life of a dense chunk's workgroup from its header alone, in shader cycles: the order table of k_track_sweep_dense starts
+// the chunks by descending cost (SweepArgs::order), so that the dispatcher's last round of workgroups holds the light ones.
+// A constant (barriers and the chains of memory trips every chunk pays), the records (P1, P3a: one thread per record, so they
+// hardly count) and the Schur products (P3b: tile pairs x groups of four landmarks).  The constants are a least-squares fit of the
+// per-chunk phase stamps (debug flag 128, scripts/dbg_sweep_trace.py) of the 3 032 chunks of C3 on the MI355X, the mean of the fits
+// in table order (32 565, -8.9, 158.1) and in this order (25 787, 16.5, 177.0); residual 5.5-7.5 k of a mean life of 40.6 k cycles
+// (DESIGN.md "Measured on MI355X, round 13").  Only the order of the costs matters.  Integers: the host and the device build must
+// sort alike.
+constexpr int32_t kSweepCostBase = 29000, kSweepCostRec = 4, kSweepCostPair = 168;
+__host__ __device__ inline int32_t dense_sweep_cost(int nrec, int npt, int ncam) {
+  const int nt = (6 * ncam + 15) / 16;
+  return kSweepCostBase + kSweepCostRec * nrec + kSweepCostPair * (nt * (nt + 1) / 2) * ((npt + 3) / 4);
+}
+// ... and the table's sort key: descending cost, ties by ascending chunk (an ascending sort of unique 64-bit keys)
+__host__ __device__ inline uint64_t dense_sweep_order_key(const ChunkHdr& H, int cix) {
+  return ((uint64_t)(0x7fffffffu - (uint32_t)dense_sweep_cost(H.nrec, H.npt, H.ncam)) << 32) | (uint32_t)cix;
+}
+
 // One destination of the slab reduction: a 6x6 block of S (kind 0: all 36 entries, 1: a diagonal block, upper triangle) or a camera's
 // vectors (kind 2).  Destinations with many sources are split into parts (every part adds atomically into the zeroed buffer).
 struct RedDest { int32_t kind; int32_t dst; int32_t s0, s1; };
@@ -499,6 +517,7 @@ struct SweepArgs {
   double* slab;             // slabs of the dense chunks (k_track_sweep_dense -> k_reduce_slabs)
   int32_t chunk0;           // first chunk of this launch (blockIdx.x + chunk0 indexes `chunks` and `part`)
   int32_t pad0_;
+  const int32_t* order;     // k_track_sweep_dense: workgroup b takes chunk order[b] (heaviest first, dense_sweep_cost); NULL: chunk b + chunk0
   // outputs of the track sweep (accumulated, caller zeroes)
   BlockSky sky;    // where a block of S lives
   double* Sblk;    // block skyline of the upper block triangle, 36 doubles per block

@@ -52,6 +52,9 @@ class DevBuilder {
   // stage1 must have run (the builder's stream).
   int slab_tables(const ChunkHdr* d_chunks, int n_dense, const int32_t* d_chunk_cams, const BlockSky& sky, int64_t nsb, int ncv, const int32_t* d_diag_block,
                   DeviceBlocks& own, RedDest** d_dests, int32_t* n_dests, int32_t** d_srcs, int64_t* n_srcs);
+  // the order table of the dense sweep (SweepArgs::order: chunks by descending dense_sweep_cost, ties by ascending index) from the
+  // device copy of the chunk headers, [n_dense] from `own`; enqueued on the builder's stream (stage1 must have run)
+  int sweep_order(const ChunkHdr* d_chunks, int n_dense, DeviceBlocks& own, int32_t** d_order);
 
  private:
   struct Impl;

@@ -38,8 +38,12 @@ __global__ __launch_bounds__(kThreads, 3) void k_track_sweep_dense(SweepArgs A) 
   // One workgroup per chunk.  Persistent workgroups (3 per CU taking chunks from a cost-sorted list through a shared counter) were
   // measured and dropped: the slots stay full, but every chunk then takes longer (wave life 21.5 -> 24.7 us at C3: the sweep is
   // bound by the CU's shared pipes, not by the 22 % of slot time the dispatcher leaves empty) — 0.118 against 0.111 ms.
+  // What stays of that list is the ORDER: the dispatcher starts workgroups by ascending blockIdx.x, and workgroup b takes chunk
+  // order[b], heaviest first (dense_sweep_cost in common.h), so the chunks that run long start in the first round and the last
+  // round holds the light ones.  One scalar load in front of the header (MPSFM_SWEEP_ORDER=0: no table, chunk b + chunk0).
   // (the body requests the control block itself, beside the chunk header: the radius given here is what it uses without one)
-  dense_sweep_chunk<false>(A, blockIdx.x + A.chunk0, A.radius, nullptr, S, A.part);
+  const int cix = A.order ? A.order[blockIdx.x] : (int)blockIdx.x + A.chunk0;
+  dense_sweep_chunk<false>(A, cix, A.radius, nullptr, S, A.part);
 }
 
 // One wave per destination part: sums the part's slab sources in table order and adds the sum into the (zeroed) reduced buffer.

@@ -284,7 +284,8 @@ __device__ __forceinline__ void dense_sweep_chunk(const SweepArgs& A, int cix, d
   if constexpr (!kLocal) {
     if (A.adopt_on) {
       adopt = A.ctl != nullptr && __builtin_amdgcn_readfirstlane(accepted) != 0;
-      const int64_t g0 = (int64_t)(cix - A.chunk0) * kThreads + tid, gstep = (int64_t)A.nchunks * kThreads;
+      // (dealt by workgroup, not by chunk: under SweepArgs::order the two differ, and every element is still covered exactly once)
+      const int64_t g0 = (int64_t)blockIdx.x * kThreads + tid, gstep = (int64_t)A.nchunks * kThreads;
       for (int64_t e = g0; e < A.nred; e += gstep) A.red[e] = 0.0;
       // direct form: what the dense solve accumulates into, and the live tiles of A (the slab reduction adds into them)
 #pragma unroll

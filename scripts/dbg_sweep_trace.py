@@ -1,5 +1,7 @@
 """Phase durations inside k_track_sweep_dense from shader-clock stamps (debug flag 128): per wave and chunk the cycles between
-start | P0 done | barrier | P1 done | barrier | P2+P3a done | barrier | products + slab stores done | P4 + partial sums | barrier."""
+start | P0 done | barrier | P1 done | barrier | P2+P3a done | barrier | products + slab stores done | P4 + partial sums | barrier.
+MPSFM_SWEEP_ORDER=0 traces the launch in table order.  The last lines fit the chunk's life to its header — the cost model of
+dense_sweep_cost (csrc/common.h): a nrec + b pairs ceil(npt / 4) + c — and give the start order's effect on the tail."""
 import sys, ctypes as C
 import numpy as np
 sys.path.insert(0, '.')
@@ -31,3 +33,23 @@ wc = t2[:, :, 13] - t2[:, :, 12]
 print(f"  shader clock / 100 MHz reference: {np.sum(t2[:, :, 9] - t2[:, :, 0]) / np.sum(wc):.2f} (clock64 ticks per 10 ns); wave life {wc.mean() * 0.01:.2f} us; "
       f"first wave start -> last wave end {(t2[:, :, 13].max() - t2[:, :, 12].min()) * 0.01:.1f} us; sum of wave lives / (1024 SIMDs x 3 slots) = {wc.sum() * 0.01 / 3072:.1f} us")
 print(f"  wave life {tot:9.0f} cycles; kernel span {(t[:, :, 9].max() - t[:, :, 0].min()):.0f} cycles")
+# ---- the cost model of the order table against the stamps: least squares of the chunk's life (first stamp of any wave -> last) on its header
+hdr = h.debug_table(0, np.int32).reshape(-1, 12)[:n]
+nrec, npt, ncam = (hdr[:, k].astype(np.float64) for k in (1, 3, 5))
+nt = np.ceil(6 * ncam / 16)
+work = nt * (nt + 1) / 2 * np.ceil(npt / 4)
+life = t[:, :, 9].max(1) - t[:, :, 0].min(1)
+prod = d[:, :, 6].max(1)
+for what, y in (("chunk life", life), ("products phase (max over waves)", prod)):
+    X = np.stack([nrec, work, np.ones(n)], 1)
+    coef, *_ = np.linalg.lstsq(X, y, rcond=None)
+    res = y - X @ coef
+    print(f"  fit of the {what}: {coef[0]:.1f} cycles per record + {coef[1]:.1f} per (tile pair x 4 landmarks) + {coef[2]:.0f}; ratio {coef[1] / coef[0]:.2f}; "
+          f"residual rms {np.sqrt(np.mean(res ** 2)):.0f} of mean {y.mean():.0f} cycles")
+cost = h.debug_table(36, np.int32).astype(np.float64)
+print(f"  dense_sweep_cost against the life: correlation {np.corrcoef(cost, life)[0, 1]:.3f}; mean cost {cost.mean():.0f}, mean life {life.mean():.0f} cycles")
+start = (t2[:, :, 12].min(1) - t2[:, :, 12].min()) * 0.01
+end = (t2[:, :, 13].max(1) - t2[:, :, 12].min()) * 0.01
+last = np.argsort(end)[-8:][::-1]
+print("  the chunks that end last (chunk: cameras, start us, end us): " + ", ".join(f"{c}: {int(ncam[c])}, {start[c]:.1f}, {end[c]:.1f}" for c in last))
+print(f"  90 % of the chunks have ended after {np.percentile(end, 90):.1f} us, 99 % after {np.percentile(end, 99):.1f} us, all after {end.max():.1f} us")

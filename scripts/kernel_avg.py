@@ -24,4 +24,4 @@ for want in a.names:
         d = sorted(d)
         kept = d[a.solves:] if len(d) > a.solves else d
         print(f"{name.split('(')[0]:60s} launches {len(d):5d} all {sum(d) / len(d) / 1e3:9.3f} us | without the {len(d) - len(kept)} shortest "
-              f"(<= {d[len(d) - len(kept) - 1] / 1e3 if len(kept) < len(d) else 0:.2f} us): {sum(kept) / len(kept) / 1e3:9.3f} us  min {kept[0] / 1e3:.2f} max {kept[-1] / 1e3:.2f}")
+              f"(<= {d[len(d) - len(kept) - 1] / 1e3 if len(kept) < len(d) else 0:.2f} us): {sum(kept) / len(kept) / 1e3:9.3f} us  median {kept[len(kept) // 2] / 1e3:.2f} min {kept[0] / 1e3:.2f} max {kept[-1] / 1e3:.2f}")
