@@ -36,10 +36,9 @@ __global__ __launch_bounds__(kT) void k_ap_p3p(uint64_t seed, int64_t t0, int32_
     x[k][0] = p.u[idx[k]]; x[k][1] = p.v[idx[k]];
     X[k][0] = p.X[idx[k]]; X[k][1] = p.Y[idx[k]]; X[k][2] = p.Z[idx[k]];
   }
-  double P[4 * 12];
-  const int nm = ap_p3p(x, X, P);
   double* out = models + (size_t)i * 48;
-  for (int k = 0; k < 48; ++k) out[k] = k < 12 * nm ? P[k] : 0.0;  // a zero model puts every point at depth 0: no inliers
+  const int nm = ap_p3p(x, X, out);  // straight into the table: a private array indexed by the model count would live in scratch
+  for (int k = 12 * nm; k < 48; ++k) out[k] = 0.0;  // a zero model puts every point at depth 0: no inliers
   nmod[i] = nm;
 }
 

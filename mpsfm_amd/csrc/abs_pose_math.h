@@ -175,15 +175,30 @@ __host__ __device__ inline int ap_p3p(const double x[3][2], const double X[3][3]
   ap_quartic_roots(c, z);
   // the real roots in ascending order: a root finder's own order is arbitrary, and the order of the models decides which one a
   // trial scores first (LO-RANSAC's decisions and its stop inside a trial depend on it)
-  double vr[4];
+  // (The list is appended to, insertion-sorted and read with every index a constant after unrolling: indexed by nr or by
+  // a loop counter it would live in scratch on the device.  The comparisons and their order are the plain loops'.)
+  double vr[4] = {0.0, 0.0, 0.0, 0.0};
   int nr = 0;
+#pragma unroll
   for (int r = 0; r < 4; ++r)
-    if (fabs(z[r].im) <= kApMaxRootImag) vr[nr++] = z[r].re;
-  for (int i = 1; i < nr; ++i)
-    for (int j = i; j > 0 && vr[j] < vr[j - 1]; --j) { const double tv = vr[j]; vr[j] = vr[j - 1]; vr[j - 1] = tv; }
+    if (fabs(z[r].im) <= kApMaxRootImag) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        if (s == nr) vr[s] = z[r].re;
+      ++nr;
+    }
+#pragma unroll
+  for (int i = 1; i < 4; ++i) {
+    bool go = i < nr;  // for (j = i; j > 0 && vr[j] < vr[j - 1]; --j) swap
+#pragma unroll
+    for (int j = i; j > 0; --j) {
+      go = go && vr[j] < vr[j - 1];
+      if (go) { const double tv = vr[j]; vr[j] = vr[j - 1]; vr[j - 1] = tv; }
+    }
+  }
   int nm = 0;
   for (int r = 0; r < nr; ++r) {
-    const double v = vr[r];  // s3 / s1
+    const double v = r == 0 ? vr[0] : r == 1 ? vr[1] : r == 2 ? vr[2] : vr[3];  // s3 / s1
     if (v < 0) continue;
     const double den = 2 * (cg - v * ca);
     if (den == 0.0) continue;

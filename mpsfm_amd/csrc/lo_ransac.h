@@ -138,9 +138,12 @@ inline void sum_rows(const T* part, int nblocks, int K, S* out) {
 }
 
 // ---- scoring -----------------------------------------------------------------------------------------------------------
+// The body of k_lo_score and of its batched form (two_view_batch.hip): workgroup blockIdx.x of the nblk along the n
+// observations scores the tile of kLoTile models at blockIdx.y (models: the problem's first model) and writes the tile's row of
+// partial counts and sums, part[model][nblk].  Every thread of the workgroup calls it (it holds two barriers).
 template <class P>
-__global__ __launch_bounds__(kLoT) void k_lo_score(const double* __restrict__ models, int32_t nmodels, int32_t n, typename P::Pts p, double thr2,
-                                                    int32_t* __restrict__ part_cnt, double* __restrict__ part_sum) {
+__device__ __forceinline__ void lo_score_tile(const double* __restrict__ models, int32_t nmodels, int32_t n, const typename P::Pts& p, double thr2,
+                                              int32_t nblk, int32_t* __restrict__ part_cnt, double* __restrict__ part_sum) {
   constexpr int K = P::kModel;
   __shared__ double sm[kLoTile * K];
   __shared__ double red_s[kLoWaves][kLoTile];
@@ -155,7 +158,7 @@ __global__ __launch_bounds__(kLoT) void k_lo_score(const double* __restrict__ mo
   double sum[kLoTile];
 #pragma unroll
   for (int m = 0; m < kLoTile; ++m) { cnt[m] = 0; sum[m] = 0.0; }
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += (int32_t)gridDim.x * kLoT) {
+  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
     const typename P::Obs o = P::load(p, i);
 #pragma unroll
     for (int m = 0; m < kLoTile; ++m) {
@@ -176,19 +179,32 @@ __global__ __launch_bounds__(kLoT) void k_lo_score(const double* __restrict__ mo
     int c = 0;
     double s = 0.0;
     for (int w = 0; w < kLoWaves; ++w) { c += red_c[w][threadIdx.x]; s += red_s[w][threadIdx.x]; }
-    if (m < nmodels) { part_cnt[(size_t)m * gridDim.x + blockIdx.x] = c; part_sum[(size_t)m * gridDim.x + blockIdx.x] = s; }
+    if (m < nmodels) { part_cnt[(size_t)m * nblk + blockIdx.x] = c; part_sum[(size_t)m * nblk + blockIdx.x] = s; }
   }
+}
+
+template <class P>
+__global__ __launch_bounds__(kLoT) void k_lo_score(const double* __restrict__ models, int32_t nmodels, int32_t n, typename P::Pts p, double thr2,
+                                                    int32_t* __restrict__ part_cnt, double* __restrict__ part_sum) {
+  lo_score_tile<P>(models, nmodels, n, p, thr2, (int32_t)gridDim.x, part_cnt, part_sum);
+}
+
+// The body of k_lo_score_sum and of its batched form: a model's row of nparts partial counts and sums, added in ascending
+// block order
+__device__ __forceinline__ void lo_score_sum_row(const int32_t* __restrict__ part_cnt, const double* __restrict__ part_sum, int32_t nparts,
+                                                 int32_t* __restrict__ cnt, double* __restrict__ sum) {
+  int c = 0;
+  double s = 0.0;
+  for (int b = 0; b < nparts; ++b) { c += part_cnt[b]; s += part_sum[b]; }
+  *cnt = c;
+  *sum = s;
 }
 
 static __global__ __launch_bounds__(kLoT) void k_lo_score_sum(const int32_t* __restrict__ part_cnt, const double* __restrict__ part_sum,
                                                                int32_t nmodels, int32_t nparts, int32_t* __restrict__ cnt, double* __restrict__ sum) {
   const int32_t m = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x;
   if (m >= nmodels) return;
-  int c = 0;
-  double s = 0.0;
-  for (int b = 0; b < nparts; ++b) { c += part_cnt[(size_t)m * nparts + b]; s += part_sum[(size_t)m * nparts + b]; }
-  cnt[m] = c;
-  sum[m] = s;
+  lo_score_sum_row(part_cnt + (size_t)m * nparts, part_sum + (size_t)m * nparts, nparts, cnt + m, sum + m);
 }
 
 template <int K> struct LoModel { double m[K]; };
@@ -216,16 +232,25 @@ struct LoReport {
   int64_t num_trials = 0, max_num_trials = 0, num_models = 0, lo_rounds = 0, num_batches = 0;
 };
 
+// the trials a call runs at most: max_num_trials, or what min_inlier_ratio needs at the call's confidence
+inline int64_t lo_max_trials(const mpsfm_ransac_options& o, int sample) {
+  return std::min<int64_t>(o.max_num_trials, lo_num_trials((int64_t)(o.min_inlier_ratio * 100000.0), 100000, o.confidence, o.dyn_num_trials_multiplier, sample));
+}
+// trials per batch: batch_trials or the problem's default, at most the call's trials
+template <class P>
+int64_t lo_batch_cap(const mpsfm_ransac_options& o) {
+  const int32_t B = o.batch_trials > 0 ? o.batch_trials : P::kDefaultBatch;
+  return std::max<int64_t>(1, std::min<int64_t>(B, lo_max_trials(o, P::kSample)));
+}
+
 // best_model [P::kModel]: meaningful when rep.best.num_inliers >= P::kSample.  The scope is open and timed.
 template <class P>
 int lo_ransac(P& prob, CallScope& A, const mpsfm_ransac_options& o, LoReport& rep, double* best_model) {
   constexpr int K = P::kModel, S = P::kSlots, L = P::kLocal;
   static_assert(L <= S, "the local models are scored in the partial rows of one trial");
   const int32_t n = prob.n;
-  const int64_t max_trials = std::min<int64_t>(
-      o.max_num_trials, lo_num_trials((int64_t)(o.min_inlier_ratio * 100000.0), 100000, o.confidence, o.dyn_num_trials_multiplier, P::kSample));
-  const int32_t B = o.batch_trials > 0 ? o.batch_trials : P::kDefaultBatch;
-  const int32_t Bcap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(B, max_trials));
+  const int64_t max_trials = lo_max_trials(o, P::kSample);
+  const int32_t Bcap = (int32_t)lo_batch_cap<P>(o);
   const int32_t Mcap = S * Bcap;             // batch models; L more slots after them for the local models
   const int nbx = lo_blocks(n, 4 * kLoT);    // scoring workgroups along the observations
 

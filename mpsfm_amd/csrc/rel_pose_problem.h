@@ -22,33 +22,47 @@ constexpr int kGramK = 46;          // count, then the upper triangle of Q^T Q r
 
 struct RpPts { const double *u1, *v1, *u2, *v2; };
 
-__global__ __launch_bounds__(kFiveT) void k_rp_five(uint64_t seed, int64_t t0, int32_t nb, int32_t n, RpPts p, double* __restrict__ models,
-                                                     int32_t* __restrict__ nmod) {
+// The kernels below and their batched forms (two_view_batch.hip) are two callers of one body each.  A body takes what its
+// callers read from their arguments or from a descriptor row: the trial, or the number nblk of workgroups along the problem's
+// observations (its own workgroup is blockIdx.x, as in block_reduce_rows), the points, the model and the output pointers,
+// already at the problem's rows.
+
+// Trial t of k_rp_five, by thread threadIdx.x of a workgroup of kFiveT: the five-index sample and the five-point solver in the
+// thread's LDS slice; up to kRpMaxModels models at out (zeros pad) and their number.  flatten: wherever two kernels of one
+// translation unit call this body the solver's stages have two callers, and the inliner would otherwise leave them as calls
+// with their arrays in scratch.
+__device__ __forceinline__ __attribute__((flatten)) void rp_five_trial(uint64_t seed, int64_t t, int32_t n, const RpPts& p, double* __restrict__ out,
+                                                                       int32_t* __restrict__ nmod) {
   __shared__ double work[kFiveT * RP_WORK];
-  const int32_t i = (int32_t)blockIdx.x * kFiveT + (int32_t)threadIdx.x;
-  if (i >= nb) return;
   int32_t idx[kRpSample];
-  lo_sample<kRpSample>(seed, t0 + i, n, idx);
+  lo_sample<kRpSample>(seed, t, n, idx);
   double u1[kRpSample], v1[kRpSample], u2[kRpSample], v2[kRpSample];
 #pragma unroll
   for (int k = 0; k < kRpSample; ++k) { u1[k] = p.u1[idx[k]]; v1[k] = p.v1[idx[k]]; u2[k] = p.u2[idx[k]]; v2[k] = p.v2[idx[k]]; }
   const RpW w{work + threadIdx.x, kFiveT};
-  double* out = models + (size_t)i * 9 * kRpMaxModels;
   int nm = 0;
   if (rp_nullspace5(u1, v1, u2, v2, w)) nm = rp_models_from_nullspace(w, out);
   for (int k = 9 * nm; k < 9 * kRpMaxModels; ++k) out[k] = 0.0;
-  nmod[i] = nm;
+  *nmod = nm;
+}
+
+__global__ __launch_bounds__(kFiveT) void k_rp_five(uint64_t seed, int64_t t0, int32_t nb, int32_t n, RpPts p, double* __restrict__ models,
+                                                     int32_t* __restrict__ nmod) {
+  const int32_t i = (int32_t)blockIdx.x * kFiveT + (int32_t)threadIdx.x;
+  if (i >= nb) return;
+  rp_five_trial(seed, t0 + i, n, p, models + (size_t)i * 9 * kRpMaxModels, nmod + i);
 }
 
 using RpModel = LoModel<9>;
 
-__global__ __launch_bounds__(kT) void k_rp_gram(RpModel Ein, double thr2, int32_t n, RpPts p, double* __restrict__ part) {
+// k_rp_gram: count and Q^T Q of the inliers of E among the workgroup's observations -> its row of part
+__device__ __forceinline__ void rp_gram_block(const double* E, double thr2, int32_t n, const RpPts& p, int32_t nblk, double* __restrict__ part) {
   double acc[kGramK];
 #pragma unroll
   for (int k = 0; k < kGramK; ++k) acc[k] = 0.0;
-  for (int32_t i = (int32_t)blockIdx.x * kT + (int32_t)threadIdx.x; i < n; i += (int32_t)gridDim.x * kT) {
+  for (int32_t i = (int32_t)blockIdx.x * kT + (int32_t)threadIdx.x; i < n; i += nblk * kT) {
     const double u1 = p.u1[i], v1 = p.v1[i], u2 = p.u2[i], v2 = p.v2[i];
-    if (!(rp_sampson(Ein.m, u1, v1, u2, v2) <= thr2)) continue;
+    if (!(rp_sampson(E, u1, v1, u2, v2) <= thr2)) continue;
     double q[9];
     rp_q_row(u1, v1, u2, v2, q);
     acc[0] += 1.0;
@@ -59,6 +73,10 @@ __global__ __launch_bounds__(kT) void k_rp_gram(RpModel Ein, double thr2, int32_
       for (int c = r; c < 9; ++c) acc[k++] += q[r] * q[c];
   }
   block_reduce_rows<kGramK>(acc, part);
+}
+
+__global__ __launch_bounds__(kT) void k_rp_gram(RpModel Ein, double thr2, int32_t n, RpPts p, double* __restrict__ part) {
+  rp_gram_block(Ein.m, thr2, n, p, (int32_t)gridDim.x, part);
 }
 
 struct RpCands { double P[4][12]; double max_depth[4]; };
@@ -106,6 +124,22 @@ struct RpProblem {
     hipLaunchKernelGGL(k_rp_five, dim3((unsigned)((nb + kFiveT - 1) / kFiveT)), dim3(kFiveT), 0, st, seed, t0, nb, n, pts, models, nmod);
   }
 
+  // the host half of the local estimator (one signature for every problem of the two-view legs; this one has no moments
+  // stage): the summed k_rp_gram row -> the models of the nullspace of Q^T Q, and their number
+  static int local_models(const double* /* moments */, const double g[kGramK], double* out) {
+    if (g[0] < kRpSample) return 0;
+    double G[9][9], V[9][9], ev[9];
+    for (int r = 0, k = 1; r < 9; ++r)
+      for (int c = r; c < 9; ++c, ++k) G[r][c] = G[c][r] = g[k];
+    sym_eig<9>(G, V, ev);  // ascending
+    if (!(ev[4] > kRpRankTol * kRpRankTol * ev[8])) return 0;
+    double work[RP_WORK];
+    const RpW w{work, 1};
+    for (int k = 0; k < 4; ++k)
+      for (int i = 0; i < 9; ++i) w[RP_N + 9 * k + i] = V[i][3 - k];
+    return rp_models_from_nullspace(w, out);
+  }
+
   // EssentialMatrixFivePointEstimator::Estimate on the inliers of Ein (n > 5: the nullspace of Q^T Q): up to 10 models
   int local(CallScope& A, const double* Ein, double* out, int& nm) {
     nm = 0;
@@ -118,17 +152,7 @@ struct RpProblem {
     if (int rc = A.end()) return rc;
     double g[kGramK];
     sum_rows(h_part.data(), npx, kGramK, g);
-    if (g[0] < kRpSample) return 0;
-    double G[9][9], V[9][9], ev[9];
-    for (int r = 0, k = 1; r < 9; ++r)
-      for (int c = r; c < 9; ++c, ++k) G[r][c] = G[c][r] = g[k];
-    sym_eig<9>(G, V, ev);  // ascending
-    if (!(ev[4] > kRpRankTol * kRpRankTol * ev[8])) return 0;
-    double work[RP_WORK];
-    const RpW w{work, 1};
-    for (int k = 0; k < 4; ++k)
-      for (int i = 0; i < 9; ++i) w[RP_N + 9 * k + i] = V[i][3 - k];
-    nm = rp_models_from_nullspace(w, out);
+    nm = local_models(nullptr, g, out);
     return 0;
   }
 };

@@ -1,7 +1,7 @@
 // Calibrated two-view geometry of many image pairs in one call (mpsfm_two_view_geometry_batch; include/mpsfm_hip.h, DESIGN.md
 // section 4k): the pairs of a group run every leg as one lockstep LO-RANSAC.  Each kernel here is a single-pair kernel of
 // two_view_problem.h / rel_pose_problem.h / lo_ransac.h with one more grid dimension, the problem, and a descriptor table in
-// place of the by-value arguments; the device functions and the order of operations are the single call's, so every pair's
+// place of the by-value arguments: it reads its problem's row and calls the body the single-pair kernel calls, so every pair's
 // result is bitwise that of mpsfm_two_view_geometry.  f64 throughout.
 #include "two_view_problem.h"
 
@@ -31,67 +31,29 @@ __device__ __forceinline__ RpPts bt_pts(const double* __restrict__ pts, const Bt
   return RpPts{b, b + d.n, b + 2 * (size_t)d.n, b + 3 * (size_t)d.n};
 }
 
-// flatten: this file also carries rel_pose_problem.h's copy of k_rp_five (never launched from here), and with two callers the
-// inliner would leave the five-point solver's stages as calls with their arrays in scratch
-__global__ __launch_bounds__(kFiveT) __attribute__((flatten)) void k_bt_five(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ models,
+// the minimal solvers over (trial, problem)
+__global__ __launch_bounds__(kFiveT) void k_bt_five(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ models,
                                                      int32_t* __restrict__ nmod) {
-  __shared__ double work[kFiveT * RP_WORK];
   const BtDesc& d = D[blockIdx.y];
   const int32_t i = (int32_t)blockIdx.x * kFiveT + (int32_t)threadIdx.x;
   if (i >= d.nb) return;
-  const RpPts p = bt_pts(pts, d);
-  int32_t idx[kRpSample];
-  lo_sample<kRpSample>(d.seed, d.t0 + i, d.n, idx);
-  double u1[kRpSample], v1[kRpSample], u2[kRpSample], v2[kRpSample];
-#pragma unroll
-  for (int k = 0; k < kRpSample; ++k) { u1[k] = p.u1[idx[k]]; v1[k] = p.v1[idx[k]]; u2[k] = p.u2[idx[k]]; v2[k] = p.v2[idx[k]]; }
-  const RpW w{work + threadIdx.x, kFiveT};
-  double* out = models + ((size_t)d.mod_off + (size_t)i * kRpMaxModels) * 9;
-  int nm = 0;
-  if (rp_nullspace5(u1, v1, u2, v2, w)) nm = rp_models_from_nullspace(w, out);
-  for (int k = 9 * nm; k < 9 * kRpMaxModels; ++k) out[k] = 0.0;
-  nmod[d.nmod_off + i] = nm;
+  rp_five_trial(d.seed, d.t0 + i, d.n, bt_pts(pts, d), models + ((size_t)d.mod_off + (size_t)i * kRpMaxModels) * 9, nmod + d.nmod_off + i);
 }
 
 __global__ __launch_bounds__(kSevenT) void k_bt_f7(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ models,
                                                     int32_t* __restrict__ nmod) {
-  __shared__ double work[kSevenT * TVF_WORK];
-  __shared__ int32_t sidx[kSevenT * kTvFSample];
   const BtDesc& d = D[blockIdx.y];
   const int32_t i = (int32_t)blockIdx.x * kSevenT + (int32_t)threadIdx.x;
   if (i >= d.nb) return;
-  const RpPts p = bt_pts(pts, d);
-  int32_t* idx = sidx + kTvFSample * threadIdx.x;
-  lo_sample<kTvFSample>(d.seed, d.t0 + i, d.n, idx);
-  double u1[kTvFSample], v1[kTvFSample], u2[kTvFSample], v2[kTvFSample];
-#pragma unroll
-  for (int k = 0; k < kTvFSample; ++k) { u1[k] = p.u1[idx[k]]; v1[k] = p.v1[idx[k]]; u2[k] = p.u2[idx[k]]; v2[k] = p.v2[idx[k]]; }
-  const RpW w{work + threadIdx.x, kSevenT};
-  double* out = models + ((size_t)d.mod_off + (size_t)i * kTvFMaxModels) * 9;
-  const int nm = tv_seven_point(u1, v1, u2, v2, w, out);
-  for (int k = 9 * nm; k < 9 * kTvFMaxModels; ++k) out[k] = 0.0;
-  nmod[d.nmod_off + i] = nm;
+  tv_f7_trial(d.seed, d.t0 + i, d.n, bt_pts(pts, d), models + ((size_t)d.mod_off + (size_t)i * kTvFMaxModels) * 9, nmod + d.nmod_off + i);
 }
 
 __global__ __launch_bounds__(kFourT) void k_bt_h4(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ models,
                                                    int32_t* __restrict__ nmod) {
-  __shared__ double work[kFourT * TVH_WORK];
   const BtDesc& d = D[blockIdx.y];
   const int32_t i = (int32_t)blockIdx.x * kFourT + (int32_t)threadIdx.x;
   if (i >= d.nb) return;
-  const RpPts p = bt_pts(pts, d);
-  int32_t idx[kTvHSample];
-  lo_sample<kTvHSample>(d.seed, d.t0 + i, d.n, idx);
-  double u1[kTvHSample], v1[kTvHSample], u2[kTvHSample], v2[kTvHSample];
-#pragma unroll
-  for (int k = 0; k < kTvHSample; ++k) { u1[k] = p.u1[idx[k]]; v1[k] = p.v1[idx[k]]; u2[k] = p.u2[idx[k]]; v2[k] = p.v2[idx[k]]; }
-  const RpW w{work + threadIdx.x, kFourT};
-  double H[9];
-  const bool ok = tv_four_point(u1, v1, u2, v2, w, H);
-  double* out = models + ((size_t)d.mod_off + (size_t)i) * 9;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) out[k] = ok ? H[k] : 0.0;
-  nmod[d.nmod_off + i] = ok ? 1 : 0;
+  tv_h4_trial(d.seed, d.t0 + i, d.n, bt_pts(pts, d), models + ((size_t)d.mod_off + (size_t)i) * 9, nmod + d.nmod_off + i);
 }
 
 __global__ __launch_bounds__(kLoT) void k_bt_t1(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ models,
@@ -99,196 +61,64 @@ __global__ __launch_bounds__(kLoT) void k_bt_t1(const BtDesc* __restrict__ D, co
   const BtDesc& d = D[blockIdx.y];
   const int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x;
   if (i >= d.nb) return;
-  const RpPts p = bt_pts(pts, d);
-  int32_t idx[1];
-  lo_sample<1>(d.seed, d.t0 + i, d.n, idx);
-  double* out = models + ((size_t)d.mod_off + (size_t)i) * 2;
-  out[0] = p.u2[idx[0]] - p.u1[idx[0]];
-  out[1] = p.v2[idx[0]] - p.v1[idx[0]];
-  nmod[d.nmod_off + i] = 1;
+  tv_t1_trial(d.seed, d.t0 + i, d.n, bt_pts(pts, d), models + ((size_t)d.mod_off + (size_t)i) * 2, nmod + d.nmod_off + i);
 }
 
 // k_lo_score over (observation block, model tile, problem)
 template <class P>
 __global__ __launch_bounds__(kLoT) void k_bt_score(const BtDesc* __restrict__ D, const double* __restrict__ pts, const double* __restrict__ models,
                                                     int32_t* __restrict__ part_cnt, double* __restrict__ part_sum) {
-  constexpr int K = P::kModel;
-  __shared__ double sm[kLoTile * K];
-  __shared__ double red_s[kLoWaves][kLoTile];
-  __shared__ int red_c[kLoWaves][kLoTile];
   const BtDesc& d = D[blockIdx.z];
-  const int32_t nblk = d.nblk, nmodels = d.nmodels, n = d.n;
-  const int m0 = (int)blockIdx.y * kLoTile;
-  if ((int32_t)blockIdx.x >= nblk || m0 >= nmodels) return;
-  const double* mod = models + (size_t)d.mod_off * K;
-  const typename P::Pts p = bt_pts(pts, d);
-  const double thr2 = d.thr2;
-  for (int k = threadIdx.x; k < kLoTile * K; k += kLoT) {
-    const int m = m0 + k / K;
-    sm[k] = m < nmodels ? mod[(size_t)m0 * K + k] : 0.0;
-  }
-  __syncthreads();
-  int cnt[kLoTile];
-  double sum[kLoTile];
-#pragma unroll
-  for (int m = 0; m < kLoTile; ++m) { cnt[m] = 0; sum[m] = 0.0; }
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
-    const typename P::Obs o = P::load(p, i);
-#pragma unroll
-    for (int m = 0; m < kLoTile; ++m) {
-      const double r = P::residual(sm + K * m, o);
-      if (r <= thr2) { cnt[m] += 1; sum[m] += r; }
-    }
-  }
-  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-#pragma unroll
-  for (int m = 0; m < kLoTile; ++m) {
-    const int c = lo_wave_sum(cnt[m]);
-    const double s = lo_wave_sum(sum[m]);
-    if (lane == 0) { red_c[wave][m] = c; red_s[wave][m] = s; }
-  }
-  __syncthreads();
-  if (threadIdx.x < kLoTile) {
-    const int m = m0 + (int)threadIdx.x;
-    int c = 0;
-    double s = 0.0;
-    for (int w = 0; w < kLoWaves; ++w) { c += red_c[w][threadIdx.x]; s += red_s[w][threadIdx.x]; }
-    if (m < nmodels) {
-      const size_t at = (size_t)d.part_off + (size_t)m * nblk + blockIdx.x;
-      part_cnt[at] = c;
-      part_sum[at] = s;
-    }
-  }
+  if ((int32_t)blockIdx.x >= d.nblk || (int)blockIdx.y * kLoTile >= d.nmodels) return;
+  lo_score_tile<P>(models + (size_t)d.mod_off * P::kModel, d.nmodels, d.n, bt_pts(pts, d), d.thr2, d.nblk, part_cnt + d.part_off,
+                   part_sum + d.part_off);
 }
 
-// k_lo_score_sum over (model, problem): the problem's partial rows in ascending block order
+// k_lo_score_sum over (model, problem)
 __global__ __launch_bounds__(kLoT) void k_bt_sum(const BtDesc* __restrict__ D, const int32_t* __restrict__ part_cnt, const double* __restrict__ part_sum,
                                                   int32_t* __restrict__ cnt, double* __restrict__ sum) {
   const BtDesc& d = D[blockIdx.y];
   const int32_t m = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x;
   if (m >= d.nmodels) return;
-  const int32_t nparts = d.nblk;
-  const size_t at = (size_t)d.part_off + (size_t)m * nparts;
-  int c = 0;
-  double s = 0.0;
-  for (int b = 0; b < nparts; ++b) { c += part_cnt[at + b]; s += part_sum[at + b]; }
-  cnt[d.out_off + m] = c;
-  sum[d.out_off + m] = s;
+  const size_t at = (size_t)d.part_off + (size_t)m * d.nblk;
+  lo_score_sum_row(part_cnt + at, part_sum + at, d.nblk, cnt + d.out_off + m, sum + d.out_off + m);
 }
 
+// the reductions of the local estimators over (observation block, problem): k_tv_moments, k_tv_gram, k_rp_gram, k_tv_tsum
 template <bool kHomography>
 __global__ __launch_bounds__(kLoT) void k_bt_moments(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ part) {
   const BtDesc& d = D[blockIdx.y];
-  const int32_t nblk = d.nblk, n = d.n;
-  if ((int32_t)blockIdx.x >= nblk) return;
-  const RpPts p = bt_pts(pts, d);
-  const double thr2 = d.thr2;
-  double M[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) M[k] = d.model[k];
-  double acc[kMomK] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
-    const double u1 = p.u1[i], v1 = p.v1[i], u2 = p.u2[i], v2 = p.v2[i];
-    if (!(tv_residual<kHomography>(M, u1, v1, u2, v2) <= thr2)) continue;
-    acc[0] += 1.0; acc[1] += u1; acc[2] += v1; acc[3] += u2; acc[4] += v2;
-  }
-  block_reduce_rows<kMomK>(acc, part + (size_t)d.part_off * kMomK);
+  if ((int32_t)blockIdx.x >= d.nblk) return;
+  tv_moments_block<kHomography>(d.model, d.thr2, d.n, bt_pts(pts, d), d.nblk, part + (size_t)d.part_off * kMomK);
 }
 
 template <bool kHomography>
 __global__ __launch_bounds__(kLoT) void k_bt_gram(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ part) {
   const BtDesc& d = D[blockIdx.y];
-  const int32_t nblk = d.nblk, n = d.n;
-  if ((int32_t)blockIdx.x >= nblk) return;
-  const RpPts p = bt_pts(pts, d);
-  const double thr2 = d.thr2;
+  if ((int32_t)blockIdx.x >= d.nblk) return;
   const TvCentre c{d.centre[0], d.centre[1], d.centre[2], d.centre[3]};
-  double M[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) M[k] = d.model[k];
-  double acc[kGram9K];
-#pragma unroll
-  for (int k = 0; k < kGram9K; ++k) acc[k] = 0.0;
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
-    const double u1 = p.u1[i], v1 = p.v1[i], u2 = p.u2[i], v2 = p.v2[i];
-    if (!(tv_residual<kHomography>(M, u1, v1, u2, v2) <= thr2)) continue;
-    const double x1 = u1 - c.c1x, y1 = v1 - c.c1y, x2 = u2 - c.c2x, y2 = v2 - c.c2y;
-    if constexpr (kHomography) {
-      double a[9], b[9];
-      tv_h_rows(x1, y1, x2, y2, a, b);
-      int k = 0;
-#pragma unroll
-      for (int r = 0; r < 9; ++r)
-#pragma unroll
-        for (int cc = r; cc < 9; ++cc) acc[k++] += a[r] * a[cc] + b[r] * b[cc];
-    } else {
-      double q[9];
-      rp_q_row(x1, y1, x2, y2, q);
-      int k = 0;
-#pragma unroll
-      for (int r = 0; r < 9; ++r)
-#pragma unroll
-        for (int cc = r; cc < 9; ++cc) acc[k++] += q[r] * q[cc];
-    }
-  }
-  block_reduce_rows<kGram9K>(acc, part + (size_t)d.part_off * kGram9K);
+  tv_gram_block<kHomography>(d.model, d.thr2, d.n, bt_pts(pts, d), c, d.nblk, part + (size_t)d.part_off * kGram9K);
 }
 
-// k_rp_gram over (observation block, problem)
 __global__ __launch_bounds__(kLoT) void k_bt_egram(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ part) {
   const BtDesc& d = D[blockIdx.y];
-  const int32_t nblk = d.nblk, n = d.n;
-  if ((int32_t)blockIdx.x >= nblk) return;
-  const RpPts p = bt_pts(pts, d);
-  const double thr2 = d.thr2;
-  double M[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) M[k] = d.model[k];
-  double acc[kGramK];
-#pragma unroll
-  for (int k = 0; k < kGramK; ++k) acc[k] = 0.0;
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
-    const double u1 = p.u1[i], v1 = p.v1[i], u2 = p.u2[i], v2 = p.v2[i];
-    if (!(rp_sampson(M, u1, v1, u2, v2) <= thr2)) continue;
-    double q[9];
-    rp_q_row(u1, v1, u2, v2, q);
-    acc[0] += 1.0;
-    int k = 1;
-#pragma unroll
-    for (int r = 0; r < 9; ++r)
-#pragma unroll
-      for (int c = r; c < 9; ++c) acc[k++] += q[r] * q[c];
-  }
-  block_reduce_rows<kGramK>(acc, part + (size_t)d.part_off * kGramK);
+  if ((int32_t)blockIdx.x >= d.nblk) return;
+  rp_gram_block(d.model, d.thr2, d.n, bt_pts(pts, d), d.nblk, part + (size_t)d.part_off * kGramK);
 }
 
 __global__ __launch_bounds__(kLoT) void k_bt_tsum(const BtDesc* __restrict__ D, const double* __restrict__ pts, double* __restrict__ part) {
   const BtDesc& d = D[blockIdx.y];
-  const int32_t nblk = d.nblk, n = d.n;
-  if ((int32_t)blockIdx.x >= nblk) return;
-  const RpPts p = bt_pts(pts, d);
-  const double thr2 = d.thr2, t0 = d.model[0], t1 = d.model[1];
-  double acc[kTsumK] = {0.0, 0.0, 0.0};
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
-    const double dx = p.u2[i] - p.u1[i], dy = p.v2[i] - p.v1[i];
-    const double ex = dx - t0, ey = dy - t1;
-    if (!(ex * ex + ey * ey <= thr2)) continue;
-    acc[0] += 1.0; acc[1] += dx; acc[2] += dy;
-  }
-  block_reduce_rows<kTsumK>(acc, part + (size_t)d.part_off * kTsumK);
+  if ((int32_t)blockIdx.x >= d.nblk) return;
+  tv_tsum_block(d.model, d.thr2, d.n, bt_pts(pts, d), d.nblk, part + (size_t)d.part_off * kTsumK);
 }
 
-// k_lo_mask over (observation, problem)
+// k_lo_mask over (observation, problem): one line of P's own functions, kept as its own text
 template <class P>
 __global__ __launch_bounds__(kLoT) void k_bt_mask(const BtDesc* __restrict__ D, const double* __restrict__ pts, uint8_t* __restrict__ mask) {
   const BtDesc& d = D[blockIdx.y];
   const int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x;
   if (i >= d.n) return;
-  const typename P::Pts p = bt_pts(pts, d);
-  double M[P::kModel];
-#pragma unroll
-  for (int k = 0; k < P::kModel; ++k) M[k] = d.model[k];
-  mask[(size_t)d.out_off + i] = P::residual(M, P::load(p, i)) <= d.thr2 ? 1 : 0;
+  mask[(size_t)d.out_off + i] = P::residual(d.model, P::load(bt_pts(pts, d), i)) <= d.thr2 ? 1 : 0;
 }
 
 struct BtPoseDesc {
@@ -301,41 +131,10 @@ struct BtPoseDesc {
 __global__ __launch_bounds__(kLoT) void k_bt_pose(const BtPoseDesc* __restrict__ D, const double* __restrict__ pts, const uint8_t* __restrict__ mask_all,
                                                    int32_t* __restrict__ part, double* __restrict__ angle_all) {
   const BtPoseDesc& d = D[blockIdx.y];
-  const int32_t nblk = d.nblk, n = d.n;
-  if ((int32_t)blockIdx.x >= nblk) return;
+  if ((int32_t)blockIdx.x >= d.nblk) return;
   const double* pb = pts + d.base;
-  const RpPts p{pb, pb + n, pb + 2 * (size_t)n, pb + 3 * (size_t)n};
-  const uint8_t* mask = mask_all + d.mask_off;
-  double* angle = angle_all + d.angle_off;
-  const int ncand = d.c.ncand;
-  int cnt[4] = {0, 0, 0, 0};
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
-    const bool on = mask[i] != 0;
-    TriView a{}, b{};
-    a.P[0] = 1.0; a.P[5] = 1.0; a.P[10] = 1.0;
-    a.xn[0] = p.u1[i]; a.xn[1] = p.v1[i];
-    b.xn[0] = p.u2[i]; b.xn[1] = p.v2[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      double ang = -1.0;
-      if (on && k < ncand) {
-#pragma unroll
-        for (int e = 0; e < 12; ++e) b.P[e] = d.c.P[k][e];
-        double X[3];
-        tri_two_view(a, b, X);
-        const double d1 = X[2], d2 = tri_depth(b.P, X);
-        const double maxd = d.c.max_depth[k];
-        if (d1 > DBL_EPSILON && d1 < maxd && d2 > DBL_EPSILON && d2 < maxd) {
-          cnt[k] += 1;
-          const double C1[3] = {0.0, 0.0, 0.0};
-          const double C2[3] = {d.c.C2[k][0], d.c.C2[k][1], d.c.C2[k][2]};
-          ang = tri_angle(C1, C2, X);
-        }
-      }
-      angle[(size_t)k * n + i] = ang;
-    }
-  }
-  block_reduce_rows<4>(cnt, part + (size_t)d.part_off * 4);
+  const RpPts p{pb, pb + d.n, pb + 2 * (size_t)d.n, pb + 3 * (size_t)d.n};
+  tv_pose_block(d.c, d.n, p, mask_all + d.mask_off, d.nblk, part + (size_t)d.part_off * 4, angle_all + d.angle_off);
 }
 
 // ---- the lockstep engine ---------------------------------------------------------------------------------------------------
@@ -474,7 +273,9 @@ int bt_replay(BtProb& s, const mpsfm_ransac_options& o, int64_t max_trials, cons
   }
 }
 
-template <class P> struct BtLeg;  // the reduction row length of a leg's local estimator
+// the reduction row length of a leg's local estimator; its host half is P::local_models (and P::enough, P::centre where the
+// estimator has a moments stage), the functions P::local calls
+template <class P> struct BtLeg;
 template <> struct BtLeg<RpProblem> { static constexpr int kRed = kGramK; };
 template <bool kH> struct BtLeg<TvProblem<kH>> { static constexpr int kRed = kGram9K; };
 template <> struct BtLeg<TvTranslation> { static constexpr int kRed = kTsumK; };
@@ -484,15 +285,6 @@ template <class P>
 size_t bt_leg_bytes(int32_t n, int64_t Bcap) {
   const size_t M = (size_t)P::kSlots * (size_t)Bcap;
   return M * (size_t)lo_blocks(n, 4 * kLoT) * 12 + M * (P::kModel * 8 + 12) + (size_t)Bcap * 4;
-}
-
-inline int64_t bt_max_trials(const mpsfm_ransac_options& o, int sample) {
-  return std::min<int64_t>(o.max_num_trials, lo_num_trials((int64_t)(o.min_inlier_ratio * 100000.0), 100000, o.confidence, o.dyn_num_trials_multiplier, sample));
-}
-template <class P>
-int64_t bt_batch_cap(const mpsfm_ransac_options& o) {
-  const int32_t B = o.batch_trials > 0 ? o.batch_trials : P::kDefaultBatch;
-  return std::max<int64_t>(1, std::min<int64_t>(B, bt_max_trials(o, P::kSample)));
 }
 
 // One leg type over the problems `pr` (ascending pair order) of a group, in lockstep: every step generates, scores and
@@ -505,8 +297,8 @@ int bt_leg(BtCtx& X, const mpsfm_ransac_options& o, const double* d_pts, std::ve
   const size_t np = pr.size();
   if (np == 0) return 0;
   CallScope& A = X.A;
-  const int64_t max_trials = bt_max_trials(o, P::kSample);
-  const int64_t Bcap = bt_batch_cap<P>(o);
+  const int64_t max_trials = lo_max_trials(o, P::kSample);
+  const int64_t Bcap = lo_batch_cap<P>(o);
   const int64_t Mcap = S * Bcap;
   int64_t parts = 0, reds = 0;
   int max_nbx = 0, max_npx = 0;
@@ -636,8 +428,11 @@ int bt_leg(BtCtx& X, const mpsfm_ransac_options& o, const double* d_pts, std::ve
       base_desc(d, who[j]);
       d.nblk = s.npx;
       d.part_off = s.red_off;
-      if (stage == 1 && R == kGram9K)
-        for (int k = 0; k < 4; ++k) d.centre[k] = s.mom[1 + k] / s.mom[0];
+      if constexpr (R == kGram9K)
+        if (stage == 1) {
+          const TvCentre c = P::centre(s.mom);
+          d.centre[0] = c.c1x; d.centre[1] = c.c1y; d.centre[2] = c.c2x; d.centre[3] = c.c2y;
+        }
     }
     const BtDesc* dd = nullptr;
     if (int rc = X.up(who.size(), &dd)) return rc;
@@ -669,12 +464,11 @@ int bt_leg(BtCtx& X, const mpsfm_ransac_options& o, const double* d_pts, std::ve
   auto lo_round = [&](const std::vector<size_t>& who) -> int {
     std::vector<size_t> cur = who, nxt;
     if constexpr (R == kGram9K) {  // F, H: moments first
-      constexpr bool kH = std::is_same<P, TvProblem<true>>::value;
       if (int rc = reduce(cur, 0)) return rc;
       for (size_t i : cur) {
         BtProb& s = pr[i];
         sum_rows(h_red.data() + (size_t)kMomK * s.red_off, s.npx, kMomK, s.mom);
-        if (!(s.mom[0] < (kH ? 4.0 : 8.0))) nxt.push_back(i);
+        if (P::enough(s.mom)) nxt.push_back(i);
       }
       cur.swap(nxt);
       nxt.clear();
@@ -685,28 +479,7 @@ int bt_leg(BtCtx& X, const mpsfm_ransac_options& o, const double* d_pts, std::ve
         BtProb& s = pr[i];
         double g[R];
         sum_rows(h_red.data() + (size_t)R * s.red_off, s.npx, R, g);
-        if constexpr (std::is_same<P, RpProblem>::value) {
-          if (g[0] < kRpSample) continue;
-          double G[9][9], V[9][9], ev[9];
-          for (int r = 0, k = 1; r < 9; ++r)
-            for (int c = r; c < 9; ++c, ++k) G[r][c] = G[c][r] = g[k];
-          sym_eig<9>(G, V, ev);  // ascending
-          if (!(ev[4] > kRpRankTol * kRpRankTol * ev[8])) continue;
-          double work[RP_WORK];
-          const RpW w{work, 1};
-          for (int k = 0; k < 4; ++k)
-            for (int e = 0; e < 9; ++e) w[RP_N + 9 * k + e] = V[e][3 - k];
-          s.nl = rp_models_from_nullspace(w, s.Lm);
-        } else if constexpr (std::is_same<P, TvTranslation>::value) {
-          if (g[0] < 1.0) continue;
-          s.Lm[0] = g[1] / g[0];
-          s.Lm[1] = g[2] / g[0];
-          s.nl = 1;
-        } else {
-          constexpr bool kH = std::is_same<P, TvProblem<true>>::value;
-          const bool ok = kH ? tv_homography_from_gram(s.mom, g, s.Lm) : tv_eight_point_from_gram(s.mom, g, s.Lm);
-          s.nl = ok ? 1 : 0;
-        }
+        s.nl = P::local_models(s.mom, g, s.Lm);
         if (s.nl > 0) nxt.push_back(i);
       }
       cur.swap(nxt);
@@ -1073,7 +846,7 @@ extern "C" int mpsfm_two_view_geometry_batch(int64_t num_pairs, const int64_t* p
   mpsfm_two_view_batch_report rep{};
   mpsfm_ransac_options oe = o->ransac;
   if (oe.batch_trials == 0) oe.batch_trials = kTvEBatch;
-  const int64_t BE = bt_batch_cap<RpProblem>(oe), BF = bt_batch_cap<TvProblem<false>>(o->ransac), BH = bt_batch_cap<TvProblem<true>>(o->ransac);
+  const int64_t BE = lo_batch_cap<RpProblem>(oe), BF = lo_batch_cap<TvProblem<false>>(o->ransac), BH = lo_batch_cap<TvProblem<true>>(o->ransac);
   for (int64_t g0 = 0; g0 < num_pairs;) {
     int64_t g1 = g0;
     if (pairs_per_group > 0) {

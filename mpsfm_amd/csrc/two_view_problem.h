@@ -37,52 +37,68 @@ constexpr int kTvEBatch = 256, kTvFBatch = 256, kTvHBatch = 256, kTvTBatch = 128
 
 using TvModel = LoModel<9>;
 
-__global__ __launch_bounds__(kSevenT) void k_tv_f7(uint64_t seed, int64_t t0, int32_t nb, int32_t n, RpPts p, double* __restrict__ models,
-                                                    int32_t* __restrict__ nmod) {
+// The bodies of the kernels and of their batched forms (two_view_batch.hip), as in rel_pose_problem.h: the trial, or the
+// number nblk of workgroups along the problem's observations, and the output pointers at the problem's rows are arguments.
+
+// trial t of k_tv_f7, by thread threadIdx.x of a workgroup of kSevenT
+__device__ __forceinline__ void tv_f7_trial(uint64_t seed, int64_t t, int32_t n, const RpPts& p, double* __restrict__ out, int32_t* __restrict__ nmod) {
   __shared__ double work[kSevenT * TVF_WORK];
   __shared__ int32_t sidx[kSevenT * kTvFSample];  // the sampler indexes its output at run time: LDS too (odd stride, no bank conflict)
-  const int32_t i = (int32_t)blockIdx.x * kSevenT + (int32_t)threadIdx.x;
-  if (i >= nb) return;
   int32_t* idx = sidx + kTvFSample * threadIdx.x;
-  lo_sample<kTvFSample>(seed, t0 + i, n, idx);
+  lo_sample<kTvFSample>(seed, t, n, idx);
   double u1[kTvFSample], v1[kTvFSample], u2[kTvFSample], v2[kTvFSample];
 #pragma unroll
   for (int k = 0; k < kTvFSample; ++k) { u1[k] = p.u1[idx[k]]; v1[k] = p.v1[idx[k]]; u2[k] = p.u2[idx[k]]; v2[k] = p.v2[idx[k]]; }
   const RpW w{work + threadIdx.x, kSevenT};
-  double* out = models + (size_t)i * 9 * kTvFMaxModels;
   const int nm = tv_seven_point(u1, v1, u2, v2, w, out);
   for (int k = 9 * nm; k < 9 * kTvFMaxModels; ++k) out[k] = 0.0;
-  nmod[i] = nm;
+  *nmod = nm;
 }
 
-__global__ __launch_bounds__(kFourT) void k_tv_h4(uint64_t seed, int64_t t0, int32_t nb, int32_t n, RpPts p, double* __restrict__ models,
-                                                   int32_t* __restrict__ nmod) {
-  __shared__ double work[kFourT * TVH_WORK];
-  const int32_t i = (int32_t)blockIdx.x * kFourT + (int32_t)threadIdx.x;
+__global__ __launch_bounds__(kSevenT) void k_tv_f7(uint64_t seed, int64_t t0, int32_t nb, int32_t n, RpPts p, double* __restrict__ models,
+                                                    int32_t* __restrict__ nmod) {
+  const int32_t i = (int32_t)blockIdx.x * kSevenT + (int32_t)threadIdx.x;
   if (i >= nb) return;
+  tv_f7_trial(seed, t0 + i, n, p, models + (size_t)i * 9 * kTvFMaxModels, nmod + i);
+}
+
+// trial t of k_tv_h4, by thread threadIdx.x of a workgroup of kFourT
+__device__ __forceinline__ void tv_h4_trial(uint64_t seed, int64_t t, int32_t n, const RpPts& p, double* __restrict__ out, int32_t* __restrict__ nmod) {
+  __shared__ double work[kFourT * TVH_WORK];
   int32_t idx[kTvHSample];
-  lo_sample<kTvHSample>(seed, t0 + i, n, idx);
+  lo_sample<kTvHSample>(seed, t, n, idx);
   double u1[kTvHSample], v1[kTvHSample], u2[kTvHSample], v2[kTvHSample];
 #pragma unroll
   for (int k = 0; k < kTvHSample; ++k) { u1[k] = p.u1[idx[k]]; v1[k] = p.v1[idx[k]]; u2[k] = p.u2[idx[k]]; v2[k] = p.v2[idx[k]]; }
   const RpW w{work + threadIdx.x, kFourT};
   double H[9];
   const bool ok = tv_four_point(u1, v1, u2, v2, w, H);
-  double* out = models + (size_t)i * 9;
 #pragma unroll
   for (int k = 0; k < 9; ++k) out[k] = ok ? H[k] : 0.0;
-  nmod[i] = ok ? 1 : 0;
+  *nmod = ok ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kFourT) void k_tv_h4(uint64_t seed, int64_t t0, int32_t nb, int32_t n, RpPts p, double* __restrict__ models,
+                                                   int32_t* __restrict__ nmod) {
+  const int32_t i = (int32_t)blockIdx.x * kFourT + (int32_t)threadIdx.x;
+  if (i >= nb) return;
+  tv_h4_trial(seed, t0 + i, n, p, models + (size_t)i * 9, nmod + i);
+}
+
+// trial t of k_tv_t1
+__device__ __forceinline__ void tv_t1_trial(uint64_t seed, int64_t t, int32_t n, const RpPts& p, double* __restrict__ out, int32_t* __restrict__ nmod) {
+  int32_t idx[1];
+  lo_sample<1>(seed, t, n, idx);
+  out[0] = p.u2[idx[0]] - p.u1[idx[0]];
+  out[1] = p.v2[idx[0]] - p.v1[idx[0]];
+  *nmod = 1;
 }
 
 __global__ __launch_bounds__(kLoT) void k_tv_t1(uint64_t seed, int64_t t0, int32_t nb, int32_t n, RpPts p, double* __restrict__ models,
                                                  int32_t* __restrict__ nmod) {
   const int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x;
   if (i >= nb) return;
-  int32_t idx[1];
-  lo_sample<1>(seed, t0 + i, n, idx);
-  models[2 * (size_t)i] = p.u2[idx[0]] - p.u1[idx[0]];
-  models[2 * (size_t)i + 1] = p.v2[idx[0]] - p.v1[idx[0]];
-  nmod[i] = 1;
+  tv_t1_trial(seed, t0 + i, n, p, models + 2 * (size_t)i, nmod + i);
 }
 
 template <bool kHomography>
@@ -92,26 +108,32 @@ __device__ __forceinline__ double tv_residual(const double* M, double u1, double
 }
 
 template <bool kHomography>
-__global__ __launch_bounds__(kLoT) void k_tv_moments(TvModel M, double thr2, int32_t n, RpPts p, double* __restrict__ part) {
+__device__ __forceinline__ void tv_moments_block(const double* M, double thr2, int32_t n, const RpPts& p, int32_t nblk, double* __restrict__ part) {
   double acc[kMomK] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += (int32_t)gridDim.x * kLoT) {
+  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
     const double u1 = p.u1[i], v1 = p.v1[i], u2 = p.u2[i], v2 = p.v2[i];
-    if (!(tv_residual<kHomography>(M.m, u1, v1, u2, v2) <= thr2)) continue;
+    if (!(tv_residual<kHomography>(M, u1, v1, u2, v2) <= thr2)) continue;
     acc[0] += 1.0; acc[1] += u1; acc[2] += v1; acc[3] += u2; acc[4] += v2;
   }
   block_reduce_rows<kMomK>(acc, part);
 }
 
+template <bool kHomography>
+__global__ __launch_bounds__(kLoT) void k_tv_moments(TvModel M, double thr2, int32_t n, RpPts p, double* __restrict__ part) {
+  tv_moments_block<kHomography>(M.m, thr2, n, p, (int32_t)gridDim.x, part);
+}
+
 struct TvCentre { double c1x, c1y, c2x, c2y; };
 
 template <bool kHomography>
-__global__ __launch_bounds__(kLoT) void k_tv_gram(TvModel M, double thr2, int32_t n, RpPts p, TvCentre c, double* __restrict__ part) {
+__device__ __forceinline__ void tv_gram_block(const double* M, double thr2, int32_t n, const RpPts& p, const TvCentre& c, int32_t nblk,
+                                              double* __restrict__ part) {
   double acc[kGram9K];
 #pragma unroll
   for (int k = 0; k < kGram9K; ++k) acc[k] = 0.0;
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += (int32_t)gridDim.x * kLoT) {
+  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
     const double u1 = p.u1[i], v1 = p.v1[i], u2 = p.u2[i], v2 = p.v2[i];
-    if (!(tv_residual<kHomography>(M.m, u1, v1, u2, v2) <= thr2)) continue;
+    if (!(tv_residual<kHomography>(M, u1, v1, u2, v2) <= thr2)) continue;
     const double x1 = u1 - c.c1x, y1 = v1 - c.c1y, x2 = u2 - c.c2x, y2 = v2 - c.c2y;
     if constexpr (kHomography) {
       double a[9], b[9];
@@ -134,15 +156,24 @@ __global__ __launch_bounds__(kLoT) void k_tv_gram(TvModel M, double thr2, int32_
   block_reduce_rows<kGram9K>(acc, part);
 }
 
-__global__ __launch_bounds__(kLoT) void k_tv_tsum(LoModel<2> M, double thr2, int32_t n, RpPts p, double* __restrict__ part) {
+template <bool kHomography>
+__global__ __launch_bounds__(kLoT) void k_tv_gram(TvModel M, double thr2, int32_t n, RpPts p, TvCentre c, double* __restrict__ part) {
+  tv_gram_block<kHomography>(M.m, thr2, n, p, c, (int32_t)gridDim.x, part);
+}
+
+__device__ __forceinline__ void tv_tsum_block(const double* t, double thr2, int32_t n, const RpPts& p, int32_t nblk, double* __restrict__ part) {
   double acc[kTsumK] = {0.0, 0.0, 0.0};
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += (int32_t)gridDim.x * kLoT) {
+  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
     const double dx = p.u2[i] - p.u1[i], dy = p.v2[i] - p.v1[i];
-    const double ex = dx - M.m[0], ey = dy - M.m[1];
+    const double ex = dx - t[0], ey = dy - t[1];
     if (!(ex * ex + ey * ey <= thr2)) continue;
     acc[0] += 1.0; acc[1] += dx; acc[2] += dy;
   }
   block_reduce_rows<kTsumK>(acc, part);
+}
+
+__global__ __launch_bounds__(kLoT) void k_tv_tsum(LoModel<2> M, double thr2, int32_t n, RpPts p, double* __restrict__ part) {
+  tv_tsum_block(M.m, thr2, n, p, (int32_t)gridDim.x, part);
 }
 
 struct TvCands {
@@ -155,10 +186,10 @@ struct TvCands {
 // CheckCheirality of every candidate on the chosen inliers (normalised points): per workgroup the number of inliers
 // triangulated in front of both cameras, and per (candidate, match) CalculateTriangulationAngle of that point with
 // projection centres 0 and -R^T t (-1 where the match is not chosen or fails the depth test)
-__global__ __launch_bounds__(kLoT) void k_tv_pose(TvCands c, int32_t n, RpPts p, const uint8_t* __restrict__ mask, int32_t* __restrict__ part,
-                                                   double* __restrict__ angle /* [4][n] */) {
+__device__ __forceinline__ void tv_pose_block(const TvCands& c, int32_t n, const RpPts& p, const uint8_t* __restrict__ mask, int32_t nblk,
+                                              int32_t* __restrict__ part, double* __restrict__ angle /* [4][n] */) {
   int cnt[4] = {0, 0, 0, 0};
-  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += (int32_t)gridDim.x * kLoT) {
+  for (int32_t i = (int32_t)blockIdx.x * kLoT + (int32_t)threadIdx.x; i < n; i += nblk * kLoT) {
     const bool on = mask[i] != 0;
     TriView a{}, b{};
     a.P[0] = 1.0; a.P[5] = 1.0; a.P[10] = 1.0;
@@ -183,6 +214,11 @@ __global__ __launch_bounds__(kLoT) void k_tv_pose(TvCands c, int32_t n, RpPts p,
     }
   }
   block_reduce_rows<4>(cnt, part);
+}
+
+__global__ __launch_bounds__(kLoT) void k_tv_pose(TvCands c, int32_t n, RpPts p, const uint8_t* __restrict__ mask, int32_t* __restrict__ part,
+                                                   double* __restrict__ angle) {
+  tv_pose_block(c, n, p, mask, (int32_t)gridDim.x, part, angle);
 }
 
 // ---- the problem descriptions of lo_ransac.h ---------------------------------------------------------------------------
@@ -211,6 +247,15 @@ struct TvProblem {
       hipLaunchKernelGGL(k_tv_f7, dim3((unsigned)((nb + kSevenT - 1) / kSevenT)), dim3(kSevenT), 0, st, seed, t0, nb, n, pts, models, nmod);
   }
 
+  // the host half of the local estimator, from the summed rows of k_tv_moments and k_tv_gram: whether the inliers are enough
+  // for the Gram stage, the centre that stage subtracts, and the model (RpProblem::local_models' signature)
+  static bool enough(const double mom[kMomK]) { return !(mom[0] < (kHomography ? 4.0 : 8.0)); }
+  static TvCentre centre(const double mom[kMomK]) { return {mom[1] / mom[0], mom[2] / mom[0], mom[3] / mom[0], mom[4] / mom[0]}; }
+  static int local_models(const double mom[kMomK], const double g[kGram9K], double* out) {
+    const bool ok = kHomography ? tv_homography_from_gram(mom, g, out) : tv_eight_point_from_gram(mom, g, out);
+    return ok ? 1 : 0;
+  }
+
   // the eight-point estimator / the normalised DLT on the inliers of Min: moments, then the centred Gram matrix
   int local(CallScope& A, const double* Min, double* out, int& nm) {
     nm = 0;
@@ -223,8 +268,8 @@ struct TvProblem {
     if (int rc = A.end()) return rc;
     double mom[kMomK];
     sum_rows(h_part.data(), npx, kMomK, mom);
-    if (mom[0] < (kHomography ? 4.0 : 8.0)) return 0;
-    const TvCentre c{mom[1] / mom[0], mom[2] / mom[0], mom[3] / mom[0], mom[4] / mom[0]};
+    if (!enough(mom)) return 0;
+    const TvCentre c = centre(mom);
     if (int rc = A.begin()) return rc;
     hipLaunchKernelGGL(k_tv_gram<kHomography>, dim3((unsigned)npx), dim3(kLoT), 0, A.st, m, thr2, n, pts, c, d_part);
     MPSFM_TRY(hipGetLastError());
@@ -232,8 +277,7 @@ struct TvProblem {
     if (int rc = A.end()) return rc;
     double g[kGram9K];
     sum_rows(h_part.data(), npx, kGram9K, g);
-    const bool ok = kHomography ? tv_homography_from_gram(mom, g, out) : tv_eight_point_from_gram(mom, g, out);
-    nm = ok ? 1 : 0;
+    nm = local_models(mom, g, out);
     return 0;
   }
 };
@@ -260,6 +304,14 @@ struct TvTranslation {
     hipLaunchKernelGGL(k_tv_t1, dim3((unsigned)((nb + kLoT - 1) / kLoT)), dim3(kLoT), 0, st, seed, t0, nb, n, pts, models, nmod);
   }
 
+  // the mean of the inliers from the summed k_tv_tsum row (RpProblem::local_models' signature)
+  static int local_models(const double* /* moments */, const double s[kTsumK], double* out) {
+    if (s[0] < 1.0) return 0;
+    out[0] = s[1] / s[0];
+    out[1] = s[2] / s[0];
+    return 1;
+  }
+
   int local(CallScope& A, const double* tin, double* out, int& nm) {
     nm = 0;
     LoModel<2> m{{tin[0], tin[1]}};
@@ -270,10 +322,7 @@ struct TvTranslation {
     if (int rc = A.end()) return rc;
     double s[kTsumK];
     sum_rows(h_part.data(), npx, kTsumK, s);
-    if (s[0] < 1.0) return 0;
-    out[0] = s[1] / s[0];
-    out[1] = s[2] / s[0];
-    nm = 1;
+    nm = local_models(nullptr, s, out);
     return 0;
   }
 };

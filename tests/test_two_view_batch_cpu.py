@@ -257,30 +257,89 @@ NEW_KERNELS = ("k_bt_five", "k_bt_f7", "k_bt_h4", "k_bt_t1", "k_bt_score", "k_bt
                "k_bt_tsum", "k_bt_mask", "k_bt_pose")
 
 
-def test_new_kernels_compile_for_gfx950_without_scratch():
+# (LDS bytes, occupancy in waves per SIMD) of every kernel of the four translation units that hold the LO-RANSAC kernels, the
+# copies a unit carries without launching them included, at the commit before the single-pair and the batched kernels shared
+# their bodies (the same compile at that commit).  <E>, <F>, <H>, <T>, <A>: RpProblem, TvProblem<false>, TvProblem<true> (and
+# the bool templates), TvTranslation, ApProblem.
+PARENT_LDS_OCCUPANCY = {
+    "two_view_batch.hip": {
+        "k_bt_egram": (1472, 4), "k_bt_f7": (46848, 1), "k_bt_five": (60416, 1), "k_bt_gram<F>": (1440, 4), "k_bt_gram<H>": (1440, 4),
+        "k_bt_h4": (45568, 1), "k_bt_mask<E>": (0, 8), "k_bt_mask<F>": (0, 8), "k_bt_mask<H>": (0, 8), "k_bt_moments<F>": (160, 8),
+        "k_bt_moments<H>": (160, 8), "k_bt_pose": (64, 3), "k_bt_score<E>": (1920, 1), "k_bt_score<F>": (1920, 1),
+        "k_bt_score<H>": (1920, 1), "k_bt_score<T>": (1024, 4), "k_bt_sum": (0, 8), "k_bt_t1": (0, 8), "k_bt_tsum": (96, 8),
+        "k_lo_score_sum": (0, 8), "k_rp_cheirality": (64, 4), "k_rp_five": (60416, 1), "k_rp_gram": (1472, 4), "k_tv_f7": (46848, 1),
+        "k_tv_h4": (45568, 1), "k_tv_pose": (64, 3), "k_tv_t1": (0, 8), "k_tv_tsum": (96, 8),
+    },
+    "two_view.hip": {
+        "k_lo_mask<E>": (0, 8), "k_lo_mask<F>": (0, 8), "k_lo_mask<H>": (0, 8), "k_lo_score<E>": (1920, 1), "k_lo_score<F>": (1920, 1),
+        "k_lo_score<H>": (1920, 1), "k_lo_score<T>": (1024, 4), "k_lo_score_sum": (0, 8), "k_rp_cheirality": (64, 4),
+        "k_rp_five": (60416, 1), "k_rp_gram": (1472, 4), "k_tv_f7": (46848, 1), "k_tv_gram<F>": (1440, 4), "k_tv_gram<H>": (1440, 4),
+        "k_tv_h4": (45568, 1), "k_tv_moments<F>": (160, 8), "k_tv_moments<H>": (160, 8), "k_tv_pose": (64, 3), "k_tv_t1": (0, 8),
+        "k_tv_tsum": (96, 8),
+    },
+    "rel_pose.hip": {
+        "k_lo_mask<E>": (0, 8), "k_lo_score<E>": (1920, 1), "k_lo_score_sum": (0, 8), "k_rp_cheirality": (64, 4), "k_rp_five": (60416, 1),
+        "k_rp_gram": (1472, 4),
+    },
+    "abs_pose.hip": {
+        "k_ap_p3p": (0, 3), "k_ap_pass<1>": (144, 8), "k_ap_pass<2>": (192, 8), "k_ap_pass<3>": (2496, 2), "k_ap_pass<4>": (1248, 4),
+        "k_ap_pass<5>": (96, 7), "k_lo_mask<A>": (0, 8), "k_lo_score<A>": (2304, 1), "k_lo_score_sum": (0, 8),
+    },
+}
+
+
+@pytest.fixture(scope="module")
+def resource_reports():
+    """{translation unit: (the compiler's output, {kernel: (VGPRs, SGPRs, LDS bytes, scratch bytes, occupancy)})}: every function
+    the resource-usage report lists, the four units compiled side by side"""
+    from mpsfm_amd import build
+
+    procs = {s: subprocess.Popen([build._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
+                                  os.path.join(build.CSRC, s), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
+                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for s in PARENT_LDS_OCCUPANCY}
+    reports = {}
+    for s, proc in procs.items():
+        out, _ = proc.communicate()
+        assert proc.returncode == 0, out
+        rows = {}
+        for name, body in re.findall(r"Function Name: (\S+)(.*?LDS Size \[bytes/block\]: \d+)", out, flags=re.S):
+            tag = name
+            m = re.search(r"\d(k_[a-z0-9_]+)(.*)", name)  # the mangled name: <length><name>E... or, for a template, <name>I<arguments>E...
+            if m:
+                tag, rest = m.groups()
+                if rest.startswith("I"):
+                    tag += ("<H>" if "Lb1" in rest else "<F>" if "Lb0" in rest else "<T>" if "TvTranslation" in rest else
+                            "<E>" if "RpProblem" in rest else "<A>" if "ApProblem" in rest else "<%s>" % rest[3:rest.index("E")])
+            assert tag not in rows, (tag, name)
+            rows[tag] = tuple(int(re.search(key + r": (\d+)", body).group(1)) for key in (
+                "VGPRs", "TotalSGPRs", r"LDS Size \[bytes/block\]", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]"))
+        reports[s] = (out, rows)
+    print("kernel: (VGPRs, SGPRs, LDS bytes, scratch bytes, occupancy)")
+    for s, (_, rows) in reports.items():
+        print(f" {s}")
+        for k, v in sorted(rows.items()):
+            print(f"  {k}: {v}")
+    return reports
+
+
+def test_new_kernels_compile_for_gfx950_without_scratch(resource_reports):
     from mpsfm_amd import build
 
     assert "two_view_batch.hip" in build.SOURCES and "two_view_problem.h" in build.HEADERS
-    src = os.path.join(build.CSRC, "two_view_batch.hip")
-    r = subprocess.run([build._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", src, "-o", os.devnull,
-                        "-Rpass-analysis=kernel-resource-usage"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    found = {}
-    for name, body, lds in re.findall(r"Function Name: (\S+)(.*?)LDS Size \[bytes/block\]: (\d+)", r.stdout, flags=re.S):
-        for k in NEW_KERNELS:
-            if k + "E" in name or k + "I" in name:  # the mangled name: <length><name>E... or, for a template, <name>I...
-                tag = k + ("<H>" if "Lb1" in name else "<F>" if "Lb0" in name else "<T>" if "TvTranslation" in name else
-                           "<E>" if "RpProblem" in name else "")
-                found[tag] = (int(re.search(r"VGPRs: (\d+)", body).group(1)), int(lds),
-                              int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", body).group(1)))
-    print("kernel: (VGPRs, LDS bytes, scratch bytes)")
-    for k, v in sorted(found.items()):
-        print(f"  {k}: {v}")
+    # every kernel of the four units keeps the LDS bytes and the occupancy it had before the bodies were shared, and has no
+    # scratch: the copy of k_rp_five that two_view_batch.hip carries had 768 bytes of it then, and k_ap_p3p 432 (its list of real
+    # roots and its models were indexed by run-time counts)
+    for s, (out, rows) in resource_reports.items():
+        assert {k: (lds, occ) for k, (_, _, lds, _, occ) in rows.items()} == PARENT_LDS_OCCUPANCY[s], s
+        assert all(scratch == 0 for _, _, _, scratch, _ in rows.values()), (s, rows)
+    out, rows = resource_reports["two_view_batch.hip"]
+    found = {k: (vgprs, lds, scratch) for k, (vgprs, _, lds, scratch, _) in rows.items() if k.startswith("k_bt_")}
     for k in NEW_KERNELS:
         hits = [v for name, v in found.items() if name == k or name.startswith(k + "<")]
-        assert hits, (k, r.stdout)
+        assert hits, (k, out)
         assert all(scratch == 0 for _, _, scratch in hits), (k, hits)
     assert {t for t in found if t.startswith("k_bt_score")} == {"k_bt_score<E>", "k_bt_score<F>", "k_bt_score<H>", "k_bt_score<T>"}
     assert {t for t in found if t.startswith("k_bt_mask")} == {"k_bt_mask<E>", "k_bt_mask<F>", "k_bt_mask<H>"}
     for k in ("k_bt_five", "k_bt_f7", "k_bt_h4"):
         assert found[k][1] <= 64 * 1024  # the per-thread LDS slices fit a workgroup's 64 KiB
+
