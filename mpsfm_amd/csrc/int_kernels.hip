@@ -6,6 +6,7 @@
 // never materialised as CSR; each pixel keeps its diagonal, its right and its lower coupling.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -19,7 +20,7 @@ namespace mpsfm {
 constexpr int kIT = 256;  // threads per workgroup
 // Pixels per thread in the CG kernels, chosen per solve: one image (112 k pixels) is latency-bound and fastest
 // with 1; a batch of full-size maps is bandwidth-bound and 23 % faster with 2 (more bytes in flight per lane).
-constexpr size_t kPixSwitch = 400000;  // total pixels of the batch from which 2 pixels per thread are used
+constexpr size_t kPixSwitch = 400000;  // total pixels of the batch from which 2 pixels per thread are used (MPSFM_INT_PIX overrides)
 
 // A batch of B images of one size: every per-pixel array is [B][N] (w4: [B][4][N]); part is [B][G][8],
 // state [B][8].  Kernels are launched on a (G, B) grid; blockIdx.y picks the image.
@@ -579,7 +580,9 @@ static void int_launch_prepare(const mpsfm_int_problem* P0, IntBatch& U, hipStre
 // 16 iterations.  its[b] / conv[b] are written for the active images.
 static int int_run_cg(IntBatch& U, hipStream_t st, double rtol, int max_iter, int* its, bool* conv) {
   IntDev& D = U.D;
-  const int pix = ((size_t)U.B * U.N >= kPixSwitch) ? 2 : 1;
+  // MPSFM_INT_PIX=1/2 forces the pixels per thread (tests; read per call, both callers); anything else keeps the rule
+  const int force_pix = [] { const char* e = std::getenv("MPSFM_INT_PIX"); const int v = e ? std::atoi(e) : 0; return (v == 1 || v == 2) ? v : 0; }();
+  const int pix = force_pix ? force_pix : (((size_t)U.B * U.N >= kPixSwitch) ? 2 : 1);
   const int Gc = (int)((U.N + (size_t)kIT * pix - 1) / ((size_t)kIT * pix));  // workgroups (= partial rows) of the CG kernels
   const dim3 grid(Gc, U.B);
   MPSFM_TRY(hipMemsetAsync(D.state, 0, sizeof(double) * 8 * U.B, st));
