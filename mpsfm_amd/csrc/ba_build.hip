@@ -218,8 +218,8 @@ static int alloc_work_buffers(mpsfm_ba_handle* h, const BuildOptions& opt) {
   for (double** p : {&h->d_q, &h->d_q2, &h->d_q0}) if ((rc = own.alloc(p, ncs * 4))) return rc;
   for (double** p : {&h->d_t, &h->d_t2, &h->d_t0}) if ((rc = own.alloc(p, ncs * 3))) return rc;
   for (double** p : {&h->d_pts, &h->d_pts2, &h->d_pts0, &h->d_ps, &h->d_diagV}) if ((rc = own.alloc(p, nps * 3))) return rc;
-  // every chunk dense, no long track (fused_prologue's condition in solve_impl): the track sweep hands the landmark factors on
-  if (h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks) if ((rc = own.alloc(&h->d_pt_fac, nps * 9))) return rc;
+  // every chunk dense, no long track (fused_prologue's condition in solve_form): the track sweep hands the landmark factors on
+  if (all_dense(h)) if ((rc = own.alloc(&h->d_pt_fac, nps * 9))) return rc;
   if ((rc = own.alloc(&h->d_cs, ncs * 6))) return rc;
   if ((rc = own.alloc(&h->d_camtab, ncs * kCamRec))) return rc;
   if ((rc = own.alloc(&h->d_camtab2, ncs * kCamRec))) return rc;
@@ -256,7 +256,7 @@ static int alloc_work_buffers(mpsfm_ba_handle* h, const BuildOptions& opt) {
   }
   // Small problems (local bundle adjustment): the whole trust-region loop in one cooperative launch, one workgroup per chunk
   h->local_ok = false;
-  if (opt.local_lm && !sharded(h) && h->nlong == 0 && h->nchunks > 0 && h->n_dense == h->nchunks && h->ncv >= 1 && h->ncv <= kLocalCams &&
+  if (opt.local_lm && !sharded(h) && all_dense(h) && h->ncv >= 1 && h->ncv <= kLocalCams &&
       h->n_user == 6 * h->ncv && h->nchunks <= local_lm_max_chunks(h->device)) {
     h->local_log_cap = std::max(h->opt.max_num_iterations, 0) + 2;
     if ((rc = own.alloc(&h->d_local_acc, (size_t)2 * kLocalAccDoubles))) return rc;
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256) void k_dest_cols(const RedDest* __restrict__ d
 }
 // every chunk dense, no long track, one rank, a level plan (the solve adds the conditions that can change from solve to solve)
 static int build_direct_tables(mpsfm_ba_handle* h) {
-  if (sharded(h) || h->nlong != 0 || h->n_dense <= 0 || h->n_dense != h->nchunks || !h->lp.valid || !h->lp.damp_in_launch0 || h->n <= 0 || h->n_red_dests <= 0)
+  if (sharded(h) || !all_dense(h) || !h->lp.valid || !h->lp.damp_in_launch0 || h->n <= 0 || h->n_red_dests <= 0)
     return 0;
   const CholPlan& PL = h->plan;
   std::vector<int32_t> col((size_t)std::max(h->ncv, 1), 0);

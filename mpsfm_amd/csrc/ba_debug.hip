@@ -1,5 +1,6 @@
 // Test hooks, timing probes and table dumps of libmpsfm_hip: every mpsfm_debug_* entry point and the single-phase runs of the
-// bundle adjustment (one sweep, one dense solve, the reduced system).  Nothing here is on the path of a solve.
+// bundle adjustment (one sweep, one dense solve, the reduced system).  Nothing here is on the path of a solve; the single-phase runs
+// enqueue the solve's own pieces (ba_handle.h) under a SolveForm whose fields they override, and read no switch themselves.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -192,9 +193,7 @@ int mpsfm_debug_pt_handoff(mpsfm_ba_handle* h) { return h && h->d_pt_fac != null
 
 // 1: a solve on this handle, under the switches set now, takes the direct form of the front (the slab reduction adds into the tiles of
 // the dense solve, no k_assemble), 0: it launches k_assemble
-int mpsfm_debug_direct_front(mpsfm_ba_handle* h) {
-  return h && direct_front(h) ? 1 : 0;
-}
+int mpsfm_debug_direct_front(mpsfm_ba_handle* h) { return h && solve_form(h).direct ? 1 : 0; }
 
 // Test hook (tests/test_gpu_direct_assemble.py): one track sweep and slab reduction at the current state and `radius` in both forms.
 // A_parent: the tiles k_assemble leaves behind Sblk; A_direct: the tiles the direct slab reduction leaves, after the sweep's own zero
@@ -205,10 +204,11 @@ int mpsfm_debug_direct_front(mpsfm_ba_handle* h) {
 // of y that the direct form did not leave exactly zero.
 int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_parent, double* A_direct, double* damp, uint8_t* live, int64_t info[4]) {
   if (!h || !A_parent || !A_direct || !damp || !live || !info) return fail(MPSFM_EINVAL, "handle or output is NULL");
-  if (!mpsfm_debug_direct_front(h)) return fail(MPSFM_EUNSUPPORTED, "the handle does not take the direct form of the front");
+  SolveForm f = solve_form(h);
+  if (!f.direct) return fail(MPSFM_EUNSUPPORTED, "the handle does not take the direct form of the front");
   MPSFM_TRY(hipSetDevice(h->device));
-  read_sweep_order_switch(h);
-  if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
+  f.pt_handoff = f.fused_prologue = f.direct = false;  // the parent's form first; neither sweep starts writing pt_fac here
+  if (!h->scales_ready) if (int rc = prepare_scales(h, f)) return rc;
   hipStream_t s = h->stream;
   const int nt = h->nt;
   const size_t ntiles = (size_t)(nt + 1) * (size_t)(nt + 2) / 2;
@@ -218,14 +218,13 @@ int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_par
   for (int32_t id : h->plan.asm_tiles) { live[(size_t)id] = 1; std::fill(img.begin() + (size_t)id * 1024, img.begin() + ((size_t)id + 1) * 1024, nan); }
   // the parent's form: zeroed reduced buffer, sweep, reduction into Sblk, k_assemble
   MPSFM_TRY(hipMemcpyAsync(h->d_A, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice, s));
-  if (int rc = run_track_sweep(h, radius)) return rc;
+  if (int rc = run_track_sweep(h, f, radius, nullptr, /*in_loop=*/false)) return rc;
   run_assemble(h, radius);
   MPSFM_TRY(hipMemcpyAsync(A_parent, h->d_A, sizeof(double) * img.size(), hipMemcpyDeviceToHost, s));
   MPSFM_TRY(hipStreamSynchronize(s));
-  // the direct form: the sweep zeroes, the reduction adds into the tiles
-  SweepArgs a = sweep_args(h, radius);
-  a.adopt_on = 1; a.adopt_nc = h->nc;  // (no control block: nothing is adopted, the zero fill runs)
-  direct_zero_args(h, a);
+  // the direct form: the sweep zeroes, the reduction adds into the tiles — the front solve_impl enqueues, through run_track_sweep
+  SweepArgs a{};
+  direct_zero_args(h, a);  // (only to know what the zero fill covers)
   MPSFM_TRY(hipMemcpyAsync(h->d_A, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice, s));
   for (int k = 0; k < 2; ++k) MPSFM_TRY(hipMemsetAsync(a.zero_p[k], 0xff, sizeof(double) * (size_t)a.zero_n[k], s));
   // the inverse accumulators: the ones the roles write as NaNs, the others are zero since the handle's creation and stay so
@@ -238,9 +237,8 @@ int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_par
         std::fill(pimg.begin() + id * 1024, pimg.begin() + (id + 1) * 1024, nan);
       }
   MPSFM_TRY(hipMemcpyAsync(a.zero_P, pimg.data(), sizeof(double) * npinv, hipMemcpyHostToDevice, s));
-  launch_track_sweep_dense(a, h->n_dense, s);
-  const DirectAsm da = direct_asm(h);
-  launch_reduce_slabs(h->d_red_dests, h->n_red_dests, h->d_red_srcs, h->d_slab, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, nullptr, s, &da);
+  f.fused_prologue = f.direct = true;
+  if (int rc = run_track_sweep(h, f, radius, nullptr, /*in_loop=*/true)) return rc;  // (no control block: nothing is adopted, the zero fill runs)
   std::vector<double> pinv(npinv), y((size_t)std::max(h->n_user, 1)), dcol((size_t)nt * 32);
   MPSFM_TRY(hipMemcpyAsync(A_direct, h->d_A, sizeof(double) * img.size(), hipMemcpyDeviceToHost, s));
   MPSFM_TRY(hipMemcpyAsync(pinv.data(), a.zero_P, sizeof(double) * pinv.size(), hipMemcpyDeviceToHost, s));
@@ -248,7 +246,6 @@ int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_par
   MPSFM_TRY(hipMemcpyAsync(dcol.data(), h->d_diag_col, sizeof(double) * dcol.size(), hipMemcpyDeviceToHost, s));
   MPSFM_TRY(hipStreamSynchronize(s));
   MPSFM_TRY(hipGetLastError());
-  h->last_radius = radius;
   const int32_t* slot_of_col = h->plan.slot_of_col.empty() ? nullptr : h->plan.slot_of_col.data();
   for (int g = 0; g < nt * 32; ++g)
     damp[g] = vec_index(slot_of_col, g, h->n) < 0 ? -1.0 : std::min(std::max(dcol[(size_t)g], h->opt.min_lm_diagonal), h->opt.max_lm_diagonal) / radius;
@@ -262,18 +259,13 @@ int mpsfm_debug_direct_assemble(mpsfm_ba_handle* h, double radius, double* A_par
 int mpsfm_ba_sweep_once(mpsfm_ba_handle* h, double radius, float* elapsed_ms) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   MPSFM_TRY(hipSetDevice(h->device));
-  read_sweep_order_switch(h);
-  if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
+  SolveForm f = solve_form(h);
+  f.pt_handoff = f.fused_prologue = f.direct = false;  // the plain sweep into the zeroed reduced buffer; pt_fac is not written
+  if (!h->scales_ready) if (int rc = prepare_scales(h, f)) return rc;
   MPSFM_TRY(hipMemsetAsync(h->d_red, 0, sizeof(double) * (size_t)h->red_count, h->stream));
-  SweepArgs a = sweep_args(h, radius);
-  // the three parts of the sweep between events: dense chunks | reduction of their slabs | general chunks and long tracks
+  // the three launches of the solve's sweep between events (mpsfm_ba_sweep_parts): ev0 and ev3 bracket them alone
   MPSFM_TRY(hipEventRecord(h->ev[0], h->stream));
-  launch_track_sweep_dense(a, h->n_dense, h->stream);
-  MPSFM_TRY(hipEventRecord(h->ev[1], h->stream));
-  launch_reduce_slabs(h->d_red_dests, h->n_red_dests, h->d_red_srcs, h->d_slab, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, nullptr, h->stream);
-  MPSFM_TRY(hipEventRecord(h->ev[2], h->stream));
-  a.chunk0 = h->n_dense;
-  launch_track_sweep(a, h->nchunks - h->n_dense, false, h->stream);
+  if (int rc = launch_sweeps(h, sweep_args(h, f, radius, nullptr), false, h->ev + 1)) return rc;
   MPSFM_TRY(hipEventRecord(h->ev[3], h->stream));
   if (h->nchunks + h->nlong > 0) launch_reduce_cols(h->d_part, h->nchunks + h->nlong, 4, 3, 1u << 2, h->d_redsc, h->stream);
   MPSFM_TRY(hipStreamSynchronize(h->stream));
@@ -287,7 +279,7 @@ int mpsfm_ba_sweep_once(mpsfm_ba_handle* h, double radius, float* elapsed_ms) {
 
 // Test hook (tests/test_gpu_update_once.py): ONE update sweep at the handle's current state, `radius` and a GIVEN camera step, in the
 // form asked for.  The track sweep runs first through run_track_sweep (it leaves g_c for the gradient maximum and, with the hand-off,
-// F and g_p of every landmark); then the camera update and launch_update_sweep as solve_impl's enqueue_back orders them, without a
+// F and g_p of every landmark); then enqueue_update, the piece solve_impl's enqueue_back runs (camera update, update sweep), without a
 // control block; then the reduction of part2 in the order of the one-rank loop (reduce_cols_block's, which k_lm_reduce_decide repeats).
 // yc [n = reduced_dim]: the camera step in scaled coordinates, caller's camera order (what mpsfm_ba_get_dense_solution returns).
 // form: bit 0 hand-off of the landmark factors (needs the handle's buffer), bit 1 fused camera update (needs every chunk dense and no
@@ -308,31 +300,21 @@ int mpsfm_debug_update_once(mpsfm_ba_handle* h, double radius, const double* yc,
   for (int i = 0; i < n; ++i)
     if (!std::isfinite(yc[i])) return fail(MPSFM_EINVAL, "yc is not finite");
   if (sharded(h)) return fail(MPSFM_EUNSUPPORTED, "update_once: one rank only");
-  const bool handoff = (form & 1) != 0, fused_cam = (form & 2) != 0;
-  const bool all_dense = h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks;
-  if (handoff && !h->d_pt_fac) return fail(MPSFM_EUNSUPPORTED, "the handle has no hand-off buffer (a general chunk or a long track)");
-  if (fused_cam && !all_dense) return fail(MPSFM_EUNSUPPORTED, "the fused camera update needs every chunk dense and no long track");
+  SolveForm f = solve_form(h);
+  f.pt_handoff = (form & 1) != 0; f.fused_cam = (form & 2) != 0;  // the caller's form, whatever the switches say
+  if (f.pt_handoff && !h->d_pt_fac) return fail(MPSFM_EUNSUPPORTED, "the handle has no hand-off buffer (a general chunk or a long track)");
+  if (f.fused_cam && !all_dense(h)) return fail(MPSFM_EUNSUPPORTED, "the fused camera update needs every chunk dense and no long track");
   MPSFM_TRY(hipSetDevice(h->device));
-  read_sweep_order_switch(h);
-  if (!h->scales_ready) if (int rc = prepare_scales(h)) return rc;
+  if (!h->scales_ready) if (int rc = prepare_scales(h, f)) return rc;
   hipStream_t s = h->stream;
-  if (int rc = run_track_sweep(h, radius, nullptr, false, false, handoff)) return rc;
+  if (int rc = run_track_sweep(h, f, radius, nullptr, /*in_loop=*/false)) return rc;
   std::vector<double> ys((size_t)std::max(h->n_user, 1), 0.0);
   for (int i = 0; i < n; ++i) ys[(size_t)(6 * h->nat_slot[(size_t)(i / 6)] + i % 6)] = yc[i];
   MPSFM_TRY(hipMemcpyAsync(h->d_yc, ys.data(), sizeof(double) * ys.size(), hipMemcpyHostToDevice, s));
   if (h->np > 0) MPSFM_TRY(hipMemcpyAsync(h->d_pts2, h->d_pts, sizeof(double) * 3 * h->np, hipMemcpyDeviceToDevice, s));  // (as solve_impl: landmarks outside every chunk)
   if (rows > 0) MPSFM_TRY(hipMemsetAsync(h->d_part2, 0xff, sizeof(double) * 8 * (size_t)rows, s));  // NaN: a row no workgroup writes shows
   MPSFM_TRY(hipMemsetAsync(h->d_scal, 0xff, sizeof(double) * U_COUNT, s));
-  CamUpdArgs cu{1, h->nc, h->d_cam_slot, h->d_cam_of_slot, h->d_q, h->d_t, h->d_cs, h->d_gc, h->d_intr, h->d_intr_idx,
-                h->d_q2, h->d_t2, h->d_camtab2, h->d_scal, h->d_fail};
-  if (!fused_cam)
-    launch_cam_update(h->nc, h->d_cam_slot, h->d_q, h->d_t, h->d_cs, h->d_yc, h->d_gc, h->d_q2, h->d_t2, h->d_scal, s, h->d_intr, h->d_intr_idx,
-                      h->d_camtab2, h->d_fail, nullptr);
-  {
-    SweepArgs a = sweep_args(h, radius, nullptr);
-    if (handoff) a.pt_fac = h->d_pt_fac;
-    launch_update_sweep(a, h->nchunks, s, fused_cam ? &cu : nullptr);
-  }
+  enqueue_update(h, f, radius, nullptr);
   if (rows > 0) launch_reduce_cols(h->d_part2, rows, 8, 5, 0u, h->d_scal, s);
   std::vector<double> sorted((size_t)h->np * 3), sorted_ps((size_t)h->np * 3), sc((size_t)U_COUNT);
   if (h->np > 0) MPSFM_TRY(hipMemcpyAsync(sorted.data(), h->d_pts2, sizeof(double) * 3 * (size_t)h->np, hipMemcpyDeviceToHost, s));
@@ -549,9 +531,10 @@ int mpsfm_debug_local_skew(int32_t chunk, int32_t phase_mask, int64_t ticks) {
 int mpsfm_ba_dense_solve_once(mpsfm_ba_handle* h, float* elapsed_ms) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   MPSFM_TRY(hipSetDevice(h->device));
-  h->ov.entry_list = chol_entry_list();
+  SolveForm f = solve_form(h);
+  f.direct = false;  // the system is what the last sweep left in the reduced buffer: k_assemble runs, whatever form a solve would take
   MPSFM_TRY(hipEventRecord(h->ev[0], h->stream));
-  if (int rc = run_dense(h, h->last_radius)) return rc;
+  if (int rc = run_dense(h, f, h->last_radius, nullptr)) return rc;
   MPSFM_TRY(hipEventRecord(h->ev[1], h->stream));
   MPSFM_TRY(hipMemsetAsync(h->d_fail, 0, sizeof(int), h->stream));  // no k_cam_update follows here to re-arm the flag
   MPSFM_TRY(hipStreamSynchronize(h->stream));
@@ -570,7 +553,6 @@ int mpsfm_debug_dense_solve_given(mpsfm_ba_handle* h, const double* S, const dou
   if (!h || !S || !rhs || !failed) return fail(MPSFM_EINVAL, "handle, S, rhs or failed is NULL");
   if (n != h->n_user || h->n <= 0) return fail(MPSFM_EINVAL, "n does not match the reduced dimension");
   MPSFM_TRY(hipSetDevice(h->device));
-  h->ov.entry_list = chol_entry_list();
   run_assemble(h, h->last_radius);
   const int nt = h->nt, N = nt * 32;
   std::vector<int32_t> cam_of_slot((size_t)std::max(h->ncv, 1), -1);
@@ -593,6 +575,7 @@ int mpsfm_debug_dense_solve_given(mpsfm_ba_handle* h, const double* S, const dou
         }
     }
   MPSFM_TRY(hipMemcpyAsync(h->d_A, A.data(), sizeof(double) * A.size(), hipMemcpyHostToDevice, h->stream));
+  h->ov.entry_list = solve_form(h).entry_list;
   launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, h->stream, &h->ov, &h->lp, nullptr);
   int flag = 0;
   MPSFM_TRY(hipMemcpyAsync(&flag, h->d_fail, sizeof(int), hipMemcpyDeviceToHost, h->stream));

@@ -40,7 +40,6 @@ struct mpsfm_ba_handle {
   int32_t* d_red_srcs = nullptr;
   int32_t* d_sweep_order = nullptr;        // [n_dense] the chunk the b-th workgroup of k_track_sweep_dense takes: heaviest first (SweepArgs::order)
   int64_t slab_units = 0;                  // 18-double units of d_slab
-  bool sweep_order_on = true;              // MPSFM_SWEEP_ORDER, read per solve (read_sweep_order_switch): false: sweep_args leaves the table out
   mpsfm::RedDestCols* d_red_cols = nullptr;  // direct form of the slab reduction (DirectAsm): where every destination part lands; NULL: the
                                            // handle has a general chunk, a long track, several ranks or no level plan and keeps k_assemble
   double* d_diag_col = nullptr;            // [32 nt] diag U by system column, for the damping in the first level launch
@@ -93,6 +92,8 @@ struct mpsfm_ba_handle {
 namespace mpsfm {
 
 inline bool sharded(const mpsfm_ba_handle* h) { return h->opt.allreduce != nullptr || h->comm != nullptr; }
+// every chunk dense, no long track: the dense sweep can adopt and zero, its landmark factors can be handed on, one workgroup per chunk
+inline bool all_dense(const mpsfm_ba_handle* h) { return h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks; }
 
 // ---- ba_build.hip: handle creation
 // What the phases of the table build produce.
@@ -130,26 +131,42 @@ void comm_destroy(void* comm);
 int allreduce_host(mpsfm_ba_handle* h, double* buf, int64_t count);
 int allreduce_dev(mpsfm_ba_handle* h, double* buf, int64_t count);
 
-// ---- ba_solver.hip: the pieces of an iteration the probes of ba_debug.hip run on their own
-SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);
+// ---- ba_solver.hip: the form of a solve, and the pieces of an iteration that the solve and the probes of ba_debug.hip both enqueue
+// What one solve does where the code has a choice: the eight run-time switches combined with the handle's structure, decided in
+// solve_form and nowhere else, per solve and per probe call (never kept: tests flip the switches between solves on one handle).
+// A probe states the form it wants by overriding fields of the form it read.
+struct SolveForm {
+  bool sweep_order;     // the dense sweep takes its chunks heaviest first (SweepArgs::order); MPSFM_SWEEP_ORDER=0: in table order
+  bool entry_list;      // MPSFM_CHOL_ENTRY=list: the level launches walk item -> source list -> operands instead of launch records
+  bool pt_handoff;      // the track sweep hands the landmark factors to the update sweep (d_pt_fac); MPSFM_PT_HANDOFF=0: recomputed
+  bool fused_prologue;  // all_dense: the dense sweep adopts an accepted candidate and zeroes the reduced buffer itself (sharded runs
+                        // too: the exchange comes behind the slab reduction); MPSFM_FUSE_PROLOGUE=0: k_lm_prologue
+  bool fused_cam;       // ... and the update sweep forms the candidate cameras itself (CamUpdArgs); MPSFM_FUSE_CAM=0: k_cam_update
+  bool direct;          // ... and, one rank, level-scheduled with inverse accumulators: the slab reduction adds straight into the tiles
+                        // of the dense solve, whose first level launch damps (DirectAsm); MPSFM_ASSEMBLE=launch: k_assemble
+  bool speculate;       // the host enqueues ahead of an iteration's decision; MPSFM_LM_SPECULATE=0: it waits for every decision
+  int force_split;      // MPSFM_LM_SPLIT=0/1: the whole next iteration / only its front half ahead; -1: by the front's measured length
+  bool can_split;       // the front half alone may go ahead at all: speculate, one rank, fused_prologue
+};
+SolveForm solve_form(const mpsfm_ba_handle* h);
+SweepArgs sweep_args(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl);
 // Jacobi column scales from the Jacobian at the current state (Ceres: iteration 0 only)
-int prepare_scales(mpsfm_ba_handle* h);
-// one track sweep at the current state: fills the reduced buffer and its scalar tail (inside the solve loop the prologue kernel
-// has zeroed the buffer; single-rank runs reduce the partials with the decision)
-int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool in_loop = false, bool adopt = false, bool handoff = false,
-                    bool direct = false);
-void run_assemble(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);  // the first launch of run_dense (h->n > 0)
-// direct: the track sweep ran with direct_front() — A holds the undamped system, no k_assemble, the first level launch damps
-int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr, bool direct = false);
-// May this solve take the direct form of the front (DirectAsm in common.h)?  The handle's tables allow it, the solve is level-scheduled
-// with inverse accumulators, and MPSFM_ASSEMBLE=launch (read per solve) does not force k_assemble.
-bool direct_front(mpsfm_ba_handle* h);
-DirectAsm direct_asm(const mpsfm_ba_handle* h);
+int prepare_scales(mpsfm_ba_handle* h, const SolveForm& f);
+void unit_camtab(mpsfm_ba_handle* h);  // unit camera scales and the camera table at the current state
+// the full track sweep in its three launches: dense chunks | reduction of their slabs | general chunks and long tracks, all adding
+// into the zeroed reduced buffer (direct: into the tiles of the dense solve); marks (may be NULL): two events recorded between them
+int launch_sweeps(mpsfm_ba_handle* h, SweepArgs a, bool direct, hipEvent_t* marks = nullptr);
+// one track sweep at the current state: fills the reduced buffer and its scalar tail.  in_loop: as the front of an iteration, where
+// the prologue (kernel or f.fused_prologue) zeroes the buffer and single-rank runs reduce the partials with the decision
+int run_track_sweep(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl, bool in_loop);
+void run_assemble(mpsfm_ba_handle* h, double radius, const LmCtl* ctl = nullptr);  // the first launch of run_dense (h->n > 0, not direct)
+// f.direct: the track sweep ran in the direct form, A holds the undamped system: no k_assemble, the first level launch damps
+int run_dense(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl);
+// the candidate of a camera step in d_yc: k_cam_update unless f.fused_cam, then the update sweep
+void enqueue_update(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl);
 // the zero fill of the direct form, dealt over the dense sweep's workgroups (SweepArgs::zero_*): camera vectors, y, diag U by column,
 // the inverse accumulators the roles write and the live tiles of A
 void direct_zero_args(mpsfm_ba_handle* h, SweepArgs& a);
-void read_sweep_order_switch(mpsfm_ba_handle* h);  // MPSFM_SWEEP_ORDER into h->sweep_order_on
-bool chol_entry_list();  // MPSFM_CHOL_ENTRY=list, read per solve into DenseOverlap::entry_list
 
 // the single-launch solver's skew hook (mpsfm_debug_local_skew): process-wide like g_dbg_flags, read when a solve is launched
 struct LocalSkew { int32_t chunk = 0, mask = 0; int64_t ticks = 0; };

@@ -1,9 +1,10 @@
 // The solve of libmpsfm_hip's bundle adjustment: the Levenberg-Marquardt control loop (Ceres 2.1 TrustRegionMinimizer semantics
 // with the default pyceres.SolverOptions() that reference mpsfm/sfm/mapper/bundle_adjustment.py:285-293 uses), as a chain of
 // launches or, for small problems, as one cooperative launch (local_lm.hip), and the core C ABI of include/mpsfm_hip.h: create,
-// solve, state and cost.  All arithmetic on problem data runs in the HIP kernels behind ba_launch.h; this file orders launches
-// and reads the accept/reject decisions from a handful of scalars.  Handle creation: ba_build.hip; sums over ranks: ba_comm.hip;
-// probes: ba_debug.hip.
+// solve, state and cost.  All arithmetic on problem data runs in the HIP kernels behind ba_launch.h; this file decides the form of
+// a solve once (solve_form: the only reader of the run-time switches), orders launches and reads the accept/reject decisions from a
+// handful of scalars.  Handle creation: ba_build.hip; sums over ranks: ba_comm.hip; probes: ba_debug.hip, which enqueue the pieces
+// of an iteration defined here with fields of the form overridden.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -17,7 +18,27 @@ namespace mpsfm {
 
 LocalSkew g_local_skew;
 
-SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
+// Every run-time switch of a solve is read here, per solve and per probe call, and combined with what the handle can do.
+SolveForm solve_form(const mpsfm_ba_handle* h) {
+  auto on = [](const char* name, int unset) { const char* e = std::getenv(name); return e ? (std::atoi(e) != 0 ? 1 : 0) : unset; };
+  auto is = [](const char* name, const char* value) { const char* e = std::getenv(name); return e && std::strcmp(e, value) == 0; };
+  SolveForm f{};
+  f.sweep_order = on("MPSFM_SWEEP_ORDER", 1);
+  f.entry_list = is("MPSFM_CHOL_ENTRY", "list");
+  f.pt_handoff = on("MPSFM_PT_HANDOFF", 1) && h->d_pt_fac != nullptr;
+  f.fused_prologue = on("MPSFM_FUSE_PROLOGUE", 1) && all_dense(h);
+  f.fused_cam = on("MPSFM_FUSE_CAM", 1) && f.fused_prologue;
+  // (the zero fill of the direct form rides on the fused prologue; d_red_cols exists only on one rank with all_dense and a level
+  // plan that damps in its first launch: build_direct_tables)
+  f.direct = f.fused_prologue && !is("MPSFM_ASSEMBLE", "launch") && h->d_red_cols != nullptr && !sharded(h) && h->n > 0 &&
+             dense_level(&h->ov, &h->lp) && dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp) != nullptr;
+  f.speculate = on("MPSFM_LM_SPECULATE", 1);
+  f.force_split = on("MPSFM_LM_SPLIT", -1);
+  f.can_split = f.speculate && !sharded(h) && f.fused_prologue;
+  return f;
+}
+
+SweepArgs sweep_args(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl) {
   SweepArgs a{};
   a.ctl = ctl;
   a.chunks = h->d_chunks; a.chunk_cams = h->d_chunk_cams; a.rec_cam = h->rt.rec_cam; a.rec_meta = h->rt.rec_meta;
@@ -30,7 +51,8 @@ SweepArgs sweep_args(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
   a.Sblk = h->d_Sblk; a.gc = h->d_gc; a.wv = h->d_wv; a.diagU = h->d_diagU; a.part = h->d_part; a.diagV = h->d_diagV;
   a.yc = h->d_yc; a.camtab2 = h->d_camtab2; a.pts2 = h->d_pts2; a.part2 = h->d_part2;
   a.slab = h->d_slab; a.chunk0 = 0;
-  a.order = h->sweep_order_on ? h->d_sweep_order : nullptr;
+  a.order = f.sweep_order ? h->d_sweep_order : nullptr;
+  if (f.pt_handoff) a.pt_fac = h->d_pt_fac;  // written by the dense track sweep, read by the update sweep; nobody else looks
   return a;
 }
 
@@ -59,16 +81,18 @@ static int cost_of_records(mpsfm_ba_handle* h, bool fixed, double* out3) {
   return 0;
 }
 
-int prepare_scales(mpsfm_ba_handle* h) {
+void unit_camtab(mpsfm_ba_handle* h) {
+  launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 0, h->d_cs, h->stream);
+  launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, h->stream);
+}
+int prepare_scales(mpsfm_ba_handle* h, const SolveForm& f) {
   hipStream_t s = h->stream;
-  launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 0, h->d_cs, s);
   launch_pt_scales(h->np, h->rt.pt_kv, h->d_diagV, 0, h->d_ps, s);
-  launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, s);
+  unit_camtab(h);
   if (h->opt.jacobi_scaling) {
     MPSFM_TRY(hipMemsetAsync(h->d_diagU, 0, sizeof(double) * (size_t)std::max(h->n_user, 1), s));
     MPSFM_TRY(hipMemsetAsync(h->d_diagV, 0, sizeof(double) * 3 * (size_t)std::max<int64_t>(h->np, 1), s));
-    SweepArgs a = sweep_args(h, 1.0);
-    launch_track_sweep(a, h->nchunks, true, s);
+    launch_track_sweep(sweep_args(h, f, 1.0, nullptr), h->nchunks, true, s);
     if (int rc = allreduce_dev(h, h->d_diagU, h->n_user)) return rc;
     launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 1, h->d_cs, s);
     launch_pt_scales(h->np, h->rt.pt_kv, h->d_diagV, 1, h->d_ps, s);
@@ -79,24 +103,20 @@ int prepare_scales(mpsfm_ba_handle* h) {
   return 0;
 }
 
-// the full track sweep: dense chunks through their slabs (k_track_sweep_dense + k_reduce_slabs), the others and the long
-// tracks through the general kernels (global atomics); all of them add into the zeroed reduced buffer
-static void launch_sweeps(mpsfm_ba_handle* h, SweepArgs a, hipStream_t s, bool direct) {
+// dense chunks through their slabs (k_track_sweep_dense + k_reduce_slabs), the others and the long tracks through the general
+// kernels (global atomics)
+int launch_sweeps(mpsfm_ba_handle* h, SweepArgs a, bool direct, hipEvent_t* marks) {
+  hipStream_t s = h->stream;
   launch_track_sweep_dense(a, h->n_dense, s);
-  const DirectAsm da = direct ? direct_asm(h) : DirectAsm{};
+  if (marks) MPSFM_TRY(hipEventRecord(marks[0], s));
+  const DirectAsm da{h->d_red_cols, h->d_A, h->d_diag_col, h->nt};
   launch_reduce_slabs(h->d_red_dests, h->n_red_dests, h->d_red_srcs, h->d_slab, h->d_Sblk, h->d_gc, h->d_wv, h->d_diagU, a.ctl, s, direct ? &da : nullptr);
+  if (marks) MPSFM_TRY(hipEventRecord(marks[1], s));
   a.chunk0 = h->n_dense;
   launch_track_sweep(a, h->nchunks - h->n_dense, false, s);
+  return 0;
 }
 
-bool direct_front(mpsfm_ba_handle* h) {
-  const char* e = std::getenv("MPSFM_ASSEMBLE");
-  if (e && std::strcmp(e, "launch") == 0) return false;
-  const char* f = std::getenv("MPSFM_FUSE_PROLOGUE");  // the zero fill rides on the sweep's fused prologue (solve_impl)
-  if (f && std::atoi(f) == 0) return false;
-  return h->d_red_cols != nullptr && !sharded(h) && h->n > 0 && dense_level(&h->ov, &h->lp) && dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp) != nullptr;
-}
-DirectAsm direct_asm(const mpsfm_ba_handle* h) { return DirectAsm{h->d_red_cols, h->d_A, h->d_diag_col, h->nt}; }
 void direct_zero_args(mpsfm_ba_handle* h, SweepArgs& a) {
   a.red = h->d_gc; a.nred = h->red_count - h->sblk_count;  // Sblk is neither written nor read
   a.zero_p[0] = h->d_yc; a.zero_n[0] = h->n_user;
@@ -105,18 +125,18 @@ void direct_zero_args(mpsfm_ba_handle* h, SweepArgs& a) {
   a.zero_P = dense_pinv(h->d_dwork, h->nt, &h->ov, &h->lp); a.zero_ptiles = h->lp.d_pinv_tiles; a.zero_nptiles = h->lp.n_pinv_tiles;
 }
 
-int run_track_sweep(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool in_loop, bool adopt, bool handoff, bool direct) {
+int run_track_sweep(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl, bool in_loop) {
   hipStream_t s = h->stream;
+  const bool adopt = in_loop && f.fused_prologue, direct = adopt && f.direct;
   if (!in_loop) launch_zero(h->d_red, h->red_count, ctl, s);
-  SweepArgs a = sweep_args(h, radius, ctl);
+  SweepArgs a = sweep_args(h, f, radius, ctl);
   if (adopt) {
     a.adopt_on = 1; a.adopt_nc = h->nc;
     a.pts_rw = h->d_pts; a.q_rw = h->d_q; a.t_rw = h->d_t; a.camtab_rw = h->d_camtab; a.q2 = h->d_q2; a.t2 = h->d_t2;
     a.red = h->d_red; a.nred = h->red_count;
     if (direct) direct_zero_args(h, a);
   }
-  if (handoff) a.pt_fac = h->d_pt_fac;
-  launch_sweeps(h, a, s, direct && adopt);
+  if (int rc = launch_sweeps(h, a, direct)) return rc;
   if (h->nchunks + h->nlong > 0 && !(in_loop && !sharded(h)))
     launch_reduce_cols(h->d_part, h->nchunks + h->nlong, 4, 3, 1u << 2, h->d_redsc, s, sharded(h) ? nullptr : h->d_scal + U_X_COST,
                        sharded(h) ? (h->opt.rank > 0 ? h->opt.rank : 0) % kMaxRankSlots : -1);
@@ -136,14 +156,25 @@ void run_assemble(mpsfm_ba_handle* h, double radius, const LmCtl* ctl) {
   launch_assemble(as, h->stream);
 }
 
-int run_dense(mpsfm_ba_handle* h, double radius, const LmCtl* ctl, bool direct) {
+int run_dense(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl) {
   // d_fail is zero here: cleared at creation and re-armed by k_cam_update after every read
   if (h->n > 0) {
-    if (!direct) run_assemble(h, radius, ctl);
+    if (!f.direct) run_assemble(h, radius, ctl);
     const DampArgs damp{h->d_diag_col, h->lp.d_col_slot, h->lp.d_level0, h->n, h->opt.min_lm_diagonal, h->opt.max_lm_diagonal, radius};
-    launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, h->stream, &h->ov, &h->lp, ctl, direct ? &damp : nullptr);
+    h->ov.entry_list = f.entry_list;  // (the field launch_dense_solve reads)
+    launch_dense_solve(h->d_A, h->d_dwork, h->nt, h->n, h->d_yc, h->d_fail, h->stream, &h->ov, &h->lp, ctl, f.direct ? &damp : nullptr);
   }
   return 0;
+}
+
+// k_cam_update unless the update sweep forms the candidate cameras itself (f.fused_cam: CamUpdArgs), then the update sweep
+void enqueue_update(mpsfm_ba_handle* h, const SolveForm& f, double radius, const LmCtl* ctl) {
+  const CamUpdArgs cu{1, h->nc, h->d_cam_slot, h->d_cam_of_slot, h->d_q, h->d_t, h->d_cs, h->d_gc, h->d_intr, h->d_intr_idx,
+                      h->d_q2, h->d_t2, h->d_camtab2, h->d_scal, h->d_fail};
+  if (!f.fused_cam)
+    launch_cam_update(h->nc, h->d_cam_slot, h->d_q, h->d_t, h->d_cs, h->d_yc, h->d_gc, h->d_q2, h->d_t2, h->d_scal, h->stream,
+                      h->d_intr, h->d_intr_idx, h->d_camtab2, h->d_fail, ctl);
+  launch_update_sweep(sweep_args(h, f, radius, ctl), h->nchunks, h->stream, f.fused_cam ? &cu : nullptr);
 }
 
 // ---- what the two forms of the trust-region loop share ---------------------------------------------------------------------
@@ -194,31 +225,26 @@ constexpr int kLocalRefused = 1;
 // has been decided (solve_impl).  Twice the shortest front measured on MI355X, 19 us, where the forced split still did not lose
 // (DESIGN.md, round 9): the host's wake-up from the event wait varies from call to call.
 constexpr double kSplitMinFront = 40e-6;
-// MPSFM_PT_HANDOFF=0: the update sweep recomputes the landmark factors everywhere (the comparison path); read per solve
-// MPSFM_CHOL_ENTRY=list: the level launches walk item -> source list -> operands instead of reading launch records (the comparison
-// path of dense_chol.hip); read per solve like the switch above
-bool chol_entry_list() { const char* e = std::getenv("MPSFM_CHOL_ENTRY"); return e && std::strcmp(e, "list") == 0; }
-// MPSFM_SWEEP_ORDER=0: every workgroup of the dense sweep takes chunk blockIdx.x + chunk0 instead of the order table's (the comparison
-// path: same chunks, same outputs, another start order); read per solve and by the probes that sweep
-void read_sweep_order_switch(mpsfm_ba_handle* h) { const char* e = std::getenv("MPSFM_SWEEP_ORDER"); h->sweep_order_on = !(e && std::atoi(e) == 0); }
-static bool pt_handoff_enabled() { const char* e = std::getenv("MPSFM_PT_HANDOFF"); return !(e && std::atoi(e) == 0); }
+// What both forms of the loop start from: the cost of the fixed records in three free slots of the zeroed scalar block (it stays on
+// the device and enters the control block there), the column scales, the initial control block
+static int enqueue_lm_preamble(mpsfm_ba_handle* h, const SolveForm& f) {
+  MPSFM_TRY(hipMemsetAsync(h->d_scal, 0, sizeof(double) * U_COUNT, h->stream));
+  launch_fixed_cost(h, h->d_scal + 12);
+  if (int rc = prepare_scales(h, f)) return rc;
+  h->h_ctl[0] = initial_ctl(h->opt);  // x_norm and fixed_cost: from the device scalars
+  MPSFM_TRY(hipMemcpyAsync(h->d_ctl, &h->h_ctl[0], sizeof(LmCtl), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
 
-static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
+static int solve_local(mpsfm_ba_handle* h, const SolveForm& f, mpsfm_ba_summary* sum) {
   hipStream_t s = h->stream;
   const mpsfm_ba_options& o = h->opt;
-  launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 0, h->d_cs, s);
-  launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, s);
-  double* fixed_parts = h->d_scal + 12;  // three free slots of the scalar block
-  MPSFM_TRY(hipMemsetAsync(h->d_scal, 0, sizeof(double) * U_COUNT, s));
-  launch_fixed_cost(h, fixed_parts);
-  if (int rc = prepare_scales(h)) return rc;
-  h->h_ctl[0] = initial_ctl(o);
-  MPSFM_TRY(hipMemcpyAsync(h->d_ctl, &h->h_ctl[0], sizeof(LmCtl), hipMemcpyHostToDevice, s));
+  unit_camtab(h);  // the camera table at the initial point (unit scales) for the fixed cost
+  if (int rc = enqueue_lm_preamble(h, f)) return rc;
   MPSFM_TRY(hipMemsetAsync(h->d_local_acc, 0, sizeof(double) * 2 * kLocalAccDoubles, s));
   MPSFM_TRY(hipMemsetAsync(h->d_local_sync, 0, sizeof(int64_t) * 16, s));
   LocalArgs la{};
-  la.A = sweep_args(h, 0.0, nullptr);
-  if (pt_handoff_enabled()) la.A.pt_fac = h->d_pt_fac;  // phase A -> phase D of the chunk's own workgroup
+  la.A = sweep_args(h, f, 0.0, nullptr);  // (the hand-off: phase A -> phase D of the chunk's own workgroup)
   la.ctl = h->d_ctl;
   la.o = lm_opts_of(o);
   la.log = o.verbose > 0 ? h->d_local_log : nullptr;
@@ -226,7 +252,7 @@ static int solve_local(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   la.part[0] = h->d_part; la.part[1] = h->d_part + (size_t)h->nchunks * 4;  // (nlong == 0 here; the chain only ever uses the first half)
   la.bar = reinterpret_cast<int32_t*>(h->d_local_sync); la.clk = reinterpret_cast<long long*>(h->d_local_sync + 1);
   la.ncv = h->ncv; la.nc = h->nc; la.nchunks = h->nchunks;
-  la.q = h->d_q; la.t = h->d_t; la.camtab = h->d_camtab; la.pts = h->d_pts; la.cs = h->d_cs; la.fixed_parts = fixed_parts;
+  la.q = h->d_q; la.t = h->d_t; la.camtab = h->d_camtab; la.pts = h->d_pts; la.cs = h->d_cs; la.fixed_parts = h->d_scal + 12;
   la.skew_chunk = g_local_skew.chunk; la.skew_mask = g_local_skew.ticks > 0 ? g_local_skew.mask : 0; la.skew_ticks = g_local_skew.ticks;
   if (launch_local_lm(la, s) != (int)hipSuccess) {
     (void)hipGetLastError();
@@ -259,7 +285,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   MPSFM_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const mpsfm_ba_options& o = h->opt;
-  read_sweep_order_switch(h);
+  const SolveForm f = solve_form(h);  // decided once: solve_local and every launch below take it from here
   std::memset(sum, 0, sizeof(*sum));
   MPSFM_TRY(hipStreamSynchronize(s));
   const auto t_begin = clk::now();
@@ -272,13 +298,11 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
     return rc;
   };
   if (h->local_ok) {
-    const int rc = solve_local(h, sum);
+    const int rc = solve_local(h, f, sum);
     if (rc != kLocalRefused) return finish(rc);
   }
 
-  // camera table at the initial point (unit scales) for the fixed cost
-  launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 0, h->d_cs, s);
-  launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, s);
+  unit_camtab(h);  // the camera table at the initial point (unit scales) for the fixed cost
   if (h->n == 0 && h->nvarpts_global == 0.0) {  // nothing to solve: the two costs as host values
     double fx[3], c3[3];
     if (int rc = cost_of_records(h, true, fx)) return rc;
@@ -295,9 +319,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   // Nothing in front of the loop needs the host — the cost of the fixed blocks and the state norm stay on the device and enter
   // the control block there (k_lm_init); three stream synchronisations less per solve.  Sharded runs sum them over the ranks
   // in one small exchange on the device.
-  MPSFM_TRY(hipMemsetAsync(h->d_scal, 0, sizeof(double) * U_COUNT, s));
-  launch_fixed_cost(h, h->d_scal + 12);
-  if (int rc = prepare_scales(h)) return rc;
+  if (int rc = enqueue_lm_preamble(h, f)) return rc;
   if (h->np > 0) MPSFM_TRY(hipMemcpyAsync(h->d_pts2, h->d_pts, sizeof(double) * 3 * h->np, hipMemcpyDeviceToDevice, s));
   // initial x norm: cameras through a zero-step camera update, landmarks by a reduction
   MPSFM_TRY(hipMemsetAsync(h->d_yc, 0, sizeof(double) * (size_t)std::max(h->n_user, 1), s));
@@ -316,8 +338,6 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   // decision) following once the outcome of iteration i is known to be "go on": the solve then ends with two dead launches instead
   // of some twenty.  The host has the front's run time to wake up, read the control block and enqueue the first back launch, so
   // the split is taken where the front measured long enough for that (kSplitMinFront), on one rank and with all chunks dense.
-  h->h_ctl[0] = initial_ctl(o);  // x_norm and fixed_cost: from the device scalars
-  MPSFM_TRY(hipMemcpyAsync(h->d_ctl, &h->h_ctl[0], sizeof(LmCtl), hipMemcpyHostToDevice, s));
   double* sums = nullptr;
   if (sharded(h)) {
     sums = h->d_costpart;  // (free again: its reductions are queued in front)
@@ -328,41 +348,21 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   const LmOpts lo = lm_opts_of(o);
   const LmCtl* ctl = h->d_ctl;
   const double no_radius = 0.0;  // inside the loop the kernels read the radius from the control block
-  const bool fuse_prologue = [] { const char* e = std::getenv("MPSFM_FUSE_PROLOGUE"); return !(e && std::atoi(e) == 0); }();
-  const bool fuse_cam = [] { const char* e = std::getenv("MPSFM_FUSE_CAM"); return !(e && std::atoi(e) == 0); }();
-  const bool pt_handoff = pt_handoff_enabled() && h->d_pt_fac != nullptr;  // (allocated where all chunks are dense and no track is long)
-  h->ov.entry_list = chol_entry_list();
-  // all chunks dense: the dense sweep adopts an accepted candidate and zeroes the reduced buffer itself (sharded runs too: the
-  // exchange of the reduced buffer comes behind the slab reduction, the camera scalars are the same on every rank)
-  const bool fused_prologue = fuse_prologue && h->nlong == 0 && h->n_dense > 0 && h->n_dense == h->nchunks;
-  // ... and one rank, level-scheduled: the slab reduction adds straight into the tiles of the dense solve, no k_assemble (DirectAsm)
-  const bool direct = fused_prologue && direct_front(h);  // (d_red_cols exists only where every chunk is dense and no track is long)
   auto enqueue_front = [&](int it) -> int {
     hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
     MPSFM_TRY(hipEventRecord(ev[0], s));
-    if (!fused_prologue)
+    if (!f.fused_prologue)
       launch_lm_prologue(h->d_ctl, h->d_red, h->red_count, h->nc, h->np, h->d_q, h->d_t, h->d_camtab, h->d_pts, h->d_q2, h->d_t2, h->d_camtab2, h->d_pts2, s);
-    if (int rc = run_track_sweep(h, no_radius, ctl, true, fused_prologue, pt_handoff, direct)) return rc;
+    if (int rc = run_track_sweep(h, f, no_radius, ctl, /*in_loop=*/true)) return rc;
     if (int rc = allreduce_dev(h, h->d_red, h->red_count)) return rc;
     MPSFM_TRY(hipEventRecord(ev[1], s));
     return 0;
   };
   auto enqueue_back = [&](int it) -> int {
     hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
-    if (int rc = run_dense(h, no_radius, ctl, direct)) return rc;
+    if (int rc = run_dense(h, f, no_radius, ctl)) return rc;
     MPSFM_TRY(hipEventRecord(ev[2], s));
-    // all chunks dense and one rank: the update sweep forms the candidate cameras itself (CamUpdArgs)
-    const bool fused_cam = fuse_cam && fused_prologue;
-    CamUpdArgs cu{1, h->nc, h->d_cam_slot, h->d_cam_of_slot, h->d_q, h->d_t, h->d_cs, h->d_gc, h->d_intr, h->d_intr_idx,
-                  h->d_q2, h->d_t2, h->d_camtab2, h->d_scal, h->d_fail};
-    if (!fused_cam)
-      launch_cam_update(h->nc, h->d_cam_slot, h->d_q, h->d_t, h->d_cs, h->d_yc, h->d_gc, h->d_q2, h->d_t2, h->d_scal, s,
-                        h->d_intr, h->d_intr_idx, h->d_camtab2, h->d_fail, ctl);
-    {
-      SweepArgs a = sweep_args(h, no_radius, ctl);
-      if (pt_handoff) a.pt_fac = h->d_pt_fac;
-      launch_update_sweep(a, h->nchunks, s, fused_cam ? &cu : nullptr);
-    }
+    enqueue_update(h, f, no_radius, ctl);
     if (!sharded(h)) {
       launch_lm_reduce_decide(h->d_part, h->d_part2, h->nchunks + h->nlong, h->d_ctl, h->d_scal, lo, &h->h_ctl[it & 1], s);
     } else {
@@ -381,14 +381,11 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
   LmCtl last = h->h_ctl[0];
   if (last.term == kLmRunning) {
     if (int rc = enqueue_iteration(1)) return rc;
-    const bool speculate = [] { const char* e = std::getenv("MPSFM_LM_SPECULATE"); return !(e && std::atoi(e) == 0); }();  // per solve: tests switch it
-    // MPSFM_LM_SPLIT=0/1 forces the choice between the whole iteration and its front half ahead (where the split is possible at all)
-    const int force_split = [] { const char* e = std::getenv("MPSFM_LM_SPLIT"); return e ? (std::atoi(e) != 0 ? 1 : 0) : -1; }();
-    const bool can_split = speculate && !sharded(h) && fused_prologue;
     for (int it = 1;; ++it) {
       // ahead of the news about iteration `it`; the front's length: ev0 -> ev1 of the last iteration read (this handle's previous solve at first)
-      const bool split = can_split && (force_split >= 0 ? force_split == 1 : h->split_front_s >= kSplitMinFront);
-      if (speculate) { if (int rc = split ? enqueue_front(it + 1) : enqueue_iteration(it + 1)) return rc; }
+      // (MPSFM_LM_SPLIT forces the choice between the whole iteration and its front half where the split is possible at all)
+      const bool split = f.can_split && (f.force_split >= 0 ? f.force_split == 1 : h->split_front_s >= kSplitMinFront);
+      if (f.speculate) { if (int rc = split ? enqueue_front(it + 1) : enqueue_iteration(it + 1)) return rc; }
       hipEvent_t* ev = (it & 1) ? h->ev2 : h->ev;
       MPSFM_TRY(hipEventSynchronize(ev[3]));
       MPSFM_TRY(hipGetLastError());
@@ -400,7 +397,7 @@ static int solve_impl(mpsfm_ba_handle* h, mpsfm_ba_summary* sum) {
       last = h->h_ctl[it & 1];
       if (o.verbose > 0) print_iteration(it, last, last.fixed_cost);
       if (last.term != kLmRunning) break;
-      if (!speculate) { if (int rc = enqueue_iteration(it + 1)) return rc; }
+      if (!f.speculate) { if (int rc = enqueue_iteration(it + 1)) return rc; }
       else if (split) { if (int rc = enqueue_back(it + 1)) return rc; }
     }
     // the iteration that ended the solve may have been accepted (iteration or radius limit); the copy is idempotent
@@ -521,8 +518,7 @@ int mpsfm_ba_solve(const mpsfm_ba_problem* problem, mpsfm_ba_state* state, const
 int mpsfm_ba_eval_cost(mpsfm_ba_handle* h, double* cost_reproj, double* cost_depth) {
   if (!h) return fail(MPSFM_EINVAL, "handle is NULL");
   MPSFM_TRY(hipSetDevice(h->device));
-  launch_cam_scales(h->nc, h->d_cam_slot, h->d_cmask, h->d_diagU, 0, h->d_cs, h->stream);
-  launch_build_camtab(h->nc, h->d_q, h->d_t, h->d_intr, h->d_intr_idx, h->d_cs, h->d_camtab, h->stream);
+  unit_camtab(h);
   h->scales_ready = false;
   double a[3], b[3];
   if (int rc = cost_of_records(h, false, a)) return rc;
