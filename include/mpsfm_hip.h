@@ -524,9 +524,9 @@ int mpsfm_depth_consistency(int32_t n_images, mpsfm_dc_image* images /* [n_image
                             uint8_t* const* codes /* [2 n_pairs] pointers to Hs*Ws, or NULL */,
                             mpsfm_dc_summary* summary /* may be NULL */);
 
-/* ---- options of the two LO-RANSAC estimators below (their defaults differ: see each typedef) ---- */
+/* ---- options of the LO-RANSAC estimators below (their defaults differ: see each typedef) ---- */
 typedef struct mpsfm_ransac_options {
-  double max_error;                  /* pixels */
+  double max_error;                  /* pixels (mpsfm_align3d_estimate: the units of tgt) */
   double min_inlier_ratio;
   double confidence;
   double dyn_num_trials_multiplier;
@@ -1551,6 +1551,97 @@ int mpsfm_filter_scene(const mpsfm_tri_graph* graph, const mpsfm_tri_state* stat
                        uint8_t* point_fate /* [n_points] */, uint8_t* point_risky /* [n_points] */,
                        double* point_max_angle /* [n_points], may be NULL */, double* kp_sq_err /* [n_kp], may be NULL */,
                        mpsfm_scene_filter_info* info /* may be NULL */);
+
+/* ---- 3D-3D alignment: rigid and similarity LO-RANSAC of two point sets, the least-squares fit on its own, and the RGB-D pair
+ *    registration built on them (reference icp/main.py:105-193 with icp/depth_to_3d.py and icp/interpolate.py, the fork's only
+ *    addition to upstream MP-SfM).  Loop, options and names are modelled on COLMAP 3.11's EstimateRigid3dRobust /
+ *    EstimateSim3dRobust (LORANSAC over a closed-form 3-point solver) as recalled; parity with pycolmap is unpinned.  The fork's
+ *    own loop (5000 fixed trials of np.random.choice, inliers counted by |q - (R p + t)| < 0.1, no local optimisation, no scale)
+ *    is not reproduced trial by trial: its closed form (rigid_transform_3D) and its lifting are, see below.
+ *
+ *    mpsfm_align3d_estimate.  Model: tgt ~ s R src + t, s == 1 when with_scale == 0.  Residual: |tgt_i - (s R src_i + t)|^2,
+ *    evaluated as written (s (R p) + t, no fused multiply-add); inlier: residual <= max_error^2, max_error in the units of tgt.
+ *    Loop: LO-RANSAC with sample size 3, one model per trial; support measure, min_inlier_ratio cap, dynamic bound and stop test
+ *    as in mpsfm_abs_pose_estimate (exponent 3).  Sampler: the counter recipe of mpsfm_abs_pose_estimate, the first three
+ *    distinct indices.  Minimal solver: centroids, the 3 x 3 cross-covariance of the centred points, the rotation by Horn's
+ *    quaternion method (always det R = +1: a mirrored set gets the best proper rotation, as the fork's reflection fix does);
+ *    with_scale: s = sum (q - mq)^T R (p - mp) / sum |p - mp|^2 (Umeyama); t = mq - s R mp.  Rules of ours that COLMAP and
+ *    the fork leave open: a sample gives no model when its three source points or its three target points are collinear
+ *    (sin^2 of the angle at the first point <= 1e-20, P3P's test; it covers coincident points), or when its scale is not finite
+ *    and positive.  Local estimator: a sample model that becomes the best with more than 3 inliers starts up to 10 rounds of the
+ *    same closed form over its current inlier set, continued while the inlier count grows.  Its sums are reduced on the device
+ *    in a fixed order in two passes, so the covariance is centred: count, sum p, sum q; then the 9 cross terms, the 6 + 6
+ *    scatter terms of source and target and sum |p - mp|^2, with the inlier test evaluated from the incoming model inside the
+ *    reduction.  The fit gives no model when fewer than 3 points are selected or when the source or the target scatter matrix has
+ *    its second-largest eigenvalue <= 1e-12 x its largest (points on a line; a planar set is fine).
+ *    tgt_from_src = [R | t] row-major with R orthonormal, det R = +1, and scale apart: tgt = scale R src + t.
+ *    inlier_mask[i] = 1 for the inliers of the final model.  n < 3, n > INT32_MAX, NULL pointers, non-finite inputs and invalid
+ *    options are MPSFM_EINVAL before any HIP call.  No model: result->success = 0 and return value 0.  Results are identical
+ *    run to run and for every batch_trials.
+ *
+ *    mpsfm_align3d_fit: the local estimator on its own (the non-robust estimate_rigid3d / estimate_sim3d) over the points with
+ *    mask[i] != 0 (mask NULL: all), same reductions, same degeneracy rule; num_inliers = the number of points used,
+ *    num_models = 1 on success, the other counters 0.  Argument checks as above (no options).
+ *
+ *    mpsfm_lift_keypoints: icp/depth_to_3d.py + icp/interpolate.py in one launch, one thread per keypoint; the point map is never
+ *    materialised.  The four corner points at (c, r) = (trunc(x) + {0, 1}, trunc(y) + {0, 1}) are ((c - cx) z) / fx,
+ *    ((r - cy) z) / fy, z; with ax = x - trunc(x), ay = y - trunc(y) the result is
+ *        a00 (1 - ax) (1 - ay) + a01 ax (1 - ay) + a10 (1 - ax) ay + a11 ax ay      (a01: column + 1, a10: row + 1)
+ *    evaluated left to right without fused multiply-adds: bit for bit the fork's float64 result.  VALIDITY (the fork has no rule:
+ *    it indexes out of range or interpolates zero depth; icp/save_pcd.py treats z == 0 as absent): a keypoint is valid iff
+ *    x >= 0, y >= 0, trunc(x) + 1 <= W - 1, trunc(y) + 1 <= H - 1, all four corner depths are finite and > 0, and the lifted
+ *    point is finite (no overflow).  A NaN coordinate is invalid.  An invalid keypoint gets xyz = 0 and valid = 0.
+ *    MPSFM_EINVAL before any HIP call: NULL pointers, H or W < 1, H W > INT32_MAX, n < 0 or > INT32_MAX, intrinsics that are
+ *    not finite or a zero focal length.  n == 0: no device.
+ *
+ *    mpsfm_depth_pair_register: everything of icp/main.py behind the matcher in one call.  Both ends of each match
+ *    (matches[i] = {keypoint of image 0, keypoint of image 1}) are lifted; matches whose two ends are both valid are compacted on
+ *    the device in match order (one host wait delivers their count) and mpsfm_align3d_estimate's loop runs on them, source =
+ *    image 0, target = image 1; its mask is scattered back to the matches.  valid[i]: both ends valid; lifted0 / lifted1 [m][3]:
+ *    the lifted ends (zeros where that end is invalid); inlier_mask[i] = 0 for invalid matches.  Fewer than 3 valid matches:
+ *    success = 0.  The result equals, bit for bit, two mpsfm_lift_keypoints calls, a host compaction and mpsfm_align3d_estimate
+ *    with the same options.  MPSFM_EINVAL before any HIP call: as mpsfm_lift_keypoints for both maps, a match index out of
+ *    range, invalid options.  m == 0: success = 0, no device.  One PINHOLE pair per call. ---- */
+/* defaults: max_error 0.1 (the fork's pts_bound), min_inlier_ratio 0.1, confidence 0.99, dyn_num_trials_multiplier 3.0,
+ * min_num_trials 100, max_num_trials 5000 (the fork's trial count) */
+typedef mpsfm_ransac_options mpsfm_align3d_options;
+
+typedef struct mpsfm_align3d_result {
+  double tgt_from_src[12];  /* [R | t] row-major; tgt = scale R src + t */
+  double scale;             /* 1 for a rigid model */
+  int64_t num_inliers;      /* mpsfm_align3d_fit: points used */
+  int64_t num_trials;       /* LORANSAC's report.num_trials */
+  int64_t max_num_trials;   /* after the min_inlier_ratio cap */
+  int64_t num_models;       /* model slots scored (all batches, one per trial) */
+  int32_t success;
+  int32_t lo_rounds;        /* local estimates run */
+  int32_t num_batches;
+  float ms;                 /* device time of the launches (HIP events), transfers and host work excluded */
+} mpsfm_align3d_result;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_align3d_result) == 152 && offsetof(mpsfm_align3d_result, scale) == 96 &&
+                  offsetof(mpsfm_align3d_result, success) == 136,
+              "ABI of mpsfm_align3d_result");
+#endif
+
+int mpsfm_align3d_estimate(int64_t n, const double* src /* [n][3] */, const double* tgt /* [n][3] */, int32_t with_scale,
+                           const mpsfm_align3d_options* options, int32_t device, uint8_t* inlier_mask /* [n] */,
+                           mpsfm_align3d_result* result);
+
+int mpsfm_align3d_fit(int64_t n, const double* src /* [n][3] */, const double* tgt /* [n][3] */, const uint8_t* mask /* [n] or NULL */,
+                      int32_t with_scale, int32_t device, mpsfm_align3d_result* result);
+
+int mpsfm_lift_keypoints(int32_t H, int32_t W, const double* depth /* [H][W] */, const double* intr /* PINHOLE fx fy cx cy */,
+                         int64_t n, const double* xy /* [n][2] pixels of the map */, int32_t device, double* xyz /* [n][3] */,
+                         uint8_t* valid /* [n] */);
+
+int mpsfm_depth_pair_register(int32_t H0, int32_t W0, const double* depth0 /* [H0][W0] */, const double* intr0,
+                              int32_t H1, int32_t W1, const double* depth1 /* [H1][W1] */, const double* intr1,
+                              int64_t n0, const double* xy0 /* [n0][2] */, int64_t n1, const double* xy1 /* [n1][2] */,
+                              int64_t m, const int32_t* matches /* [m][2] */, int32_t with_scale,
+                              const mpsfm_align3d_options* options, int32_t device, uint8_t* valid /* [m] */,
+                              uint8_t* inlier_mask /* [m] */, double* lifted0 /* [m][3] */, double* lifted1 /* [m][3] */,
+                              mpsfm_align3d_result* result);
 
 #ifdef __cplusplus
 }

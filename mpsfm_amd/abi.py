@@ -201,13 +201,20 @@ class CRansacOptions(C.Structure):
                 ("seed", C.c_uint64), ("batch_trials", C.c_int32), ("reserved", C.c_int32)]
 
 
-CAbsPoseOptions = CRelPoseOptions = CRansacOptions  # typedefs of mpsfm_ransac_options in the header
+CAbsPoseOptions = CRelPoseOptions = CAlign3dOptions = CRansacOptions  # typedefs of mpsfm_ransac_options in the header
 
 
 class CAbsPoseResult(C.Structure):
     _c_name_ = "mpsfm_abs_pose_result"
     _fields_ = [("cam_from_world", C.c_double * 12), ("num_inliers", C.c_int64), ("num_trials", C.c_int64), ("max_num_trials", C.c_int64),
                 ("num_models", C.c_int64), ("success", C.c_int32), ("lo_rounds", C.c_int32), ("num_batches", C.c_int32), ("ms", C.c_float)]
+
+
+class CAlign3dResult(C.Structure):
+    _c_name_ = "mpsfm_align3d_result"
+    _fields_ = [("tgt_from_src", C.c_double * 12), ("scale", C.c_double), ("num_inliers", C.c_int64), ("num_trials", C.c_int64),
+                ("max_num_trials", C.c_int64), ("num_models", C.c_int64), ("success", C.c_int32), ("lo_rounds", C.c_int32),
+                ("num_batches", C.c_int32), ("ms", C.c_float)]
 
 
 class CRelPoseResult(C.Structure):
@@ -497,6 +504,10 @@ SIGNATURES = {
     "mpsfm_visibility_scores": (C.c_int, [I32, P, P, P, P, P, P, I32, I32, P, P, P, P]),
     "mpsfm_local_bundles": (C.c_int, [I32, P, P, I32, P, I32, F64, I32, P, P, P, P, P]),
     "mpsfm_filter_scene": (C.c_int, [P, P, P, P, P, P, I32, P, P, P, P, P, P]),
+    "mpsfm_align3d_estimate": (C.c_int, [I64, P, P, I32, P, I32, P, P]),
+    "mpsfm_align3d_fit": (C.c_int, [I64, P, P, P, I32, I32, P]),
+    "mpsfm_lift_keypoints": (C.c_int, [I32, I32, P, P, I64, P, I32, P, P]),
+    "mpsfm_depth_pair_register": (C.c_int, [I32, I32, P, P, I32, I32, P, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, P, P, P]),
 }
 
 # include/mpsfm_hip_debug.h: test and diagnostic hooks, outside the stable ABI

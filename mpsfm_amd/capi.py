@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
-    ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CCorrGraphInfo, CDcImage, CDebugLmCtl, CDebugLmOpts, CDcSummary, CDepthGather, CDepthPriorConf,
+    ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CAlign3dOptions, CAlign3dResult, CCorrGraphInfo, CDcImage, CDebugLmCtl, CDebugLmOpts, CDcSummary, CDepthGather, CDepthPriorConf,
     CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CLiftInfo, CLiftMaps, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
     CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CSceneFilterInfo, CSceneFilterOptions, CSceneQueryInfo, CTriGraph, CTriState, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
@@ -659,6 +659,95 @@ def rel_pose_estimate(points1, points2, intr1, intr2, device=0, **options) -> di
                                          mask.ctypes.data, C.byref(R)))
     return dict(_ransac_report(R, mask, n), E=np.array(R.E[:]).reshape(3, 3), cam2_from_cam1=np.array(R.cam2_from_cam1[:]).reshape(3, 4),
                 num_cheirality_points=int(R.num_cheirality_points))
+
+
+# the reference's icp/main.py where it sets a value (pts_bound 0.1, 5000 trials), pycolmap 3.11 RANSACOptions() as recalled otherwise
+ALIGN3D_DEFAULTS = dict(max_error=0.1, min_inlier_ratio=0.1, confidence=0.99, dyn_num_trials_multiplier=3.0, min_num_trials=100,
+                        max_num_trials=5000, seed=0, batch_trials=0)
+
+
+def _align3d_report(R, mask: np.ndarray, n: int) -> dict:
+    return dict(_ransac_report(R, mask, n), tgt_from_src=np.array(R.tgt_from_src[:]).reshape(3, 4), scale=float(R.scale))
+
+
+def _point_pairs(src, tgt):
+    p = np.ascontiguousarray(src, np.float64).reshape(-1, 3)
+    q = np.ascontiguousarray(tgt, np.float64).reshape(-1, 3)
+    if len(p) != len(q):
+        raise ValueError("src and tgt differ in length")
+    return p, q
+
+
+def align3d_estimate(src, tgt, with_scale=False, device=0, **options) -> dict:
+    """mpsfm_align3d_estimate: LO-RANSAC of tgt ~ s R src + t (s = 1 unless with_scale) over [n, 3] point pairs.
+    `options`: keys of ALIGN3D_DEFAULTS.  Returns dict(success, tgt_from_src [3,4] = [R | t], scale, num_inliers,
+    inlier_mask bool [n], num_trials, max_num_trials, num_models, lo_rounds, num_batches, ms)."""
+    opt = _ransac_options(ALIGN3D_DEFAULTS, options)
+    p, q = _point_pairs(src, tgt)
+    n = len(p)
+    mask = np.zeros(max(n, 1), np.uint8)
+    R = CAlign3dResult()
+    _check(lib().mpsfm_align3d_estimate(n, p.ctypes.data, q.ctypes.data, int(bool(with_scale)), C.byref(opt), int(device), mask.ctypes.data,
+                                        C.byref(R)))
+    return _align3d_report(R, mask, n)
+
+
+def align3d_fit(src, tgt, mask=None, with_scale=False, device=0) -> dict:
+    """mpsfm_align3d_fit: the least-squares tgt ~ s R src + t over the pairs that `mask` keeps (None: all).  Returns
+    dict(success, tgt_from_src [3,4], scale, num_inliers = points used, ms)."""
+    p, q = _point_pairs(src, tgt)
+    n = len(p)
+    sel = None
+    if mask is not None:
+        sel = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, np.uint8)
+        if len(sel) != n:
+            raise ValueError("mask and points differ in length")
+    R = CAlign3dResult()
+    _check(lib().mpsfm_align3d_fit(n, p.ctypes.data, q.ctypes.data, None if sel is None else sel.ctypes.data, int(bool(with_scale)),
+                                   int(device), C.byref(R)))
+    return dict(success=bool(R.success), tgt_from_src=np.array(R.tgt_from_src[:]).reshape(3, 4), scale=float(R.scale),
+                num_inliers=int(R.num_inliers), ms=float(R.ms))
+
+
+def _depth_map(depth, intr):
+    """A float32 or float64 [H, W] map as the float64 array the library reads (float32 widens exactly), and its intrinsics."""
+    d = np.asarray(depth)
+    if d.ndim != 2 or d.dtype not in (np.float32, np.float64):
+        raise ValueError("a depth map is a float32 or float64 [H, W] array")
+    return np.ascontiguousarray(d, np.float64), np.ascontiguousarray(intr, np.float64).reshape(4)
+
+
+def lift_keypoints(depth, intr, xy, device=0):
+    """mpsfm_lift_keypoints: keypoints [n, 2] (pixels of the map) bilinearly sampled from the point map of `depth` [H, W] with
+    PINHOLE intr = (fx, fy, cx, cy).  Returns (xyz float64 [n, 3], valid bool [n]); invalid keypoints are zeros."""
+    d, K = _depth_map(depth, intr)
+    kp = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    n = len(kp)
+    xyz, valid = np.zeros((max(n, 1), 3)), np.zeros(max(n, 1), np.uint8)
+    _check(lib().mpsfm_lift_keypoints(d.shape[0], d.shape[1], d.ctypes.data, K.ctypes.data, n, kp.ctypes.data, int(device),
+                                      xyz.ctypes.data, valid.ctypes.data))
+    return xyz[:n], valid[:n].astype(bool)
+
+
+def depth_pair_register(depth0, intr0, depth1, intr1, xy0, xy1, matches, with_scale=False, device=0, **options) -> dict:
+    """mpsfm_depth_pair_register: both ends of matches [m, 2] (keypoint of image 0, of image 1) lifted through their depth maps
+    and aligned, source = image 0.  `options`: keys of ALIGN3D_DEFAULTS.  Returns align3d_estimate's dict with inlier_mask
+    over the matches, plus valid bool [m], lifted0 and lifted1 float64 [m, 3]."""
+    opt = _ransac_options(ALIGN3D_DEFAULTS, options)
+    d0, K0 = _depth_map(depth0, intr0)
+    d1, K1 = _depth_map(depth1, intr1)
+    k0 = np.ascontiguousarray(xy0, np.float64).reshape(-1, 2)
+    k1 = np.ascontiguousarray(xy1, np.float64).reshape(-1, 2)
+    mt = np.ascontiguousarray(matches, np.int32).reshape(-1, 2)
+    m = len(mt)
+    valid, mask = np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.uint8)
+    l0, l1 = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3))
+    R = CAlign3dResult()
+    _check(lib().mpsfm_depth_pair_register(d0.shape[0], d0.shape[1], d0.ctypes.data, K0.ctypes.data, d1.shape[0], d1.shape[1],
+                                           d1.ctypes.data, K1.ctypes.data, len(k0), k0.ctypes.data, len(k1), k1.ctypes.data, m,
+                                           mt.ctypes.data, int(bool(with_scale)), C.byref(opt), int(device), valid.ctypes.data,
+                                           mask.ctypes.data, l0.ctypes.data, l1.ctypes.data, C.byref(R)))
+    return dict(_align3d_report(R, mask, m), valid=valid[:m].astype(bool), lifted0=l0[:m], lifted1=l1[:m])
 
 
 # COLMAP 3.11 TwoViewGeometryOptions as recalled (mpsfm_two_view_default_options)

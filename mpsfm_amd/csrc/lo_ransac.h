@@ -11,7 +11,7 @@
 // The host walks the batch's table in trial order (best-model updates, the local optimisation, the dynamic bound, the
 // stop rule), so the result is the sequential loop's.
 //
-// A problem description P is a plain struct (abs_pose.hip, rel_pose.hip):
+// A problem description P is a plain struct (abs_pose.hip, rel_pose.hip, align3d.hip):
 //   static constexpr int kSample, kModel (doubles per model), kSlots (models per trial), kLocal (<= kSlots: models of one
 //                    local estimate), kDefaultBatch
 //   struct Pts (SoA pointers, passed to kernels by value), struct Obs
