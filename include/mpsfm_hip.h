@@ -1643,6 +1643,98 @@ int mpsfm_depth_pair_register(int32_t H0, int32_t W0, const double* depth0 /* [H
                               uint8_t* inlier_mask /* [m] */, double* lifted0 /* [m][3] */, double* lifted1 /* [m][3] */,
                               mpsfm_align3d_result* result);
 
+/* ---- Dense point-to-plane ICP of an RGB-D pair: the refinement behind mpsfm_depth_pair_register, over every depth pixel
+ *    instead of a few hundred keypoints (the fork's icp/main.py stops at the RANSAC).  Projective association, one linearisation
+ *    and one 6 x 6 solve per iteration, the whole loop enqueued without a host wait.  All f64, every expression rounded as
+ *    written (no fused multiply-add).  PINHOLE intr = fx, fy, cx, cy.  Model: x1 = s (R x0) + t, mpsfm_depth_pair_register's
+ *    tgt_from_src; s is an input held constant, the ICP refines R and t only.
+ *
+ *    Vertex of pixel (r, c): V = (((c - cx) z) / fx, ((r - cy) z) / fy, z), mpsfm_lift_keypoints' expression at integer
+ *    coordinates; valid iff z is finite and > 0.
+ *    Normal of an interior pixel: a = V(r, c + 1) - V(r, c - 1), b = V(r + 1, c) - V(r - 1, c), m = a x b, n = m / sqrt(m.m);
+ *    valid iff the five vertices are valid, |z_nb - z_c| <= edge_ratio z_c for the four neighbours, m.m is finite and > 0 and
+ *    n.V != 0; negated where n.V > 0, so it faces the camera.  Border pixels have no normal.  An invalid normal is stored as
+ *    zeros.
+ *    Source set: the pixels of map 0 with a valid normal and r % stride == 0 && c % stride == 0.
+ *    Association at the pose (R, t): p' = s (R p) + t; p'_z > 0; u = (p'_x / p'_z) fx1 + cx1, v likewise; ci = floor(u + 0.5),
+ *    ri = floor(v + 0.5), tested as doubles against 0 <= ci <= W1 - 1, 0 <= ri <= H1 - 1 (a NaN fails); the target pixel
+ *    (ri, ci) needs a valid normal n1, its vertex is q; |p' - q|^2 <= max_distance^2; (R n0).n1 >= cos(max_angle_deg), the
+ *    cosine formed once on the host.  A source pixel fails at the first test it does not pass; rejected[] counts the causes:
+ *    0 not in front or outside the map, 1 no target normal, 2 distance, 3 angle.
+ *    Linearisation: r = n1.(p' - q), J = [p' x n1, n1] for the left increment p' + w x p' + v; A = sum J J^T, b = - sum J r,
+ *    sum r^2 and the counts, reduced in a fixed order without atomics: per workgroup, then the workgroups' rows in order.  The
+ *    partition into threads and workgroups depends on H0, W0 and stride only.
+ *    Step: A scaled symmetrically to unit diagonal and factored by Cholesky without pivoting; singular when a diagonal entry of
+ *    A is <= 0 or a pivot of the scaled matrix is <= 1e-10.  Else xi = (w, v) = A^-1 b, R <- exp(w) R, t <- exp(w) t + v by
+ *    Rodrigues' formula (I + [w]x below |w| = 1e-12).
+ *    Endings (status): CONVERGED |w| <= eps_rotation and |v| <= eps_translation after the step is applied; TOO_FEW_PAIRS the
+ *    pair count is < min_pairs, the pose of the previous iteration is kept; SINGULAR the pose is kept; MAX_ITERATIONS otherwise.
+ *    iterations counts the linearisations formed, the one that ended the loop included; info, rhs, num_pairs, rejected and
+ *    rmse = sqrt(sum r^2 / num_pairs) (0 without pairs) are those of the last one.
+ *    trace (may be NULL) [options->max_iterations][4]: pair count, rmse, |w|, |v| per iteration (|w| = |v| = 0 where no step
+ *    was taken), zeros past `iterations`.
+ *
+ *    mpsfm_depth_normals: the normal map on its own; normals [H][W][3], valid [H][W].
+ *    mpsfm_depth_pair_icp: the loop from init [12] = [R | t] row-major and scale.  One host wait per call.
+ *    mpsfm_depth_pair_register_dense: mpsfm_depth_pair_register, then, when it found a model, mpsfm_depth_pair_icp from that
+ *    model on the maps already on the device: bit for bit the two calls one after the other.  No model (or m == 0): success = 0
+ *    and *icp zeroed.
+ *    MPSFM_EINVAL before any HIP call: NULL pointers (trace excepted), H or W < 3 (mpsfm_depth_normals: < 1), H W > INT32_MAX,
+ *    intrinsics that are not finite or a zero focal length, init or scale not finite, scale <= 0, options out of range
+ *    (max_distance > 0, 0 <= max_angle_deg <= 180, edge_ratio >= 0, eps >= 0, all finite; 1 <= max_iterations <= 64;
+ *    min_pairs >= 6; stride >= 1).  Non-finite or non-positive depths are data: holes.  One PINHOLE pair per call. ---- */
+#define MPSFM_ICP_MAX_ITERATIONS 64
+enum { MPSFM_ICP_CONVERGED = 0, MPSFM_ICP_MAX_ITERATIONS_REACHED = 1, MPSFM_ICP_TOO_FEW_PAIRS = 2, MPSFM_ICP_SINGULAR = 3 };
+
+/* defaults: max_distance 0.1 (the fork's pts_bound), max_angle_deg 30, edge_ratio 0.05, eps_rotation 1e-6, eps_translation 1e-6,
+ * max_iterations 30, min_pairs 100, stride 1 */
+typedef struct mpsfm_icp_options {
+  double max_distance;     /* units of the depth maps */
+  double max_angle_deg;
+  double edge_ratio;
+  double eps_rotation;     /* radians */
+  double eps_translation;
+  int32_t max_iterations;  /* 1 .. MPSFM_ICP_MAX_ITERATIONS */
+  int32_t min_pairs;       /* >= 6 */
+  int32_t stride;          /* >= 1 */
+  int32_t reserved;
+} mpsfm_icp_options;
+
+typedef struct mpsfm_icp_result {
+  double tgt_from_src[12];  /* [R | t] row-major; tgt = scale R src + t */
+  double scale;             /* the input scale */
+  double info[36];          /* A of the last linearisation formed, row-major, order (w, v) */
+  double rhs[6];            /* b of the last linearisation formed */
+  double rmse;
+  int64_t num_pairs;
+  int64_t rejected[4];
+  int32_t iterations;
+  int32_t status;           /* MPSFM_ICP_* */
+  float ms;                 /* device time of the launches (HIP events), transfers excluded */
+  int32_t reserved;
+} mpsfm_icp_result;
+#ifdef __cplusplus
+static_assert(sizeof(mpsfm_icp_result) == 504 && offsetof(mpsfm_icp_result, scale) == 96 && offsetof(mpsfm_icp_result, iterations) == 488,
+              "ABI of mpsfm_icp_result");
+#endif
+
+int mpsfm_depth_normals(int32_t H, int32_t W, const double* depth /* [H][W] */, const double* intr, double edge_ratio, int32_t device,
+                        double* normals /* [H][W][3] */, uint8_t* valid /* [H][W] */);
+
+int mpsfm_depth_pair_icp(int32_t H0, int32_t W0, const double* depth0 /* [H0][W0] */, const double* intr0, int32_t H1, int32_t W1,
+                         const double* depth1 /* [H1][W1] */, const double* intr1, const double* init /* [12] */, double scale,
+                         const mpsfm_icp_options* options, int32_t device, double* trace /* [max_iterations][4] or NULL */,
+                         mpsfm_icp_result* result);
+
+int mpsfm_depth_pair_register_dense(int32_t H0, int32_t W0, const double* depth0 /* [H0][W0] */, const double* intr0,
+                                    int32_t H1, int32_t W1, const double* depth1 /* [H1][W1] */, const double* intr1,
+                                    int64_t n0, const double* xy0 /* [n0][2] */, int64_t n1, const double* xy1 /* [n1][2] */,
+                                    int64_t m, const int32_t* matches /* [m][2] */, int32_t with_scale,
+                                    const mpsfm_align3d_options* options, const mpsfm_icp_options* icp_options, int32_t device,
+                                    uint8_t* valid /* [m] */, uint8_t* inlier_mask /* [m] */, double* lifted0 /* [m][3] */,
+                                    double* lifted1 /* [m][3] */, mpsfm_align3d_result* result,
+                                    double* trace /* [max_iterations][4] or NULL */, mpsfm_icp_result* icp);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,20 @@ class CAlign3dResult(C.Structure):
                 ("num_batches", C.c_int32), ("ms", C.c_float)]
 
 
+class CIcpOptions(C.Structure):
+    _c_name_ = "mpsfm_icp_options"
+    _fields_ = [("max_distance", C.c_double), ("max_angle_deg", C.c_double), ("edge_ratio", C.c_double), ("eps_rotation", C.c_double),
+                ("eps_translation", C.c_double), ("max_iterations", C.c_int32), ("min_pairs", C.c_int32), ("stride", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class CIcpResult(C.Structure):
+    _c_name_ = "mpsfm_icp_result"
+    _fields_ = [("tgt_from_src", C.c_double * 12), ("scale", C.c_double), ("info", C.c_double * 36), ("rhs", C.c_double * 6),
+                ("rmse", C.c_double), ("num_pairs", C.c_int64), ("rejected", C.c_int64 * 4), ("iterations", C.c_int32),
+                ("status", C.c_int32), ("ms", C.c_float), ("reserved", C.c_int32)]
+
+
 class CRelPoseResult(C.Structure):
     _c_name_ = "mpsfm_rel_pose_result"
     _fields_ = [("E", C.c_double * 9), ("cam2_from_cam1", C.c_double * 12), ("num_inliers", C.c_int64), ("num_trials", C.c_int64),
@@ -508,6 +522,9 @@ SIGNATURES = {
     "mpsfm_align3d_fit": (C.c_int, [I64, P, P, P, I32, I32, P]),
     "mpsfm_lift_keypoints": (C.c_int, [I32, I32, P, P, I64, P, I32, P, P]),
     "mpsfm_depth_pair_register": (C.c_int, [I32, I32, P, P, I32, I32, P, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, P, P, P]),
+    "mpsfm_depth_normals": (C.c_int, [I32, I32, P, P, F64, I32, P, P]),
+    "mpsfm_depth_pair_icp": (C.c_int, [I32, I32, P, P, I32, I32, P, P, P, F64, P, I32, P, P]),
+    "mpsfm_depth_pair_register_dense": (C.c_int, [I32, I32, P, P, I32, I32, P, P, I64, P, I64, P, I64, P, I32, P, P, I32, P, P, P, P, P, P, P]),
 }
 
 # include/mpsfm_hip_debug.h: test and diagnostic hooks, outside the stable ABI

@@ -12,7 +12,7 @@ import numpy as np
 
 from .abi import (  # noqa: F401 - declared in abi.py; these names stay importable from here
     ALLREDUCE_FN, LIB_PATH, SIGNATURES, CAbsPoseOptions, CAbsPoseResult, CAlign3dOptions, CAlign3dResult, CCorrGraphInfo, CDcImage, CDebugLmCtl, CDebugLmOpts, CDcSummary, CDepthGather, CDepthPriorConf,
-    CDepthPriorOutput, CDepthPriorProblem, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CLiftInfo, CLiftMaps, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
+    CDepthPriorOutput, CDepthPriorProblem, CIcpOptions, CIcpResult, CInitCandidates, CInitPair, CIntProblem, CIntSummary, CLiftInfo, CLiftMaps, CMatchBatchReport, CMatchInfo, CMatchOptions, CNmsInfo,
     CNormalPriorConf, CNormalPriorOutput, CNormalPriorProblem, COptions, CPriorSummary, CProblem, CRansacOptions, CRecipInfo,
     CRecipOptions, CRegImage, CRelPoseOptions, CRetrievalInfo, CSceneFilterInfo, CSceneFilterOptions, CSceneQueryInfo, CTriGraph, CTriState, CRetrievalOptions, CRelPoseResult, CState, CSummary, CTracks, CTriCandidates, CTwoViewBatchReport, CTwoViewLeg, CTwoViewOptions,
     CTwoViewResult, CWarpInfo, CWarpOptions, MpsfmHipError, lib,
@@ -748,6 +748,79 @@ def depth_pair_register(depth0, intr0, depth1, intr1, xy0, xy1, matches, with_sc
                                            mt.ctypes.data, int(bool(with_scale)), C.byref(opt), int(device), valid.ctypes.data,
                                            mask.ctypes.data, l0.ctypes.data, l1.ctypes.data, C.byref(R)))
     return dict(_align3d_report(R, mask, m), valid=valid[:m].astype(bool), lifted0=l0[:m], lifted1=l1[:m])
+
+
+ICP_DEFAULTS = dict(max_distance=0.1, max_angle_deg=30.0, edge_ratio=0.05, eps_rotation=1e-6, eps_translation=1e-6, max_iterations=30,
+                    min_pairs=100, stride=1)
+ICP_STATUS = ("converged", "max_iterations", "too_few_pairs", "singular")  # MPSFM_ICP_*
+
+
+def _icp_options(options: dict) -> CIcpOptions:
+    o = dict(ICP_DEFAULTS)
+    unknown = set(options) - set(o)
+    if unknown:
+        raise KeyError(f"unknown option(s) {sorted(unknown)}")
+    o.update(options)
+    return CIcpOptions(float(o["max_distance"]), float(o["max_angle_deg"]), float(o["edge_ratio"]), float(o["eps_rotation"]),
+                       float(o["eps_translation"]), int(o["max_iterations"]), int(o["min_pairs"]), int(o["stride"]), 0)
+
+
+def _icp_report(R, trace: np.ndarray) -> dict:
+    it = int(R.iterations)
+    return dict(tgt_from_src=np.array(R.tgt_from_src[:]).reshape(3, 4), scale=float(R.scale), info=np.array(R.info[:]).reshape(6, 6),
+                rhs=np.array(R.rhs[:]), rmse=float(R.rmse), num_pairs=int(R.num_pairs), rejected=[int(v) for v in R.rejected],
+                iterations=it, status=ICP_STATUS[int(R.status)], trace=trace[:it].copy(), ms=float(R.ms))
+
+
+def depth_normals(depth, intr, edge_ratio=ICP_DEFAULTS["edge_ratio"], device=0):
+    """mpsfm_depth_normals: the camera-facing normals of a depth map [H, W] by central differences of its vertex map.  Returns
+    (normals float64 [H, W, 3], valid bool [H, W]); pixels without a normal (border, hole, depth edge) are zeros."""
+    d, K = _depth_map(depth, intr)
+    H, W = d.shape
+    normals, valid = np.zeros((H, W, 3)), np.zeros((H, W), np.uint8)
+    _check(lib().mpsfm_depth_normals(H, W, d.ctypes.data, K.ctypes.data, float(edge_ratio), int(device), normals.ctypes.data,
+                                     valid.ctypes.data))
+    return normals, valid.astype(bool)
+
+
+def depth_pair_icp(depth0, intr0, depth1, intr1, init, scale=1.0, device=0, **options) -> dict:
+    """mpsfm_depth_pair_icp: dense point-to-plane ICP of map 0 onto map 1 from init [3, 4] = [R | t] at the fixed `scale`.
+    `options`: keys of ICP_DEFAULTS.  Returns dict(tgt_from_src [3,4], scale, info [6,6], rhs [6], rmse, num_pairs, rejected [4],
+    iterations, status (a name of ICP_STATUS), trace [iterations, 4] = pair count, rmse, |w|, |v|, ms)."""
+    opt = _icp_options(options)
+    d0, K0 = _depth_map(depth0, intr0)
+    d1, K1 = _depth_map(depth1, intr1)
+    T = np.ascontiguousarray(init, np.float64).reshape(12)
+    trace = np.zeros((max(int(opt.max_iterations), 1), 4))
+    R = CIcpResult()
+    _check(lib().mpsfm_depth_pair_icp(d0.shape[0], d0.shape[1], d0.ctypes.data, K0.ctypes.data, d1.shape[0], d1.shape[1], d1.ctypes.data,
+                                      K1.ctypes.data, T.ctypes.data, float(scale), C.byref(opt), int(device), trace.ctypes.data, C.byref(R)))
+    return _icp_report(R, trace)
+
+
+def depth_pair_register_dense(depth0, intr0, depth1, intr1, xy0, xy1, matches, with_scale=False, device=0, icp=None, **options) -> dict:
+    """mpsfm_depth_pair_register_dense: depth_pair_register, then depth_pair_icp from its model on the maps already on the
+    device.  `options`: keys of ALIGN3D_DEFAULTS; `icp`: a dict with keys of ICP_DEFAULTS.  Returns depth_pair_register's dict
+    plus refined = depth_pair_icp's dict (None when no model was found)."""
+    opt = _ransac_options(ALIGN3D_DEFAULTS, options)
+    iopt = _icp_options(dict(icp or {}))
+    d0, K0 = _depth_map(depth0, intr0)
+    d1, K1 = _depth_map(depth1, intr1)
+    k0 = np.ascontiguousarray(xy0, np.float64).reshape(-1, 2)
+    k1 = np.ascontiguousarray(xy1, np.float64).reshape(-1, 2)
+    mt = np.ascontiguousarray(matches, np.int32).reshape(-1, 2)
+    m = len(mt)
+    valid, mask = np.zeros(max(m, 1), np.uint8), np.zeros(max(m, 1), np.uint8)
+    l0, l1 = np.zeros((max(m, 1), 3)), np.zeros((max(m, 1), 3))
+    trace = np.zeros((max(int(iopt.max_iterations), 1), 4))
+    R, RI = CAlign3dResult(), CIcpResult()
+    _check(lib().mpsfm_depth_pair_register_dense(d0.shape[0], d0.shape[1], d0.ctypes.data, K0.ctypes.data, d1.shape[0], d1.shape[1],
+                                                 d1.ctypes.data, K1.ctypes.data, len(k0), k0.ctypes.data, len(k1), k1.ctypes.data, m,
+                                                 mt.ctypes.data, int(bool(with_scale)), C.byref(opt), C.byref(iopt), int(device),
+                                                 valid.ctypes.data, mask.ctypes.data, l0.ctypes.data, l1.ctypes.data, C.byref(R),
+                                                 trace.ctypes.data, C.byref(RI)))
+    return dict(_align3d_report(R, mask, m), valid=valid[:m].astype(bool), lifted0=l0[:m], lifted1=l1[:m],
+                refined=_icp_report(RI, trace) if R.success else None)
 
 
 # COLMAP 3.11 TwoViewGeometryOptions as recalled (mpsfm_two_view_default_options)

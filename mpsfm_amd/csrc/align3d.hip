@@ -10,13 +10,15 @@
 //   k_a3_lift_matches  one thread per match: both ends lifted
 //   k_a3_compact       one workgroup: the valid matches in match order as the estimator's SoA points
 //   k_a3_scatter       the estimator's mask back to the matches
-// f64 throughout.
+// a3_register_check / a3_register_device (align3d_device.h) are mpsfm_depth_pair_register in two halves, so that
+// mpsfm_depth_pair_register_dense (depth_icp.hip) continues on the same scope and the same uploaded maps.  f64 throughout.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "align3d_device.h"
 #include "align3d_math.h"
 #include "common.h"
 #include "lo_ransac.h"
@@ -204,8 +206,6 @@ void a3_soa(int32_t n, const double* src, const double* tgt, std::vector<double>
 A3Pts a3_pts(const double* d, size_t stride) { return A3Pts{d, d + stride, d + 2 * stride, d + 3 * stride, d + 4 * stride, d + 5 * stride}; }
 
 // ---- lifting -----------------------------------------------------------------------------------------------------------
-struct A3Map { const double* depth; int32_t H, W; double intr[4]; };
-
 __global__ __launch_bounds__(kT) void k_a3_lift(A3Map m, int64_t n, const double* __restrict__ xy, double* __restrict__ xyz, uint8_t* __restrict__ valid) {
   const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
   if (i >= n) return;
@@ -364,11 +364,12 @@ extern "C" int mpsfm_lift_keypoints(int32_t H, int32_t W, const double* depth, c
   return 0;
 }
 
-extern "C" int mpsfm_depth_pair_register(int32_t H0, int32_t W0, const double* depth0, const double* intr0, int32_t H1, int32_t W1,
-                                         const double* depth1, const double* intr1, int64_t n0, const double* xy0, int64_t n1,
-                                         const double* xy1, int64_t m64, const int32_t* matches, int32_t with_scale,
-                                         const mpsfm_align3d_options* o, int32_t device, uint8_t* valid, uint8_t* inlier_mask,
-                                         double* lifted0, double* lifted1, mpsfm_align3d_result* result) {
+namespace mpsfm {
+
+int a3_register_check(int32_t H0, int32_t W0, const double* depth0, const double* intr0, int32_t H1, int32_t W1,
+                       const double* depth1, const double* intr1, int64_t n0, const double* xy0, int64_t n1, const double* xy1, int64_t m64,
+                       const int32_t* matches, int32_t with_scale, const mpsfm_align3d_options* o, uint8_t* valid, uint8_t* inlier_mask,
+                       double* lifted0, double* lifted1, mpsfm_align3d_result* result) {
   if (result) *result = mpsfm_align3d_result{};
   if (!o || !result) return fail(MPSFM_EINVAL, "NULL pointer");
   if (!a3_map_valid(H0, W0, depth0, intr0) || !a3_map_valid(H1, W1, depth1, intr1))
@@ -381,11 +382,14 @@ extern "C" int mpsfm_depth_pair_register(int32_t H0, int32_t W0, const double* d
     if (matches[2 * (size_t)i] < 0 || matches[2 * (size_t)i] >= n0 || matches[2 * (size_t)i + 1] < 0 || matches[2 * (size_t)i + 1] >= n1)
       return fail(MPSFM_EINVAL, "match index out of range");
   if (!lo_options_valid(*o)) return fail(MPSFM_EINVAL, "invalid RANSAC options");
-  if (m == 0) return 0;
-  if (int rc = open_device(device)) return rc;
+  return 0;
+}
 
-  CallScope A;
-  if (int rc = A.open(true)) return rc;
+int a3_register_device(CallScope& A, int32_t H0, int32_t W0, const double* depth0, const double* intr0, int32_t H1, int32_t W1,
+                       const double* depth1, const double* intr1, int64_t n0, const double* xy0, int64_t n1, const double* xy1, int64_t m64,
+                       const int32_t* matches, int32_t with_scale, const mpsfm_align3d_options* o, uint8_t* valid, uint8_t* inlier_mask,
+                       double* lifted0, double* lifted1, mpsfm_align3d_result* result, A3Map* map0, A3Map* map1) {
+  const int32_t m = (int32_t)m64;
   A3Map m0{A.put(depth0, (size_t)H0 * W0), H0, W0, {intr0[0], intr0[1], intr0[2], intr0[3]}};
   A3Map m1{A.put(depth1, (size_t)H1 * W1), H1, W1, {intr1[0], intr1[1], intr1[2], intr1[3]}};
   const double* d_xy0 = A.put(xy0, 2 * (size_t)n0);
@@ -423,6 +427,28 @@ extern "C" int mpsfm_depth_pair_register(int32_t H0, int32_t W0, const double* d
     }
   }
   MPSFM_TRY(A.down(inlier_mask, d_mask_m, (size_t)m));
+  if (map0) *map0 = m0;
+  if (map1) *map1 = m1;
+  return 0;
+}
+
+}  // namespace mpsfm
+
+extern "C" int mpsfm_depth_pair_register(int32_t H0, int32_t W0, const double* depth0, const double* intr0, int32_t H1, int32_t W1,
+                                         const double* depth1, const double* intr1, int64_t n0, const double* xy0, int64_t n1,
+                                         const double* xy1, int64_t m64, const int32_t* matches, int32_t with_scale,
+                                         const mpsfm_align3d_options* o, int32_t device, uint8_t* valid, uint8_t* inlier_mask,
+                                         double* lifted0, double* lifted1, mpsfm_align3d_result* result) {
+  if (int rc = a3_register_check(H0, W0, depth0, intr0, H1, W1, depth1, intr1, n0, xy0, n1, xy1, m64, matches, with_scale, o, valid, inlier_mask,
+                                 lifted0, lifted1, result))
+    return rc;
+  if (m64 == 0) return 0;
+  if (int rc = open_device(device)) return rc;
+  CallScope A;
+  if (int rc = A.open(true)) return rc;
+  if (int rc = a3_register_device(A, H0, W0, depth0, intr0, H1, W1, depth1, intr1, n0, xy0, n1, xy1, m64, matches, with_scale, o, valid,
+                                  inlier_mask, lifted0, lifted1, result, nullptr, nullptr))
+    return rc;
   result->ms = (float)A.ms;
   return 0;
 }

@@ -1,5 +1,6 @@
 """3D-3D alignment over libmpsfm_hip: ``estimate_rigid3d`` / ``estimate_sim3d``, their ``_robust`` forms and
-``register_depth_pair``.
+``register_depth_pair``; dense point-to-plane ICP of an RGB-D pair behind it: ``depth_to_normals``, ``refine_depth_pair``,
+``register_depth_pair_dense`` (``csrc/depth_icp.hip``).
 
 The reference has no estimator of this kind under ``mpsfm/``; its fork adds ``icp/main.py``, which registers an RGB-D pair
 with 5000 Python iterations of 3-point rigid alignment (``rigid_transform_3D``, :149-175) over depth-lifted keypoint matches.
@@ -23,6 +24,7 @@ from .absolute_pose import _Rotation3d
 
 RANSAC_DEFAULTS = {k: v for k, v in capi.ALIGN3D_DEFAULTS.items() if k not in ("seed", "batch_trials")}
 RANSAC_DEFAULTS["random_seed"] = -1
+ICP_DEFAULTS = dict(capi.ICP_DEFAULTS)
 
 
 class Sim3d:
@@ -107,3 +109,43 @@ def register_depth_pair(kps0, kps1, matches, depth0, depth1, intr0, intr1, with_
         return None
     return {"tgt_from_src": _transform(res), "num_inliers": res["num_inliers"], "inlier_mask": res["inlier_mask"], "valid": res["valid"],
             "lifted0": res["lifted0"], "lifted1": res["lifted1"], "report": res}
+
+
+def depth_to_normals(depth, intr, edge_ratio=ICP_DEFAULTS["edge_ratio"], device=0):
+    """The camera-facing normal map of a depth map (float32 or float64 [H, W]; PINHOLE intr = fx, fy, cx, cy) as the ICP forms
+    it: central differences of the vertex map, no normal on the border, over a hole or across a depth edge (a neighbour's depth
+    differs by more than ``edge_ratio`` of the pixel's).  Returns (normals [H, W, 3], valid bool [H, W])."""
+    return capi.depth_normals(depth, intr, edge_ratio=edge_ratio, device=device)
+
+
+def _pose_and_scale(tgt_from_src, scale):
+    if isinstance(tgt_from_src, Sim3d):
+        return np.concatenate([tgt_from_src.rotation.matrix(), tgt_from_src.translation[:, None]], axis=1), tgt_from_src.scale
+    return np.asarray(tgt_from_src, np.float64).reshape(3, 4), 1.0 if scale is None else float(scale)
+
+
+def _refined(res) -> dict:
+    return {"tgt_from_src": _transform(res), "status": res["status"], "iterations": res["iterations"], "num_pairs": res["num_pairs"],
+            "rmse": res["rmse"], "information": res["info"], "trace": res["trace"], "report": res}
+
+
+def refine_depth_pair(depth0, depth1, intr0, intr1, tgt_from_src, scale=None, device=0, **icp):
+    """Dense projective point-to-plane ICP of depth map 0 onto depth map 1 from ``tgt_from_src``: a ``Sim3d`` (its scale is kept),
+    or a 3 x 4 array [R | t] with ``scale`` (default 1).  The scale is held constant; R and t are refined.  ``icp``: keys of
+    ICP_DEFAULTS.  Returns ``{"tgt_from_src" (Sim3d), "status" ("converged", "max_iterations", "too_few_pairs", "singular"),
+    "iterations", "num_pairs", "rmse", "information" [6, 6] (order rotation, translation), "trace" [iterations, 4], "report"}``;
+    ``report`` is capi.depth_pair_icp's dict."""
+    T, s = _pose_and_scale(tgt_from_src, scale)
+    return _refined(capi.depth_pair_icp(depth0, intr0, depth1, intr1, T, scale=s, device=device, **icp))
+
+
+def register_depth_pair_dense(kps0, kps1, matches, depth0, depth1, intr0, intr1, with_scale=False, device=0, icp=None, **ransac):
+    """``register_depth_pair`` followed by ``refine_depth_pair`` from its model, in one call that uploads the maps once.  ``icp``: a
+    dict with keys of ICP_DEFAULTS; ``ransac``: keys of RANSAC_DEFAULTS.  Returns None when the RANSAC finds no model, else
+    ``register_depth_pair``'s dict plus ``"refined"``: ``refine_depth_pair``'s dict."""
+    res = capi.depth_pair_register_dense(depth0, intr0, depth1, intr1, kps0, kps1, matches, with_scale=with_scale, device=device, icp=icp,
+                                         **_ransac_kwargs(ransac))
+    if not res["success"]:
+        return None
+    return {"tgt_from_src": _transform(res), "num_inliers": res["num_inliers"], "inlier_mask": res["inlier_mask"], "valid": res["valid"],
+            "lifted0": res["lifted0"], "lifted1": res["lifted1"], "report": res, "refined": _refined(res["refined"])}
