@@ -84,7 +84,11 @@ void tile_pattern(const CamGraph& g, const std::vector<int32_t>& slot_of_nat, co
 // cuts (only without a forced depth): orders from a dissection by minimal window separators of a linear arrangement compete too
 // (graphs of 64 cameras and more whose chosen chain has 8 levels or more).  One of them replaces the choice above only with at
 // least two levels less, the inverse accumulators kept (nt <= pinv_max_tiles) where that choice has them, and no panel / trailing
-// item beyond the 2 / 4 sources of k_chol_level's unrolled forms — otherwise the plan is what cuts = false gives, table for table
+// item beyond the 2 / 4 sources of k_chol_level's unrolled forms — otherwise the plan is what cuts = false gives, table for table.
+// Beside the greedy tree of every hand-over limit (each part's best single cut) its refitted twin competes under the same rules:
+// the same tree brought to a chain one tile column shorter by cutting anew only the parts that are too long (refit, fit_dissect:
+// a bounded depth-first search, the same on any number of threads).  A refitted plan that breaks the source limits gives way
+// to the greedy one, that one to the legacy plan
 typedef void (*PlanParallelFor)(int n, void (*fn)(void* ctx, int i), void* ctx);
 void plan_auto(const CamGraph& g, int forced_depth, bool forced, bool cuts, int pinv_max_tiles, int inv_rows, CholPlan& P, PlanParallelFor pfor = nullptr);
 

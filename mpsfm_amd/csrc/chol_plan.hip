@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "../../include/mpsfm_hip_debug.h"
+#include "host_parts.h"
 
 namespace mpsfm {
 namespace {
@@ -20,6 +21,7 @@ constexpr int kMinCutCams = 64;   // ... and on graphs of at least this many cam
 constexpr int kMinCutLevels = 8;  // the window-separator orders are tried on chains of at least this many levels
 constexpr int kMinCutGain = 2;    // ... and taken for at least this many levels less: one level (~8 us per iteration) is within what
                                   // their padding columns and extra products may cost, two are not
+constexpr int kFitWork = 2;        // refit: cameras of the parts laid out anew, in graphs (2: one half of an orbit, all the way down)
 constexpr int kFastPanelSrc = 2, kFastTrailSrc = 4;  // sources the unrolled forms of k_chol_level take (dense_chol.hip: kPanelBatch, kTrailBatch)
 constexpr double kMaxPlanProducts = 3.0e6;  // tile products beyond which no item table is built (tens of MB of tables, seconds to build)
 
@@ -236,35 +238,59 @@ int tree_depth(const std::vector<Seg>& tree, int node) {  // separators above th
 
 struct WindowCut { int lo = 0, hi = 0; long cost = 1L << 60; int sep = 0, skew = 0; };  // separator [lo, hi) of the arrangement, trimmed sizes
 
-// the best window of one arrangement of a connected part; pos / far are scratch of g.n entries
-void best_window(const CamGraph& g, const Mask& in, const std::vector<int>& arr, std::vector<int>& pos, std::vector<int>& far, WindowCut& best, int& best_arr, int arr_id) {
+// far[q] / near[q]: the last / first position of an arrangement adjacent to position q (q itself if none); pos: scratch of g.n entries
+void reach_of(const CamGraph& g, const Mask& in, const std::vector<int>& arr, std::vector<int>& pos, std::vector<int>& far, std::vector<int>* near) {
   const int m = (int)arr.size();
   for (int q = 0; q < m; ++q) pos[(size_t)arr[(size_t)q]] = q;
   for (int q = 0; q < m; ++q) {
-    int f = q;
+    int f = q, n = q;
     const uint64_t* r = g.row(arr[(size_t)q]);
     for (int w = 0; w < g.words; ++w) {
       uint64_t b = r[w] & in[(size_t)w];
-      while (b) { f = std::max(f, pos[(size_t)(w * 64 + __builtin_ctzll(b))]); b &= b - 1; }
+      while (b) { const int p = pos[(size_t)(w * 64 + __builtin_ctzll(b))]; f = std::max(f, p); n = std::min(n, p); b &= b - 1; }
     }
     far[(size_t)q] = f;
+    if (near) (*near)[(size_t)q] = n;
   }
+}
+
+// every window of an arrangement of m cameras given its far[]: visit(c, e, nl, ns, nr) with the separator [c, e) and the sizes of
+// the left part, the separator and the right part once the window cameras that see nothing beyond the window have gone to the left
+// near (optional): those of the rest that see nothing before the window are counted to the right part, as split_at_window() does
+template <class Visit>
+void windows_of(const std::vector<int>& far, const std::vector<int>* near, int m, Visit&& visit) {
   int reach = -1;  // max far[0 .. c)
   for (int c = 1; c < m; ++c) {
     reach = std::max(reach, far[(size_t)c - 1]);
     const int e = std::max(c, reach + 1);
     if (e >= m) break;  // reach only grows: no later window leaves a right part
     if (e == c) continue;  // (a connected part has no empty separator)
-    int back = 0;  // window cameras that see nothing beyond the window go to the left part
-    for (int q = c; q < e; ++q) back += far[(size_t)q] < e;
-    const int nl = c + back, ns = e - c - back, nr = m - e;
+    int back = 0, front = 0;  // window cameras that see nothing beyond the window go to the left part
+    for (int q = c; q < e; ++q) {
+      if (far[(size_t)q] < e) ++back;
+      else if (near && (*near)[(size_t)q] >= c) ++front;
+    }
+    const int nl = c + back, ns = e - c - back - front, nr = m - e + front;
     if (ns <= 0) continue;
+    visit(c, e, nl, ns, nr);
+  }
+}
+
+template <class Visit>
+void for_each_window(const CamGraph& g, const Mask& in, const std::vector<int>& arr, std::vector<int>& pos, std::vector<int>& far, Visit&& visit) {
+  reach_of(g, in, arr, pos, far, nullptr);
+  windows_of(far, nullptr, (int)arr.size(), visit);
+}
+
+// the best window of one arrangement by the chain of ONE cut in tiles
+void best_window(const CamGraph& g, const Mask& in, const std::vector<int>& arr, std::vector<int>& pos, std::vector<int>& far, WindowCut& best, int& best_arr, int arr_id) {
+  for_each_window(g, in, arr, pos, far, [&](int c, int e, int nl, int ns, int nr) {
     const long cost = std::max(seg_tiles(nl), seg_tiles(nr)) + seg_tiles(ns);
     const int skew = std::abs(nl - nr);
     if (cost < best.cost || (cost == best.cost && (ns < best.sep || (ns == best.sep && skew < best.skew)))) {
       best.lo = c; best.hi = e; best.cost = cost; best.sep = ns; best.skew = skew; best_arr = arr_id;
     }
-  }
+  });
 }
 
 using Tree = std::vector<Seg>;  // node 0 is the root
@@ -275,6 +301,22 @@ int graft(Tree& t, Tree&& sub) {  // appends a tree, returns where its root went
     t.push_back(std::move(s));
   }
   return off;
+}
+
+// the three node sets of the window [lo, hi) of an arrangement: window cameras that see nothing on the right go
+// to the left part, those that then see nothing on the left to the right one.  false: no separator is left, or nothing beside it
+bool split_at_window(Sub& S, const std::vector<int>& ar, int lo, int hi, std::vector<int>& A, std::vector<int>& sep, std::vector<int>& B) {
+  std::vector<int> keep, right;
+  A.assign(ar.begin(), ar.begin() + lo); sep.assign(ar.begin() + lo, ar.begin() + hi); B.assign(ar.begin() + hi, ar.end());
+  S.set_nodes(B);
+  for (int v : sep) { if (S.degree(v) > 0) keep.push_back(v); else A.push_back(v); }
+  sep.swap(keep); keep.clear();
+  S.set_nodes(A);
+  for (int v : sep) { if (S.degree(v) > 0) keep.push_back(v); else right.push_back(v); }
+  if (keep.empty() || keep.size() >= ar.size()) return false;
+  sep.swap(keep);
+  B.insert(B.begin(), right.begin(), right.end());  // (all three in the order of the arrangement)
+  return true;
 }
 
 Tree cut_dissect(Sub& S, const std::vector<int>& nodes, int move_up) {
@@ -297,15 +339,8 @@ Tree cut_dissect(Sub& S, const std::vector<int>& nodes, int move_up) {
     int which = -1;
     for (int a = 0; a < kArr; ++a) best_window(S.g, S.in, arr[a], pos, far, cut, which, a);
     if (which >= 0 && cut.cost <= seg_tiles(m)) {
-      const std::vector<int>& ar = arr[which];
-      std::vector<int> A(ar.begin(), ar.begin() + cut.lo), sep(ar.begin() + cut.lo, ar.begin() + cut.hi), B(ar.begin() + cut.hi, ar.end()), keep;
-      S.set_nodes(B);
-      for (int v : sep) { if (S.degree(v) > 0) keep.push_back(v); else A.push_back(v); }
-      sep.swap(keep); keep.clear();
-      S.set_nodes(A);  // and those that see nothing on the left side go to the right one
-      for (int v : sep) { if (S.degree(v) > 0) keep.push_back(v); else B.push_back(v); }
-      if (!keep.empty() && (int)keep.size() < m) {
-        sep.swap(keep);
+      std::vector<int> A, sep, B;
+      if (split_at_window(S, arr[which], cut.lo, cut.hi, A, sep, B)) {
         std::sort(A.begin(), A.end()); std::sort(B.begin(), B.end()); std::sort(sep.begin(), sep.end());
         Tree cand(1);
         const int ca = graft(cand, cut_dissect(S, A, move_up));
@@ -319,6 +354,168 @@ Tree cut_dissect(Sub& S, const std::vector<int>& nodes, int move_up) {
   }
   rcm(S, nodes, t[0].cams);
   return t;
+}
+
+// ---- dissection to a GIVEN chain (round 14) -------------------------------------------------------------------------------------
+// cut_dissect() takes every part's best single cut.  That balances a cut in the tiles of its two sides as they are, not as they
+// will be once they are cut themselves: at C3 one half of the orbit came out a tile column longer than the other (a leaf chain
+// of four beside one of two), and the root waited for it.  fit_dissect() asks the other way round: can this part be laid out
+// with a chain of at most T tile columns?  A part that fits T undivided gets its greedy tree (refit(), below, keeps every
+// greedy subtree that is short enough: only parts on the critical path are cut differently, or once more).  Otherwise the part
+// is laid out breadth-first from a pseudo-peripheral camera and smoothed, and for every separator size in tiles ts < T, the window that leaves
+// the smaller larger side is tried (for sides of one kind, the one with fewer cameras fits if any does), and both sides must
+// fit T - ts.  The hand-over of flatten() is counted where a size is turned into tiles (a segment a camera or two over a tile
+// boundary is a tile shorter), and every tree that is put together is checked with chain_tiles(), which knows what the
+// children hand up.  Depth first, the first tree that fits wins; `budget` counts down the cameras of the parts laid out.
+inline int handed_tiles(int cams, bool is_root, int move_up) {  // tiles of a segment after the hand-over, as in flatten()
+  if (!is_root) {
+    const int whole = (6 * cams) / kTileCols * kTileCols / 6, over = cams - whole;
+    if (over > 0 && over <= move_up && whole > 0 && (6 * cams) % kTileCols != 0) cams = whole;
+  }
+  return seg_tiles(cams);
+}
+
+// A breadth-first order lists the cameras of one level in the order of the caller's numbering, and a window is as wide as the
+// worst of them.  Here every camera moves to the mean position of itself and its neighbours, twice: inside a level the cameras
+// that see further back come first, whatever they are called (pos: scratch of g.n entries).
+void smoothed(const CamGraph& g, const Mask& in, const std::vector<int>& from, std::vector<int>& pos, std::vector<int>& out) {
+  const int m = (int)from.size();
+  out = from;
+  std::vector<std::pair<double, int>> key((size_t)m);
+  for (int sweep = 0; sweep < 2; ++sweep) {
+    for (int q = 0; q < m; ++q) pos[(size_t)out[(size_t)q]] = q;
+    for (int q = 0; q < m; ++q) {
+      long sum = q, cnt = 1;
+      const uint64_t* r = g.row(out[(size_t)q]);
+      for (int w = 0; w < g.words; ++w) {
+        uint64_t b = r[w] & in[(size_t)w];
+        while (b) { sum += pos[(size_t)(w * 64 + __builtin_ctzll(b))]; ++cnt; b &= b - 1; }
+      }
+      key[(size_t)q] = {(double)sum / (double)cnt, q};
+    }
+    std::sort(key.begin(), key.end());
+    std::vector<int> next((size_t)m);
+    for (int q = 0; q < m; ++q) next[(size_t)q] = out[(size_t)key[(size_t)q].second];
+    out.swap(next);
+  }
+}
+
+bool fit_dissect(Sub& S, const std::vector<int>& nodes, int T, bool is_root, int move_up, int& budget, Tree& out) {
+  const int m = (int)nodes.size();
+  if (T <= 0 || (budget -= m) < 0) return false;
+  std::vector<std::vector<int>> comps;
+  components(S, nodes, comps);
+  if (comps.size() > 1) {
+    Tree t(1);
+    for (const auto& c : comps) {
+      Tree sub;
+      if (!fit_dissect(S, c, T, false, move_up, budget, sub)) return false;
+      const int ch = graft(t, std::move(sub));
+      t[0].child.push_back(ch);
+    }
+    int up = 0;
+    if (chain_tiles(t, 0, is_root, move_up, up) > T) return false;
+    out = std::move(t);
+    return true;
+  }
+  int up = 0;
+  if (handed_tiles(m, is_root, move_up) <= T) {  // fits undivided: the greedy tree, which is no longer than that
+    Tree greedy = cut_dissect(S, nodes, move_up);
+    if (chain_tiles(greedy, 0, is_root, move_up, up) > T) return false;
+    out = std::move(greedy);
+    return true;
+  }
+  if (m < 3) return false;
+  constexpr int kArr = 2;  // breadth-first from a pseudo-peripheral camera, smoothed; forwards and backwards
+  std::vector<int> arr[kArr], pos((size_t)S.g.n, 0), far[kArr], near[kArr], ls;
+  {
+    std::vector<int> bfs;
+    pseudo_peripheral(S, nodes, bfs, ls);  // (leaves S.in = nodes)
+    smoothed(S.g, S.in, bfs, pos, arr[0]);
+  }
+  arr[1].assign(arr[0].rbegin(), arr[0].rend());
+  for (int a = 0; a < kArr; ++a) { far[a].resize((size_t)m); near[a].resize((size_t)m); }
+  reach_of(S.g, S.in, arr[0], pos, far[0], &near[0]);
+  for (int q = 0; q < m; ++q) { far[1][(size_t)(m - 1 - q)] = m - 1 - near[0][(size_t)q]; near[1][(size_t)(m - 1 - q)] = m - 1 - far[0][(size_t)q]; }
+  struct Win { int arr = -1, lo = 0, hi = 0, side = 0, sep = 0, ts = 0; };
+  std::vector<Win> wins;
+  int ts_min = T;
+  for (int a = 0; a < kArr; ++a)
+    windows_of(far[a], &near[a], m, [&](int c, int e, int nl, int ns, int nr) {
+      const int ts = handed_tiles(ns, is_root, move_up);
+      ts_min = std::min(ts_min, ts);
+      if (ts < T) wins.push_back(Win{a, c, e, std::max(nl, nr), ns, ts});
+    });
+  // A side larger than what T - ts tiles can hold is not tried.  What they can hold is reckoned with separators half as wide as
+  // the narrowest of THIS part, in tiles, for every cut below (half: a window of an orbit cuts two fronts, the windows of its
+  // arcs one).  True of a graph that looks the same everywhere, a guess elsewhere — which may miss a tree there, and keeps a
+  // search that cannot succeed from walking the whole part.
+  const int ts_below = (ts_min + 1) / 2;
+  std::vector<int> holds((size_t)T, 0);  // [t]: cameras a chain of t tiles can hold
+  for (int k = 1; k < T; ++k) {
+    const auto leaf = [&](int t) { return kTileCols * t / 6 + move_up; };
+    holds[(size_t)k] = std::max(leaf(k), k > ts_below ? 2 * holds[(size_t)(k - ts_below)] + leaf(ts_below) : 0);
+  }
+  std::vector<Win> by_tiles((size_t)T);  // [ts]: the window of ts separator tiles with the smaller larger side
+  for (const Win& c : wins) {
+    Win& w = by_tiles[(size_t)c.ts];
+    if (c.side > holds[(size_t)(T - c.ts)]) continue;
+    if (w.arr < 0 || c.side < w.side || (c.side == w.side && c.sep < w.sep)) w = c;
+  }
+  for (int ts = 1; ts < T; ++ts) {
+    const Win& w = by_tiles[(size_t)ts];
+    if (w.arr < 0) continue;
+    std::vector<int> A, sep, B;
+    if (!split_at_window(S, arr[w.arr], w.lo, w.hi, A, sep, B)) continue;
+    std::sort(A.begin(), A.end()); std::sort(B.begin(), B.end()); std::sort(sep.begin(), sep.end());
+    const int rest = T - handed_tiles((int)sep.size(), is_root, move_up);
+    Tree cand(1), left, right;
+    if (!fit_dissect(S, A, rest, false, move_up, budget, left) || !fit_dissect(S, B, rest, false, move_up, budget, right)) continue;
+    const int ca = graft(cand, std::move(left));
+    const int cb = graft(cand, std::move(right));
+    cand[0].child = {ca, cb};
+    rcm(S, sep, cand[0].cams);
+    if (chain_tiles(cand, 0, is_root, move_up, up) <= T) { out = std::move(cand); return true; }
+  }
+  return false;
+}
+
+void subtree_cams(const Tree& t, int node, std::vector<int>& cams) {
+  cams.insert(cams.end(), t[(size_t)node].cams.begin(), t[(size_t)node].cams.end());
+  for (int c : t[(size_t)node].child) subtree_cams(t, c, cams);
+}
+Tree subtree(const Tree& t, int node) {
+  Tree s(1);
+  s[0].cams = t[(size_t)node].cams;
+  for (int c : t[(size_t)node].child) { const int ch = graft(s, subtree(t, c)); s[0].child.push_back(ch); }
+  return s;
+}
+
+// A tree brought to a chain of at most T tile columns with as little of it cut anew as will do: a subtree that is short enough
+// stays; one that is not first keeps its separator and shortens what is too long below it, and only if that fails is laid
+// out again as a whole by fit_dissect().  On the greedy tree of C3 this re-cuts one eighth of the orbit.
+bool refit(Sub& S, const Tree& t, int node, int T, bool is_root, int move_up, int& budget, Tree& out) {
+  int up = 0;
+  if (chain_tiles(t, node, is_root, move_up, up) <= T) { out = subtree(t, node); return true; }
+  if (T <= 0 || budget < 0) return false;
+  const Seg& seg = t[(size_t)node];
+  const int rest = T - (seg.cams.empty() ? 0 : handed_tiles((int)seg.cams.size(), is_root, move_up));
+  if (!seg.child.empty() && rest > 0) {
+    Tree cand(1);
+    cand[0].cams = seg.cams;
+    bool ok = true;
+    for (int c : seg.child) {
+      Tree sub;
+      if (!(ok = refit(S, t, c, rest, false, move_up, budget, sub))) break;
+      const int ch = graft(cand, std::move(sub));
+      cand[0].child.push_back(ch);
+    }
+    if (ok && chain_tiles(cand, 0, is_root, move_up, up) <= T) { out = std::move(cand); return true; }
+  }
+  std::vector<int> nodes;
+  subtree_cams(t, node, nodes);
+  std::sort(nodes.begin(), nodes.end());
+  return fit_dissect(S, nodes, T, is_root, move_up, budget, out);
 }
 
 }  // namespace
@@ -525,8 +722,10 @@ void plan_auto(const CamGraph& g, int forced_depth, bool forced, bool cuts, int 
   // the other), the cheapest by the launch-cost model wins, ties go to the first in this list (what the sequential loop chose)
   // cut: an order from the dissection by window separators (below).  Its tree is built and rated by tile arithmetic beside the
   // legacy candidates (`chain`, O(cameras)); `rated`: it has its symbolic factorisation too
-  struct Cand { int depth, move_up; CholPlan P; std::vector<uint8_t> pat; bool cut = false, rated = false; int chain = 0; };
+  // fit: a cut candidate of the second pass, dissected to a given chain (fit_dissect) from what its first-pass twin reached
+  struct Cand { int depth, move_up; CholPlan P; std::vector<uint8_t> pat; bool cut = false, rated = false; int chain = 0; bool fit = false; Tree tree; };
   std::vector<Cand> cands;
+  cands.reserve(32);  // (never grows beyond: the passes hold pointers into it)
   for (int d = -1; d <= (forced ? -1 : dmax); ++d) {
     const int depth = forced ? forced_depth : d;
     for (int move_up : {0, 2, 4}) {
@@ -537,18 +736,29 @@ void plan_auto(const CamGraph& g, int forced_depth, bool forced, bool cuts, int 
   const size_t n_legacy = cands.size();
   if (cuts && !forced && g.n >= kMinCutCams)
     for (int move_up : {0, 2, 4}) { cands.push_back(Cand{0, move_up, CholPlan(), {}}); cands.back().cut = true; }
+  const size_t n_greedy = cands.size();
   auto evaluate = [&](Cand& c) {
     CholPlan& P = c.P;
     if (c.cut && !c.rated) {  // first pass: the tree, its chain in tiles and the order it gives
       Sub S(g);
       std::vector<int> all((size_t)g.n);
       for (int i = 0; i < g.n; ++i) all[(size_t)i] = i;
-      const Tree tree = cut_dissect(S, all, c.move_up);
+      c.tree = cut_dissect(S, all, c.move_up);
       int up = 0;
-      c.depth = tree_depth(tree, 0);
-      c.chain = chain_tiles(tree, 0, true, c.move_up, up);
-      slots_from_tree(tree, g.n, c.move_up, P.slot_of_nat, P.col_of_slot, P.n);
+      c.depth = tree_depth(c.tree, 0);
+      c.chain = chain_tiles(c.tree, 0, true, c.move_up, up);
+      slots_from_tree(c.tree, g.n, c.move_up, P.slot_of_nat, P.col_of_slot, P.n);
       return;
+    }
+    if (c.fit) {  // second pass: the greedy tree (c.tree) brought to the chain c.chain, then its symbolic factorisation
+      Sub S(g);
+      Tree found;
+      int up = 0, budget = kFitWork * g.n;
+      if (!refit(S, c.tree, 0, c.chain, true, c.move_up, budget, found)) { c.rated = false; return; }
+      c.tree.swap(found);
+      c.depth = tree_depth(c.tree, 0);
+      c.chain = chain_tiles(c.tree, 0, true, c.move_up, up);
+      slots_from_tree(c.tree, g.n, c.move_up, P.slot_of_nat, P.col_of_slot, P.n);
     }
     P.ncv = g.n; P.nd_depth = c.depth;
     P.nslots = g.n;
@@ -578,49 +788,65 @@ void plan_auto(const CamGraph& g, int forced_depth, bool forced, bool cuts, int 
   for (size_t i = 1; i < n_legacy; ++i)
     if (cands[i].P.est_us < cands[bi].P.est_us - 1e-9) bi = i;
   const size_t legacy = bi;
+  size_t greedy = legacy;  // the choice without the fitted trees (what round 12 took): what stands if a fitted plan is refused below
   // The second family: dissection by minimal window separators.  Only the best few trees by their arithmetic (an upper bound
   // of the levels, met on every graph tried) get a symbolic factorisation, and only where the arithmetic promises a gain.
   // Not taken on a short chain (fewer than kMinCutLevels levels: at most a launch or two to gain, against more padding
   // columns), which also keeps small systems on the plans the kernels' tests are built around.
   if (cands.size() > n_legacy && cands[legacy].P.nlevels >= kMinCutLevels) {
     constexpr size_t kMaxCutCands = 2;
+    const int want = cands[legacy].P.nlevels - kMinCutGain;  // a chain worth a symbolic factorisation
     todo.clear();
-    for (size_t i = n_legacy; i < cands.size(); ++i) {
+    for (size_t i = n_legacy; i < n_greedy; ++i) {
       Cand& c = cands[i];
-      bool known = c.depth < 1 || c.chain + kMinCutGain > cands[legacy].P.nlevels;  // nothing was cut, or too little to gain
+      bool known = c.depth < 1 || c.chain > want;  // nothing was cut, or too little to gain
       for (const Cand* o : todo) known = known || (o->P.slot_of_nat == c.P.slot_of_nat && o->P.col_of_slot == c.P.col_of_slot);
       if (!known) todo.push_back(&c);
     }
     std::stable_sort(todo.begin(), todo.end(), [](const Cand* a, const Cand* b) { return a->chain < b->chain; });
     if (todo.size() > kMaxCutCands) todo.resize(kMaxCutCands);
+    // ... and beside them one fitted tree per hand-over limit: a chain at least one tile column below the greedy tree's, and
+    // short enough to be taken
+    for (size_t i = n_legacy; i < n_greedy; ++i) {
+      if (cands[i].depth < 1) continue;
+      cands.push_back(Cand{0, cands[i].move_up, CholPlan(), {}});
+      cands.back().cut = cands.back().fit = true;
+      cands.back().chain = std::min(cands[i].chain - 1, want);
+      cands.back().tree = cands[i].tree;
+    }
+    for (size_t i = n_greedy; i < cands.size(); ++i) todo.push_back(&cands[i]);
     for (Cand* c : todo) c->rated = true;
     if (!todo.empty()) evaluate_all(todo);
     // A cut-search order replaces the legacy choice only with fewer levels (by kMinCutGain), and only if it keeps the inverse
     // accumulators where the legacy plan has them; among several, the fewest levels, then the cost model.
     const CholPlan& L = cands[legacy].P;
     for (size_t i = n_legacy; i < cands.size(); ++i) {
+      if (i == n_greedy) greedy = bi;
       const CholPlan& C = cands[i].P;
       if (!cands[i].rated || C.nlevels <= 0 || C.nlevels + kMinCutGain > L.nlevels || (L.nt <= pinv_max_tiles && C.nt > pinv_max_tiles)) continue;
       if (bi == legacy || C.nlevels < cands[bi].P.nlevels || (C.nlevels == cands[bi].P.nlevels && C.est_us < cands[bi].P.est_us - 1e-9)) bi = i;
     }
+    if (cands.size() == n_greedy) greedy = bi;
   }
-  best = std::move(cands[bi].P);
-  std::vector<uint8_t> best_pat = std::move(cands[bi].pat);
-  plan_from_pattern(best_pat, best.nt, best.nt <= pinv_max_tiles, inv_rows, best, /*tables=*/true);
-  if (bi != legacy) {
-    // ... and only if its items stay in the unrolled forms of k_chol_level (a panel with up to kFastPanelSrc sources, a trailing
-    // tile with up to kFastTrailSrc): a level of the slower list loops can cost what a level less saves.  Otherwise, and on any
-    // tie or loss above, the legacy plan stands as it was, table for table.
+  // ... and only if its items stay in the unrolled forms of k_chol_level (a panel with up to kFastPanelSrc sources, a trailing
+  // tile with up to kFastTrailSrc): a level of the slower list loops can cost what a level less saves.  A fitted plan that does
+  // not gives way to the greedy tree's, that one to the legacy plan, which, as on any tie or loss above, stands as it was, table
+  // for table.
+  std::vector<uint8_t> best_pat;
+  const size_t picks[3] = {bi, greedy, legacy};
+  for (int k = 0; k < 3; ++k) {
+    const size_t pick = picks[k];
+    if (k > 0 && pick == picks[k - 1]) continue;  // (refused a moment ago)
+    best = std::move(cands[pick].P);
+    best_pat = std::move(cands[pick].pat);
+    plan_from_pattern(best_pat, best.nt, best.nt <= pinv_max_tiles, inv_rows, best, /*tables=*/true);
+    if (pick == legacy) break;
     int psrc = 0, tsrc = 0;
     for (const CholItem& it : best.items) {
       if (it.type == kItemPanel) psrc = std::max<int>(psrc, it.nsrc);
       if (it.type == kItemTrail) tsrc = std::max<int>(tsrc, it.nsrc);
     }
-    if (psrc > kFastPanelSrc || tsrc > kFastTrailSrc) {
-      best = std::move(cands[legacy].P);
-      best_pat = std::move(cands[legacy].pat);
-      plan_from_pattern(best_pat, best.nt, best.nt <= pinv_max_tiles, inv_rows, best, /*tables=*/true);
-    }
+    if (psrc <= kFastPanelSrc && tsrc <= kFastTrailSrc) break;
   }
   best.nat_of_slot.assign((size_t)best.nslots, -1);
   for (int i = 0; i < g.n; ++i) best.nat_of_slot[(size_t)best.slot_of_nat[(size_t)i]] = i;
@@ -646,7 +872,9 @@ mpsfm_plan_handle* mpsfm_debug_plan_create(const uint8_t* adj, int32_t n, int32_
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) if (i != j && adj[(size_t)i * n + j]) g.set(i, j);
   auto* h = new mpsfm_plan_handle();
-  mpsfm::plan_auto(g, depth, depth >= -1, /*cuts=*/depth == -3, pinv_max_tiles, inv_rows, h->P);
+  // (-3 on the host threads a handle plans with, MPSFM_HOST_THREADS: the plan must not depend on how many there are)
+  mpsfm::plan_auto(g, depth, depth >= -1, /*cuts=*/depth == -3, pinv_max_tiles, inv_rows, h->P,
+                   depth != -3 ? nullptr : [](int n, void (*fn)(void*, int), void* ctx) { mpsfm::run_parts(n, [&](int t, int) { fn(ctx, t); }); });
   return h;
 }
 void mpsfm_debug_plan_destroy(mpsfm_plan_handle* h) { delete h; }
