@@ -423,6 +423,35 @@ typedef struct mpsfm_depth_gather {
 int mpsfm_depth_blocks(const mpsfm_depth_gather* g, int32_t device, uint8_t* flags /* [n_obs] */, double* depth,
                        double* depth3d, double* magnitude, double* param, double* whitened /* each [n_obs] */);
 
+/* -- row f3, the other half: the per-image prior scale fit of Optimizer.__build_shiftscale_problem
+ *    (mpsfm/sfm/mapper/bundle_adjustment.py:187-242) and the robust sigma of update_truncation_multiplier (:295-333,
+ *    fit_robust_gaussian_mad :10-15) over the same descriptor, with exact medians selected on the device: one host wait
+ *    and O(n_images) results per call.  obs_img must not decrease (MPSFM_EINVAL otherwise): an image's observations
+ *    are a range.  d, v = bilinear samples of the depth and the validity map, z = camera-frame depth, all formed as
+ *    mpsfm_depth_blocks forms them.  PINHOLE only; one map set per call; the maps are uploaded by every call.
+ *    what & FIT, per image i with img_mode[i] = 1 (0: the image is skipped, the reference's `continue`):
+ *      base selection v == 1 (n_valid counts it); img_filter[i] = 1 keeps 1/f < d / z < f (f = g->scale_filter_factor),
+ *      2 keeps 1/1.5 < map_scale[i] / (z / max(d, 1e-6) * im_scale[i]) < 1.5; r = max(z / d, 1e-6), a NaN stays a NaN.
+ *      fit_counts[i] = n_valid, n_sel, n_nan (NaNs among the selected r); fit_ratio[i] = the order statistics of rank
+ *      (m - 1) / 2 and m / 2 among the m = n_sel - n_nan ranked r (NaN when m = 0): np.median(np.log(r)) is
+ *      0.5 (log lo + log hi), NaN when n_nan > 0; fit_flags[i]: EMPTY = n_sel is 0, EMPTY_METRIC = also filter 2.
+ *    what & SIGMA, over all observations of the call: selection v == 1 and d > 0,
+ *      w = (log d - log z) / max(sqrt(var) / d, 1e-6); sigma_counts = n_sel, n_nan; sigma_stats = mu (mean of the two
+ *      middle order statistics of the ranked w), mad (the same of |w - mu|; NaN when one of them is a NaN); both NaN
+ *      when nothing is ranked.  sigma = 1.4826 mad, NaN when n_nan > 0.
+ *    ratio, whitened [n_obs] and selected [n_obs] (bit 0: v == 1 of a fitted image, bit 1: selected for FIT, bit 2:
+ *    selected for SIGMA) are optional (NULL: not written).  n_obs = 0: 0, with empty results.  Integer atomics only:
+ *    every output is the same bit pattern whatever the scheduling. ------------------------------------------------- */
+#define MPSFM_DEPTH_STATS_FIT 1
+#define MPSFM_DEPTH_STATS_SIGMA 2
+#define MPSFM_DEPTH_STATS_EMPTY 1u
+#define MPSFM_DEPTH_STATS_EMPTY_METRIC 2u
+int mpsfm_depth_stats(const mpsfm_depth_gather* g, int32_t what, const uint8_t* img_mode /* [n_images] */,
+                      const uint8_t* img_filter /* [n_images] */, const double* im_scale /* [n_images] */,
+                      const double* map_scale /* [n_images] */, int32_t device, int64_t* fit_counts /* [n_images][3] */,
+                      double* fit_ratio /* [n_images][2] */, uint32_t* fit_flags /* [n_images] */, int64_t* sigma_counts /* [2] */,
+                      double* sigma_stats /* [2] */, double* ratio, double* whitened, uint8_t* selected);
+
 /* -- depth-from-normals integration: replaces the per-image solve of Image.integrate()
  *    (mpsfm/sfm/scene/image/integration.py:133-137 -> _integrate :383-520): IRLS over a 5-point SPD
  *    system on the H*W log-depths with Jacobi-preconditioned CG (scipy/cupy `cg` semantics), bilateral

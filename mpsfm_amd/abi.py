@@ -484,6 +484,7 @@ SIGNATURES = {
     "mpsfm_triangulator_stats": (C.c_int, [P, _i64p, _i64p, _i64p]),
     "mpsfm_tri_estimate_batch": (C.c_int, [P, I32, P, P, P]),
     "mpsfm_depth_blocks": (C.c_int, [P, I32, P, P, P, P, P, P]),
+    "mpsfm_depth_stats": (C.c_int, [P, I32, P, P, P, P, I32, P, P, P, P, P, P, P, P]),
     "mpsfm_integrate_depth": (C.c_int, [P, I32, P, P]),
     "mpsfm_integrate_depth_batch": (C.c_int, [I32, P, I32, P, P]),
     "mpsfm_integration_variances": (C.c_int, [P, I32, I32, I32, P, P, F64, I32, P, P, P]),

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmpsfm_hip.so")
-SOURCES = ["ba_kernels.hip", "sweep_dense.hip", "local_lm.hip", "build_dev.hip", "build_host.hip", "dense_chol.hip", "dev_resources.hip", "ba_comm.hip", "ba_build.hip", "ba_solver.hip", "ba_debug.hip", "tri_kernels.hip", "int_kernels.hip", "prior_kernels.hip", "triangulator.hip", "chol_plan.hip", "depth_consistency.hip", "abs_pose.hip", "rel_pose.hip", "two_view.hip", "two_view_batch.hip", "registration.hip", "dense_matches.hip", "descriptor_matches.hip", "descriptor_matches_batch.hip", "retrieval.hip", "reciprocal_matches.hip", "warp_matches.hip", "mono_priors.hip", "corr_graph.hip", "scene_queries.hip", "lift_tracks.hip", "scene_filter.hip", "align3d.hip", "depth_icp.hip"]
+SOURCES = ["ba_kernels.hip", "sweep_dense.hip", "local_lm.hip", "build_dev.hip", "build_host.hip", "dense_chol.hip", "dev_resources.hip", "ba_comm.hip", "ba_build.hip", "ba_solver.hip", "ba_debug.hip", "tri_kernels.hip", "int_kernels.hip", "prior_kernels.hip", "triangulator.hip", "chol_plan.hip", "depth_consistency.hip", "abs_pose.hip", "rel_pose.hip", "two_view.hip", "two_view_batch.hip", "registration.hip", "dense_matches.hip", "descriptor_matches.hip", "descriptor_matches_batch.hip", "retrieval.hip", "reciprocal_matches.hip", "warp_matches.hip", "mono_priors.hip", "corr_graph.hip", "scene_queries.hip", "lift_tracks.hip", "scene_filter.hip", "align3d.hip", "depth_icp.hip", "depth_stats.hip"]
 HEADERS = ["common.h", "dev_resources.h", "ba_launch.h", "ba_handle.h", "devbuild.h", "build_host.h", "host_parts.h", "sweep_common.h", "sweep_dense_body.h", "sweep_update_body.h", "dense_tile.h", "lm_decide.h", "local_lm.h", "tri_math.h", "bilinear_sample.h", "abs_pose_math.h", "rel_pose_math.h", "rel_pose_problem.h", "two_view_math.h", "two_view_problem.h", "chol_plan.h", "call_scope.h", "lo_ransac.h", "point_grid.h", "resize_taps.h", "sim_tile.h", "sim_top2.h", "sim_topk.h", "local_bundle_walk.h", "tri_launch.h", "scene_filter_check.h", "align3d_math.h", "align3d_device.h", "icp_math.h", os.path.join("..", "..", "include", "mpsfm_hip.h"),
            os.path.join("..", "..", "include", "mpsfm_hip_debug.h")]
 

@@ -384,10 +384,8 @@ def lift_tracks(tr: Tracks, xyz, activated, depth_maps, valid_maps, sx, sy, min_
     return dict(risky=risky.astype(bool), lift_el=lift_el, lift_depth=lift_depth, lift_xyz=lift_xyz, el_keep=keep.astype(bool), info=info)
 
 
-def depth_blocks(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts, scale_filter_factor=1.5,
-                 multiplier=2.0, device=0):
-    """mpsfm_depth_blocks: the depth-block selection of a whole bundle in one launch.  `depth_maps` / `valid_maps`: one
-    [H,W] array per image.  Returns dict(flags uint8 [n], depth, depth3d, magnitude, param, whitened float64 [n])."""
+def _depth_gather(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts, scale_filter_factor, multiplier):
+    """Fills a CDepthGather; returns (G, the arrays it points into, n_images, n_obs)."""
     n_img = len(depth_maps)
     dm = [np.ascontiguousarray(m, np.float64) for m in depth_maps]
     vm = [np.ascontiguousarray(m, np.uint8) for m in valid_maps]
@@ -409,10 +407,54 @@ def depth_blocks(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_x
     G.obs_img, G.obs_xy, G.obs_var, G.obs_pt = obs_img.ctypes.data, obs_xy.ctypes.data, obs_var.ctypes.data, obs_pt.ctypes.data
     G.n_pts, G.pts = len(pts), pts.ctypes.data
     G.scale_filter, G.scale_filter_factor, G.gross_outliers, G.multiplier = 1, float(scale_filter_factor), 0, float(multiplier)
+    return G, (dm, vm, hh, ww, sx, sy, cam_quat, cam_t, obs_img, obs_pt, obs_xy, obs_var, pts, dptr, vptr), n_img, n
+
+
+def depth_blocks(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts, scale_filter_factor=1.5,
+                 multiplier=2.0, device=0):
+    """mpsfm_depth_blocks: the depth-block selection of a whole bundle in one launch.  `depth_maps` / `valid_maps`: one
+    [H,W] array per image.  Returns dict(flags uint8 [n], depth, depth3d, magnitude, param, whitened float64 [n])."""
+    G, _keep, n_img, n = _depth_gather(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts,
+                                       scale_filter_factor, multiplier)
     out = {k: np.zeros(n) for k in ("depth", "depth3d", "magnitude", "param", "whitened")}
     out["flags"] = np.zeros(n, np.uint8)
     _check(lib().mpsfm_depth_blocks(C.byref(G), device, out["flags"].ctypes.data, out["depth"].ctypes.data, out["depth3d"].ctypes.data,
                                     out["magnitude"].ctypes.data, out["param"].ctypes.data, out["whitened"].ctypes.data))
+    return out
+
+
+STATS_FIT, STATS_SIGMA = 1, 2              # MPSFM_DEPTH_STATS_FIT / _SIGMA
+STATS_EMPTY, STATS_EMPTY_METRIC = 1, 2     # flag bits of a fitted image
+SEL_VALID, SEL_FIT, SEL_SIGMA = 1, 2, 4    # bits of `selected`
+
+
+def depth_stats(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts, what=STATS_FIT | STATS_SIGMA,
+                mode=None, filter=None, im_scale=None, map_scale=None, scale_filter_factor=1.5, per_obs=False, device=0):
+    """mpsfm_depth_stats: the per-image prior scale fit (what & STATS_FIT) and the whole-call robust sigma (what & STATS_SIGMA)
+    with exact medians selected on the device.  The arguments of depth_blocks plus, per image, `mode` (0 skip / 1 fit; default 1),
+    `filter` (0 none / 1 scale / 2 metric scale; default 0), `im_scale` and `map_scale` (default 1).  `obs_img` must not decrease.
+    Returns dict(n_valid, n_sel, n_nan int64 [n_img], ratio_lo, ratio_hi float64 [n_img], flags uint32 [n_img], sigma_n_sel,
+    sigma_n_nan, mu, mad) — the keys of the parts asked for — and with per_obs also ratio, whitened float64 [n], selected uint8 [n]."""
+    G, _keep, n_img, n = _depth_gather(depth_maps, valid_maps, sx, sy, cam_quat, cam_t, obs_img, obs_xy, obs_var, obs_pt, pts,
+                                       scale_filter_factor, 1.0)
+    per_image = lambda a, dtype, fill: np.full(n_img, fill, dtype) if a is None else np.ascontiguousarray(a, dtype)  # noqa: E731
+    mode, filter = per_image(mode, np.uint8, 1), per_image(filter, np.uint8, 0)
+    im_scale, map_scale = per_image(im_scale, np.float64, 1.0), per_image(map_scale, np.float64, 1.0)
+    if not (len(mode) == len(filter) == len(im_scale) == len(map_scale) == n_img):
+        raise ValueError("mode, filter, im_scale and map_scale take one entry per image")
+    counts, ratio2, flags = np.zeros((max(n_img, 1), 3), np.int64), np.zeros((max(n_img, 1), 2)), np.zeros(max(n_img, 1), np.uint32)
+    s_counts, s_stats = np.zeros(2, np.int64), np.zeros(2)
+    obs = dict(ratio=np.zeros(n), whitened=np.zeros(n), selected=np.zeros(n, np.uint8)) if per_obs else {}
+    ptr = lambda k: obs[k].ctypes.data if per_obs else None  # noqa: E731
+    _check(lib().mpsfm_depth_stats(C.byref(G), int(what), mode.ctypes.data, filter.ctypes.data, im_scale.ctypes.data, map_scale.ctypes.data,
+                                   int(device), counts.ctypes.data, ratio2.ctypes.data, flags.ctypes.data, s_counts.ctypes.data,
+                                   s_stats.ctypes.data, ptr("ratio"), ptr("whitened"), ptr("selected")))
+    out = dict(obs)
+    if what & STATS_FIT:
+        out.update(n_valid=counts[:n_img, 0].copy(), n_sel=counts[:n_img, 1].copy(), n_nan=counts[:n_img, 2].copy(),
+                   ratio_lo=ratio2[:n_img, 0].copy(), ratio_hi=ratio2[:n_img, 1].copy(), flags=flags[:n_img].copy())
+    if what & STATS_SIGMA:
+        out.update(sigma_n_sel=int(s_counts[0]), sigma_n_nan=int(s_counts[1]), mu=float(s_stats[0]), mad=float(s_stats[1]))
     return out
 
 

@@ -19,6 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ...baseclass import BaseClass
+from ...capi import STATS_EMPTY, STATS_EMPTY_METRIC, STATS_FIT, STATS_SIGMA  # constants only: the library is loaded by the first call
 from ...utils.ids import index_in_sorted, unique_ids
 from ...problem import LOSS_BY_NAME, LOSS_CAUCHY, LOSS_SOFT_L1, LOSS_TRIVIAL, BAProblem
 from ..scene.prior_gather import F_GROSS, F_POSITIVE, F_SCALE, F_VALID, gather_bundle
@@ -62,6 +63,11 @@ class HipBackend:
         from ... import capi
 
         return capi.depth_blocks(device=self.device, **kw)
+
+    def depth_stats(self, **kw) -> dict:
+        from ... import capi
+
+        return capi.depth_stats(device=self.device, **kw)
 
 
 class _SortedIndex:
@@ -114,7 +120,12 @@ class Optimizer(BaseClass):
         "verbose": 0,
     }
 
-    def _init(self, mpsfm_rec, correspondences=None, backend=None):
+    def _init(self, mpsfm_rec, correspondences=None, backend=None, stats="host"):
+        """`stats`: where the medians of optimize_prior_shiftscale and update_truncation_multiplier are taken — "host" (the
+        per-image NumPy loop / the downloaded per-observation arrays) or "device" (one backend.depth_stats call each)."""
+        if stats not in ("host", "device"):
+            raise ValueError(f"stats must be 'host' or 'device', not {stats!r}")
+        self.stats = stats
         self.mpsfm_rec = mpsfm_rec
         self.correspondences = correspondences
         self.truncation_multiplier = 1
@@ -350,6 +361,8 @@ class Optimizer(BaseClass):
     # ------------------------------------------------------------------------------------------
     def _build_shiftscale_problem(self, bundle, allow_scale_filter=False, allow_metric_scale_filter=False):
         """Per-image median log-scale of projected vs prior depth (reference :187-242; no Ceres)."""
+        if self.stats == "device":
+            return self._build_shiftscale_problem_device(bundle, allow_scale_filter, allow_metric_scale_filter)
         conf, rec = self.conf, self.mpsfm_rec
         shift_scale = {}
         scale_filter, factor = conf.scale_filter, conf.scale_filter_factor
@@ -379,6 +392,49 @@ class Optimizer(BaseClass):
             shift_scale[imid] = np.array([0.0, np.median(np.log((z / odepth).clip(1e-6, None)))])
         return shift_scale, True
 
+    def _build_shiftscale_problem_device(self, bundle, allow_scale_filter=False, allow_metric_scale_filter=False):
+        """The same fit with the sampling, the filters and the medians of all images in one backend.depth_stats call: the host
+        decides per image what the loop above decides (skip, which filter, the map scale), gathers once, and walks the
+        O(n_images) results in optim_ids order, with the reference's early return at the first image the metric-scale filter
+        empties."""
+        conf, rec = self.conf, self.mpsfm_rec
+        scale_filter, factor = conf.scale_filter, conf.scale_filter_factor
+        metric, single = conf.metric_scale_filter, conf.single_rescale
+        plan = {}  # imid -> (filter, map_scale) of the images that are fitted
+        for imid in bundle["optim_ids"]:
+            if (factor or metric) and ("ref_id" in bundle and imid != bundle["ref_id"] and single):
+                continue
+            if allow_metric_scale_filter and metric and ((imid == bundle["ref_id"]) or (not single)):
+                plan[imid] = (2, np.mean([rec.images[i].depth.scale for i in bundle["optim_ids"] if i != imid]))
+            elif allow_scale_filter and scale_filter and not allow_metric_scale_filter:
+                plan[imid] = (1, 1.0)
+            else:
+                plan[imid] = (0, 1.0)
+        g = gather_bundle(rec, list(plan), "prior", activated_only=False)
+        row = {}
+        if g is not None:
+            row = {imid: k for k, imid in enumerate(g["images"])}
+            out = self.backend.depth_stats(
+                depth_maps=g["depth_maps"], valid_maps=g["valid_maps"], sx=g["sx"], sy=g["sy"], cam_quat=g["cam_quat"], cam_t=g["cam_t"],
+                obs_img=g["obs_img"], obs_xy=g["obs_xy"], obs_var=g["obs_var"], obs_pt=g["obs_pt"], pts=self._coordinates(g["point_ids"]),
+                what=STATS_FIT, filter=[plan[i][0] for i in g["images"]], im_scale=[rec.images[i].depth.scale for i in g["images"]],
+                map_scale=[plan[i][1] for i in g["images"]], scale_filter_factor=factor if factor else 1.5)
+        shift_scale = {}
+        for imid, (filt, map_scale) in plan.items():
+            k = row.get(imid)  # None: an image without observations, so nothing is selected
+            flags = out["flags"][k] if k is not None else STATS_EMPTY | (STATS_EMPTY_METRIC if filt == 2 else 0)
+            if flags & STATS_EMPTY_METRIC:
+                self.log("WARNING: all points are outliers for the metric scale fit; using the map scale", level=0)
+                shift_scale[imid] = np.array([0.0, np.log(map_scale / rec.images[imid].depth.scale)])
+                return shift_scale, True
+            if (flags & STATS_EMPTY) or out["n_nan"][k] > 0:
+                proposed = np.nan  # np.median of nothing, or of values with a NaN among them
+            else:
+                with np.errstate(divide="ignore"):
+                    proposed = 0.5 * (np.log(out["ratio_lo"][k]) + np.log(out["ratio_hi"][k]))
+            shift_scale[imid] = np.array([0.0, proposed])
+        return shift_scale, True
+
     def optimize_prior_shiftscale(self, bundle, **kwargs):
         """{imid: (shift, scale)} (reference :268-274)."""
         shift_scale, success = self._build_shiftscale_problem(bundle, **kwargs)
@@ -390,13 +446,21 @@ class Optimizer(BaseClass):
         """sigma of the whitened log-depth errors by MAD over the given images (reference :295-333); the per-keypoint
         sampling, projection and whitening run in the same launch as the depth-block selection."""
         g = gather_bundle(self.mpsfm_rec, imids, "update")
-        out = self.backend.depth_blocks(
-            depth_maps=g["depth_maps"], valid_maps=g["valid_maps"], sx=g["sx"], sy=g["sy"], cam_quat=g["cam_quat"], cam_t=g["cam_t"],
-            obs_img=g["obs_img"], obs_xy=g["obs_xy"], obs_var=g["obs_var"], obs_pt=g["obs_pt"], pts=self._coordinates(g["point_ids"]),
-            scale_filter_factor=self.conf.scale_filter_factor, multiplier=1.0)
-        f = out["flags"]
-        sel = ((f & F_VALID) != 0) & ((f & F_POSITIVE) != 0)
-        _, sigma = fit_robust_gaussian_mad(out["whitened"][sel])
+        if self.stats == "device":
+            out = self.backend.depth_stats(
+                depth_maps=g["depth_maps"], valid_maps=g["valid_maps"], sx=g["sx"], sy=g["sy"], cam_quat=g["cam_quat"], cam_t=g["cam_t"],
+                obs_img=g["obs_img"], obs_xy=g["obs_xy"], obs_var=g["obs_var"], obs_pt=g["obs_pt"], pts=self._coordinates(g["point_ids"]),
+                what=STATS_SIGMA)
+            # two scalars come back instead of six per-observation arrays; np.median's answers for a NaN and for no element
+            sigma = np.float64(np.nan if out["sigma_n_nan"] > 0 or out["sigma_n_sel"] == 0 else 1.4826 * out["mad"])
+        else:
+            out = self.backend.depth_blocks(
+                depth_maps=g["depth_maps"], valid_maps=g["valid_maps"], sx=g["sx"], sy=g["sy"], cam_quat=g["cam_quat"], cam_t=g["cam_t"],
+                obs_img=g["obs_img"], obs_xy=g["obs_xy"], obs_var=g["obs_var"], obs_pt=g["obs_pt"], pts=self._coordinates(g["point_ids"]),
+                scale_filter_factor=self.conf.scale_filter_factor, multiplier=1.0)
+            f = out["flags"]
+            sel = ((f & F_VALID) != 0) & ((f & F_POSITIVE) != 0)
+            _, sigma = fit_robust_gaussian_mad(out["whitened"][sel])
         self.truncation_multiplier = sigma
         if self.conf.min_truncation_mult is not None:
             self.truncation_multiplier = max(self.truncation_multiplier, self.conf.min_truncation_mult)

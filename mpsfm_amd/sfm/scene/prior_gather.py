@@ -15,14 +15,16 @@ from ...utils.ids import unique_ids
 F_VALID, F_POSITIVE, F_SCALE, F_GROSS = 1, 2, 4, 8
 
 
-def gather_bundle(rec, imids, depth_type="update"):
+def gather_bundle(rec, imids, depth_type="update", activated_only=True):
     """Concatenated per-observation inputs of the given images (those with an activated depth map and at least one
-    observation).  Returns a dict of arrays plus `images` (the image ids, in order) and `point_ids` (sorted unique)."""
+    observation; `activated_only=False` also takes images whose map is not activated: the prior scale fit reads the prior
+    of an image before it is activated).  Returns a dict of arrays plus `images` (the image ids, in order) and `point_ids`
+    (sorted unique).  An image's observations are a range: `obs_img` does not decrease."""
     images, maps, valids, sx, sy, quat, trans = [], [], [], [], [], [], []
     o_img, o_xy, o_var, o_pid, o_p2d = [], [], [], [], []
     for imid in imids:
         image = rec.images[imid]
-        if not image.depth.activated:
+        if activated_only and not image.depth.activated:
             continue
         p2Ds = np.asarray(image.get_observation_point2D_idxs(), dtype=np.int64)
         if len(p2Ds) == 0:
